@@ -13,15 +13,21 @@ reward, actions ~ U(-1,1) float32 already resident in HBM, auto-reset on.
 Episodes are DESYNCHRONISED by default: every env starts at its own random point of its 50-step episode, as in any training
 run after its first few hundred steps, so a short timed window is representative (with lock-stepped episodes all 8192 envs
 reset on the same step and a 20-step window measures one phase of the episode only; `--lockstep` keeps that mode and the
-default run reports it next to the headline figure).
+`--full` run reports it next to the headline figure).
 
 Weak scaling: every rank owns 8192 envs keyed by global env id; there is no collective on the step path (RCCL is used
 once, after the timed region, to reduce the episode statistics for logging: mycobotgym_amd.sharding.reduce_episode_stats).
 
-The default 1-GPU run also times, as `secondary` entries with their own `roofline`: Reach with the IK controller (100
+A plain run measures the headline workload only: set-up, W warm-up steps, K timed steps, the result line.  With `--full`
+the 1-GPU run also times, as `secondary` entries with their own `roofline`: Reach with the IK controller (100
 sub-steps per step), PickAndPlace (configs[2]: cube resting on the table, random actions), PickAndPlace during a scripted
 grasp (pad contacts: the coupled robot + cube solve), and PickAndPlace with per-reset domain randomisation (configs[4]'s
-per-GPU workload).
+per-GPU workload); it also reports the lock-stepped variant, the cost of the packaged step() over the raw launch, and the
+CPU oracle's rate on the host cores (`cpu_baseline`, Reach only).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned (the engine's output buffers:
+observation, goals, reward, flags, final observation, episode return and length) as DIR/<name>.npy in float64 (float32 for
+the boolean flags); inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 Prints ONE JSON line on rank 0.
 """
@@ -171,6 +177,31 @@ def roofline(case, n, kernel_ms):
     return out
 
 
+DUMP_MAX_BYTES = 64_000_000      # the whole dump, every rank's files and their .npy headers included
+NPY_HEADER_BYTES = 256           # an upper bound of one .npy header (format 1.0 pads it to a multiple of 64: 128 here)
+
+
+def dump_outputs(buf, out_dir, rank, world):
+    """The step's output buffers -> out_dir/<name>.npy (float64; bools as float32).  When a rank's share of DUMP_MAX_BYTES
+    would be exceeded, a fixed seeded sample of environments (the same rows of every array, listed in env_index.npy) is
+    written instead."""
+    import numpy as np
+    arrs = {k: v.detach().cpu().numpy() for k, v in buf.items()}
+    arrs = {k: a.astype(np.float32 if a.dtype == np.bool_ else np.float64, copy=False) for k, a in arrs.items()}
+    n = next(iter(arrs.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(a.shape[0], 1) for a in arrs.values())
+    budget = DUMP_MAX_BYTES // world - NPY_HEADER_BYTES * (len(arrs) + 1)       # + 1: env_index.npy
+    if n * row_bytes > budget:
+        keep = budget // (row_bytes + 8)          # + 8: the row's entry in env_index
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def _rehearsal_engine(rank):
     """Stand-in for MyCobotVecEnv under BENCH_REHEARSE_PLUMBING=1 (see main): same constructor / reset / set_state / step_async /
     _buf / close surface on CPU tensors; a step sleeps (longer on higher ranks, so that the MAX over ranks is visible).  Not an engine."""
@@ -202,9 +233,15 @@ def main():
                     help="PickAndPlace from the 'gripper closing over the cube' state (pad contacts in the timed window)")
     ap.add_argument("--lockstep", action="store_true", help="all episodes start together (every env resets on the same step)")
     ap.add_argument("--envs-per-gpu", type=int, default=N_ENVS_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the lock-stepped variant, the secondary workloads, the step() packaging cost and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the lock-stepped, secondary and step() legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64; flags float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     case = args.case
     if case is None:
         case = args.task + "-" + args.controller + ("-dr" if args.dr else "") + ("-grasp" if args.scripted_grasp else "")
@@ -252,7 +289,7 @@ def main():
     K, W = args.steps, args.warmup
     env_offset, total_envs = shard(rank, world, n)
 
-    def run(case, steps, warmup, lockstep):
+    def run(case, steps, warmup, lockstep, dump_dir=None):
         task, controller, dr, grasp = CASES[case]
         pnp = task == "pnp"
         envs = MyCobotVecEnv(n, has_object=pnp, controller_type=controller, reward_type="dense", device=dev,
@@ -294,14 +331,16 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=red_dev or dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if dump_dir is not None:            # off the timed region: the buffers still hold the last timed step's outputs
+            dump_outputs(envs._buf, dump_dir, rank, world)
         # logging path: episode statistics of the last step reduced over ranks (RCCL), off the timed region
         b = envs._buf
         stats = reduce_episode_stats(b["ep_return"], b["ep_length"], b["is_success"], b["truncated"], device=red_dev)
         envs.close()
         return dt, kernel_ms, stats
 
-    def entry(case, steps, warmup, lockstep):
-        dt, kernel_ms, stats = run(case, steps, warmup, lockstep)
+    def entry(case, steps, warmup, lockstep, dump_dir=None):
+        dt, kernel_ms, stats = run(case, steps, warmup, lockstep, dump_dir)
         sub = 100 if CASES[case][1] == "IK" else 20
         v = total_envs * steps / dt
         return {"case": case, "workload": describe(case, n, lockstep), "env_steps_per_sec": v, "ms_per_step": dt / steps * 1e3,
@@ -326,7 +365,7 @@ def main():
         envs.close()
         return out
 
-    main_e = entry(case, K, W, args.lockstep)
+    main_e = entry(case, K, W, args.lockstep, args.dump_outputs)
     task, controller = CASES[case][0], CASES[case][1]
     out = {
         "metric": "env-steps/sec (whole node), MyCobot Reach, N_envs=8192/GPU" if task == "reach" else
@@ -343,8 +382,8 @@ def main():
     if rehearse:
         out.update(value=None, rehearsal=True, data="none: plumbing rehearsal without the engine (BENCH_REHEARSE_PLUMBING=1)", roofline=None,
                    rehearsal_detail={"rank0_env_offset": env_offset, "total_envs": total_envs, "max_over_ranks_wall_s": main_e["ms_per_step"] * K / 1e3})
-    if world == 1 and not args.no_secondary and case == "reach-joint" and not args.lockstep and not rehearse:
-        # bounded so that the default run still finishes within a few minutes (the grasp case runs ~10 ms per step)
+    if args.full and world == 1 and not args.no_secondary and case == "reach-joint" and not args.lockstep and not rehearse:
+        # bounded so that the --full run still finishes within a few minutes (the grasp case runs ~10 ms per step)
         k2, w2 = max(min(K, 200) // 2, 20), max(min(W, 100) // 2, 5)
         out["lockstep"] = {k: v for k, v in entry(case, K, W, True).items() if k != "roofline"}
         # random-policy contact workloads: at least 60 untimed steps first, so that every env has passed a reset at its own time and the
@@ -353,7 +392,7 @@ def main():
         out["secondary"] = [entry(c, k2 if c != "pnp-joint-grasp" else min(k2, 40), warm_of(c), False) for c in DEFAULT_SECONDARY]
         out["api_step_cost"] = api_step_cost(case, 200)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and task == "reach" and not rehearse:
+        if args.full and not args.no_cpu_baseline and world == 1 and task == "reach" and not rehearse:
             out["cpu_baseline"] = cpu_baseline(controller)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -9,17 +9,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _launch(nproc, gpus, steps=12, warmup=3, extra_env=None):
+def _launch(nproc, gpus, steps=12, warmup=3, extra_env=None, extra_args=()):
     env = dict(os.environ, BENCH_REHEARSE_PLUMBING="1", OMP_NUM_THREADS="1")
     env.update(extra_env or {})
     port = 29600 + os.getpid() % 1000 + nproc
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup)]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup), *extra_args]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
 
 
@@ -56,3 +57,59 @@ def test_single_process_rehearsal_line():
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 1 and j["rehearsal"] is True and "secondary" not in j and "cpu_baseline" not in j
+
+
+REHEARSAL_OUTPUTS = {"ep_return": np.float64, "ep_length": np.float64, "is_success": np.float32, "truncated": np.float32}
+
+
+def test_dump_outputs_rehearsal(tmp_path):
+    """--dump-outputs DIR: one .npy per output buffer, float64 (flags float32), the same arrays from two runs with the same
+    arguments; at world size 2 every rank writes its own shard."""
+    env = dict(os.environ, BENCH_REHEARSE_PLUMBING="1")
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sorted(os.listdir(d)) == sorted(k + ".npy" for k in REHEARSAL_OUTPUTS)
+        dumps.append({k: np.load(d / (k + ".npy")) for k in REHEARSAL_OUTPUTS})
+    for k, dt in REHEARSAL_OUTPUTS.items():
+        assert dumps[0][k].dtype == dt and dumps[0][k].shape == (8192,), k
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    d = tmp_path / "world2"
+    r = _launch(2, 2, steps=4, warmup=1, extra_args=("--dump-outputs", str(d)))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(d)) == sorted(f"{k}.rank{q}.npy" for k in REHEARSAL_OUTPUTS for q in range(2))
+    assert np.all(np.load(d / "ep_return.rank1.npy") == 2.0)          # rank 1's stand-in returns 2
+
+
+@pytest.mark.parametrize("world", [1, 3])
+def test_dump_outputs_sample_stays_within_the_cap(tmp_path, monkeypatch, world):
+    """Above the cap (64 MB for the whole dump, every rank's files and headers included) a fixed seeded sample of environments
+    is written: the same rows of every array, listed in env_index.npy, the same rows from run to run."""
+    import torch
+    import bench
+    n, cap = 5000, 200_000
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", cap)
+    rows = torch.arange(n, dtype=torch.float64)
+    buf = {"obs": rows[:, None].repeat(1, 10), "reward": -rows, "truncated": (torch.arange(n) % 3) == 0,
+           "ep_length": torch.arange(n, dtype=torch.int32)}
+    got = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        for rank in range(world):
+            bench.dump_outputs(buf, str(d), rank, world)
+        files = sorted(os.listdir(d))
+        suffix = [f".rank{q}" for q in range(world)] if world > 1 else [""]
+        assert files == sorted(f"{a}{s}.npy" for a in ("obs", "reward", "truncated", "ep_length", "env_index") for s in suffix)
+        assert sum(os.path.getsize(d / f) for f in files) <= cap
+        a = {f[:-4]: np.load(d / f) for f in files}
+        s = suffix[0]
+        idx = a["env_index" + s]
+        assert idx.dtype == np.float64 and 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+        assert a["obs" + s].dtype == np.float64 and np.array_equal(a["obs" + s], np.repeat(idx[:, None], 10, axis=1))
+        assert np.array_equal(a["reward" + s], -idx) and np.array_equal(a["ep_length" + s], idx)
+        assert a["truncated" + s].dtype == np.float32 and np.array_equal(a["truncated" + s], (idx % 3 == 0).astype(np.float32))
+        got.append(a)
+    assert all(np.array_equal(got[0][k], got[1][k]) for k in got[0])

@@ -4,14 +4,13 @@ These are the only machine-checkable numbers the reference itself contains (it s
 constants such as "FK(EEF, qpos=0) equals the mocap body's rest pose".  They pin the kinematic tree, the
 include/default-class resolution and the keyframes of the compiled tables.
 """
+import json
 import os
 
 import numpy as np
 import pytest
 
 from tests.common import ASSETS, load_json
-
-REF_ASSETS = "/root/reference/mycobotgym/envs/assets"
 
 
 def _np(tab):
@@ -116,11 +115,38 @@ def test_generated_header_is_current():
     assert open(hdr).read() == before
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference tree not present (GPU box)")
+def _same(fresh, stored, where):
+    """Equal tables: numbers to rtol 1e-12 (atol 1e-15), everything else exactly."""
+    if isinstance(stored, dict):
+        assert isinstance(fresh, dict) and fresh.keys() == stored.keys(), where
+        for k in stored:
+            _same(fresh[k], stored[k], f"{where}.{k}")
+    elif isinstance(stored, list):
+        assert isinstance(fresh, list) and len(fresh) == len(stored), where
+        for i, (f, s) in enumerate(zip(fresh, stored)):
+            _same(f, s, f"{where}[{i}]")
+    elif isinstance(stored, float) and not isinstance(fresh, (bool, str)):
+        assert np.isclose(fresh, stored, rtol=1e-12, atol=1e-15), (where, fresh, stored)
+    else:
+        assert fresh == stored and type(fresh) is type(stored), (where, fresh, stored)
+
+
 def test_tables_reproducible_from_reference():
-    from mycobotgym_amd.model.mjcf import MjcfCompiler, _to_jsonable
-    fresh = _to_jsonable(MjcfCompiler(os.path.join(REF_ASSETS, "mycobot280.xml")).compile())
+    """The committed tables are what the current compiler makes from the upstream MJCF: build() compiles it into
+    oracle/_ref/tables (oracle/ref_tables.py), stamped with the hash of the compiler sources that made them."""
+    from oracle import ref_tables
+    st = ref_tables.read_stamp()
+    if st is None:
+        pytest.skip("oracle/_ref/tables not built: build() found no upstream MyCobotGym checkout ($MCG_REFERENCE)")
+    assert st["compiler_sha256"] == ref_tables.compiler_hash(), \
+        "oracle/_ref/tables were compiled by other compiler sources: run build() where the upstream checkout is readable"
+    assert sorted(st["tables"]) == sorted(j[0] for j in ref_tables.JOBS)
+    fresh = {}
+    for name in st["tables"]:
+        with open(os.path.join(ref_tables.OUT, name + ".json")) as f:
+            fresh[name] = json.load(f)
+        _same(fresh[name], load_json(name), name)
     stored = load_json("mycobot280")
     for k in ("body_mass", "body_pos", "body_ipos", "jnt_axis", "qpos0", "body_inertia"):
-        assert np.allclose(np.asarray(fresh[k], dtype=float), np.asarray(stored[k], dtype=float), rtol=1e-12, atol=1e-15), k
-    assert fresh["body_name"] == stored["body_name"] and fresh["eq"] == stored["eq"]
+        assert np.allclose(np.asarray(fresh["mycobot280"][k], dtype=float), np.asarray(stored[k], dtype=float), rtol=1e-12, atol=1e-15), k
+    assert fresh["mycobot280"]["body_name"] == stored["body_name"] and fresh["mycobot280"]["eq"] == stored["eq"]
