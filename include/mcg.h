@@ -170,7 +170,18 @@ const char* mcg_last_error(void);
 int mcg_default_model(int variant, mcg_model* out);
 
 /* polytopes: the mesh geoms' collision tables in the robot bodies' frames (layout: mycobotgym_amd/model/polytope.py: pack), n_polytopes
-   doubles, host memory; NULL = the built-in tables of the reference's meshes */
+   doubles, host memory; NULL = the built-in tables of the reference's meshes.  A custom model goes with the block specialised with it
+   (the polytopes move with the bodies they ride on).  With the cube in the physics (PickAndPlace, or Reach with reward_shaping) these
+   are checked on the host, before any HIP call:
+     MCG_ERR_ARG          the block's index: per mesh, all eight meta entries whole numbers in [0, n_polytopes], V >= 1, F, E >= 0,
+                          Vpad, Fpad, Epad multiples of 64 with Fpad, Epad >= 64, counts within their pads, the arrays after the meta
+                          region and inside the block;
+     MCG_ERR_ARG          the block against the model: every vertex of mesh m inside mesh_box[m] and within body[].hull_rad of the body
+                          it rides on (1e-12 slack);
+     MCG_ERR_UNSUPPORTED  the model against the broad-phase gates of the kernels (csrc/mcg_cube.hpp: GATE_*): the gripper's reach from
+                          the link6 origin (|r| summed along each chain plus hull_rad, or plus the pad's centre and half-diagonal) below
+                          0.17 m, that reach plus |cube_half| below 0.2 m, each pad's half-diagonal below 0.02 m, |cube_half| below 0.05 m.
+                          The message names the gate. */
 int mcg_create(const mcg_config* cfg, const mcg_model* model /* NULL = variant 0 */, const double* polytopes, int64_t n_polytopes,
                int device, mcg_env** out);
 void mcg_destroy(mcg_env* env);

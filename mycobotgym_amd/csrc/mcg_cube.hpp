@@ -44,6 +44,12 @@ MCG_DEV bool pair_has_cube(int type) { return type < PAIR_TABLE_PADR || type >= 
 MCG_DEV bool pair_mesh_static(int type) { return type >= PAIR_STATIC_MESH0 && type < PAIR_MESH0_CUBE; }
 MCG_DEV bool pair_mesh_cube(int type) { return type >= PAIR_MESH0_CUBE; }
 MCG_DEV int mesh_body(int m) { return m < 6 ? m : (m < 8 ? 5 : m - 2); }
+// Broad-phase gates of the gripper and the cube (step_pnp's contact pass), in metres.  They are tuned to the MyCobot-280 and hold for any
+// model whose conservative bounds stay below them; mcg_create refuses a model whose bounds do not (MCG_ERR_UNSUPPORTED).
+constexpr double GATE_CUBE_REACH = 0.2;      // link6 origin to cube centre: the gripper's parts and pads are tested against the cube
+constexpr double GATE_STATIC_REACH = 0.17;   // link6 origin to the table box / above the ground: ... against the table and the ground
+constexpr double GATE_PAD_GROUND = 0.02;     // pad centre height: a pad is tested against the ground
+constexpr double GATE_CUBE_GROUND = 0.05;    // cube centre height: the cube is tested against the ground
 // the robot body of a pair (-1: none): pads ride on the finger links (bodies 7, 9)
 MCG_DEV int pair_robot_body(int type) {
   const int m = type >= PAIR_MESH0_CUBE ? type - PAIR_MESH0_CUBE : type - PAIR_STATIC_MESH0;
@@ -565,12 +571,12 @@ struct CubeSys {
         } });
       MCG_TICK2(ST_A_G);
       const real dxe = p[0] - Cb.pos[0], dye = p[1] - Cb.pos[1], dze = p[2] - Cb.pos[2];
-      reach = dxe*dxe + dye*dye + dze*dze < 0.2 * 0.2;                  // link6 origin within 20 cm of the cube
+      reach = dxe*dxe + dye*dye + dze*dze < GATE_CUBE_REACH * GATE_CUBE_REACH;      // link6 origin within 20 cm of the cube
       // a pad's far corner is at most 0.16 m from the link6 origin (and so is every point of the gripper's links): the gripper can only
-      // touch the table / the ground from within 0.17 m
+      // touch the table / the ground from within 0.17 m (mcg_create checks the model's bound against the gate)
       real dtab = 0;
       _Pragma("unroll") for (int k = 0; k < 3; k++) { const real e = fmax(fabs(p[k] - tp[k]) - th[k], 0.0); dtab = fma(e, e, dtab); }
-      const bool nearstat = dtab < 0.17 * 0.17 || p[2] < 0.17;
+      const bool nearstat = dtab < GATE_STATIC_REACH * GATE_STATIC_REACH || p[2] < GATE_STATIC_REACH;
       padlive = reach || nearstat;
       if (__any(padlive)) {
         static_for<2>([&](auto Sd) {
@@ -594,14 +600,14 @@ struct CubeSys {
       }
     }
     // ground plane: pads, cube
-    if (__any(padlive && (pc[0][2] < 0.02 || pc[1][2] < 0.02))) {
+    if (__any(padlive && (pc[0][2] < GATE_PAD_GROUND || pc[1][2] < GATE_PAD_GROUND))) {
       static_for<2>([&](auto Sd) { constexpr int sd = Sd;
-        const bool low = padlive && pc[sd][2] < 0.02;
+        const bool low = padlive && pc[sd][2] < GATE_PAD_GROUND;
         const real far[3] = {pc[sd][0], pc[sd][1], low ? pc[sd][2] : 1.0};
         ground_box(CL, far, Rs[sd], ph[sd], PAIR_TABLE_PADR + sd); });
     }
-    if (__any(Cb.pos[2] < 0.05)) {
-      const bool low = Cb.pos[2] < 0.05;
+    if (__any(Cb.pos[2] < GATE_CUBE_GROUND)) {
+      const bool low = Cb.pos[2] < GATE_CUBE_GROUND;
       const real far[3] = {Cb.pos[0], Cb.pos[1], low ? Cb.pos[2] : 1.0};
       ground_box(CL, far, Rc, hc, PAIR_TABLE_CUBE);
     }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -978,6 +979,93 @@ __global__ void copy_state_kernel(View V, mcg_state S, int to_engine) {
   if (S.episode) { if (to_engine) V.episode(i) = S.episode[i]; else S.episode[i] = V.episode(i); }
 }
 
+// ------------------------------------------------------------------------------------------- host checks of mcg_create
+// A caller's polytope block and model block are checked on the host before any HIP call: the kernels walk the block's own index, and
+// the broad phase trusts mesh_box, hull_rad and the GATE_* literals (mcg_cube.hpp).  On failure: false, and the reason in `why`.
+double norm3(const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
+
+bool polytope_index_ok(const double* pb, size_t np, char* why, size_t nwhy) {
+  for (int m = 0; m < MCG_NMESH; m++) {
+    const double* meta = pb + 8 * m;     // {V, F, E, offset, Vpad, Fpad, Epad, 0} (mycobotgym_amd/model/polytope.py: pack)
+    for (int k = 0; k < 8; k++)
+      if (!(meta[k] >= 0 && meta[k] <= (double)np && meta[k] == std::floor(meta[k]))) {
+        snprintf(why, nwhy, "mesh %d: meta[%d] = %g is not a whole number in [0, %zu]", m, k, meta[k], np);
+        return false;
+      }
+    const double end = meta[3] + 3 * meta[4] + 4 * meta[5] + 13 * meta[6];
+    const bool ok = meta[0] >= 1 && meta[0] <= meta[4] && meta[1] <= meta[5] && meta[2] <= meta[6]
+        && meta[5] >= 64 && meta[6] >= 64                         // a wave reads one face / edge per lane: Fpad, Epad of at least 64
+        && meta[3] >= 8 * MCG_NMESH && end <= (double)np
+        && ((long long)meta[4] % 64) == 0 && ((long long)meta[5] % 64) == 0 && ((long long)meta[6] % 64) == 0
+        && meta[4] <= 64 * MESH_VCH && meta[5] <= 64 * MESH_FCH;      // (the narrow phase holds a family's table in registers: csrc/mcg_mesh.hpp)
+    if (!ok) {
+      snprintf(why, nwhy, "mesh %d: inconsistent counts / offset (V %g F %g E %g offset %g pads %g %g %g, block of %zu)", m, meta[0], meta[1],
+               meta[2], meta[3], meta[4], meta[5], meta[6], np);
+      return false;
+    }
+  }
+  return true;
+}
+
+// every vertex of polytope m inside mesh_box[m] and within hull_rad of the body it rides on (the broad phase's two bounds)
+bool polytopes_fit_model(const double* pb, const mcg_model* mm, char* why, size_t nwhy) {
+  const double slack = 1e-12;
+  for (int m = 0; m < MCG_NMESH; m++) {
+    const double* meta = pb + 8 * m;
+    const long long nv = (long long)meta[0], vp = (long long)meta[4], off = (long long)meta[3];
+    const int body = m < 6 ? m : (m < 8 ? 5 : m - 2);               // mesh_body(m), mcg_cube.hpp
+    const double* box = mm->mesh_box[m];
+    for (long long k = 0; k < nv; k++) {
+      const double v[3] = {pb[off + k], pb[off + vp + k], pb[off + 2 * vp + k]};
+      for (int a = 0; a < 3; a++)
+        if (!(std::fabs(v[a] - box[a]) <= box[3 + a] + slack)) {
+          snprintf(why, nwhy, "vertex %lld of mesh %d lies outside mcg_model.mesh_box[%d] (axis %d)", k, m, m, a);
+          return false;
+        }
+      if (!(norm3(v) <= mm->body[body].hull_rad + slack)) {
+        snprintf(why, nwhy, "vertex %lld of mesh %d lies %.6g m from body %d's origin, beyond its hull_rad %.6g", k, m, norm3(v), body,
+                 mm->body[body].hull_rad);
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+// the model's conservative bounds against the broad-phase gates of step_pnp (cube_half: as the kernels see it, zero for a hidden cube)
+bool model_within_gates(const mcg_model* mm, const double* cube_half, char* why, size_t nwhy) {
+  // farthest point of the gripper's parts and pads from the link6 origin: |r| summed along the chain, plus hull_rad or the pad's corner
+  double reach = 0;
+  for (int sd = 0; sd < 2; sd++) {
+    const int g = 6 + 2 * sd, f = 7 + 2 * sd, h = 10 + sd;
+    const double rg = norm3(mm->body[g].r), rf = norm3(mm->body[f].r);
+    reach = std::fmax(reach, rg + mm->body[g].hull_rad);
+    reach = std::fmax(reach, rg + rf + mm->body[f].hull_rad);
+    reach = std::fmax(reach, norm3(mm->body[h].r) + mm->body[h].hull_rad);
+    reach = std::fmax(reach, rg + rf + norm3(mm->pad_box[sd]) + norm3(mm->pad_box[sd] + 3));
+  }
+  const double crad = norm3(cube_half);
+  if (!(reach < GATE_STATIC_REACH)) {
+    snprintf(why, nwhy, "the gripper reaches %.6g m from the link6 origin, not below the static gate GATE_STATIC_REACH = %g", reach, GATE_STATIC_REACH);
+    return false;
+  }
+  if (!(reach + crad < GATE_CUBE_REACH)) {
+    snprintf(why, nwhy, "gripper reach %.6g m + cube radius %.6g m is not below the cube gate GATE_CUBE_REACH = %g", reach, crad, GATE_CUBE_REACH);
+    return false;
+  }
+  for (int sd = 0; sd < 2; sd++)
+    if (!(norm3(mm->pad_box[sd] + 3) < GATE_PAD_GROUND)) {
+      snprintf(why, nwhy, "pad %d's half-diagonal %.6g m is not below the pad ground gate GATE_PAD_GROUND = %g", sd, norm3(mm->pad_box[sd] + 3),
+               GATE_PAD_GROUND);
+      return false;
+    }
+  if (!(crad < GATE_CUBE_GROUND)) {
+    snprintf(why, nwhy, "the cube's half-diagonal %.6g m is not below the cube ground gate GATE_CUBE_GROUND = %g", crad, GATE_CUBE_GROUND);
+    return false;
+  }
+  return true;
+}
+
 }  // namespace
 
 // ================================================================================================== host ABI
@@ -1024,6 +1112,19 @@ int mcg_create(const mcg_config* c, const mcg_model* model, const double* polyto
     if (!ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_create: solimp power must be 1 or 2 (the MJCF default is 2)%s");
   }
   if (c->frame_skip <= 0 || c->control_steps <= 0 || c->max_episode_steps <= 0) return fail(MCG_ERR_ARG, "mcg_create: frame_skip, control_steps, max_episode_steps must be positive%s");
+  const bool cube_physics = c->has_object || (c->reward_type == MCG_REWARD_SHAPING && !c->has_object);     // C.has_object below
+  if (cube_physics) {     // the PickAndPlace kernels: the polytope block, its fit to the model, the broad-phase gates (host only, before any HIP call)
+    const mcg_model* mm = model ? model : &kDefaultModels[0];
+    const double* pb = polytopes ? polytopes : kDefaultPolytopes;
+    const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;
+    char why[200];
+    if (!polytope_index_ok(pb, np, why, sizeof(why))) return fail(MCG_ERR_ARG, "mcg_create: inconsistent polytope block: %s", why);
+    if (!polytopes_fit_model(pb, mm, why, sizeof(why)))
+      return fail(MCG_ERR_ARG, "mcg_create: the polytope block does not fit the model (pass the block specialised with it): %s", why);
+    const bool hidden = !c->has_object;
+    const double cube_half[3] = {hidden ? 0.0 : mm->cube_half[0], hidden ? 0.0 : mm->cube_half[1], hidden ? 0.0 : mm->cube_half[2]};
+    if (!model_within_gates(mm, cube_half, why, sizeof(why))) return fail(MCG_ERR_UNSUPPORTED, "mcg_create: unsupported model: %s", why);
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MCG_ERR_HIP, "mcg_create: no HIP device (this engine has no CPU path)%s");
   if (device < 0 || device >= ndev) return fail(MCG_ERR_ARG, "mcg_create: bad device index%s");
@@ -1075,18 +1176,8 @@ int mcg_create(const mcg_config* c, const mcg_model* model, const double* polyto
   if (err == hipSuccess) err = hipMalloc(&e->d_model, sizeof(mcg_model));
   if (err == hipSuccess) err = hipMalloc(&e->d_cnt, sizeof(mcg_counters));
   if (err == hipSuccess && C.has_object) {
-    const double* pb = polytopes ? polytopes : kDefaultPolytopes;
+    const double* pb = polytopes ? polytopes : kDefaultPolytopes;            // checked above
     const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;
-    // the block's own index must stay inside it (a kernel walks these offsets)
-    bool ok = true;
-    for (int m = 0; m < MCG_NMESH && ok; m++) {
-      const double* meta = pb + 8 * m;
-      const double end = meta[3] + 3 * meta[4] + 4 * meta[5] + 13 * meta[6];
-      ok = meta[0] >= 1 && meta[0] <= meta[4] && meta[1] <= meta[5] && meta[2] <= meta[6] && meta[3] >= 8 * MCG_NMESH && end <= (double)np
-           && ((long long)meta[4] % 64) == 0 && ((long long)meta[5] % 64) == 0 && ((long long)meta[6] % 64) == 0
-           && meta[4] <= 64 * MESH_VCH && meta[5] <= 64 * MESH_FCH;      // (the narrow phase holds a family's table in registers: csrc/mcg_mesh.hpp)
-    }
-    if (!ok) { mcg_destroy(e); return fail(MCG_ERR_ARG, "mcg_create: inconsistent polytope block%s"); }
     err = hipMalloc(&e->d_poly, np * sizeof(double));
     if (err == hipSuccess) err = hipMemcpy(e->d_poly, pb, np * sizeof(double), hipMemcpyHostToDevice);
   }

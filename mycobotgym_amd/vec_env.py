@@ -37,11 +37,14 @@ def load_table(has_object: bool, mesh_inertia: str = "legacy", mocap: bool = Fal
     return load_model(os.path.join(_ASSETS, name + ".json"))
 
 
-def initial_state(has_object: bool, fetch_env: bool, mesh_inertia: str = "legacy", mocap: bool = False):
+def initial_state(has_object: bool, fetch_env: bool, mesh_inertia: str = "legacy", mocap: bool = False, table: Optional[dict] = None):
     """(init_qpos, init_qvel, init_ctrl, initial_gripper_xpos, height_offset): what ``_env_setup`` and the
     constructor snapshot (mycobot.py:78-82, 450-472).  Non-fetch: qpos0 / zero ctrl; fetch: keyframe 0.
-    ``init_ctrl`` always has the engine's 7 slots; the mocap model's single (finger) actuator is slot 6."""
+    ``init_ctrl`` always has the engine's 7 slots; the mocap model's single (finger) actuator is slot 6.
+    ``table``: a compiled model table (``load_model`` output) to take all of it from instead of the built-in tables."""
     from .model.specialize import initial_gripper_xpos
+    if table is not None:
+        return _table_initial_state(table, has_object, fetch_env, mesh_inertia, mocap)
     full = load_table(True, mesh_inertia, mocap)
     tab = full if has_object else load_table(False, mesh_inertia, mocap)
     nq, nv = tab["nq"], tab["nv"]
@@ -60,6 +63,33 @@ def initial_state(has_object: bool, fetch_env: bool, mesh_inertia: str = "legacy
     return qpos, qvel, ctrl, igx, height
 
 
+def _table_initial_state(table: dict, has_object: bool, fetch_env: bool, mesh_inertia: str, mocap: bool):
+    """initial_state of one given table: its qpos0 (or keyframe 0), the EEF site and the z of site object0 by its own kinematics.  A table
+    without the cube (Reach) has no object0 site: its height_offset, which Reach does not read, is the built-in one."""
+    from .model.mjcf import _np_model
+    from .model.refdyn import kinematics
+    from .model.specialize import initial_gripper_xpos
+    tab = _np_model(table)
+    nq, nv = (19, 18) if has_object else (12, 12)            # the engine's state: the cube's free joint with PickAndPlace only
+    if fetch_env:
+        key = tab["keys"][0]
+        qfull = np.asarray(key["qpos"], dtype=np.float64)[:tab["nq"]].copy()
+        qvel = np.asarray(key["qvel"], dtype=np.float64)[:nv].copy()
+        ctrl = np.zeros(7); kc = np.asarray(key["ctrl"], dtype=np.float64)
+        ctrl[7 - len(kc):] = kc
+    else:
+        qfull = np.asarray(tab["qpos0"], dtype=np.float64).copy()
+        qvel = np.zeros(nv); ctrl = np.zeros(7)
+    if len(qfull) < nq:
+        raise ValueError(f"the table has {len(qfull)} qpos entries; this configuration needs {nq} (PickAndPlace needs the cube)")
+    igx = initial_gripper_xpos(tab, qfull)
+    if "object0" in tab["site_name"]:
+        height = float(kinematics(tab, qfull)["site_xpos"][tab["site_name"].index("object0")][2])
+    else:
+        height = initial_state(has_object, fetch_env, mesh_inertia, mocap)[4]
+    return qfull[:nq], qvel, ctrl, igx, height
+
+
 class MyCobotVecEnv:
     metadata = {"render_modes": [], "render_fps": 25}      # mycobot.py:28
 
@@ -70,7 +100,10 @@ class MyCobotVecEnv:
                  env_id_offset: int = 0, auto_reset: bool = True, mesh_inertia: str = "legacy",
                  domain_randomization: Optional[dict] = None, model_path: Optional[str] = None,
                  image_obs: bool = False, model: Optional["_abi.McgModel"] = None, weld_rule: str = "common", contact_rule: str = "mujoco",
-                 **unused):
+                 table: Optional[dict] = None, polytopes: Optional[np.ndarray] = None, **unused):
+        """``table``: a compiled model table (``mjcf.load_model`` output) to run instead of the built-in model: it is specialised, its
+        collision polytopes go to the engine with it, and the initial state (qpos, gripper position, height offset) is its own.
+        ``model`` / ``polytopes``: a raw ``mcg_model`` block and the polytope block specialised with it (NULL: the built-in one)."""
         if image_obs:
             raise NotImplementedError("image observations (-v1 ids, MyCobotImgEnv) need a rasteriser: out of scope")
         if controller_type == "delta_joint":
@@ -91,7 +124,7 @@ class MyCobotVecEnv:
             want = f"mycobot280{'_mocap' if controller_type == 'mocap' else ''}.xml"
             if os.path.basename(str(model_path)) != want:
                 raise ValueError(f"model_path {model_path!r}: this engine runs the precompiled {want} only (compile another MJCF with "
-                                 "tools/compile_model.py and pass it as model=McgModel.from_spec(...))")
+                                 "tools/compile_model.py and pass the table as table=...)")
         self.num_envs = int(num_envs)
         self.has_object, self.fetch_env = bool(has_object), bool(fetch_env)
         # Reach + reward_shaping keeps the (hidden) cube in the physics: stage_rewards reads it (mycobot.py:402-448, 475-481)
@@ -103,7 +136,15 @@ class MyCobotVecEnv:
         self.obj_range = obj_range
 
         mocap = controller_type == "mocap"
-        qpos, qvel, ctrl, igx, height = initial_state(self.has_object or self.hidden_object, self.fetch_env, mesh_inertia, mocap)
+        if table is not None:
+            if model is not None or polytopes is not None:
+                raise ValueError("table= specialises its own model and polytope blocks: do not pass model= or polytopes= with it")
+            from .model.mjcf import _np_model
+            from .model.specialize import specialize
+            spec = specialize(_np_model(table), weld_rule=weld_rule, contact_rule=contact_rule)
+            model = _abi.McgModel.from_spec(spec)
+            polytopes = spec.get("polytopes")          # absent from a table without the cube (Reach): the kernels collide nothing there
+        qpos, qvel, ctrl, igx, height = initial_state(self.has_object or self.hidden_object, self.fetch_env, mesh_inertia, mocap, table=table)
         self.initial_gripper_xpos, self.height_offset = igx, height
         cfg = _abi.McgConfig()
         cfg.n_envs = self.num_envs; cfg.has_object = int(self.has_object)
@@ -135,7 +176,10 @@ class MyCobotVecEnv:
         self._model = model
         self._h = C.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _abi.check(self._lib.mcg_create(C.byref(cfg), C.byref(model), None, 0, dev_index, C.byref(self._h)), "mcg_create")      # built-in polytope tables
+        # polytopes None: the built-in collision tables; the array must outlive mcg_create only (the engine copies it)
+        poly = None if polytopes is None else np.ascontiguousarray(np.asarray(polytopes, dtype=np.float64).reshape(-1))
+        _abi.check(self._lib.mcg_create(C.byref(cfg), C.byref(model), None if poly is None else poly.ctypes.data,
+                                        0 if poly is None else len(poly), dev_index, C.byref(self._h)), "mcg_create")
         self.obs_dim = self._lib.mcg_obs_dim(self._h)
         self.action_dim = self._lib.mcg_action_dim(self._h)
         self.nq, self.nv = self._lib.mcg_nq(self._h), self._lib.mcg_nv(self._h)

@@ -29,10 +29,63 @@ def soften_gains(tab, scale=0.1):
     return tab
 
 
+def perturbed_table(name, seed=0):
+    """A deterministic perturbation of built-in table `name` (mycobot280, mycobot280_reach, mycobot280_mocap) that moves numbers every kernel
+    family reads: a 5 mm flange spacer (polytopes of the flange and the gripper base, the gripper's bodies, the EEF site, the mocap weld
+    point), arm links +-1-2 mm, mass x U(0.9, 1.1) with the inertia alike and the CoM +-1 mm, damping / armature x U(0.8, 1.2), arm joint
+    ranges 5 % narrower, servo gains x U(0.95, 1.05), a cube of half-size 12 mm on a table 4 mm higher, pads 0.5 mm larger, cube friction
+    x 1.2, mesh friction x 0.9, the EEF site +-1 mm.  Every change keeps specialize's structural asserts.  Test-only."""
+    tab = json.loads(json.dumps(load_json(name)))
+    rng = np.random.default_rng(seed)
+    bi, gname = tab["body_name"].index, tab["geom_name"]
+    sign = lambda: float(rng.choice([-1.0, 1.0]))
+    tab["body_pos"][bi("flange")][0] += 0.005
+    for b in ("link2", "link3", "link4", "link5", "link6"):
+        for k in range(3):
+            tab["body_pos"][bi(b)][k] += sign() * rng.uniform(0.001, 0.002)
+    for b in range(tab["nbody"]):
+        if tab["body_mass"][b] <= 0:
+            continue
+        f = rng.uniform(0.9, 1.1)
+        tab["body_mass"][b] *= f
+        tab["body_inertia"][b] = [f * x for x in tab["body_inertia"][b]]
+        if tab["body_name"][b] != "object0":                       # the cube stays centred (and axis-aligned: body_iquat untouched)
+            tab["body_ipos"][b] = [x + rng.uniform(-0.001, 0.001) for x in tab["body_ipos"][b]]
+    tab["dof_damping"] = [x * rng.uniform(0.8, 1.2) for x in tab["dof_damping"]]
+    tab["dof_armature"] = [x * rng.uniform(0.8, 1.2) for x in tab["dof_armature"]]
+    for j in range(6):                                             # the arm's hinges: 5 % narrower about the centre
+        lo, hi = tab["jnt_range"][j]
+        c, h = 0.5 * (lo + hi), 0.5 * (hi - lo)
+        tab["jnt_range"][j] = [c - 0.95 * h, c + 0.95 * h]
+    for a in tab["actuators"]:                                     # position servos: gainprm[0] = kp, biasprm = (0, -kp, -kv)
+        fp, fv = rng.uniform(0.95, 1.05), rng.uniform(0.95, 1.05)
+        a["gainprm"][0] *= fp; a["biasprm"][1] *= fp; a["biasprm"][2] *= fv
+    if "object0" in gname:
+        gc = gname.index("object0")
+        old = tab["geom_size"][gc][2]
+        tab["geom_size"][gc] = [0.012, 0.012, 0.012]
+        tab["geom_friction"][gc] = [1.2 * x for x in tab["geom_friction"][gc]]
+        tab["body_pos"][bi("table")][2] += 0.004
+        dz = 0.004 + (0.012 - old)                                  # the cube still rests on the table top
+        tab["body_pos"][bi("object0")][2] += dz
+        qadr = tab["jnt_qposadr"][tab["jnt_name"].index("object0:joint")]
+        tab["qpos0"][qadr + 2] += dz
+    for g in ("right_finger_layer", "left_finger_layer"):
+        if g in gname:
+            tab["geom_size"][gname.index(g)] = [x + 0.0005 for x in tab["geom_size"][gname.index(g)]]
+    for g in range(tab["ngeom"]):
+        if tab["geom_type"][g] == 7:
+            tab["geom_friction"][g] = [0.9 * x for x in tab["geom_friction"][g]]
+    s = tab["site_name"].index("EEF")
+    tab["site_pos"][s] = [x + sign() * 0.001 for x in tab["site_pos"][s]]
+    return tab
+
+
 def make_oracle(n, has_object=False, controller_type="joint", fetch_env=False, reward_type="dense", seed=0,
                 env_id_offset=0, mesh_inertia="legacy", frame_skip=20, control_steps=5, max_episode_steps=50,
                 target_in_the_air=True, distance_threshold=0.01, auto_reset=True, n_threads=None, table=None,
-                domain_randomization=None, block_gripper=False, weld_rule="common", contact_rule="mujoco"):
+                domain_randomization=None, block_gripper=False, weld_rule="common", contact_rule="mujoco", initial=None):
+    """`initial`: (qpos, qvel, ctrl, initial_gripper_xpos, height_offset) to use instead of vec_env.initial_state's."""
     from oracle import pyoracle as po
     from mycobotgym_amd.vec_env import initial_state
     mocap = controller_type == "mocap"
@@ -47,7 +100,7 @@ def make_oracle(n, has_object=False, controller_type="joint", fetch_env=False, r
     if weld_rule == "mujoco" or contact_rule == "keyframe":
         # study switches: rule[0] = 1 rotational weight on the weld's rows 3-5; rule[3] = 2 Rpy = 4 mu^2 R (the keyframes' rest height)
         model._set_i("rule", [1 if weld_rule == "mujoco" else 0, 0, 0, 2 if contact_rule == "keyframe" else 0, 0, 0, 0, 0])
-    qpos, qvel, ctrl, igx, height = initial_state(has_cube, fetch_env, mesh_inertia, mocap)
+    qpos, qvel, ctrl, igx, height = initial if initial is not None else initial_state(has_cube, fetch_env, mesh_inertia, mocap, table=table)
     ctrl = ctrl[7 - tab["nu"]:]                  # the oracle's ctrl has the model's nu entries (mocap model: the finger only)
     cfg = po.EnvConfig()
     cfg.n_envs = n; cfg.has_object = int(has_object)
@@ -57,7 +110,7 @@ def make_oracle(n, has_object=False, controller_type="joint", fetch_env=False, r
         mb = tab["body_mocap"].index(True)
         pose = list(tab["body_pos"][mb]) + list(tab["body_quat"][mb])
         if fetch_env:
-            key = load_json(table_name(True, mesh_inertia, True))["keys"][0]
+            key = (table if table is not None else load_json(table_name(True, mesh_inertia, True)))["keys"][0]
             pose = list(key["mpos"]) + list(key["mquat"])
         for k, v in enumerate(pose): cfg.init_mocap[k] = v
     cfg.reward_type = {"sparse": 0, "dense": 1, "reward_shaping": 2}[reward_type]
@@ -88,16 +141,11 @@ def make_oracle(n, has_object=False, controller_type="joint", fetch_env=False, r
 
 
 def make_pair(n, device="cuda:0", table=None, **kw):
-    """HIP engine + CPU oracle with one configuration.  `table`: optional modified model table for both."""
+    """HIP engine + CPU oracle with one configuration.  `table`: optional modified model table for both (the engine specialises it,
+    polytopes and initial state included: MyCobotVecEnv(table=...))."""
     from mycobotgym_amd import MyCobotVecEnv
     okw = dict(kw)
-    model = None
-    if table is not None:
-        from mycobotgym_amd._abi import McgModel
-        from mycobotgym_amd.model.mjcf import _np_model
-        from mycobotgym_amd.model.specialize import specialize
-        model = McgModel.from_spec(specialize(_np_model(table)))
-    envs = MyCobotVecEnv(n, device=device, has_object=kw.pop("has_object", False), model=model, **kw)
+    envs = MyCobotVecEnv(n, device=device, has_object=kw.pop("has_object", False), table=table, **kw)
     ora = make_oracle(n, table=table, **okw)
     return envs, ora
 

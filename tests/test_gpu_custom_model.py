@@ -1,0 +1,270 @@
+"""GPU parity on a PERTURBED model (tests/common.py: perturbed_table): the kernels read every number from the model block and the polytope
+block, so a caller's model must give what the oracle gives for the same table -- contacts against the independent exact rule (flange and
+gripper base moved by a 5 mm spacer, poses at the broad-phase gates), per-sub-step and whole-env-step parity, reset draws from the table's
+own initial state.  The bounds are those of the built-in counterparts."""
+import numpy as np
+import pytest
+
+from tests import indep_collision as ic
+from tests.common import perturbed_table
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def torch_cuda(built):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
+    return torch
+
+
+def _kernel_contacts_checked(torch, tab, Q, what):
+    """mcg_debug_contacts of an engine on `tab` at the states Q against the exact rule, geom poses from the oracle's kinematics of `tab`."""
+    from oracle import pyoracle as po
+    from mycobotgym_amd import MyCobotVecEnv
+    from mycobotgym_amd.model.mjcf import _np_model
+    from mycobotgym_amd.model.specialize import specialize
+    n = len(Q)
+    spec = specialize(_np_model(tab))
+    envs = MyCobotVecEnv(n, has_object=True, controller_type="joint", reward_type="dense", seed=0, table=tab)
+    envs.reset(seed=0)
+    st = envs.get_state()
+    st["qpos"] = torch.as_tensor(Q.T.copy(), device="cuda"); st["qvel"] = torch.zeros_like(st["qvel"])
+    envs.set_state(**st)
+    kc = {k: v.cpu().numpy() for k, v in envs.debug_contacts().items()}
+    envs.close()
+    d = po.OracleData(po.OracleModel(tab, enable_contact=False))
+    stats = {}; checked = 0; types = set()
+    nb, ng = tab["nbody"], tab["ngeom"]
+    for i in range(n):
+        if kc["dropped"][i] > 0:
+            continue                                      # the cap cut this list: its tail is missing by construction
+        d.set_state(qpos=Q[i], qvel=np.zeros(18)); d.forward()
+        sc = ic.Scene(tab, spec, d.get("xpos", (nb, 3)), d.get("xmat", (nb, 9)), d.get("geom_xpos", (ng, 3)), d.get("geom_xmat", (ng, 9)))
+        ic.check_scene(sc, ic.kernel_contacts(kc["count"][i], kc["dist"][i], kc["pos"][i], kc["normal"][i], kc["type"][i]), stats, f"{what} env {i}")
+        checked += 1
+        types |= set(int(t) for t in kc["type"][i][:kc["count"][i]])
+    print(f"\n{what}: {checked} environments checked ({n - checked} cut by the cap), pair types seen {sorted(types)}; " + ic.summarize(stats))
+    return checked, types
+
+
+def test_kernel_contacts_on_the_perturbed_model_against_the_exact_rule(torch_cuda):
+    """The flange and the gripper base (polytopes moved by the spacer), the pads (grown) and the cube (grown, on a raised table)."""
+    from tests.test_gpu_pickandplace import _contact_poses, _finger_mesh_poses, _link_cube_poses
+    tab = perturbed_table("mycobot280")
+    q0 = np.array(tab["qpos0"], float)
+    out = []
+    for kind, cnt, seed in (("pad", 48, 0), ("mesh", 96, 1), ("gripper_mesh", 32, 3)):
+        for p in _contact_poses(kind, cnt, seed=seed, table=tab):
+            q = q0.copy(); q[:12] = p[:12]; out.append(q)
+    out += list(_finger_mesh_poses(48, table=tab))
+    out += list(_finger_mesh_poses(48, seed=4, meshes=("gripper_base",), table=tab))
+    out += list(_finger_mesh_poses(32, seed=8, meshes=("right_gear_link", "left_gear_link", "right_hinge_link", "left_hinge_link"), table=tab))
+    out += list(_link_cube_poses(48, meshes=("link5", "link6", "flange"), table=tab))
+    Q = np.array(out)
+    checked, types = _kernel_contacts_checked(torch_cuda, tab, Q, "perturbed model, kernel contact lists against the exact rule")
+    assert checked > 0.8 * len(Q)
+    assert {0, 1, 2}.issubset(types) and (types & {3, 4}) and (types & {28, 30}), sorted(types)
+    assert {11, 12, 25, 26}.issubset(types), sorted(types)          # flange and gripper base on the table and on the cube
+
+
+def _gate_poses(tab, count=32, seed=0):
+    """Contact poses of the gripper's gated parts (pads, gear / finger / hinge links) at the broad-phase gates: rejection-sampled arm poses
+    (finger joints over their whole ranges: the farthest the gripper reaches) with a shallow contact of such a part on the table / the ground
+    or on the cube, the decile whose link6 origin is farthest from the table box or the ground (GATE_STATIC_REACH) or from the cube centre
+    (GATE_CUBE_REACH), each then walked away from it while the contact holds.  Returns (poses, their static and cube gate distances)."""
+    from oracle import pyoracle as po
+    scope = tab["geom_name"].index("object0")
+    d = po.OracleData(po.OracleModel(tab, enable_contact=True, scope_geom=scope))
+    grip = {g for g in range(tab["ngeom"]) if (tab["geom_type"][g] == 7 and any(k in tab["geom_mesh"][g] for k in ("gear", "finger", "hinge")))
+            or tab["geom_name"][g] in ("right_finger_layer", "left_finger_layer")}
+    l6, nb = tab["body_name"].index("link6"), tab["nbody"]
+    tp = np.asarray(tab["body_pos"][1]) + np.asarray(tab["geom_pos"][1]); th = np.asarray(tab["geom_size"][1])
+    jr = np.asarray(tab["jnt_range"])
+
+    def gate(q, on_cube):
+        """Distance of the link6 origin to what a gated part touches (None: no such shallow contact)."""
+        d.set_state(qpos=q, qvel=np.zeros(18)); d.forward()
+        n = int(d.get("ncon", (1,), np.int32)[0]); raw = d.get("contact", (64, 28))
+        if n == 0 or raw[:n, 0].min() <= -2e-3: return None
+        ids = [raw[c, 26:28].copy().view(np.int32) for c in range(n)]
+        p = d.get("xpos", (nb, 3))[l6]
+        if on_cube:
+            if not any(int(i[1]) in grip and int(i[2]) == scope for i in ids): return None
+            return float(np.linalg.norm(p - q[12:15]))
+        if not any(int(i[2]) in grip and int(i[1]) != scope and int(i[1]) not in grip for i in ids): return None
+        return float(min(np.linalg.norm(np.maximum(np.abs(p - tp) - th, 0)), p[2]))
+
+    rng = np.random.default_rng(seed)
+    q0 = np.array(tab["qpos0"], float)
+    def draw():
+        q = q0.copy(); q[:6] = rng.uniform(-2.5, 2.5, 6); q[6] = q[8] = rng.uniform(0, 0.7)
+        q[7], q[9] = rng.uniform(jr[7, 0], jr[7, 1]), rng.uniform(jr[9, 0], jr[9, 1])
+        return q
+    found = {False: [], True: []}
+    while len(found[False]) < 10 * count // 2:
+        q = draw(); g = gate(q, False)
+        if g is not None: found[False].append((g, q))
+    from tests.test_gpu_pickandplace import _link_cube_poses
+    for q in _link_cube_poses(10 * count // 2, seed=seed + 1, table=tab,
+                              meshes=("right_gear_link", "right_finger_link", "left_gear_link", "left_finger_link", "right_hinge_link", "left_hinge_link")):
+        g = gate(q, True)
+        if g is not None: found[True].append((g, q))
+    poses, dist = [], {False: [], True: []}
+    for on_cube in (False, True):
+        top = sorted(found[on_cube], key=lambda x: -x[0])[:max(1, len(found[on_cube]) // 10)]
+        for g, q in top:
+            for _ in range(200):                 # walk away from the gate's reference while the gated part still touches
+                q2 = q.copy(); q2[:6] += rng.normal(0, 0.02, 6)
+                q2[7] = np.clip(q2[7] + rng.normal(0, 0.05), *jr[7]); q2[9] = np.clip(q2[9] + rng.normal(0, 0.05), *jr[9])
+                g2 = gate(q2, on_cube)
+                if g2 is not None and g2 > g: g, q = g2, q2
+            poses.append(q); dist[on_cube].append(g)
+    return np.array(poses), np.array(dist[False]), np.array(dist[True])
+
+
+def test_contacts_at_the_broad_phase_gates(torch_cuda):
+    """The grown gripper (5 mm spacer, larger pads) in contact as far from the table / the ground / the cube as it reaches: the kernels'
+    literal gates must still let these pairs through (a missed overlap fails the exact rule)."""
+    tab = perturbed_table("mycobot280")
+    Q, ds, dc = _gate_poses(tab)
+    print(f"\nposes at the gates: link6 origin to the table / ground {np.sort(ds)[::-1][:4]} .. {ds.min():.4f} (gate 0.17), "
+          f"to the cube centre {np.sort(dc)[::-1][:4]} .. {dc.min():.4f} (gate 0.2)")
+    checked, types = _kernel_contacts_checked(torch_cuda, tab, Q, "poses at the broad-phase gates")
+    assert checked == len(Q) and len(ds) >= 8 and len(dc) >= 8
+    assert ds.max() > 0.15 and dc.max() > 0.16                       # measured 0.156 and 0.169: within 1.5 cm and 3.1 cm of the gates
+
+
+def _prepare_full(poses):
+    def prepare(ora):
+        s = ora.get_state()
+        s["qpos"][:] = poses; s["qpos_lag"] = s["qpos"].copy()
+        s["ctrl"][:, :6] = poses[:, :6]; s["ctrl"][:, 6] = poses[:, 6] / 0.7
+        ora.set_state(**s)
+    return prepare
+
+
+@pytest.mark.parametrize("case", ["pads", "meshes", "gripper_base_on_cube", "fingers_on_cube"])
+def test_substeps_on_the_perturbed_model(torch_cuda, case):
+    """Teacher-forced per-sub-step parity on the perturbed PickAndPlace model: pads and meshes on the table and the ground (the flange and
+    the gripper base among them), the gripper base and the finger links on the cube.  Bounds of test_gpu_pickandplace.py."""
+    from tests.test_gpu_pickandplace import _contact_poses, _finger_mesh_poses, _pose_prepare, _substep_run
+    tab = perturbed_table("mycobot280")
+    if case == "pads":
+        prep = _pose_prepare(_contact_poses("pad", table=tab))
+    elif case == "meshes":
+        prep = _pose_prepare(_contact_poses("mesh", seed=1, table=tab))
+    elif case == "gripper_base_on_cube":
+        prep = _prepare_full(_finger_mesh_poses(count=128, seed=4, meshes=("gripper_base",), table=tab))
+    else:
+        prep = _prepare_full(_finger_mesh_poses(count=128, table=tab))
+    worst, ncon = _substep_run(torch_cuda, 128, 200, prepare=prep, hold_pose=True, table=tab)
+    print(f"\nperturbed model, {case}, 200 sub-steps x 128 envs: {worst}, contact counts seen {sorted(ncon)}")
+    assert max(ncon) >= 2
+    assert worst["obs"] < 1e-10 and worst["qpos"] < 1e-10 and worst["qvel"] < 1e-6
+
+
+def test_mocap_substeps_on_the_perturbed_model(torch_cuda):
+    """PickAndPlace + mocap on the perturbed mocap model (weld point moved by the spacer): bounds of test_mocap_with_object_substeps."""
+    from tests.common import make_pair, sync_oracle_to, step_errors
+    from tests.test_gpu_mocap import _actions
+    n = 128
+    envs, ora = make_pair(n, table=perturbed_table("mycobot280_mocap"), has_object=True, controller_type="mocap", reward_type="dense",
+                          seed=9, frame_skip=1, max_episode_steps=10 ** 9)
+    envs.reset(seed=9); ora.reset(seed=9)
+    rng = np.random.default_rng(5)
+    worst = 0.0
+    for t in range(10):
+        a = _actions(rng, n, 8)
+        for s in range(20):
+            sync_oracle_to(envs, ora)
+            e, flags_equal, o = step_errors(envs, ora, a)
+            assert flags_equal
+            worst = max(worst, e.max())
+    print(f"\nperturbed mocap + cube: 200 sub-steps x {n} envs from identical state: max obs err {worst:.2e}")
+    assert worst < 1e-12
+    envs.close()
+
+
+@pytest.mark.parametrize("name,has_object,controller", [("mycobot280_reach", False, "joint"), ("mycobot280", True, "joint"),
+                                                        ("mycobot280_reach", False, "IK")])
+def test_env_steps_on_the_perturbed_model(torch_cuda, name, has_object, controller):
+    """Whole env-steps (20 sub-steps; IK: 100) from identical state on the perturbed model: joint < 1e-8 in every env, IK within the
+    oracle's own sensitivity (as smoke() and test_gpu_parity.py)."""
+    from tests.common import make_pair, make_oracle, sync_oracle_to, step_errors, twin_errors, assert_within_oracle_sensitivity
+    n = 128
+    tab = perturbed_table(name)
+    kw = dict(has_object=has_object, controller_type=controller, reward_type="dense", seed=1)
+    envs, ora = make_pair(n, table=tab, **kw)
+    twin = make_oracle(n, table=tab, **kw) if controller == "IK" else None
+    envs.reset(seed=1); ora.reset(seed=1)
+    if twin: twin.reset(seed=1)
+    rng = np.random.default_rng(42); prng = np.random.default_rng(7)
+    errs, terrs = [], []
+    for t in range(30):
+        sync_oracle_to(envs, ora)
+        state = ora.get_state()
+        a = rng.uniform(-1, 1, (n, envs.action_dim)).astype(np.float32)
+        e, flags_equal, o = step_errors(envs, ora, a)
+        assert flags_equal
+        errs.append(e)
+        if twin: terrs.append(twin_errors(twin, state, a, o, prng))
+    envs.close()
+    if twin:
+        assert_within_oracle_sensitivity(errs, terrs, f"[perturbed {name} IK env-step]")
+        return
+    worst = float(np.concatenate(errs).max())
+    print(f"\nperturbed {name} {controller}: 30 env-steps x {n} envs from identical state, worst error {worst:.2e}")
+    assert worst < 1e-8
+
+
+@pytest.mark.parametrize("controller", ["joint", "IK"])
+def test_reset_on_the_perturbed_model(torch_cuda, controller):
+    """Reset draws on the perturbed PickAndPlace model, bit-exact against an oracle configured from the table's own initial state as the
+    oracle's kinematics give it (EEF site at qpos0, z of site object0) -- not from vec_env.initial_state."""
+    from oracle import pyoracle as po
+    from mycobotgym_amd import MyCobotVecEnv
+    from tests.common import make_oracle
+    tab = perturbed_table("mycobot280")
+    d = po.OracleData(po.OracleModel(tab, enable_contact=False))
+    q0 = np.array(tab["qpos0"], float)
+    d.set_state(qpos=q0, qvel=np.zeros(18)); d.forward()
+    sx = d.get("site_xpos", (tab["nsite"], 3))
+    igx, height = sx[tab["site_name"].index("EEF")].copy(), float(sx[tab["site_name"].index("object0")][2])
+    n = 512
+    kw = dict(has_object=True, controller_type=controller, reward_type="dense", seed=21)
+    envs = MyCobotVecEnv(n, table=tab, **kw)
+    ora = make_oracle(n, table=tab, initial=(q0, np.zeros(18), np.zeros(7), igx, height), **kw)
+    obs, _ = envs.reset(seed=21)
+    o_obs, o_ag, o_dg = ora.reset(seed=21)
+    print(f"\nperturbed reset ({controller}): gripper start {igx} / height {height:.6f} (engine: {envs.initial_gripper_xpos} / "
+          f"{envs.height_offset:.6f}); max obs error {np.abs(obs['observation'].cpu().numpy() - o_obs).max():.1e}")
+    assert np.array_equal(obs["desired_goal"].cpu().numpy(), o_dg)
+    assert np.array_equal(obs["achieved_goal"].cpu().numpy(), o_ag)             # cube xy from the same Philox draws, z on the raised table
+    assert np.abs(obs["observation"].cpu().numpy() - o_obs).max() < 1e-14
+    assert np.all(o_ag[:, 2] == height) and abs(height - 0.216) < 1e-12
+    envs.close()
+
+
+@pytest.mark.parametrize("controller", ["joint", "mocap"])
+def test_built_in_table_equals_the_default_engine(torch_cuda, controller):
+    """Control: MyCobotVecEnv(table=<the built-in table>) is MyCobotVecEnv() bit for bit over 20 env-steps (PickAndPlace)."""
+    torch = torch_cuda
+    from mycobotgym_amd import MyCobotVecEnv
+    from mycobotgym_amd.vec_env import load_table
+    n = 256
+    kw = dict(has_object=True, controller_type=controller, reward_type="dense", seed=4)
+    a_env = MyCobotVecEnv(n, **kw)
+    b_env = MyCobotVecEnv(n, table=load_table(True, mocap=controller == "mocap"), **kw)
+    oa, _ = a_env.reset(seed=4); ob, _ = b_env.reset(seed=4)
+    g = torch.Generator(device="cuda"); g.manual_seed(0)
+    for t in range(20):
+        for k in oa:
+            assert torch.equal(oa[k], ob[k]), (t, k)
+        act = torch.rand(n, a_env.action_dim, device="cuda", generator=g) * 2 - 1
+        oa, ra, _, _, _ = a_env.step(act); ob, rb, _, _, _ = b_env.step(act)
+        assert torch.equal(ra, rb), t
+    sa, sb = a_env.get_state(), b_env.get_state()
+    for k in ("qpos", "qvel", "ctrl", "warm"):
+        assert torch.equal(sa[k], sb[k]), k
+    a_env.close(); b_env.close()

@@ -29,10 +29,10 @@ def test_reset_bit_exact_with_object(torch_cuda, controller):
     envs.close()
 
 
-def _substep_run(torch, n, steps, prepare=None, seed=5, hold_pose=False):
+def _substep_run(torch, n, steps, prepare=None, seed=5, hold_pose=False, table=None):
     from tests.common import make_pair, sync_oracle_to, step_errors
     kw = dict(has_object=True, controller_type="joint", reward_type="dense", seed=seed, frame_skip=1, max_episode_steps=10 ** 9)
-    envs, ora = make_pair(n, **kw)
+    envs, ora = make_pair(n, table=table, **kw)
     envs.reset(seed=seed); ora.reset(seed=seed)
     if prepare is not None:
         prepare(ora)
@@ -103,13 +103,13 @@ def MyCobotVecEnvRest(torch, rule):
     return float((0.21 - z).mean())
 
 
-def _contact_poses(kind, count=128, seed=0):
+def _contact_poses(kind, count=128, seed=0, table=None):
     """Rejection-sampled arm poses (cube at rest on the table) with a SHALLOW contact of the wanted kind (a deep one is a violent
     state).  kind "pad": a finger pad on the table / the ground, no mesh contact; kind "mesh": a mesh geom of the arm or the gripper (collision
-    polytope, condim 3: 4 rows) on the table / the ground."""
+    polytope, condim 3: 4 rows) on the table / the ground.  `table`: another model table than the built-in one."""
     from tests.common import load_json
     from oracle import pyoracle as po
-    tab = load_json("mycobot280")
+    tab = table if table is not None else load_json("mycobot280")
     m = po.OracleModel(tab, enable_contact=True, scope_geom=tab["geom_name"].index("object0"))
     d = po.OracleData(m)
     rng = np.random.default_rng(seed)
@@ -276,17 +276,21 @@ def test_whole_env_step_from_random_policy_states(torch_cuda):
     envs.close()
 
 
-def _finger_mesh_poses(count=128, seed=2, meshes=("right_finger_link", "left_finger_link")):
+def _finger_mesh_poses(count=128, seed=2, meshes=("right_finger_link", "left_finger_link"), table=None):
     """Gripper poses around the cube (the scripted-grasp states, perturbed) in which the polytope of one of `meshes` touches the
-    cube (the oracle's contact list names the geoms); shallow contacts only (a deep one is a violent state)."""
+    cube (the oracle's contact list names the geoms); shallow contacts only (a deep one is a violent state).  `table`: another model
+    table than the built-in one (the cube of the grasp states moved to its rest height there)."""
     from tests.common import load_json
     from oracle import pyoracle as po
     from mycobotgym_amd.scenarios import grasp_state
-    tab = load_json("mycobot280")
+    builtin = load_json("mycobot280")
+    tab = table if table is not None else builtin
     scope = tab["geom_name"].index("object0")
     d1 = po.OracleData(po.OracleModel(tab, enable_contact=True, scope_geom=scope))
     geoms = {g for g in range(tab["ngeom"]) if tab["geom_type"][g] == 7 and tab["geom_mesh"][g] in meshes}
     q0 = np.asarray(grasp_state(64, seed=0)["qpos"]); q0 = q0.T if q0.shape[0] == 19 else q0
+    if table is not None:
+        q0 = q0.copy(); q0[:, 14] += tab["qpos0"][14] - builtin["qpos0"][14]
     rng = np.random.default_rng(seed)
     poses = []
     while len(poses) < count:
@@ -299,12 +303,13 @@ def _finger_mesh_poses(count=128, seed=2, meshes=("right_finger_link", "left_fin
     return np.array(poses)
 
 
-def _link_cube_poses(count=128, seed=6, meshes=("link2", "link3", "link4", "link5", "link6", "flange")):
+def _link_cube_poses(count=128, seed=6, meshes=("link2", "link3", "link4", "link5", "link6", "flange"), table=None):
     """Random arm poses with the cube put (in the air or on the table) where it just touches one of the arm's links: the pairs an arm
-    link sweeping the cube off the table goes through.  Shallow contacts only."""
+    link sweeping the cube off the table goes through.  Shallow contacts only.  `table`: another model table than the built-in one."""
     from tests.common import load_json
     from oracle import pyoracle as po
-    tab = load_json("mycobot280")
+    tab = table if table is not None else load_json("mycobot280")
+    zmin = 0.215 if table is None else tab["qpos0"][14] + 0.005              # the cube clear of the table top
     scope = tab["geom_name"].index("object0")
     d1 = po.OracleData(po.OracleModel(tab, enable_contact=True, scope_geom=scope))
     geoms = [g for g in range(tab["ngeom"]) if tab["geom_type"][g] == 7 and tab["geom_mesh"][g] in meshes]
@@ -323,7 +328,7 @@ def _link_cube_poses(count=128, seed=6, meshes=("link2", "link3", "link4", "link
         for r in np.linspace(0.09, 0.0, 46):                                    # walk the cube in until it touches
             q[12:15] = ctr + r * dirn
             quat = rng.normal(size=4); q[15:19] = quat / np.linalg.norm(quat)
-            if q[14] < 0.215: break
+            if q[14] < zmin: break
             d1.set_state(qpos=q, qvel=np.zeros(18)); d1.forward()
             n1 = int(d1.get("ncon", (1,), np.int32)[0])
             if n1 == 0: continue
