@@ -41,7 +41,8 @@ constexpr real MINVAL = 1e-15, MINIMP = 1e-4, MAXIMP = 0.9999;
 enum { ST_LOAD = 0, ST_CTRL, ST_TRIG, ST_RNE, ST_ACT, ST_CRB, ST_ROWS, ST_G0, ST_NEWTON, ST_EULER, ST_COLLIDE, ST_CUBE,
        ST_COUPLED, ST_CUBE_FIN, ST_POST, ST_N_BUILD, ST_N_FACTOR, ST_N_SOLVE, ST_N_CHECK, ST_E_RHS, ST_R_AX5, ST_R_CONNECT, ST_R_LIMITS, ST_C_MASK, ST_C_ASSEMBLE, ST_C_SCHUR, ST_C_SOLVE, ST_C_CHECK, ST_C_LS, ST_W2_WAIT1, ST_W2_COLLIDE, ST_W2_CUBE, ST_W2_WAIT2, ST_W1_WAIT, ST_A_ENTRY, ST_A_G, ST_A_TWIST, ST_A_LOOP, ST_A_MAP, ST_A_STORE,
        ST_CO_SETUP, ST_CO_ROWS, ST_CO_H0, ST_CO_RESID, ST_CO_ASM, ST_CO_FACTOR, ST_CO_SOLVE, ST_CO_CHECK, ST_CO_LS, ST_CO_OUT, ST_CO_IDLE,
-       ST_X_S1C, ST_X_NUMBERS, ST_X_S2, ST_S_S1B, ST_S_MESH, ST_S_S1C, ST_S_NUMBERS, ST_COUNT,
+       ST_X_S1C, ST_X_NUMBERS, ST_X_S2, ST_S_S1B, ST_S_MESH, ST_S_S1C, ST_S_NUMBERS,
+       ST_M_S2B, ST_H_S1, ST_H_CRB, ST_H_S2, ST_H_FACTOR, ST_H_S3, ST_Q_S1, ST_Q_BIAS, ST_Q_S2, ST_Q_COLS, ST_Q_S3, ST_COUNT,
        CN_SUBSTEP = 0, CN_NEWTON_IT, CN_LINESEARCH, CN_CUBE_IT, CN_CUBE_LS, CN_COUPLED, CN_COUPLED_IT, CN_COUPLED_LS, CN_CONTACTS, CN_COOP_ROWS, CN_COOP_LSEVAL, CN_COOP_LONG, CN_COOP_CAP, CN_COOP_12, CN_G_FAILED, CN_G_LIM, CN_G_STAT, CN_G_CUBE, CN_G_MISSING, CN_G_EXTRA, CN_G_EQ1, CN_G_EQ2, CN_G_EQ2N1, CN_MP_PAIRS, CN_MP_HITS, CN_MP_FACE, CN_MP_EXIT_B, CN_MP_EXIT_P, CN_MP_EXIT_E, CN_MP_KIND_E, CN_MP_KIND_P, CN_MP_CUBE, CN_COUNT };
 #ifdef MCG_STAGE_CLOCKS
 __device__ unsigned long long g_stage_clocks[ST_COUNT + CN_COUNT];      // stage clocks, then event counts (summed over waves)
@@ -279,6 +280,44 @@ MCG_DEV void ldl_solve(const real* A, const real* dinv, real* x) {
     static_for<k>([&](auto Ii) { constexpr int i = Ii; if constexpr (PT.nz[k][i]) x[k] = fma(-A[tri(k, i)], x[i], x[k]); });
   });
 }
+// Structure of ldl_solve<PT> on x = e_J: is x[i] structurally nonzero when the forward pass reaches row k (rows NB-1 .. k+1 done;
+// k = -1: after the whole pass), and in the backward pass when row k has taken columns 0 .. c-1 (c = k: row k done)?
+constexpr bool unit_fwd_nz(const Pattern& P, int J, int k, int i) {
+  bool z[NB] = {};
+  z[J] = true;
+  for (int r = NB - 1; r > k; r--) if (z[r]) for (int c = 0; c < r; c++) if (P.nz[r][c]) z[c] = true;
+  return z[i];
+}
+constexpr bool unit_bwd_nz(const Pattern& P, int J, int k, int c) {
+  bool z[NB] = {};
+  for (int i = 0; i < NB; i++) z[i] = unit_fwd_nz(P, J, -1, i);
+  for (int r = 0; r <= k; r++) for (int i = 0; i < (r == k ? c : r); i++) if (P.nz[r][i] && z[i]) z[r] = true;
+  return z[k];
+}
+// x = A^-1 e_J: ldl_solve<PT> with the terms on structural zeros of x left out.  Each value is the one ldl_solve computes from the
+// unit right-hand side, up to the sign of a zero (fma(-a, b, 0) is written -a * b; fma(-a, 0, c) is c).
+template <const Pattern& PT, int J>
+MCG_DEV void ldl_solve_unit(const real* A, const real* dinv, real* x) {
+  static_for<NB>([&](auto I) { constexpr int i = I; x[i] = (i == J) ? 1.0 : 0.0; });
+  static_for<NB>([&](auto Kk) {
+    constexpr int k = NB - 1 - Kk;
+    if constexpr (unit_fwd_nz(PT, J, k, k))
+      static_for<k>([&](auto Ii) { constexpr int i = Ii;
+        if constexpr (PT.nz[k][i]) {
+          if constexpr (unit_fwd_nz(PT, J, k, i)) x[i] = fma(-A[tri(k, i)], x[k], x[i]);
+          else x[i] = -A[tri(k, i)] * x[k];
+        } });
+  });
+  static_for<NB>([&](auto Kk) { constexpr int k = Kk; if constexpr (unit_fwd_nz(PT, J, -1, k)) x[k] *= dinv[k]; });
+  static_for<NB>([&](auto Kk) {
+    constexpr int k = Kk;
+    static_for<k>([&](auto Ii) { constexpr int i = Ii;
+      if constexpr (PT.nz[k][i] && unit_bwd_nz(PT, J, i, i)) {
+        if constexpr (unit_bwd_nz(PT, J, k, i)) x[k] = fma(-A[tri(k, i)], x[i], x[k]);
+        else x[k] = -A[tri(k, i)] * x[i];
+      } });
+  });
+}
 
 // dense SPD solve by L D L^T with reciprocals (no square roots, no IEEE divisions): the cube's 6x6 Newton systems
 template <int N>
@@ -358,7 +397,12 @@ constexpr int LDS_HEQ = NB * (NB + 1) / 2;            // H_eq = M + J^T D J over
 constexpr int LDS_SLOTS = 2 * (NB * (NB + 1) / 2);
 // two-wave variant (SplitA / helper_substep): factor of M + hB, its reciprocal pivots, and q published for the helper wave
 constexpr int LDS_FAC = LDS_SLOTS, LDS_FDINV = LDS_FAC + NB * (NB + 1) / 2, LDS_QB = LDS_FDINV + NB, LDS_QDB = LDS_QB + NB;
-constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM + NB, LDS_IKT = LDS_QLAG + 6, LDS_SLOTS_SPLIT = LDS_IKT + 8;      // LDS_WARM: qacc_warmstart parked between sub-steps; LDS_QLAG: q of the last forward pass; LDS_IKT: the IK controller's six ctrl increments of a control step, handed from the RNE wave to the main wave (two slots spare)
+constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM + NB, LDS_IKT = LDS_QLAG + 6;      // LDS_WARM: qacc_warmstart parked between sub-steps; LDS_QLAG: q of the last forward pass; LDS_IKT: the IK controller's six ctrl increments of a control step, handed from the RNE wave to the main wave (two slots spare)
+// The columns z6 = H^-1 e_6, z8 = H^-1 e_8 of the closed-form limit solve, handed from the RNE wave to the main wave between S2 and S2b
+// (SplitMain::limit_cols).  z6 lives in the warm-start slots: only the general iteration reads those, a sub-step that takes S2b never
+// runs it, and the Euler step after S3 writes them again.  z8 has slots of its own.
+constexpr int LDS_Z6 = LDS_WARM, LDS_Z8 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_Z8 + NB;
+static_assert(LDS_SLOTS_SPLIT * 64 * sizeof(real) <= 160 * 1024, "the split Reach kernel's LDS exceeds the 160 KB of a gfx950 workgroup");
 // The lane's LDS column.  The pointer carries the LDS address space explicitly: passed through structs as a generic
 // pointer the accesses degrade to flat_load/flat_store with 64-bit address arithmetic instead of ds_read/ds_write
 // with immediate offsets.
@@ -605,9 +649,10 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // has two more waves over the same 64 environments.  The HELPER wave computes what depends on the joint angles alone -- M by
 // the composite rigid body pass, then the L^T D L factor of M + hB for the Euler step; the RNE wave computes the bias forces;
 // the main wave does actuation and constraint rows meanwhile, then H_eq, the Newton solve and the Euler step.  Three workgroup
-// barriers per sub-step:
+// barriers per sub-step, four when the wave's only limit rows are the gear joints':
 //   S1  q(t), qd(t) are published in LDS      (the other waves may read them)
 //   S2  M(t) and passive - bias are in LDS    (main wave: g0, H_eq, Newton solve)
+//   S2b the columns z6, z8 are in LDS         (main wave: the closed-form limit solve; see limit_cols)
 //   S3  the factor of M + hB is in LDS        (main wave: a' = a - h (M + hB)^-1 (B a), which equals (M + hB)^-1 M a)
 // A split policy says which pieces other waves provide and where the exchange slots are.
 // early_heq: the J^T D J part of H_eq is assembled (and the constraint part of g0 formed) BEFORE barrier S2, while the main wave
@@ -616,10 +661,63 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // read it; only the rare general iteration does -- but in registers it stays live through the factorisation, the kernel's register peak.
 // With it the Euler step also re-reads q(t), qd(t) from the slots they were published in for the other waves (QB, QDB) instead of
 // carrying them through the solve, and the lagged configuration (q of this forward pass, for observations and IK) goes to slots QLAG.
-struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false;
+// limit_cols: when the only violated limit rows of the wave are the gear joints' (6, 8: every fresh episode starts on them), the RNE
+// wave, idle after S2, factors the same H_eq and solves for the closed-form solve's two columns z6, z8 while the main wave factors and
+// solves for abar; a fourth barrier, S2b, hands them over.  Every wave decides from the q slots whether to take S2b (gear_rows_only).
+struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, limit_cols = false;
                  static constexpr int QB = 0, QDB = 0, FS = 0, WARM = 0, QLAG = 0; };
-struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false;
+struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, limit_cols = true;
                    static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
+// The IK and mocap kernels keep the three barriers: measured with S2b, both were ~1 % slower (profiles/r05/ab_quick_all_controllers.log).
+struct SplitMainNoCols : SplitMain { static constexpr bool limit_cols = false; };
+
+// H_eq + M (the equality rows' system, from LDS) plus D on the diagonal of the limit rows in act_.  One function for every wave that
+// factors it: the RNE wave's columns (limit_cols) must come from the very same L and dinv as the main wave's solve.
+template <class SPL, class LS>
+MCG_DEV void build_H(const LS MS, real* H, const bool* act_, const real* Dl) {
+  static_for<NB>([&](auto I) { constexpr int i = I;
+    static_for<i + 1>([&](auto Jj) { constexpr int j = Jj;
+      if constexpr (PAT_E.nz[i][j]) {
+        H[tri(i, j)] = MS.ld(LDS_HEQ + tri(i, j));
+        if constexpr (SPL::early_heq && PAT_M.nz[i][j]) H[tri(i, j)] += MS.ld(LDS_M + tri(i, j));
+      } else if constexpr (PAT_H.nz[i][j]) H[tri(i, j)] = 0.0; }); });
+  static_for<10>([&](auto I) { constexpr int j = I; H[tri(j, j)] += act_[j] ? Dl[j] : 0.0; });
+}
+
+// Barrier S2b is taken by a wave (all three of the workgroup: they cover the same lanes and read the same q) when some lane has a
+// violated limit row on a gear joint and no lane one on any other joint.  Same compares as the limit rows of robot_substep.
+template <class SPL, class LS>
+MCG_DEV bool gear_rows_only(ModelPtr Pm, const LS MS) {
+  real jr[10][2];
+  { ModelPtr Q = launder(Pm); static_for<10>([&](auto I) { constexpr int j = I; jr[j][0] = Q->jnt_range[j][0]; jr[j][1] = Q->jnt_range[j][1]; }); }
+  bool gear = false, other = false;
+  static_for<10>([&](auto I) { constexpr int j = I;
+    const real q = MS.ld(SPL::QB + j);
+    const bool v = (q - jr[j][0] < 0) || (jr[j][1] - q < 0);
+    if constexpr (j == 6 || j == 8) gear = gear || v; else other = other || v; });
+  return __any(gear) && !__any(other);
+}
+
+// The closed-form solve's 2 x 2 complementarity problem over the limit rows in slots 0 and 1 (e0 / e1: the slot holds a row), enumerated
+// in closed form; returns the rows' forces times their signs, f = sg nu.
+MCG_DEV void limit_pair(bool e0, bool e1, real D0, real D1, real s0, real s1, real rb0, real rb1, real W00, real W01, real W11,
+                        real& f0, real& f1) {
+  const real A00 = rcp_nr(D0) + W00, A11 = rcp_nr(D1) + W11;
+  const real n0 = rb0 * rcp_nr(A00), n1 = rb1 * rcp_nr(A11);               // one active row
+  const real idet = rcp_nr(A00 * A11 - W01 * W01);                          // both active
+  const real b0 = (A11 * rb0 - W01 * rb1) * idet, b1 = (A00 * rb1 - W01 * rb0) * idet;
+  const bool cN = (!e0 || rb0 >= 0) && (!e1 || rb1 >= 0);
+  const bool cB = e0 && e1 && (b0 < 0) && (b1 < 0);
+  const bool c0 = e0 && (n0 < 0) && (!e1 || rb1 - W01 * n0 >= 0);
+  const bool c1 = e1 && (n1 < 0) && (rb0 - W01 * n1 >= 0);
+  // on a boundary (some r or nu within rounding of 0) two sets or none may pass: their solutions coincide there
+  real nu0 = e1 ? b0 : n0, nu1 = e1 ? b1 : 0.0;
+  nu0 = c1 ? 0.0 : nu0; nu1 = c1 ? n1 : nu1;
+  nu0 = c0 ? n0 : nu0;  nu1 = c0 ? 0.0 : nu1;
+  nu0 = cB ? b0 : nu0;  nu1 = cB ? b1 : nu1;
+  nu0 = cN ? 0.0 : nu0; nu1 = cN ? 0.0 : nu1;
+  f0 = s0 * nu0; f1 = s1 * nu1;
+}
 
 // COMMIT = false: the new q / qd / qacc_warmstart go to *next and S stays as it was (speculative sub-step of the two-wave
 // PickAndPlace kernel: discarded when the helper wave's collision pass finds a pad contact).
@@ -877,15 +975,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   static_for<NB>([&](auto I) { constexpr int i = I; g0[i] += fs[i]; });
   if constexpr (CPL::publishes) CP->publish(g0, Dl, arefl, sgl, S.qd, S.warm, !ahead);
   if constexpr (!SPL::early_heq) assemble_heq(std::true_type{});
-  auto build_H = [&](real* H, const bool* act_) {
-    static_for<NB>([&](auto I) { constexpr int i = I;
-      static_for<i + 1>([&](auto Jj) { constexpr int j = Jj;
-        if constexpr (PAT_E.nz[i][j]) {
-          H[tri(i, j)] = MS.ld(LDS_HEQ + tri(i, j));
-          if constexpr (SPL::early_heq && PAT_M.nz[i][j]) H[tri(i, j)] += MS.ld(LDS_M + tri(i, j));
-        } else if constexpr (PAT_H.nz[i][j]) H[tri(i, j)] = 0.0; }); });
-    static_for<10>([&](auto I) { constexpr int j = I; H[tri(j, j)] += act_[j] ? Dl[j] : 0.0; });
-  };
+  auto build_H = [&](real* H, const bool* act_) { mcg::build_H<SPL>(MS, H, act_, Dl); };
 
   MCG_TICK_PIN(g0, NB);
   MCG_TICK(ST_G0);
@@ -923,6 +1013,14 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     static_for<10>([&](auto I) { constexpr int j = I;
       const bool v = sgl[j] != 0;
       j1 = (v && nviol == 1) ? j : j1; j0 = (v && nviol == 0) ? j : j0; nviol += v ? 1 : 0; });
+    static_assert(!(SPL::limit_cols && CPL::enabled), "S2b is taken inside the direct solve, which a coupled solve would skip");
+    bool cols = false;                                       // barrier S2b (see gear_rows_only: the other waves decide from the q slots)
+    if constexpr (SPL::limit_cols) {
+      bool gear = false, other = false;
+      static_for<10>([&](auto I) { constexpr int j = I;
+        if constexpr (j == 6 || j == 8) gear = gear || (sgl[j] != 0); else other = other || (sgl[j] != 0); });
+      cols = __any(gear) && !__any(other);
+    }
     if (!conv && !__any(nviol > 2)) {                        // wave-uniform (conv is wave-uniform here)
       MCG_COUNT(CN_NEWTON_IT);
       real L[NB * (NB + 1) / 2], dinv[NB], x[NB];
@@ -938,7 +1036,28 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
       ldl_solve<PAT_H>(L, dinv, x);
       MCG_TICK_PIN(x, NB);
       MCG_TICK(ST_N_SOLVE);
-      if (__any(nviol > 0)) {
+      if (cols) {                                            // wave-uniform: only rows 6 and 8, in slots 0 / 1 as below
+        MCG_COUNT(CN_LINESEARCH);
+        MCG_TICK(ST_N_CHECK);
+        __syncthreads();                                     // S2b: the RNE wave's columns z6, z8 are in LDS
+        MCG_TICK(ST_M_S2B);
+        real z6[NB], z8[NB];
+        static_for<NB>([&](auto I) { constexpr int i = I; z6[i] = MS.ld(LDS_Z6 + i); z8[i] = MS.ld(LDS_Z8 + i); });
+        const bool v6 = sgl[6] != 0, v8 = sgl[8] != 0, both = v6 && v8;
+        const real D0 = v6 ? Dl[6] : (v8 ? Dl[8] : 1.0), D1 = both ? Dl[8] : 1.0;
+        const real ar0 = v6 ? arefl[6] : arefl[8], ar1 = both ? arefl[8] : 0.0;
+        const real s0 = v6 ? sgl[6] : sgl[8], s1 = both ? sgl[8] : 0.0;
+        const real xa0 = v6 ? x[6] : (v8 ? x[8] : 0.0), xa1 = both ? x[8] : 0.0;
+        real W00 = v6 ? z6[6] : (v8 ? z8[8] : 0.0), W01 = both ? z6[8] : 0.0;
+        const real W11 = both ? z8[8] : 0.0;
+        W01 *= s0 * s1;
+        const real rb0 = s0 * xa0 - ar0, rb1 = s1 * xa1 - ar1;
+        real f0, f1;
+        limit_pair(v6 || v8, both, D0, D1, s0, s1, rb0, rb1, W00, W01, W11, f0, f1);
+        // slot 0 is row 6 where row 6 is violated, else row 8; the other column enters with a zero force (finite z: exactly x)
+        const real g6 = v6 ? f0 : 0.0, g8 = v6 ? f1 : f0;
+        static_for<NB>([&](auto I) { constexpr int i = I; x[i] = fma(-z8[i], g8, fma(-z6[i], g6, x[i])); });
+      } else if (__any(nviol > 0)) {
         MCG_COUNT(CN_LINESEARCH);                            // counted in the old line search's slot: "sub-steps with limit rows"
         real D0 = 1, D1 = 1, ar0 = 0, ar1 = 0, s0 = 0, s1 = 0, xa0 = 0, xa1 = 0;
         static_for<10>([&](auto I) { constexpr int j = I;
@@ -955,21 +1074,8 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
         W01 *= s0 * s1;
         const bool e0 = nviol > 0, e1 = nviol > 1;
         const real rb0 = s0 * xa0 - ar0, rb1 = s1 * xa1 - ar1;
-        const real A00 = rcp_nr(D0) + W00, A11 = rcp_nr(D1) + W11;
-        const real n0 = rb0 * rcp_nr(A00), n1 = rb1 * rcp_nr(A11);               // one active row
-        const real idet = rcp_nr(A00 * A11 - W01 * W01);                          // both active
-        const real b0 = (A11 * rb0 - W01 * rb1) * idet, b1 = (A00 * rb1 - W01 * rb0) * idet;
-        const bool cN = (!e0 || rb0 >= 0) && (!e1 || rb1 >= 0);
-        const bool cB = e0 && e1 && (b0 < 0) && (b1 < 0);
-        const bool c0 = e0 && (n0 < 0) && (!e1 || rb1 - W01 * n0 >= 0);
-        const bool c1 = e1 && (n1 < 0) && (rb0 - W01 * n1 >= 0);
-        // on a boundary (some r or nu within rounding of 0) two sets or none may pass: their solutions coincide there
-        real nu0 = e1 ? b0 : n0, nu1 = e1 ? b1 : 0.0;
-        nu0 = c1 ? 0.0 : nu0; nu1 = c1 ? n1 : nu1;
-        nu0 = c0 ? n0 : nu0;  nu1 = c0 ? 0.0 : nu1;
-        nu0 = cB ? b0 : nu0;  nu1 = cB ? b1 : nu1;
-        nu0 = cN ? 0.0 : nu0; nu1 = cN ? 0.0 : nu1;
-        const real f0 = s0 * nu0, f1 = s1 * nu1;
+        real f0, f1;
+        limit_pair(e0, e1, D0, D1, s0, s1, rb0, rb1, W00, W01, W11, f0, f1);
         static_for<NB>([&](auto I) { constexpr int i = I; x[i] = fma(-z1[i], f1, fma(-z0[i], f0, x[i])); });
       }
       static_for<NB>([&](auto I) { constexpr int i = I; a[i] = x[i]; });
@@ -1102,6 +1208,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
 template <class SPL = SplitMain, class LS, class SIDE = NoSideWork>
 MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   __syncthreads();                                                  // S1
+  MCG_TICK(ST_H_S1);
   real cs[NB], sn[NB];
   {
     const TrigC T = load_trig();
@@ -1110,9 +1217,13 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
   static_for<NB>([&](auto I) { constexpr int i = I; pin(sn[i]); pin(cs[i]); });
   MCG_FENCE();
   crb_to_lds(Pm, cs, sn, MS);
+  bool cols = false;
+  if constexpr (SPL::limit_cols) cols = gear_rows_only<SPL>(Pm, MS);
   static_assert(!SPL::mesh_split, "the four-wave PickAndPlace kernel drives its side waves itself: helper_pre / rne_pre");
   (void)side;
+  MCG_TICK(ST_H_CRB);
   __syncthreads();                                                  // S2
+  MCG_TICK(ST_H_S2);
   if constexpr (SPL::factor_remote) {
     const real h = launder(Pm)->timestep;
     real Mh[NB * (NB + 1) / 2], dinv[NB];
@@ -1122,7 +1233,10 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
     ldl_factor<PAT_M>(Mh, dinv);
     static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_FDINV + i, dinv[i]);
       static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) MS.st(LDS_FAC + tri(i, j), Mh[tri(i, j)]); }); });
+    MCG_TICK(ST_H_FACTOR);
+    if (cols) __syncthreads();                                      // S2b (wave-uniform)
     __syncthreads();                                                // S3
+    MCG_TICK(ST_H_S3);
   }
 }
 
@@ -1130,6 +1244,7 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
 template <class SPL = SplitMain, class LS, class SIDE = NoSideWork>
 MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   __syncthreads();                                                  // S1
+  MCG_TICK(ST_Q_S1);
   real cs[NB], sn[NB], qd[NB], fs[NB];
   {
     const TrigC T = load_trig();
@@ -1139,10 +1254,31 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   MCG_FENCE();
   rne_bias(Pm, cs, sn, qd, fs);
   static_for<NB>([&](auto I) { constexpr int i = I; MS.st(SPL::FS + i, fs[i]); });
+  bool cols = false;
+  if constexpr (SPL::limit_cols) cols = gear_rows_only<SPL>(Pm, MS);
   static_assert(!SPL::mesh_split, "the four-wave PickAndPlace kernel drives its side waves itself: helper_pre / rne_pre");
   (void)side;
+  MCG_TICK(ST_Q_BIAS);
   __syncthreads();                                                  // S2
+  MCG_TICK(ST_Q_S2);
+  if constexpr (SPL::limit_cols) {
+    if (cols) {                                                     // wave-uniform
+      // the main wave's H_eq + M (no limit row active), factored by the same code: the same L and dinv to the bit
+      real L[NB * (NB + 1) / 2], dinv[NB], z[NB];
+      const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
+      const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      build_H<SPL>(MS, L, none, zero);
+      ldl_factor<PAT_H>(L, dinv);
+      ldl_solve_unit<PAT_H, 6>(L, dinv, z);
+      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_Z6 + i, z[i]); });
+      ldl_solve_unit<PAT_H, 8>(L, dinv, z);
+      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_Z8 + i, z[i]); });
+      MCG_TICK(ST_Q_COLS);
+      __syncthreads();                                              // S2b
+    }
+  }
   if constexpr (SPL::factor_remote) __syncthreads();                // S3
+  MCG_TICK(ST_Q_S3);
 }
 
 // The same two shares for the four-wave PickAndPlace kernel, up to its barrier S1b: S1, the wave's own work (M into LDS / passive - bias

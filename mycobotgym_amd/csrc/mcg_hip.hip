@@ -191,11 +191,11 @@ MCG_DEV void mocap_target(const Cfg& C, ModelPtr P, const real* qlag6, const flo
 }
 
 // SPLIT: three waves per 64 environments (see SplitMain in mcg_dynamics.hpp): launched when the grid has at most one workgroup
-// per CU, where the extra waves run on SIMDs that would idle.  144 KB of LDS per workgroup.
+// per CU, where the extra waves run on SIMDs that would idle.  160 KB of LDS per workgroup (LDS_SLOTS_SPLIT).
 template <int CONTROLLER, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, View V, const mcg_model* __restrict__ Pg,
                                                                       const float* __restrict__ actions, mcg_step_out O) {
-  typedef std::conditional_t<SPLIT, SplitMain, NoSplit> Split;
+  typedef std::conditional_t<SPLIT, std::conditional_t<CONTROLLER == MCG_CTRL_JOINT, SplitMain, SplitMainNoCols>, NoSplit> Split;
   __shared__ real lds[SPLIT ? LDS_SLOTS_SPLIT : LDS_SLOTS][64];
   const int lane = threadIdx.x & 63;
   const LaneScratch MS(&lds[0][lane]);
@@ -204,6 +204,7 @@ __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, Vie
   if (i >= C.n) return;                          // the same lanes leave in both waves: barriers stay matched
   if constexpr (SPLIT) {
     if (threadIdx.x >= 64) {                     // helper wave: M and the Euler factor; RNE wave: passive - bias forces
+      MCG_TICK_INIT();
       if constexpr (CONTROLLER == MCG_CTRL_IK) {
         // The IK controller (S2 / S3: mycobot.py:134-170, utils.py:499-556) runs on the RNE wave: the main wave carries the robot's whole
         // state through the sub-step loop, and the controller's Jacobians and 6 x 6 solve on top of it were that kernel's scratch frame
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, Vie
         // solves and leaves the six increments in the LDS_IKT slots -- C2 -- the main wave adds them to its ctrl.  The target pose is
         // formed once from the first pose and stays in the RNE wave's registers; the helper wave only passes the two barriers.
         if (threadIdx.x < 128) {
-          for (int c = 0; c < C.control_steps; c++) { __syncthreads(); __syncthreads(); for (int s = 0; s < C.frame_skip; s++) helper_substep(P, MS); }
+          for (int c = 0; c < C.control_steps; c++) { __syncthreads(); __syncthreads(); for (int s = 0; s < C.frame_skip; s++) helper_substep<Split>(P, MS); }
         } else {
           float act[8];
           _Pragma("unroll") for (int k = 0; k < 8; k++) {
@@ -237,13 +238,13 @@ __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, Vie
             ik_delta(X, tpos, tquat, dq);
             for (int k = 0; k < 6; k++) MS.st(LDS_IKT + k, dq[k]);
             __syncthreads();                                        // C2
-            for (int s = 0; s < C.frame_skip; s++) rne_substep(P, MS);
+            for (int s = 0; s < C.frame_skip; s++) rne_substep<Split>(P, MS);
           }
         }
       } else {
         const int total = C.frame_skip;
-        if (threadIdx.x < 128) { for (int s = 0; s < total; s++) helper_substep(P, MS); }
-        else { for (int s = 0; s < total; s++) rne_substep(P, MS); }
+        if (threadIdx.x < 128) { for (int s = 0; s < total; s++) helper_substep<Split>(P, MS); }
+        else { for (int s = 0; s < total; s++) rne_substep<Split>(P, MS); }
       }
       return;
     }
@@ -514,7 +515,7 @@ constexpr int PNP_SLOTS_DUAL = PNP_SLOTS_LDS;
 static_assert(PNP_SLOTS_DUAL * PNP_LANES * 8 <= 160 * 1024, "LDS of a CU");
 // robot-side split of the four-wave PickAndPlace kernel: M from the helper wave, passive - bias from the RNE wave, the constraint
 // part of H_eq assembled before barrier S2; the Euler step stays with M a (no room for the factor in LDS)
-struct SplitPnp { static constexpr bool enabled = true, rne_remote = true, factor_remote = false, early_heq = true, warm_lds = false, mesh_split = true;
+struct SplitPnp { static constexpr bool enabled = true, rne_remote = true, factor_remote = false, early_heq = true, warm_lds = false, mesh_split = true, limit_cols = false;
                   static constexpr int QB = XCH_Q, QDB = XCH_QD, FS = XCH_FS, WARM = 0, QLAG = 0, MASK0 = MP_MASK; };
 
 MCG_DEV bool flag_coupled(real f) { return (((int)f) & 2) != 0; }       // XCH_FLAG: bit 1 = the environment goes to the cooperative solve,

@@ -6,6 +6,9 @@
     MCG_LIB=ab/clocks.so python tools/stage_clocks.py [--fresh-actions]
 
 Lane 0 of every wave accumulates s_memtime deltas per stage; the table is the sum over waves and launches.
+    --reach CTRL   Reach with controller CTRL (joint, IK, mocap) only
+    --desync       desynchronised episodes (per-env random initial elapsed in [0, 50), as bench.py)
+    --legacy       a library built before the helper / RNE wave stages of the split Reach kernel existed (shorter table)
 """
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -25,7 +28,11 @@ NAMES = ["load", "controller", "sincos", "rne", "actuation", "crb->M", "rows: we
          "coop: env data, twist columns", "coop: rows", "coop: H0, g0", "coop: residuals, active set", "coop: assembly (LDS window)",
          "coop: gradient + LDL", "coop: solves + transpose", "coop: consistency check", "coop: line search", "coop: hand back", "coop: idle at S5",
          "cube wave: waiting at S1c", "cube wave: flags + solver numbers", "cube wave: waiting at S2", "M / RNE waves: waiting at S1b", "M / RNE waves: mesh phase",
-         "M / RNE waves: waiting at S1c", "M / RNE waves: solver numbers"]
+         "M / RNE waves: waiting at S1c", "M / RNE waves: solver numbers",
+         "main wave: waiting at S2b", "helper wave: waiting for q (S1)", "helper wave: CRB -> M", "helper wave: waiting at S2",
+         "helper wave: factor M+hB", "helper wave: waiting at S2b / S3", "RNE wave: waiting for q (S1)", "RNE wave: bias forces",
+         "RNE wave: waiting at S2", "RNE wave: H, factor, columns z6 z8", "RNE wave: waiting at S2b / S3"]
+if "--legacy" in sys.argv: NAMES = NAMES[:58]
 COUNTS = ["robot sub-steps", "robot Newton iterations", "robot line searches", "cube Newton iterations", "cube line searches",
           "coupled solves", "coupled Newton iterations", "coupled line searches", "wave-max contacts (per collision pass)",
           "coop active rows (sum over iterations)", "coop line-search evaluations", "coop solves whose carried active set was confirmed at once", "coop solves at the 50-iteration cap", "coop solves that started from a carried active set",
@@ -41,9 +48,14 @@ L = _abi.load()
 n = 8192
 pnpik = "--pnp-ik" in sys.argv         # PickAndPlace, IK controller, random policy only
 pnpj = "--pnp-joint" in sys.argv       # PickAndPlace, joint controller, cube resting
-for obj, ctrl, k in (((True, "mocap", 40),) if mocap else ((True, "joint", 20),) if grasp else ((True, "IK", 20),) if pnpik else ((True, "joint", 100),) if pnpj else ((False, "joint", 200), (False, "IK", 50), (True, "joint", 100), (True, "IK", 20))):
+reach = sys.argv[sys.argv.index("--reach") + 1] if "--reach" in sys.argv else None
+desync = "--desync" in sys.argv
+for obj, ctrl, k in (((False, reach, {"joint": 200, "IK": 50, "mocap": 100}[reach]),) if reach else ((True, "mocap", 40),) if mocap else ((True, "joint", 20),) if grasp else ((True, "IK", 20),) if pnpik else ((True, "joint", 100),) if pnpj else ((False, "joint", 200), (False, "IK", 50), (True, "joint", 100), (True, "IK", 20))):
     envs = MyCobotVecEnv(n, has_object=obj, controller_type=ctrl, reward_type="dense", max_episode_steps=10 ** 9 if grasp else 50)
     envs.reset(seed=0)
+    if desync:
+        g0 = torch.Generator(device="cuda"); g0.manual_seed(99)
+        envs.set_state(elapsed=torch.randint(0, 50, (n,), device="cuda", generator=g0, dtype=torch.int32))
     a = torch.rand(n, envs.action_dim, device="cuda") * 2 - 1
     if grasp:
         from mycobotgym_amd.scenarios import grasp_state
@@ -59,9 +71,9 @@ for obj, ctrl, k in (((True, "mocap", 40),) if mocap else ((True, "joint", 20),)
     assert L.mcg_debug_stage_clocks(out, 1) == 0
     cnt = list(out)[len(NAMES):]; out = list(out)[:len(NAMES)]
     tot = sum(out); waves = n // (32 if obj else 64)
-    sub = (20 if ctrl == "joint" else 100)
-    print(f"{'pnp' if obj else 'reach'}-{ctrl}: {tot / waves / k / sub:.0f} clocks per wave per sub-step (all stages / sub-steps)")
+    sub = (100 if ctrl == "IK" else 20)
+    print(f"{'pnp' if obj else 'reach'}-{ctrl}{' (desynchronised)' if desync else ''}: {tot / waves / k / sub:.0f} clocks per wave per sub-step (all stages / sub-steps)")
     for nm, v in zip(NAMES, out):
         if v: print(f"   {nm:32s} {100.0 * v / tot:5.1f} %   {v / waves / k / sub:8.0f} clk/sub-step")
-    print("   per wave-sub-step: " + ", ".join(f"{nm} {v / max(cnt[0], 1):.2f}" for nm, v in zip(COUNTS[1:], cnt[1:])))
+    print(f"   per wave-sub-step: robot sub-steps {cnt[0] / (waves * k * sub):.2f} (per workgroup), " + ", ".join(f"{nm} {v / max(cnt[0], 1):.2f}" for nm, v in zip(COUNTS[1:], cnt[1:])))
     envs.close()
