@@ -213,6 +213,41 @@ int mcg_debug_contacts(mcg_env* env, int32_t* count, int32_t* dropped, double* d
 /* Live timing of the step kernel on its own stream with HIP events (used by bench.py's roofline leg). */
 int mcg_time_steps(mcg_env* env, const float* actions, const mcg_step_out* out, int steps, void* stream, float* ms_total);
 
+/* ---- Rendering (MyCobotImgEnv / render(): mycobot.py:308-311, 517-545; cameras, light, colours: mycobot280_main.xml:7, 78-102, 258-268).
+   A ray caster over the engine's own state: the ground plane, the table, cube and target boxes, and the fourteen mesh geoms as their
+   collision polytopes (face planes, within 1 mm of the convex hulls).  Flat Lambert shading per face:
+     rgb * (ambient + diffuse * max(0, n.(-light_dir)) + head_ambient + head_diffuse * max(0, n.(-ray))), clamped, to uint8 by round-half-up.
+   Not drawn: base_link, the mocap body's guide geoms, the EEF site, specular light, the visual meshes' concavities, the gripper camera. */
+typedef struct mcg_scene {   /* one camera + light + colours; all doubles */
+  double cam_pos[3];         /* world position of the camera */
+  double cam_mat[9];         /* row-major world <- camera; columns = the camera's x (right), y (up), z; it looks along -z */
+  double fovy;               /* vertical field of view, degrees, in (0, 180) */
+  double light_dir[3];       /* directional light: direction of travel (unit) */
+  double light_ambient, light_diffuse;
+  double head_ambient, head_diffuse;     /* headlight: travels along the ray */
+  double rgb_ground[3], rgb_table[3], rgb_cube[3], rgb_target[3], rgb_mesh[3], rgb_sky[3];     /* in [0, 1] */
+  double target_half[3];     /* half sizes of the target site's (world-aligned) box */
+} mcg_scene;
+
+typedef struct mcg_render_out {      /* device pointers, any may be NULL (not all) */
+  uint8_t* rgb;    /* [N, H, W, 3] */
+  uint8_t* gray;   /* [N, H, W]    0.114 R + 0.587 G + 0.299 B per sample (the reference's BGR2GRAY on an RGB frame, utils.py:591), box average */
+  float*   depth;  /* [N, H, W]    distance along the camera's -z of the pixel-centre ray's hit; +inf = sky */
+  int8_t*  geom;   /* [N, H, W]    -1 sky, 0 ground, 1 table, 2 cube, 3 target, 4 + m = mesh m (MCG_NMESH) */
+} mcg_render_out;
+
+/* Draws every environment (mask: those with a non-zero byte; the others' images are left untouched) as the given camera sees it.
+   samples: s x s rays per pixel on a regular sub-grid, box-averaged (rgb, gray); depth and geom always come from the pixel-centre ray.
+   target_at_goal != 0: the target box sits at the environment's goal (render(), mycobot.py:308-311), otherwise at mcg_model.target0
+   (what the reference's image observations show).  The cube is drawn where it is visible in the reference: has_object only.
+   Enqueues on `stream`, does not synchronise (but for an engine's first call, which uploads the face tables with a blocking copy: draw once
+   before capturing a graph), writes no engine state.  Checked on the host before any HIP call (MCG_ERR_ARG): null
+   handle / scene / out, all four outputs null, width or height outside 1..512, samples outside 1..4, cam_mat not orthonormal to
+   1e-9, fovy outside (0, 180), a light_dir that is not a unit vector to 1e-9.  MCG_ERR_UNSUPPORTED: an engine created from a
+   caller's model without a polytope block (its meshes are unknown). */
+int mcg_render(mcg_env* env, const mcg_scene* scene, int width, int height, int samples, int target_at_goal,
+               const uint8_t* mask /* [N] device or NULL = all */, const mcg_render_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,9 +96,41 @@ class McgState(C.Structure):
                                           "ep_return", "ep_length")]
 
 
+class McgScene(C.Structure):
+    """One camera + light + colours (include/mcg.h: mcg_scene); ``from_dict`` fills it from a compiled scene (assets/scene.json)."""
+    _fields_ = [("cam_pos", d * 3), ("cam_mat", d * 9), ("fovy", d), ("light_dir", d * 3), ("light_ambient", d), ("light_diffuse", d),
+                ("head_ambient", d), ("head_diffuse", d), ("rgb_ground", d * 3), ("rgb_table", d * 3), ("rgb_cube", d * 3),
+                ("rgb_target", d * 3), ("rgb_mesh", d * 3), ("rgb_sky", d * 3), ("target_half", d * 3)]
+
+    @classmethod
+    def from_dict(cls, scene: dict, camera: str) -> "McgScene":
+        if camera not in scene["cameras"]:
+            raise ValueError(f"unknown camera {camera!r}; the scene has {sorted(scene['cameras'])}")
+        cam = scene["cameras"][camera]
+        s = cls()
+        vals = {"cam_pos": cam["pos"], "cam_mat": np.asarray(cam["mat"], dtype=np.float64).reshape(-1), "light_dir": scene["light"]["dir"],
+                "target_half": scene["target_half"]}
+        vals.update({"rgb_" + k: v for k, v in scene["rgb"].items()})
+        for k, v in vals.items():
+            dst = getattr(s, k)
+            for j, x in enumerate(v):
+                dst[j] = float(x)
+        s.fovy = float(cam["fovy"])
+        s.light_ambient, s.light_diffuse = float(scene["light"]["ambient"]), float(scene["light"]["diffuse"])
+        s.head_ambient, s.head_diffuse = float(scene["headlight"]["ambient"]), float(scene["headlight"]["diffuse"])
+        return s
+
+
+class McgRenderOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "gray", "depth", "geom")]
+
+
+GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
+
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
            "mcg_action_dim", "mcg_nq", "mcg_nv", "mcg_reset", "mcg_step", "mcg_get_state", "mcg_set_state",
-           "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts")
+           "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts",
+           "mcg_render")
 
 _lib = None
 
@@ -136,6 +168,9 @@ def load():
         L.mcg_get_counters.argtypes = [C.c_void_p, C.POINTER(McgCounters), C.c_int]
         L.mcg_debug_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mcg_time_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(McgStepOut), C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    if hasattr(L, "mcg_render"):          # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_render.argtypes = [C.c_void_p, C.POINTER(McgScene), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                 C.POINTER(McgRenderOut), C.c_void_p]
     _lib = L
     return L
 

@@ -1069,6 +1069,8 @@ bool model_within_gates(const mcg_model* mm, const double* cube_half, char* why,
 
 }  // namespace
 
+#include "mcg_render.hpp"      // RenderArgs and the launch; the kernel lives in mcg_render.hip, a code object of its own
+
 // ================================================================================================== host ABI
 struct mcg_env {
   Cfg cfg;
@@ -1078,6 +1080,11 @@ struct mcg_env {
   unsigned long long* d_cnt;      // mcg_counters
   int device;
   int num_cu;
+  float4* d_faces;     // mcg_render: the polytopes' face planes as float32 (n, d), mesh by mesh, each range padded to a multiple of four;
+  std::vector<float> faces_host;      // made at mcg_create, uploaded by the first mcg_render (an engine that never draws allocates nothing for it)
+  int foff[MCG_NMESH + 1];
+  bool render_ok;      // false: created from a caller's model that the polytope block at hand does not fit (render_why)
+  char render_why[200];
   bool no_split;       // MCG_NO_SPLIT=1 in the environment at mcg_create: always the one-wave REACH kernels (tests, A/B timing)
 };
 
@@ -1182,6 +1189,25 @@ int mcg_create(const mcg_config* c, const mcg_model* model, const double* polyto
     err = hipMalloc(&e->d_poly, np * sizeof(double));
     if (err == hipSuccess) err = hipMemcpy(e->d_poly, pb, np * sizeof(double), hipMemcpyHostToDevice);
   }
+  if (err == hipSuccess) {   // mcg_render's face table.  Engines without the cube in the physics have not had their block checked above: the same two
+    // checks decide here whether they can be drawn (they run either way: their kernels collide nothing)
+    const double* pb = polytopes ? polytopes : kDefaultPolytopes;
+    const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;
+    e->render_ok = C.has_object || (polytope_index_ok(pb, np, e->render_why, sizeof(e->render_why)) && polytopes_fit_model(pb, m, e->render_why, sizeof(e->render_why)));
+    if (e->render_ok) {
+      std::vector<float>& tab = e->faces_host;
+      for (int mm = 0; mm < MCG_NMESH; mm++) {
+        const double* meta = pb + 8 * mm;
+        const long long nf = (long long)meta[1], off = (long long)meta[3], vp = (long long)meta[4], fp = (long long)meta[5];
+        const double* f = pb + off + 3 * vp;                    // [4, Fpad]: nx ny nz d
+        e->foff[mm] = (int)(tab.size() / 4);
+        for (long long k = 0; k < nf; k++) for (int a = 0; a < 4; a++) tab.push_back((float)f[a * fp + k]);
+        while ((tab.size() / 4) % 4) { tab.insert(tab.end(), {0.0f, 0.0f, 0.0f, 1e30f}); }
+      }
+      e->foff[MCG_NMESH] = (int)(tab.size() / 4);
+      if (tab.empty()) tab.assign(4, 0.0f);
+    }
+  }
   if (err == hipSuccess) err = hipMemset(e->d_cnt, 0, sizeof(mcg_counters));
   if (err == hipSuccess) C.cnt = e->d_cnt;
   if (err == hipSuccess) err = hipMemset(e->view.d, 0, nd * sizeof(double));
@@ -1209,6 +1235,7 @@ void mcg_destroy(mcg_env* e) {
   if (e->d_model) (void)hipFree(e->d_model);
   if (e->d_poly) (void)hipFree(e->d_poly);
   if (e->d_cnt) (void)hipFree(e->d_cnt);
+  if (e->d_faces) (void)hipFree(e->d_faces);
   delete e;
 }
 
@@ -1330,6 +1357,53 @@ int mcg_debug_contacts(mcg_env* e, int32_t* count, int32_t* dropped, double* dat
   dim3 grid((e->cfg.n + PNP_LANES - 1) / PNP_LANES), block(64);
   hipLaunchKernelGGL(contacts_pnp_kernel, grid, block, 0, (hipStream_t)stream, e->cfg, e->view, e->d_model, e->d_poly, count, dropped, data);
   HIP_OK(hipGetLastError());
+  return MCG_OK;
+}
+
+int mcg_render(mcg_env* e, const mcg_scene* sc, int width, int height, int samples, int target_at_goal, const uint8_t* mask,
+               const mcg_render_out* out, void* stream) {
+  // host checks first: nothing below them touches HIP
+  if (!sc || !out) return fail(MCG_ERR_ARG, "mcg_render: null scene or output block%s");
+  if (!out->rgb && !out->gray && !out->depth && !out->geom) return fail(MCG_ERR_ARG, "mcg_render: all four outputs are null%s");
+  if (width < 1 || width > 512 || height < 1 || height > 512) return fail(MCG_ERR_ARG, "mcg_render: width and height must be in 1..512%s");
+  if (samples < 1 || samples > 4) return fail(MCG_ERR_ARG, "mcg_render: samples must be in 1..4%s");
+  if (!(sc->fovy > 0.0 && sc->fovy < 180.0)) return fail(MCG_ERR_ARG, "mcg_render: fovy must be in (0, 180) degrees%s");
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) {
+      double s = 0;
+      for (int k = 0; k < 3; k++) s += sc->cam_mat[3 * k + a] * sc->cam_mat[3 * k + b];
+      if (!(std::fabs(s - (a == b ? 1.0 : 0.0)) <= 1e-9)) return fail(MCG_ERR_ARG, "mcg_render: cam_mat is not orthonormal to 1e-9%s");
+    }
+  if (!(std::fabs(norm3(sc->light_dir) - 1.0) <= 1e-9)) return fail(MCG_ERR_ARG, "mcg_render: light_dir is not a unit vector to 1e-9%s");
+  if (!e) return fail(MCG_ERR_ARG, "mcg_render: null handle%s");
+  if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
+  if (!e->d_faces) {       // the first picture of this engine: the face table goes to the device (a blocking copy, once)
+    HIP_OK(hipSetDevice(e->device));
+    float4* d = nullptr;
+    HIP_OK(hipMalloc(&d, e->faces_host.size() * sizeof(float)));
+    const hipError_t err = hipMemcpy(d, e->faces_host.data(), e->faces_host.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (err != hipSuccess) { (void)hipFree(d); return fail(MCG_ERR_HIP, "mcg_render: %s", hipGetErrorString(err)); }
+    e->d_faces = d;
+  }
+  RenderArgs A;
+  memset(&A, 0, sizeof(A));
+  for (int k = 0; k < 3; k++) { A.cam_pos[k] = sc->cam_pos[k]; A.light[k] = sc->light_dir[k]; A.target_half[k] = (float)sc->target_half[k]; }
+  for (int k = 0; k < 9; k++) { A.cam_mat[k] = sc->cam_mat[k]; A.cam_matf[k] = (float)sc->cam_mat[k]; }
+  A.focal = (float)(0.5 * height / std::tan(0.5 * sc->fovy * 3.14159265358979323846 / 180.0));
+  A.la = (float)sc->light_ambient; A.ld = (float)sc->light_diffuse; A.ha = (float)sc->head_ambient; A.hd = (float)sc->head_diffuse;
+  const double* rgb[6] = {sc->rgb_ground, sc->rgb_table, sc->rgb_cube, sc->rgb_target, sc->rgb_mesh, sc->rgb_sky};
+  for (int c = 0; c < 6; c++) for (int k = 0; k < 3; k++) A.rgb[c][k] = (float)(255.0 * rgb[c][k]);
+  A.W = width; A.H = height; A.S = samples; A.target_at_goal = target_at_goal ? 1 : 0;
+  A.draw_cube = (e->cfg.has_object && !e->cfg.hidden) ? 1 : 0;       // the reference hides the cube in Reach (mycobot.py:475-481)
+  A.dwords = (width % 4 == 0) && ((uintptr_t)out->rgb % 4 == 0) && ((uintptr_t)out->gray % 4 == 0) && ((uintptr_t)out->depth % 16 == 0)
+             && ((uintptr_t)out->geom % 4 == 0);
+  memcpy(A.foff, e->foff, sizeof(A.foff));
+  A.faces = e->d_faces; A.mask = mask; A.out = *out;
+  const size_t lds_bytes = (size_t)RENDER_HEAD_FLOATS * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;     // built-in tables: 35 KB
+  if (lds_bytes > 64 * 1024) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: the face tables do not fit the 64 KB of LDS a workgroup asks for (about 3 200 faces)%s");
+  const hipError_t lerr = (hipError_t)launch_render(A, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
+                                                    e->view.d + (size_t)(2 * e->cfg.nq + 2 * e->cfg.nv + 7) * e->cfg.n, e->d_model);
+  if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_render: launch: %s", hipGetErrorString(lerr));
   return MCG_OK;
 }
 

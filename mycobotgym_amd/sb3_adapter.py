@@ -3,7 +3,7 @@
 The reference trains through SB3's ``DummyVecEnv`` / ``SubprocVecEnv`` around ``Monitor(gymnasium.make(id))``
 (/root/reference/mycobotgym/scripts/train.py:25-33,80-85) and evaluates with ``evaluate_policy`` reading
 ``info["is_success"]`` (scripts/eval_model.py:131).  This adapter exposes the same surface [RECALL SB3 2.0 VecEnv]:
-numpy observations ``dict[str, ndarray[N, ...]]``, ``rewards float32[N]``, ``dones bool[N]``, ``infos: list[dict]`` with
+numpy observations ``dict[str, ndarray[N, ...]]`` (the image ids: one ``uint8[N, 1, S, S]`` array), ``rewards float32[N]``, ``dones bool[N]``, ``infos: list[dict]`` with
 ``terminal_observation``, ``TimeLimit.truncated``, ``episode = {"r", "l", "t"}`` (what ``Monitor`` adds) and
 ``is_success``; ``env_method("compute_reward", ...)`` for HER.  One device->host copy per step.
 
@@ -55,7 +55,7 @@ class MyCobotSB3VecEnv:
             final = _to_numpy(info["final_observation"])
             ep_r = info["episode"]["r"].cpu().numpy(); ep_l = info["episode"]["l"].cpu().numpy()
             for i in np.nonzero(dones)[0]:
-                infos[i]["terminal_observation"] = {k: v[i] for k, v in final.items()}
+                infos[i]["terminal_observation"] = {k: v[i] for k, v in final.items()} if isinstance(final, dict) else final[i]
                 infos[i]["TimeLimit.truncated"] = bool(trunc_np[i] and not term_np[i])
                 infos[i]["episode"] = {"r": float(ep_r[i]), "l": int(ep_l[i]), "t": round(time.time() - self._t0, 6)}
         return obs_np, rew_np, dones, infos
@@ -100,7 +100,10 @@ class MyCobotSB3VecEnv:
         return self
 
 
-def _to_numpy(obs: dict) -> dict:
+def _to_numpy(obs):
+    """A Dict observation -> dict of arrays; an image observation (the -v1 ids: one uint8 tensor) -> one array."""
+    if isinstance(obs, torch.Tensor):
+        return obs.detach().cpu().numpy()
     return {k: v.detach().cpu().numpy() for k, v in obs.items()}
 
 

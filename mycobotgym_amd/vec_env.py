@@ -90,8 +90,14 @@ def _table_initial_state(table: dict, has_object: bool, fetch_env: bool, mesh_in
     return qfull[:nq], qvel, ctrl, igx, height
 
 
+def load_scene(path: Optional[str] = None) -> dict:
+    """The compiled scene (tools/compile_scene.py): the world cameras, the light, the colours."""
+    with open(path or os.path.join(_ASSETS, "scene.json")) as f:
+        return json.load(f)
+
+
 class MyCobotVecEnv:
-    metadata = {"render_modes": [], "render_fps": 25}      # mycobot.py:28
+    metadata = {"render_modes": ["rgb_array", "depth_array"], "render_fps": 25}      # mycobot.py:28
 
     def __init__(self, num_envs: int, has_object: bool = True, block_gripper: bool = False, control_steps: int = 5,
                  controller_type: str = "IK", obj_range: float = 0.1, target_in_the_air: bool = True,
@@ -105,7 +111,8 @@ class MyCobotVecEnv:
         collision polytopes go to the engine with it, and the initial state (qpos, gripper position, height offset) is its own.
         ``model`` / ``polytopes``: a raw ``mcg_model`` block and the polytope block specialised with it (NULL: the built-in one)."""
         if image_obs:
-            raise NotImplementedError("image observations (-v1 ids, MyCobotImgEnv) need a rasteriser: out of scope")
+            raise NotImplementedError("image observations (-v1 ids, MyCobotImgEnv) are a class of their own: MyCobotImgVecEnv "
+                                      "(make() picks it for the -v1 ids)")
         if controller_type == "delta_joint":
             raise NotImplementedError("delta_joint has no branch in the reference's step() (SURVEY D-10)")
         if controller_type not in _CONTROLLERS:
@@ -168,7 +175,10 @@ class MyCobotVecEnv:
             # weld_rule "mujoco": the mocap weld with MuJoCo's recalled row weights (rotational rows softer); contact_rule "keyframe": the
             # pyramid regulariser that reproduces the cube's rest height of the reference's keyframes (include/mcg.h: contact_rpy)
             from .model.specialize import specialize
-            model = _abi.McgModel.from_spec(specialize(load_table(True, mesh_inertia, mocap), weld_rule=weld_rule, contact_rule=contact_rule))
+            spec = specialize(load_table(True, mesh_inertia, mocap), weld_rule=weld_rule, contact_rule=contact_rule)
+            model = _abi.McgModel.from_spec(spec)
+            if polytopes is None:
+                polytopes = spec["polytopes"]      # the block that goes with the model
         if model is None:     # built-in block; a caller-supplied mcg_model (tests, custom robots) overrides it
             model = _abi.McgModel()
             variant = (1 if mesh_inertia == "exact" else 0) + (2 if mocap else 0)     # 2, 3: mocap body + weld (mycobot280_mocap.xml)
@@ -329,6 +339,60 @@ class MyCobotVecEnv:
                                                 self._stream(), C.byref(ms)), "mcg_time_steps")
         return float(ms.value)
 
+    # ------------------------------------------------------------------------------------------------- pictures
+    def _scene(self, camera: str, scene: Optional[dict]) -> "_abi.McgScene":
+        if scene is None:
+            if not hasattr(self, "_default_scene"):
+                self._default_scene = load_scene()
+            scene = self._default_scene
+        return _abi.McgScene.from_dict(scene, camera)
+
+    def render_into(self, out: dict, camera: str = "sideview", samples: int = 1, show_goal: bool = True,
+                    mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None):
+        """Raw form of ``render``: ``out`` maps any of rgb (uint8 [N, H, W, 3]), gray (uint8 [N, H, W]), depth (float32 [N, H, W]),
+        geom (int8 [N, H, W]) to contiguous device tensors of one H, W, which the kernel fills (where ``mask`` is set); enqueued on the
+        current stream, not synchronised."""
+        want = {"rgb": (torch.uint8, 3), "gray": (torch.uint8, None), "depth": (torch.float32, None), "geom": (torch.int8, None)}
+        hw = None
+        for k, t in out.items():
+            if k not in want:
+                raise ValueError(f"unknown output {k!r}; known: {sorted(want)}")
+            dt, last = want[k]
+            shape_ok = t.dim() == (4 if last else 3) and t.shape[0] == self.num_envs and (last is None or t.shape[3] == last)
+            if not (shape_ok and t.dtype == dt and t.is_contiguous() and t.device == self._buf["obs"].device):
+                raise ValueError(f"{k}: expected a contiguous {dt} device tensor [N, H, W{', 3' if last else ''}]")
+            if hw is not None and tuple(t.shape[1:3]) != hw:
+                raise ValueError("the outputs differ in height / width")
+            hw = tuple(t.shape[1:3])
+        m = None
+        if mask is not None:
+            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            if m.shape != (self.num_envs,):
+                raise ValueError("mask must have shape (num_envs,)")
+        ro = _abi.McgRenderOut(**{k: t.data_ptr() for k, t in out.items()})
+        sc = self._scene(camera, scene)
+        h, w = hw if hw is not None else (0, 0)
+        with torch.cuda.device(self.device):
+            _abi.check(self._lib.mcg_render(self._h, C.byref(sc), int(w), int(h), int(samples), int(bool(show_goal)),
+                                            None if m is None else C.c_void_p(m.data_ptr()), C.byref(ro), self._stream()), "mcg_render")
+        return out
+
+    def render(self, camera: str = "sideview", width: int = 480, height: int = 480, samples: int = 1, mode: str = "rgb_array",
+               mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None, show_goal: bool = True):
+        """All environments as ``camera`` sees them: ``mode="rgb_array"`` -> uint8 [N, H, W, 3], ``"depth_array"`` -> float32 [N, H, W]
+        (distance along the viewing axis, +inf = sky); device tensors.  The target site is drawn at the goal, as the reference's
+        ``_render_callback`` does (mycobot.py:308-311).  ``samples``: s x s rays per pixel, box-averaged; ``mask``: draw these environments
+        only (the others' images are zero); ``scene``: a compiled scene other than the built-in one (tools/compile_scene.py)."""
+        if mode not in self.metadata["render_modes"]:
+            raise ValueError(f"mode must be one of {self.metadata['render_modes']}, got {mode!r}")
+        n, dev = self.num_envs, self.device
+        if mode == "rgb_array":
+            out = {"rgb": torch.zeros(n, int(height), int(width), 3, dtype=torch.uint8, device=dev)}
+        else:
+            out = {"depth": torch.zeros(n, int(height), int(width), dtype=torch.float32, device=dev)}
+        self.render_into(out, camera=camera, samples=samples, show_goal=show_goal, mask=mask, scene=scene)
+        return out["rgb" if mode == "rgb_array" else "depth"]
+
     def counters(self, clear: bool = False) -> dict:
         """Event counters of the engine (include/mcg.h: mcg_counters); synchronises the device."""
         c = _abi.McgCounters()
@@ -359,8 +423,92 @@ class MyCobotVecEnv:
             pass
 
 
+class MyCobotImgVecEnv(MyCobotVecEnv):
+    """Mirror of the reference's ``MyCobotImgEnv`` (mycobot.py:517-545): the observation is the picture alone -- uint8 [N, 1, S, S], camera
+    ``sideview``, grayscale as ``preprocess_frame`` makes it (utils.py:580-595) -- not a Dict; ``achieved_goal`` / ``desired_goal`` travel
+    in ``info``.
+
+    The reference's ``_get_obs`` calls the renderer directly, not ``render()``: the target site is NOT moved to the goal in its observations
+    and stays at its MJCF position (SURVEY D-15).  ``show_goal=True`` draws it at the goal instead.
+
+    Auto-reset: the picture of the pre-reset state is ``info["final_observation"]``, and the step kernel's own auto-reset would have
+    overwritten that state.  So the engine runs with ``auto_reset=0``; a step renders, resets the finished environments with the masked
+    ``mcg_reset`` (the same per-environment random streams as the in-kernel reset) and draws those again."""
+
+    def __init__(self, num_envs: int, *args, camera: str = "sideview", image_size: int = 64, samples: int = 2, show_goal: bool = False,
+                 scene: Optional[dict] = None, auto_reset: bool = True, image_obs: bool = True, **kwargs):
+        if kwargs.get("reward_type", "sparse") == "reward_shaping":
+            raise ValueError("the reference registers no image variant for reward_shaping (mycobotgym/__init__.py:37-39)")
+        self._img_auto_reset = bool(auto_reset)
+        super().__init__(num_envs, *args, auto_reset=False, image_obs=False, **kwargs)
+        self.camera, self.image_size, self.samples, self.show_goal = camera, int(image_size), int(samples), bool(show_goal)
+        self._img_scene = scene
+        self._scene(camera, scene)                 # an unknown camera fails here, not at the first step
+        s = self.image_size
+        self.single_observation_space = Box(0, 255, (1, s, s), np.uint8)         # mycobot.py:543-545
+        self.observation_space = batch_box(self.single_observation_space, self.num_envs)
+        self._img = torch.zeros(self.num_envs, 1, s, s, dtype=torch.uint8, device=self.device)
+        self._final_img = torch.zeros_like(self._img)
+
+    def _draw(self, dst: torch.Tensor, mask: Optional[torch.Tensor] = None):
+        self.render_into({"gray": dst[:, 0]}, camera=self.camera, samples=self.samples, show_goal=self.show_goal, mask=mask,
+                         scene=self._img_scene)
+
+    def _goal_info(self, b: dict) -> dict:
+        return {"achieved_goal": b["achieved_goal"], "desired_goal": b["desired_goal"]}
+
+    def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None, mask: Optional[torch.Tensor] = None):
+        super().reset(seed=seed, options=options, mask=mask)
+        self._draw(self._img, mask)
+        return self._img.clone(), self._goal_info({k: v.clone() for k, v in self._obs().items()})
+
+    def step(self, actions, copy: bool = True):
+        """-> (image uint8 [N, 1, S, S], reward, terminated, truncated, info); info carries achieved_goal / desired_goal (after the
+        auto-reset where done), is_success, final_observation (the picture of the finished episode's last state) / _final_observation,
+        final_info-style episode statistics as the state engine's."""
+        if self._needs_reset:
+            raise RuntimeError("Cannot call env.step() before calling env.reset()")
+        a = torch.as_tensor(actions, dtype=torch.float32, device=self.device).contiguous()
+        if a.shape != (self.num_envs, self.action_dim):
+            raise ValueError(f"actions must have shape {(self.num_envs, self.action_dim)}, got {tuple(a.shape)}")
+        with torch.cuda.device(self.device):
+            _abi.check(self._lib.mcg_step(self._h, C.c_void_p(a.data_ptr()), C.byref(self._out), self._stream()), "mcg_step")
+        b = self._buf
+        # what the step itself decided, before the reset below rewrites the observation buffers
+        step_out = {k: b[k].clone() for k in ("reward", "terminated", "truncated", "is_success", "ep_return", "ep_length")}
+        done = step_out["truncated"]          # truncated = is_success | time-limit: covers terminated (D-4)
+        self._draw(self._img)
+        final_img = self._final_img
+        final_goals = {"achieved_goal": b["achieved_goal"].clone(), "desired_goal": b["desired_goal"].clone()}
+        if self._img_auto_reset:
+            final_img.copy_(self._img)
+            m = done.to(torch.uint8)
+            with torch.cuda.device(self.device):      # resets the finished environments only; rewrites their rows of obs / goals
+                _abi.check(self._lib.mcg_reset(self._h, C.c_void_p(m.data_ptr()), 0, C.c_uint64(0), C.byref(self._out), self._stream()),
+                           "mcg_reset")
+            self._draw(self._img, m)
+        reward = step_out["reward"].float() if self.reward_type == "sparse" else step_out["reward"]
+        info = {"is_success": step_out["is_success"],
+                # (the reset kernel re-derives every environment's goals from the state: keep the step's own where nothing was reset)
+                "achieved_goal": torch.where(done[:, None], b["achieved_goal"], final_goals["achieved_goal"]),
+                "desired_goal": torch.where(done[:, None], b["desired_goal"], final_goals["desired_goal"]),
+                "final_observation": final_img.clone() if copy else final_img, "_final_observation": done,
+                "final_achieved_goal": final_goals["achieved_goal"], "final_desired_goal": final_goals["desired_goal"],
+                "episode": {"r": step_out["ep_return"], "l": step_out["ep_length"]}, "_episode": done}
+        return (self._img.clone() if copy else self._img), reward, step_out["terminated"], step_out["truncated"], info
+
+    def step_async(self, actions: torch.Tensor) -> dict:
+        raise NotImplementedError("the image environment's step is several launches (step, render, masked reset, render): use step()")
+
+
+def env_class(env_id: str):
+    """The class ``make`` constructs for a registered id: ``MyCobotImgVecEnv`` for the 20 ``-v1`` ids, ``MyCobotVecEnv`` for the 30 ``-v0``."""
+    return MyCobotImgVecEnv if _spec(env_id)["image_obs"] else MyCobotVecEnv
+
+
 def make(env_id: str, num_envs: int = 1, **kwargs) -> MyCobotVecEnv:
     """``gymnasium.make``-style factory over the reference's id table, vectorised."""
     kw = _spec(env_id)
     kw.update(kwargs)
-    return MyCobotVecEnv(num_envs, **kw)
+    image_obs = kw.pop("image_obs")
+    return (MyCobotImgVecEnv if image_obs else MyCobotVecEnv)(num_envs, **kw)

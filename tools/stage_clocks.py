@@ -2,7 +2,7 @@
 """Per-stage shader-clock shares of the step kernels (development helper).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -shared -DMCG_STAGE_CLOCKS -Iinclude -Imycobotgym_amd/csrc \
-          mycobotgym_amd/csrc/mcg_hip.hip -o ab/clocks.so
+          mycobotgym_amd/csrc/mcg_hip.hip mycobotgym_amd/csrc/mcg_render.hip -o ab/clocks.so
     MCG_LIB=ab/clocks.so python tools/stage_clocks.py [--fresh-actions]
 
 Lane 0 of every wave accumulates s_memtime deltas per stage; the table is the sum over waves and launches.
