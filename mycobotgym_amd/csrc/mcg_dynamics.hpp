@@ -403,6 +403,11 @@ constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM
 // runs it, and the Euler step after S3 writes them again.  z8 has slots of its own.
 constexpr int LDS_Z6 = LDS_WARM, LDS_Z8 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_Z8 + NB;
 static_assert(LDS_SLOTS_SPLIT * 64 * sizeof(real) <= 160 * 1024, "the split Reach kernel's LDS exceeds the 160 KB of a gfx950 workgroup");
+// The sines and cosines of a sub-step, each evaluated by one of the three waves (SplitMain::trig_once), are exchanged between S1 and S1t in the
+// FACTOR slots: the main wave's last read of the factor (after S3) comes before it reaches the next S1, and the helper's next write comes
+// after the next S2, by which every wave has read its sines and cosines -- the two uses never overlap.
+constexpr int LDS_SN = LDS_FAC, LDS_CS = LDS_SN + NB;
+static_assert(LDS_SN >= LDS_FAC && LDS_CS + NB <= LDS_FDINV + NB && LDS_FDINV + NB == LDS_QB, "the sine / cosine exchange must lie inside the factor slots");
 // The lane's LDS column.  The pointer carries the LDS address space explicitly: passed through structs as a generic
 // pointer the accesses degrade to flat_load/flat_store with 64-bit address arithmetic instead of ds_read/ds_write
 // with immediate offsets.
@@ -664,12 +669,30 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // limit_cols: when the only violated limit rows of the wave are the gear joints' (6, 8: every fresh episode starts on them), the RNE
 // wave, idle after S2, factors the same H_eq and solves for the closed-form solve's two columns z6, z8 while the main wave factors and
 // solves for abar; a fourth barrier, S2b, hands them over.  Every wave decides from the q slots whether to take S2b (gear_rows_only).
-struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, limit_cols = false;
+// trig_once (round 6): the sub-step's twelve sines and cosines are evaluated once instead of once per wave: after S1 the main wave takes
+// joints 0..3, the helper 4..7, the RNE wave 8..11, and a barrier S1t hands all twenty-four to every wave through the slots LDS_SN /
+// LDS_CS (trig_exchange).
+struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, limit_cols = false,
+                                       trig_once = false;
                  static constexpr int QB = 0, QDB = 0, FS = 0, WARM = 0, QLAG = 0; };
-struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, limit_cols = true;
+struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, limit_cols = true,
+                                         trig_once = true;
                    static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
 // The IK and mocap kernels keep the three barriers: measured with S2b, both were ~1 % slower (profiles/r05/ab_quick_all_controllers.log).
 struct SplitMainNoCols : SplitMain { static constexpr bool limit_cols = false; };
+struct SplitMainOwnTrig : SplitMain { static constexpr bool trig_once = false; };      // every wave its own twelve (round 5), for A/B builds
+
+// A wave's share of the exchange (trig_once): joints FIRST .. FIRST + 3 (`q_of(i)`: the wave's copy of q_i), stored, then -- S1t -- all
+// twenty-four read back.  sincos_cw is explicit fma's throughout: the same bits whichever wave evaluates it.
+template <int FIRST, class LS, class QF>
+MCG_DEV void trig_exchange(const LS MS, QF q_of, real* sn, real* cs) {
+  {
+    const TrigC T = load_trig();
+    static_for<4>([&](auto I) { constexpr int i = FIRST + I; real s, c; sincos_cw(T, AXS[i] * q_of(std::integral_constant<int, i>{}), s, c); MS.st(LDS_SN + i, s); MS.st(LDS_CS + i, c); });
+  }
+  __syncthreads();                                                  // S1t
+  static_for<NB>([&](auto I) { constexpr int i = I; sn[i] = MS.ld(LDS_SN + i); cs[i] = MS.ld(LDS_CS + i); });
+}
 
 // H_eq + M (the equality rows' system, from LDS) plus D on the diagonal of the limit rows in act_.  One function for every wave that
 // factors it: the RNE wave's columns (limit_cols) must come from the very same L and dinv as the main wave's solve.
@@ -732,7 +755,8 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   if constexpr (SPL::enabled) __syncthreads();                     // S1
   const real h = launder(Pm)->timestep;
   real cs[NB], sn[NB];
-  {
+  if constexpr (SPL::trig_once) trig_exchange<0>(MS, [&](auto I) { return S.q[I]; }, sn, cs);
+  else {
     const TrigC T = load_trig();
     static_for<NB>([&](auto I) { constexpr int i = I; sincos_cw(T, AXS[i] * S.q[i], sn[i], cs[i]); });
   }
@@ -1204,18 +1228,26 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   return bad;
 }
 
+// A side wave's sines and cosines after S1: through the exchange (trig_once: this wave evaluates joints FIRST .. FIRST + 3), or all twelve
+// from the q slots.
+template <class SPL, int FIRST, class LS>
+MCG_DEV void side_trig(const LS MS, real* sn, real* cs) {
+  if constexpr (SPL::trig_once) trig_exchange<FIRST>(MS, [&](auto I) { return MS.ld(SPL::QB + I); }, sn, cs);
+  else {
+    const TrigC T = load_trig();
+    static_for<NB>([&](auto I) { constexpr int i = I; sincos_cw(T, AXS[i] * MS.ld(SPL::QB + i), sn[i], cs[i]); });
+  }
+  static_for<NB>([&](auto I) { constexpr int i = I; pin(sn[i]); pin(cs[i]); });
+  MCG_FENCE();
+}
+
 // The helper wave's share of one sub-step (see SplitMain).
 template <class SPL = SplitMain, class LS, class SIDE = NoSideWork>
 MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   __syncthreads();                                                  // S1
   MCG_TICK(ST_H_S1);
   real cs[NB], sn[NB];
-  {
-    const TrigC T = load_trig();
-    static_for<NB>([&](auto I) { constexpr int i = I; sincos_cw(T, AXS[i] * MS.ld(SPL::QB + i), sn[i], cs[i]); });
-  }
-  static_for<NB>([&](auto I) { constexpr int i = I; pin(sn[i]); pin(cs[i]); });
-  MCG_FENCE();
+  side_trig<SPL, 4>(MS, sn, cs);
   crb_to_lds(Pm, cs, sn, MS);
   bool cols = false;
   if constexpr (SPL::limit_cols) cols = gear_rows_only<SPL>(Pm, MS);
@@ -1246,12 +1278,8 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   __syncthreads();                                                  // S1
   MCG_TICK(ST_Q_S1);
   real cs[NB], sn[NB], qd[NB], fs[NB];
-  {
-    const TrigC T = load_trig();
-    static_for<NB>([&](auto I) { constexpr int i = I; sincos_cw(T, AXS[i] * MS.ld(SPL::QB + i), sn[i], cs[i]); qd[i] = MS.ld(SPL::QDB + i); });
-  }
-  static_for<NB>([&](auto I) { constexpr int i = I; pin(sn[i]); pin(cs[i]); });
-  MCG_FENCE();
+  side_trig<SPL, 8>(MS, sn, cs);
+  static_for<NB>([&](auto I) { constexpr int i = I; qd[i] = MS.ld(SPL::QDB + i); });
   rne_bias(Pm, cs, sn, qd, fs);
   static_for<NB>([&](auto I) { constexpr int i = I; MS.st(SPL::FS + i, fs[i]); });
   bool cols = false;

@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Instruction counts of one kernel, cut at every s_barrier and every block label, with the source functions of each stretch.
+
+A wave alone on its SIMD takes as long as the instructions it issues, so which wave is the slow one between two barriers is a count
+over the ISA, not a guess.  Dump the ISA with line tables (as for tools/isa_stats.py, plus -g1):
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++20 -S -g1 --cuda-device-only -Iinclude -Imycobotgym_amd/csrc \\
+        mycobotgym_amd/csrc/mcg_hip.hip -o /tmp/mcg.s
+    python tools/isa_segments.py /tmp/mcg.s step_reach_kernelILi0ELb1 [--min 20] [--barriers]
+
+The kernel is named by any substring of its mangled name.  One line per stretch: the label it starts at, how it ends (`barrier`, a
+branch, or falling into the next label), instructions in total / `_f64` / `ds_` / `s_load` / `v_accvgpr`, and the functions its `.loc`
+lines fall in (function = the nearest definition above the line in that source file; counts per function).  `--barriers` prints only
+the barriers, each with the last project source line before it: read the sequences of the waves side by side before a GPU run.  The counts are
+static: a stretch inside a loop or behind a wave-uniform branch is listed once, whatever the path taken.
+"""
+import bisect, collections, os, re, sys
+
+argv = sys.argv[1:]
+min_ins = 1
+if "--min" in argv:
+    k = argv.index("--min"); min_ins = int(argv[k + 1]); del argv[k:k + 2]
+args = [a for a in argv if not a.startswith("--")]
+if len(args) < 2:
+    sys.exit(__doc__)
+path, want = args[0], args[1]
+only_barriers = "--barriers" in sys.argv
+lines = open(path).read().split("\n")
+
+# .file N "dir" "name" (DWARF 5) or .file N "name"
+files, comp_dir = {}, ""
+for l in lines:
+    m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
+    if m:
+        f = os.path.join(m.group(2), m.group(3)) if m.group(3) else m.group(2)
+        if int(m.group(1)) == 0 and m.group(3): comp_dir = m.group(2)          # .file 0 "<compilation directory>" "<source>"
+        files[int(m.group(1))] = f if os.path.isabs(f) else os.path.join(comp_dir, f)
+
+DEF = re.compile(r'^\s*(?:template\s*<[^;{]*>\s*)?(?:MCG_DEV|__global__|__device__|static|inline)\b[^;=]*?\b([A-Za-z_]\w*)\s*\([^;]*$')
+_defs = {}
+def function_at(fileno, line):
+    f = files.get(fileno)
+    if f not in _defs:
+        starts, names = [], []
+        try:
+            for n, l in enumerate(open(f, errors="replace"), 1):
+                m = DEF.match(l)
+                if m and m.group(1) not in ("if", "for", "while", "switch", "return", "static_assert", "__launch_bounds__"):
+                    starts.append(n); names.append(m.group(1))
+        except OSError:
+            pass
+        _defs[f] = (starts, names)
+    starts, names = _defs[f]
+    k = bisect.bisect_right(starts, line) - 1
+    return names[k] if k >= 0 else os.path.basename(f or "?")
+
+begin = next((n for n, l in enumerate(lines) if re.match(r'^_Z\w*:', l) and want in l), None)
+if begin is None:
+    sys.exit(f"no kernel matching {want!r} in {path}")
+print(f"# {lines[begin][:-1]}")
+print(f"# {'start':>12s} {'end':8s} {'instr':>6s} {'f64':>5s} {'ds':>4s} {'s_load':>6s} {'accvgpr':>7s}  functions (instructions)")
+
+seg = dict(label="entry", ins=[], fn=collections.Counter(), src=None)
+cur_fn, cur_loc, total, nbar = "?", "?", 0, 0
+def flush(end):
+    global seg
+    ins = seg["ins"]
+    if only_barriers:
+        if end == "barrier":
+            print(f"barrier {nbar:3d}  after {seg['label']:>10s}  near {seg['src']}")
+    elif len(ins) >= min_ins or end == "barrier":
+        c = lambda p: sum(1 for i in ins if p in i)
+        fns = "  ".join(f"{f} {n}" for f, n in seg["fn"].most_common(6))
+        print(f"  {seg['label']:>12s} {end:8s} {len(ins):6d} {c('_f64'):5d} {sum(1 for i in ins if i.startswith('ds_')):4d} {c('s_load'):6d} {c('v_accvgpr'):7d}  {fns}")
+for l in lines[begin + 1:]:
+    t = l.strip()
+    if t.startswith((".end_amdhsa_kernel", ".section", ".Lfunc_end")):
+        break
+    m = re.match(r'\.loc\s+(\d+)\s+(\d+)', t)
+    if m:
+        f = files.get(int(m.group(1)), "?")
+        if not any(d in f for d in ("/rocm", "/hip/", "/clang/", "/llvm/")):      # a runtime header's line says nothing: keep the last project line
+            cur_fn = function_at(int(m.group(1)), int(m.group(2)))
+            cur_loc = f"{os.path.basename(f)}:{m.group(2)} ({cur_fn})"
+        continue
+    m = re.match(r'^(\.LBB\w+):', l)
+    if m:
+        flush("label")
+        seg = dict(label=m.group(1)[1:], ins=[], fn=collections.Counter(), src=None)
+        continue
+    if not l.startswith("\t") or not t or t.startswith((".", ";")):
+        continue
+    op = t.split()[0]
+    seg["ins"].append(op); seg["fn"][cur_fn] += 1; total += 1
+    if op == "s_barrier":
+        nbar += 1; seg["src"] = cur_loc
+        flush("barrier")
+        seg = dict(label="(cont.)", ins=[], fn=collections.Counter(), src=None)
+flush("end")
+if not only_barriers:
+    print(f"# total {total} instructions, {nbar} s_barrier")
