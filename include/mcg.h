@@ -217,7 +217,10 @@ int mcg_time_steps(mcg_env* env, const float* actions, const mcg_step_out* out, 
    A ray caster over the engine's own state: the ground plane, the table, cube and target boxes, and the fourteen mesh geoms as their
    collision polytopes (face planes, within 1 mm of the convex hulls).  Flat Lambert shading per face:
      rgb * (ambient + diffuse * max(0, n.(-light_dir)) + head_ambient + head_diffuse * max(0, n.(-ray))), clamped, to uint8 by round-half-up.
-   Not drawn: base_link, the mocap body's guide geoms, the EEF site, specular light, the visual meshes' concavities, the gripper camera. */
+   Not drawn: base_link, the finger pads, the mocap body's guide geoms, the EEF site, specular light, the visual meshes' concavities.
+   Visibility: surfaces are one-sided.  A convex geom whose entry point lies behind the camera or before the near plane is invisible
+   along that ray, which goes on to the other geoms; so a camera inside a polytope does not see it (OpenGL's back-face culling on closed
+   convex solids).  The reference's gripper camera (mycobot280_main.xml:161-166) sits inside the flange's polytope and looks out of it. */
 typedef struct mcg_scene {   /* one camera + light + colours; all doubles */
   double cam_pos[3];         /* world position of the camera */
   double cam_mat[9];         /* row-major world <- camera; columns = the camera's x (right), y (up), z; it looks along -z */
@@ -247,6 +250,16 @@ typedef struct mcg_render_out {      /* device pointers, any may be NULL (not al
    caller's model without a polytope block (its meshes are unknown). */
 int mcg_render(mcg_env* env, const mcg_scene* scene, int width, int height, int samples, int target_at_goal,
                const uint8_t* mask /* [N] device or NULL = all */, const mcg_render_out* out, void* stream);
+
+/* mcg_render with a camera that rides on a body and a near plane: scene->cam_pos and scene->cam_mat are read in the frame of engine body
+   `body` (0..11 in the order of mcg_model.body; a body without a joint of its own, such as `flange`, is welded into its jointed
+   ancestor: compose its offset into cam_pos / cam_mat, as tools/compile_scene.py does for scene["body_cameras"]), and the camera's
+   world pose is composed per environment, in float64, from that body's pose in the environment's state.  body == -1: the world, which
+   is mcg_render's meaning.  znear (metres): a hit of any geom whose depth along the camera's -z is below it is dropped for that ray,
+   which goes on to the other geoms; 0 = no near plane.  mcg_render is this entry with body = -1, znear = 0.  Host checks as
+   mcg_render's, plus (MCG_ERR_ARG): body outside -1..11, znear negative or not finite. */
+int mcg_render_mounted(mcg_env* env, const mcg_scene* scene, int body, double znear, int width, int height, int samples,
+                       int target_at_goal, const uint8_t* mask /* [N] device or NULL = all */, const mcg_render_out* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -106,7 +106,11 @@ class McgScene(C.Structure):
     def from_dict(cls, scene: dict, camera: str) -> "McgScene":
         if camera not in scene["cameras"]:
             raise ValueError(f"unknown camera {camera!r}; the scene has {sorted(scene['cameras'])}")
-        cam = scene["cameras"][camera]
+        return cls.from_camera(scene, scene["cameras"][camera])
+
+    @classmethod
+    def from_camera(cls, scene: dict, cam: dict) -> "McgScene":
+        """``cam``: pos, mat, fovy -- a world camera, or a body camera (``scene["body_cameras"]``) stated in its carrier body's frame."""
         s = cls()
         vals = {"cam_pos": cam["pos"], "cam_mat": np.asarray(cam["mat"], dtype=np.float64).reshape(-1), "light_dir": scene["light"]["dir"],
                 "target_half": scene["target_half"]}
@@ -130,7 +134,7 @@ GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
            "mcg_action_dim", "mcg_nq", "mcg_nv", "mcg_reset", "mcg_step", "mcg_get_state", "mcg_set_state",
            "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts",
-           "mcg_render")
+           "mcg_render", "mcg_render_mounted")
 
 _lib = None
 
@@ -171,6 +175,9 @@ def load():
     if hasattr(L, "mcg_render"):          # absent only from older builds selected through MCG_LIB for A/B timing
         L.mcg_render.argtypes = [C.c_void_p, C.POINTER(McgScene), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(McgRenderOut), C.c_void_p]
+    if hasattr(L, "mcg_render_mounted"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_render_mounted.argtypes = [C.c_void_p, C.POINTER(McgScene), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.POINTER(McgRenderOut), C.c_void_p]
     _lib = L
     return L
 

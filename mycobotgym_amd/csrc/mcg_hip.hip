@@ -1360,22 +1360,25 @@ int mcg_debug_contacts(mcg_env* e, int32_t* count, int32_t* dropped, double* dat
   return MCG_OK;
 }
 
-int mcg_render(mcg_env* e, const mcg_scene* sc, int width, int height, int samples, int target_at_goal, const uint8_t* mask,
-               const mcg_render_out* out, void* stream) {
-  // host checks first: nothing below them touches HIP
-  if (!sc || !out) return fail(MCG_ERR_ARG, "mcg_render: null scene or output block%s");
-  if (!out->rgb && !out->gray && !out->depth && !out->geom) return fail(MCG_ERR_ARG, "mcg_render: all four outputs are null%s");
-  if (width < 1 || width > 512 || height < 1 || height > 512) return fail(MCG_ERR_ARG, "mcg_render: width and height must be in 1..512%s");
-  if (samples < 1 || samples > 4) return fail(MCG_ERR_ARG, "mcg_render: samples must be in 1..4%s");
-  if (!(sc->fovy > 0.0 && sc->fovy < 180.0)) return fail(MCG_ERR_ARG, "mcg_render: fovy must be in (0, 180) degrees%s");
+int mcg_render_mounted(mcg_env* e, const mcg_scene* sc, int body, double znear, int width, int height, int samples, int target_at_goal,
+                       const uint8_t* mask, const mcg_render_out* out, void* stream) {
+  // host checks first: nothing below them touches HIP.  (mcg_render's texts are kept: it is this entry with body = -1, znear = 0)
+  const char* fn = (body == -1 && znear == 0.0) ? "mcg_render" : "mcg_render_mounted";
+  if (!sc || !out) return fail(MCG_ERR_ARG, "%s: null scene or output block", fn);
+  if (!out->rgb && !out->gray && !out->depth && !out->geom) return fail(MCG_ERR_ARG, "%s: all four outputs are null", fn);
+  if (width < 1 || width > 512 || height < 1 || height > 512) return fail(MCG_ERR_ARG, "%s: width and height must be in 1..512", fn);
+  if (samples < 1 || samples > 4) return fail(MCG_ERR_ARG, "%s: samples must be in 1..4", fn);
+  if (body < -1 || body >= NB) return fail(MCG_ERR_ARG, "%s: body must be -1 (the world) or an engine body 0..11", fn);
+  if (!(std::isfinite(znear) && znear >= 0.0)) return fail(MCG_ERR_ARG, "%s: znear must be finite and not negative", fn);
+  if (!(sc->fovy > 0.0 && sc->fovy < 180.0)) return fail(MCG_ERR_ARG, "%s: fovy must be in (0, 180) degrees", fn);
   for (int a = 0; a < 3; a++)
     for (int b = 0; b < 3; b++) {
       double s = 0;
       for (int k = 0; k < 3; k++) s += sc->cam_mat[3 * k + a] * sc->cam_mat[3 * k + b];
-      if (!(std::fabs(s - (a == b ? 1.0 : 0.0)) <= 1e-9)) return fail(MCG_ERR_ARG, "mcg_render: cam_mat is not orthonormal to 1e-9%s");
+      if (!(std::fabs(s - (a == b ? 1.0 : 0.0)) <= 1e-9)) return fail(MCG_ERR_ARG, "%s: cam_mat is not orthonormal to 1e-9", fn);
     }
-  if (!(std::fabs(norm3(sc->light_dir) - 1.0) <= 1e-9)) return fail(MCG_ERR_ARG, "mcg_render: light_dir is not a unit vector to 1e-9%s");
-  if (!e) return fail(MCG_ERR_ARG, "mcg_render: null handle%s");
+  if (!(std::fabs(norm3(sc->light_dir) - 1.0) <= 1e-9)) return fail(MCG_ERR_ARG, "%s: light_dir is not a unit vector to 1e-9", fn);
+  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
   if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
   if (!e->d_faces) {       // the first picture of this engine: the face table goes to the device (a blocking copy, once)
     HIP_OK(hipSetDevice(e->device));
@@ -1385,6 +1388,7 @@ int mcg_render(mcg_env* e, const mcg_scene* sc, int width, int height, int sampl
     if (err != hipSuccess) { (void)hipFree(d); return fail(MCG_ERR_HIP, "mcg_render: %s", hipGetErrorString(err)); }
     e->d_faces = d;
   }
+  const bool mounted = !(body == -1 && znear == 0.0);       // the world camera without a near plane keeps its own kernel
   RenderArgs A;
   memset(&A, 0, sizeof(A));
   for (int k = 0; k < 3; k++) { A.cam_pos[k] = sc->cam_pos[k]; A.light[k] = sc->light_dir[k]; A.target_half[k] = (float)sc->target_half[k]; }
@@ -1399,12 +1403,17 @@ int mcg_render(mcg_env* e, const mcg_scene* sc, int width, int height, int sampl
              && ((uintptr_t)out->geom % 4 == 0);
   memcpy(A.foff, e->foff, sizeof(A.foff));
   A.faces = e->d_faces; A.mask = mask; A.out = *out;
-  const size_t lds_bytes = (size_t)RENDER_HEAD_FLOATS * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;     // built-in tables: 35 KB
+  const size_t lds_bytes = (size_t)render_head_floats(mounted) * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;     // built-in tables: 35 KB
   if (lds_bytes > 64 * 1024) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: the face tables do not fit the 64 KB of LDS a workgroup asks for (about 3 200 faces)%s");
-  const hipError_t lerr = (hipError_t)launch_render(A, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
+  const hipError_t lerr = (hipError_t)launch_render(A, mounted, body, (float)znear, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
                                                     e->view.d + (size_t)(2 * e->cfg.nq + 2 * e->cfg.nv + 7) * e->cfg.n, e->d_model);
   if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_render: launch: %s", hipGetErrorString(lerr));
   return MCG_OK;
+}
+
+int mcg_render(mcg_env* e, const mcg_scene* sc, int width, int height, int samples, int target_at_goal, const uint8_t* mask,
+               const mcg_render_out* out, void* stream) {
+  return mcg_render_mounted(e, sc, -1, 0.0, width, height, samples, target_at_goal, mask, out, stream);
 }
 
 int mcg_compute_reward(const double* achieved, const double* desired, int n, int reward_type, double threshold,

@@ -9,9 +9,10 @@
 
 namespace mcg {
 
-int launch_render(const RenderArgs& A, int n, int nq, size_t lds_bytes, hipStream_t stream, const double* qpos, const double* goal,
-                  const mcg_model* model) {
-  hipLaunchKernelGGL(render_kernel, dim3(n), dim3(RENDER_LANES), lds_bytes, stream, A, qpos, goal, n, nq, model);
+int launch_render(const RenderArgs& A, bool mounted, int body, float znear, int n, int nq, size_t lds_bytes, hipStream_t stream,
+                  const double* qpos, const double* goal, const mcg_model* model) {
+  if (mounted) hipLaunchKernelGGL(render_kernel<true>, dim3(n), dim3(RENDER_LANES), lds_bytes, stream, A, qpos, goal, n, nq, model, body, znear);
+  else hipLaunchKernelGGL(render_kernel<false>, dim3(n), dim3(RENDER_LANES), lds_bytes, stream, A, qpos, goal, n, nq, model, body, znear);
   return (int)hipGetLastError();
 }
 

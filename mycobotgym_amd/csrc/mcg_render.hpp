@@ -18,6 +18,16 @@
 //      (strict `<` in ascending id order).  The tile's pixels pass through LDS so that a lane stores four consecutive pixels of a row:
 //      its bytes leave as whole dwords.
 // Nothing is written but the four output images (plain vector stores); the engine's state is only read.
+//
+// A camera mounted on a body (mcg_render_mounted; the reference's gripper_camera_rgb under `flange`) is the second instantiation of the
+// kernel, render_kernel<true>: lane 0 finishes the chain first, composes the camera's world pose in float64 from the carrier body's R, p
+// and parks it in the LDS head, and only then parks the per-body camera origins; the rays take the camera's matrix and position from
+// there, lifted into uniform registers once per wave.  It also carries the near plane.  render_kernel<false> is the world camera's
+// kernel as it was: the switch is a template parameter, so its instruction stream does not change.
+//
+// Visibility.  Surfaces are one-sided: a convex geom whose entry point lies behind the camera or before the near plane (depth along the
+// camera's -z below znear) is invisible along that ray, and the ray goes on to the other geoms.  So a camera inside a polytope does not
+// see it (OpenGL's back-face culling on closed convex solids): the gripper camera sits inside the flange's polytope and looks out of it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +45,11 @@ constexpr int RENDER_BOX_FLOATS = 8;                  // per mesh: box centre [3
 constexpr int RENDER_RGB = RENDER_FRAMES * RF_STRIDE + NMESH * RENDER_BOX_FLOATS;       // six colours x 4 floats (a lane picks its own: an LDS read, not a kernel-argument index)
 constexpr int RENDER_HEAD_FLOATS = RENDER_RGB + 6 * 4;                                  // 344: the faces follow, 16-byte aligned
 static_assert((RENDER_HEAD_FLOATS * 4) % 16 == 0, "the face table is read as b128");
+constexpr int RENDER_CAM = RENDER_HEAD_FLOATS;        // a mounted camera's head is longer: its world position [3], pad, rotation [9] (row-major world <- camera), pad
+constexpr int RENDER_CAM_MAT = RENDER_CAM + 4;
+constexpr int RENDER_HEAD_FLOATS_MOUNTED = RENDER_HEAD_FLOATS + 16;
+static_assert((RENDER_HEAD_FLOATS_MOUNTED * 4) % 16 == 0, "the face table is read as b128");
+constexpr int render_head_floats(bool mounted) { return mounted ? RENDER_HEAD_FLOATS_MOUNTED : RENDER_HEAD_FLOATS; }
 constexpr int RENDER_TILE_BYTES = (RENDER_LANES / 64) * 3 * 256 * 4;                    // per wave: 256 pixels x (packed r g b gray, depth, geom); after the faces
 constexpr float RENDER_BOX_SLACK = 1e-6f;             // the slab test is a filter: the faces decide
 
@@ -53,15 +68,19 @@ struct RenderArgs {
 };
 
 // the launch (mcg_render.hip): 0, or the hipError_t of the launch
-int launch_render(const RenderArgs& A, int n, int nq, size_t lds_bytes, hipStream_t stream, const double* qpos, const double* goal,
-                  const mcg_model* model);
+// mounted: render_kernel<true>, with A.cam_pos / A.cam_mat stated in the frame of engine body `body` (-1: the world) and the near plane
+// znear, metres along the camera's -z; otherwise the world camera's kernel, which reads neither
+int launch_render(const RenderArgs& A, bool mounted, int body, float znear, int n, int nq, size_t lds_bytes, hipStream_t stream,
+                  const double* qpos, const double* goal, const mcg_model* model);
 
 #ifdef MCG_RENDER_KERNELS      // the device code: compiled in mcg_render.hip alone (see there)
 struct RayHit { float t; int id; float nl, nd; };      // distance along the (unit) ray, geom id, n.(-light), n.(-ray) of the face hit
 
 // slab test of the ray o + t d against the box |x - c| <= h; on a hit (the ray enters from outside, in front of the camera): tin and the
-// entry face's axis
-MCG_DEV bool ray_box(const float* o, const float* d, const float* c, const float* h, float& tin, float& tout, int& axis) {
+// entry face's axis.  MOUNTED: a hit is a ray that is inside the box somewhere beyond tnear (the camera may be inside a mesh's box and
+// outside its polytope); the caller asks for tin > tnear where the box is the solid itself
+template <bool MOUNTED>
+MCG_DEV bool ray_box(const float* o, const float* d, const float* c, const float* h, float tnear, float& tin, float& tout, int& axis) {
   tin = -INFINITY; tout = INFINITY; axis = 0;
   _Pragma("unroll") for (int k = 0; k < 3; k++) {
     const float inv = __builtin_amdgcn_rcpf(d[k]);
@@ -70,7 +89,8 @@ MCG_DEV bool ray_box(const float* o, const float* d, const float* c, const float
     if (lo > tin) { tin = lo; axis = k; }
     tout = fminf(tout, hi);
   }
-  return tin <= tout && tin > 0.0f;
+  if constexpr (MOUNTED) return tin <= tout && tout > tnear;
+  else return tin <= tout && tin > 0.0f;
 }
 
 MCG_DEV void to_frame(const float* F, const float* dw, float* db) {      // db = R^T dw
@@ -78,9 +98,11 @@ MCG_DEV void to_frame(const float* F, const float* dw, float* db) {      // db =
 }
 
 // a box with its own frame (F: parked frame, or null = world with the camera at ow and the light lw)
-MCG_DEV void hit_box(RayHit& best, int id, const float* o, const float* d, const float* l, const float* c, const float* h) {
+template <bool MOUNTED>
+MCG_DEV void hit_box(RayHit& best, int id, const float* o, const float* d, const float* l, const float* c, const float* h, float tnear) {
   float tin, tout; int ax;
-  const bool hit = ray_box(o, d, c, h, tin, tout, ax) && h[0] > 0.0f && h[1] > 0.0f && h[2] > 0.0f;
+  bool hit = ray_box<MOUNTED>(o, d, c, h, tnear, tin, tout, ax) && h[0] > 0.0f && h[1] > 0.0f && h[2] > 0.0f;
+  if constexpr (MOUNTED) hit = hit && tin > tnear;
   if (hit && tin < best.t) {
     const float dk = sel3(ax, d[0], d[1], d[2]), lk = sel3(ax, l[0], l[1], l[2]);
     const float sg = dk > 0.0f ? -1.0f : 1.0f;                    // the entry face looks against the ray
@@ -88,20 +110,27 @@ MCG_DEV void hit_box(RayHit& best, int id, const float* o, const float* d, const
   }
 }
 
+// tnear: the near plane as a distance along this ray (MOUNTED alone; the world camera's entry tests stay `> 0`)
+template <bool MOUNTED>
 MCG_DEV RayHit trace(const RenderArgs& A, const float* __restrict__ lds, const float* camw, const float* lightw, const float* tpos,
-                     const float* table_c, const float* table_h, const float* cube_h, const float* dw) {
+                     const float* table_c, const float* table_h, const float* cube_h, const float* dw, float tnear) {
   RayHit best{INFINITY, -1, 0.0f, 0.0f};
   // 0: the ground plane z = 0, seen from above (infinite: the collision rule's plane)
-  if (dw[2] < 0.0f && camw[2] > 0.0f) { best.t = -camw[2] * __builtin_amdgcn_rcpf(dw[2]); best.id = 0; best.nl = -lightw[2]; best.nd = -dw[2]; }
-  hit_box(best, 1, camw, dw, lightw, table_c, table_h);
+  if constexpr (MOUNTED) {
+    const float t = -camw[2] * __builtin_amdgcn_rcpf(dw[2]);
+    if (dw[2] < 0.0f && camw[2] > 0.0f && t > tnear) { best.t = t; best.id = 0; best.nl = -lightw[2]; best.nd = -dw[2]; }
+  } else {
+    if (dw[2] < 0.0f && camw[2] > 0.0f) { best.t = -camw[2] * __builtin_amdgcn_rcpf(dw[2]); best.id = 0; best.nl = -lightw[2]; best.nd = -dw[2]; }
+  }
+  hit_box<MOUNTED>(best, 1, camw, dw, lightw, table_c, table_h, tnear);
   if (A.draw_cube) {                                               // wave-uniform
     const float* F = lds + NB * RF_STRIDE;
     float db[3]; to_frame(F, dw, db);
     const float zero[3] = {0.0f, 0.0f, 0.0f};
-    hit_box(best, 2, F + RF_O, db, F + RF_L, zero, cube_h);
+    hit_box<MOUNTED>(best, 2, F + RF_O, db, F + RF_L, zero, cube_h, tnear);
   }
-  hit_box(best, 3, camw, dw, lightw, tpos, A.target_half);
-  const float4* __restrict__ faces = (const float4*)(lds + RENDER_HEAD_FLOATS);
+  hit_box<MOUNTED>(best, 3, camw, dw, lightw, tpos, A.target_half, tnear);
+  const float4* __restrict__ faces = (const float4*)(lds + render_head_floats(MOUNTED));
   int body_at = -1;
   float db[3];
   const float* F = lds;
@@ -110,7 +139,7 @@ MCG_DEV RayHit trace(const RenderArgs& A, const float* __restrict__ lds, const f
     if (body != body_at) { body_at = body; F = lds + body * RF_STRIDE; to_frame(F, dw, db); }      // meshes 5, 6, 7 share body 5
     const float* B = lds + RENDER_FRAMES * RF_STRIDE + m * RENDER_BOX_FLOATS;
     float bin, bout; int ax;
-    const bool inbox = ray_box(F + RF_O, db, B, B + 3, bin, bout, ax) && bin < best.t;
+    const bool inbox = ray_box<MOUNTED>(F + RF_O, db, B, B + 3, tnear, bin, bout, ax) && bin < best.t;
     if (!__any(inbox)) continue;
     float tin = 0.0f, tout = INFINITY, nx = 0.0f, ny = 0.0f, nz = 0.0f;
     bool miss = false;
@@ -126,7 +155,7 @@ MCG_DEV RayHit trace(const RenderArgs& A, const float* __restrict__ lds, const f
         miss = miss || (den == 0.0f && f.w < 0.0f);
       }
     }
-    if (!miss && tin <= tout && tin > 0.0f && tin < best.t) {
+    if (!miss && tin <= tout && (MOUNTED ? tin > tnear : tin > 0.0f) && tin < best.t) {
       best.t = tin; best.id = 4 + m;
       best.nl = -(nx * F[RF_L] + ny * F[RF_L + 1] + nz * F[RF_L + 2]);
       best.nd = -(nx * db[0] + ny * db[1] + nz * db[2]);
@@ -147,9 +176,10 @@ MCG_DEV void render_joint(const TrigC& T, int sg, const real* r, real ang, real*
   }
 }
 
-MCG_DEV void render_park(const RenderArgs& A, float* lds, int slot, const real* R, const real* p) {
+// cam: the camera's world position
+MCG_DEV void render_park(const RenderArgs& A, const real* cam, float* lds, int slot, const real* R, const real* p) {
   float* F = lds + slot * RF_STRIDE;
-  const real c[3] = {A.cam_pos[0] - p[0], A.cam_pos[1] - p[1], A.cam_pos[2] - p[2]};
+  const real c[3] = {cam[0] - p[0], cam[1] - p[1], cam[2] - p[2]};
   for (int k = 0; k < 9; k++) F[k] = (float)R[k];
   for (int j = 0; j < 3; j++) {
     F[RF_O + j] = (float)(R[j] * c[0] + R[3 + j] * c[1] + R[6 + j] * c[2]);
@@ -159,18 +189,25 @@ MCG_DEV void render_park(const RenderArgs& A, float* lds, int slot, const real* 
 }
 
 namespace {       // (internal linkage, like the other kernels: a text section of its own, placed in definition order)
-// qpos: [nq, N] (the engine's state), goal: [3, N]
+// qpos: [nq, N] (the engine's state), goal: [3, N].  MOUNTED: the camera rides on body cam_body (see the head of this file); the two last
+// arguments trail the others so that the world camera's kernel, which does not read them, finds its own where they were
+template <bool MOUNTED>
 __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, const double* __restrict__ qpos, const double* __restrict__ goal,
-                                                              int n, int nq, const mcg_model* __restrict__ Pg) {
+                                                              int n, int nq, const mcg_model* __restrict__ Pg, int cam_body, float cam_znear) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int env = blockIdx.x;
   if (env >= n) return;
   if (A.mask && A.mask[env] == 0) return;                          // workgroup-uniform
   const int tid = threadIdx.x;
+  constexpr int HEAD = render_head_floats(MOUNTED);
 
   if (tid == 0) {
     const TrigC T = load_trig();
     real R[9], p[3], R5[9], p5[3];
+    // MOUNTED: the bodies' R, p wait as float64 where the faces will lie (lane 0 alone reads them back, before the barrier), the
+    // carrier's are kept: the camera's world pose has to be known before any body's camera origin can be parked
+    real* const chain = (real*)(lds + HEAD);
+    real Rb[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, pb[3] = {0.0, 0.0, 0.0};
     for (int k = 0; k < 9; k++) R[k] = Pg->base_mat[k];
     for (int k = 0; k < 3; k++) p[k] = Pg->base_pos[k];
     static_for<NB>([&](auto I) { constexpr int i = I;
@@ -184,8 +221,29 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
         for (int k = 0; k < 9; k++) R5[k] = R[k];
         for (int k = 0; k < 3; k++) p5[k] = p[k];
       }
-      render_park(A, lds, i, R, p); });
+      if constexpr (MOUNTED) {
+        for (int k = 0; k < 9; k++) chain[12 * i + k] = R[k];
+        for (int k = 0; k < 3; k++) chain[12 * i + 9 + k] = p[k];
+        if (i == cam_body) {
+          for (int k = 0; k < 9; k++) Rb[k] = R[k];
+          for (int k = 0; k < 3; k++) pb[k] = p[k];
+        }
+      } else {
+        render_park(A, A.cam_pos, lds, i, R, p);
+      } });
     static_assert(PAR[6] == 5 && PAR[7] == 6 && PAR[8] == 5 && PAR[9] == 8 && PAR[10] == 5 && PAR[11] == 5, "the chain above");
+    real camd[3];                                                  // MOUNTED: the camera's world position
+    if constexpr (MOUNTED) {                                       // world <- camera = (world <- body) (body <- camera); cam_body == -1: Rb, pb are the identity
+      for (int k = 0; k < 3; k++) {
+        camd[k] = pb[k] + Rb[3*k] * A.cam_pos[0] + Rb[3*k+1] * A.cam_pos[1] + Rb[3*k+2] * A.cam_pos[2];
+        lds[RENDER_CAM + k] = (float)camd[k];
+        for (int j = 0; j < 3; j++)
+          lds[RENDER_CAM_MAT + 3*k + j] = (float)(Rb[3*k] * A.cam_mat[j] + Rb[3*k+1] * A.cam_mat[3 + j] + Rb[3*k+2] * A.cam_mat[6 + j]);
+      }
+      lds[RENDER_CAM + 3] = 0.0f;
+      for (int k = 9; k < 12; k++) lds[RENDER_CAM_MAT + k] = 0.0f;
+      for (int i = 0; i < NB; i++) render_park(A, camd, lds, i, chain + 12 * i, chain + 12 * i + 9);
+    }
     if (A.draw_cube) {                                             // nq == 19: the free joint's position and quaternion (normalised as mj_kinematics does)
       real q[4], Rc[9], pc[3];
       for (int k = 0; k < 3; k++) pc[k] = qpos[(size_t)(NB + k) * n + env];
@@ -194,7 +252,7 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
       const bool tiny = nn < MINVAL;
       for (int k = 0; k < 4; k++) q[k] = tiny ? (k == 0 ? 1.0 : 0.0) : q[k] / nn;
       quat_to_mat(q, Rc);
-      render_park(A, lds, NB, Rc, pc);
+      render_park(A, MOUNTED ? camd : A.cam_pos, lds, NB, Rc, pc);
     } else {
       for (int k = 0; k < RF_STRIDE; k++) lds[NB * RF_STRIDE + k] = 0.0f;
     }
@@ -206,7 +264,7 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
   if (tid >= 192 && tid < 192 + 24) lds[RENDER_RGB + tid - 192] = ((tid - 192) & 3) < 3 ? A.rgb[(tid - 192) >> 2][(tid - 192) & 3] : 0.0f;
   __syncthreads();
   {   // the faces, with the camera folded in
-    float4* lf = (float4*)(lds + RENDER_HEAD_FLOATS);
+    float4* lf = (float4*)(lds + HEAD);
     const int total = A.foff[NMESH];
     for (int k = tid; k < total; k += RENDER_LANES) {
       int m = 0;
@@ -219,7 +277,14 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
   }
   __syncthreads();
 
-  const float camw[3] = {(float)A.cam_pos[0], (float)A.cam_pos[1], (float)A.cam_pos[2]};
+  // MOUNTED: the camera from the LDS head, once per wave, into uniform registers
+  float camm[3] = {0.0f, 0.0f, 0.0f}, cmat[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (MOUNTED) {
+    for (int k = 0; k < 3; k++) camm[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lds[RENDER_CAM + k])));
+    for (int k = 0; k < 9; k++) cmat[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lds[RENDER_CAM_MAT + k])));
+  }
+  const float* const cm = MOUNTED ? cmat : A.cam_matf;
+  const float camw[3] = {MOUNTED ? camm[0] : (float)A.cam_pos[0], MOUNTED ? camm[1] : (float)A.cam_pos[1], MOUNTED ? camm[2] : (float)A.cam_pos[2]};
   const float lightw[3] = {(float)A.light[0], (float)A.light[1], (float)A.light[2]};
   float tpos[3], table_c[3], table_h[3], cube_h[3];
   for (int k = 0; k < 3; k++) {
@@ -237,7 +302,7 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
   // a wave's tile passes through LDS: rays are traced in four compact 8 x 8 blocks (what a wave-wide ballot culls is a mesh that no ray
   // of 64 NEIGHBOURING pixels meets: an 8 x 8 block does that four times as finely as every fourth pixel of 16 x 16), the stores want four
   // consecutive pixels of a row per lane
-  uint32_t* tile_px = (uint32_t*)(lds + RENDER_HEAD_FLOATS + 4 * A.foff[NMESH]) + wave * (3 * 256);      // per pixel: r g b gray | depth | geom
+  uint32_t* tile_px = (uint32_t*)(lds + HEAD + 4 * A.foff[NMESH]) + wave * (3 * 256);      // per pixel: r g b gray | depth | geom
   const int ntiles = tiles_x * tiles_y;
   for (int tile0 = 0; tile0 < ntiles; tile0 += RENDER_LANES / 64) {        // the same trip count for the four waves: barriers inside
     const int tile = tile0 + wave;
@@ -255,8 +320,10 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
         const float rn = __frsqrt_rn(u * u + v * v + A.focal * A.focal);
         const float dc[3] = {u * rn, v * rn, -A.focal * rn};
         float dw[3];
-        for (int k = 0; k < 3; k++) dw[k] = A.cam_matf[3*k] * dc[0] + A.cam_matf[3*k+1] * dc[1] + A.cam_matf[3*k+2] * dc[2];
-        const RayHit h = trace(A, lds, camw, lightw, tpos, table_c, table_h, cube_h, dw);
+        for (int k = 0; k < 3; k++) dw[k] = cm[3*k] * dc[0] + cm[3*k+1] * dc[1] + cm[3*k+2] * dc[2];
+        // depth along the camera's -z = t * focal * rn: the near plane as a distance along this ray
+        const float tnear = MOUNTED ? cam_znear * __builtin_amdgcn_rcpf(A.focal * rn) : 0.0f;
+        const RayHit h = trace<MOUNTED>(A, lds, camw, lightw, tpos, table_c, table_h, cube_h, dw, tnear);
         if (centre_only || S == 1) { dep1 = h.id < 0 ? INFINITY : h.t * A.focal * rn; gid1 = h.id; }
         if (!centre_only) {
           const int ci = h.id < 0 ? 5 : (h.id < 4 ? h.id : 4);

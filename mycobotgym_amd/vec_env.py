@@ -91,7 +91,7 @@ def _table_initial_state(table: dict, has_object: bool, fetch_env: bool, mesh_in
 
 
 def load_scene(path: Optional[str] = None) -> dict:
-    """The compiled scene (tools/compile_scene.py): the world cameras, the light, the colours."""
+    """The compiled scene (tools/compile_scene.py): the world cameras, the body cameras, the light, the colours."""
     with open(path or os.path.join(_ASSETS, "scene.json")) as f:
         return json.load(f)
 
@@ -340,18 +340,29 @@ class MyCobotVecEnv:
         return float(ms.value)
 
     # ------------------------------------------------------------------------------------------------- pictures
-    def _scene(self, camera: str, scene: Optional[dict]) -> "_abi.McgScene":
+    def _scene(self, camera: str, scene: Optional[dict]):
+        """-> (McgScene, body, znear): a world camera (body -1, no near plane) or one of ``scene["body_cameras"]``, stated in the frame
+        of the engine body it rides on."""
         if scene is None:
             if not hasattr(self, "_default_scene"):
                 self._default_scene = load_scene()
             scene = self._default_scene
-        return _abi.McgScene.from_dict(scene, camera)
+        mounted = scene.get("body_cameras", {})
+        if camera in scene["cameras"]:
+            return _abi.McgScene.from_dict(scene, camera), -1, 0.0
+        if camera in mounted:
+            cam = mounted[camera]
+            return _abi.McgScene.from_camera(scene, cam), int(cam["body"]), float(cam["znear"])
+        raise ValueError(f"unknown camera {camera!r}; the scene has the world cameras {sorted(scene['cameras'])} and the body cameras "
+                         f"{sorted(mounted)}")
 
     def render_into(self, out: dict, camera: str = "sideview", samples: int = 1, show_goal: bool = True,
-                    mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None):
+                    mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None, znear: Optional[float] = None):
         """Raw form of ``render``: ``out`` maps any of rgb (uint8 [N, H, W, 3]), gray (uint8 [N, H, W]), depth (float32 [N, H, W]),
         geom (int8 [N, H, W]) to contiguous device tensors of one H, W, which the kernel fills (where ``mask`` is set); enqueued on the
-        current stream, not synchronised."""
+        current stream, not synchronised.  ``camera``: a world camera or a body camera of the scene (``gripper_camera_rgb``: it rides on
+        the flange, its pose follows each environment's arm).  ``znear``: the near plane in metres, in place of the camera's own (a
+        world camera has none: 0)."""
         want = {"rgb": (torch.uint8, 3), "gray": (torch.uint8, None), "depth": (torch.float32, None), "geom": (torch.int8, None)}
         hw = None
         for k, t in out.items():
@@ -370,11 +381,17 @@ class MyCobotVecEnv:
             if m.shape != (self.num_envs,):
                 raise ValueError("mask must have shape (num_envs,)")
         ro = _abi.McgRenderOut(**{k: t.data_ptr() for k, t in out.items()})
-        sc = self._scene(camera, scene)
+        sc, body, cam_znear = self._scene(camera, scene)
+        znear = cam_znear if znear is None else float(znear)
         h, w = hw if hw is not None else (0, 0)
+        mp = None if m is None else C.c_void_p(m.data_ptr())
         with torch.cuda.device(self.device):
-            _abi.check(self._lib.mcg_render(self._h, C.byref(sc), int(w), int(h), int(samples), int(bool(show_goal)),
-                                            None if m is None else C.c_void_p(m.data_ptr()), C.byref(ro), self._stream()), "mcg_render")
+            if body < 0 and znear == 0.0:
+                _abi.check(self._lib.mcg_render(self._h, C.byref(sc), int(w), int(h), int(samples), int(bool(show_goal)), mp, C.byref(ro),
+                                                self._stream()), "mcg_render")
+            else:
+                _abi.check(self._lib.mcg_render_mounted(self._h, C.byref(sc), body, znear, int(w), int(h), int(samples),
+                                                        int(bool(show_goal)), mp, C.byref(ro), self._stream()), "mcg_render_mounted")
         return out
 
     def render(self, camera: str = "sideview", width: int = 480, height: int = 480, samples: int = 1, mode: str = "rgb_array",
@@ -428,6 +445,10 @@ class MyCobotImgVecEnv(MyCobotVecEnv):
     ``sideview``, grayscale as ``preprocess_frame`` makes it (utils.py:580-595) -- not a Dict; ``achieved_goal`` / ``desired_goal`` travel
     in ``info``.
 
+    ``camera``: a world camera's or a body camera's name (``"gripper_camera_rgb"``: the wrist view), or a tuple of names: the observation
+    is then uint8 [N, C, S, S], one channel per camera in the order given, at the cost of one launch per camera (the channels are
+    planes of one [C, N, S, S] buffer, which the kernel fills in place; the observation is its [N, C, S, S] view).
+
     The reference's ``_get_obs`` calls the renderer directly, not ``render()``: the target site is NOT moved to the goal in its observations
     and stays at its MJCF position (SURVEY D-15).  ``show_goal=True`` draws it at the goal instead.
 
@@ -442,17 +463,23 @@ class MyCobotImgVecEnv(MyCobotVecEnv):
         self._img_auto_reset = bool(auto_reset)
         super().__init__(num_envs, *args, auto_reset=False, image_obs=False, **kwargs)
         self.camera, self.image_size, self.samples, self.show_goal = camera, int(image_size), int(samples), bool(show_goal)
+        self._cameras = (camera,) if isinstance(camera, str) else tuple(camera)
+        if not self._cameras:
+            raise ValueError("camera: a name or a non-empty tuple of names")
         self._img_scene = scene
-        self._scene(camera, scene)                 # an unknown camera fails here, not at the first step
-        s = self.image_size
-        self.single_observation_space = Box(0, 255, (1, s, s), np.uint8)         # mycobot.py:543-545
+        for cam in self._cameras:
+            self._scene(cam, scene)                # an unknown camera fails here, not at the first step
+        s, c = self.image_size, len(self._cameras)
+        self.single_observation_space = Box(0, 255, (c, s, s), np.uint8)         # mycobot.py:543-545
         self.observation_space = batch_box(self.single_observation_space, self.num_envs)
-        self._img = torch.zeros(self.num_envs, 1, s, s, dtype=torch.uint8, device=self.device)
-        self._final_img = torch.zeros_like(self._img)
+        # one contiguous [N, S, S] plane per camera; the observation is the [N, C, S, S] view of the planes
+        self._img = torch.zeros(c, self.num_envs, s, s, dtype=torch.uint8, device=self.device).permute(1, 0, 2, 3)
+        self._final_img = torch.zeros(c, self.num_envs, s, s, dtype=torch.uint8, device=self.device).permute(1, 0, 2, 3)
 
     def _draw(self, dst: torch.Tensor, mask: Optional[torch.Tensor] = None):
-        self.render_into({"gray": dst[:, 0]}, camera=self.camera, samples=self.samples, show_goal=self.show_goal, mask=mask,
-                         scene=self._img_scene)
+        for c, cam in enumerate(self._cameras):
+            self.render_into({"gray": dst[:, c]}, camera=cam, samples=self.samples, show_goal=self.show_goal, mask=mask,
+                             scene=self._img_scene)
 
     def _goal_info(self, b: dict) -> dict:
         return {"achieved_goal": b["achieved_goal"], "desired_goal": b["desired_goal"]}

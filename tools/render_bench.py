@@ -2,15 +2,23 @@
 """Device-event timing of mcg_render next to the step of the same engine.
 
     python tools/render_bench.py [--envs 8192] [--reps 20] [--out profiles/render/render_bench.json]
+    python tools/render_bench.py --alternate-against ab/parent/libmycobot_hip.so [--rounds 3] [--out ...]
 
 Per case (64 x 64 at samples 1, 2, 4 on --envs environments; 480 x 480 on 256): warm-up launches, then `reps` windows of `inner`
 back-to-back launches between two events on the launch stream; reported: median and spread of the per-launch time.  The states are
 a seeded random-policy rollout with desynchronised episodes (what a training run renders), not the reset pose.  Also: one step() of
-the -v1 image engine (step + render + masked reset + render) against the -v0 state engine of the same configuration.
+the -v1 image engine (step + render + masked reset + render) against the -v0 state engine of the same configuration.  The camera is
+`sideview`; the 64 x 64 cases at samples 1 and 2 are measured from `gripper_camera_rgb` (the camera on the flange) as well.
+
+--alternate-against LIB: the world-camera case (sideview, 64 x 64, samples 1 and 2) of this build and of another build of the library
+(the parent commit's), alternated `rounds` times in one call, each measurement in a process of its own (the library is chosen through
+MCG_LIB when the package is imported).  A world-camera picture must cost what it cost before the mounted camera: the medians are to lie
+within the other build's own min-max spread.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -42,31 +50,74 @@ def rollout(envs, steps, seed=0):
         envs.step(torch.rand(envs.num_envs, envs.action_dim, generator=g) * 2 - 1)
 
 
+def env_name(cfg):
+    task, ctrl = cfg.split("-")
+    return f"MyCobot{'Reach' if task == 'reach' else 'PickAndPlace'}-Dense-{ctrl}"
+
+
+def render_case(cfg, n, w, h, samples, camera, reps):
+    envs = mg.make(env_name(cfg) + "-v0", num_envs=n, seed=1)
+    envs.reset(seed=1)
+    rollout(envs, 30)
+    out = {"gray": torch.zeros(n, h, w, dtype=torch.uint8, device=envs.device)} if samples > 1 or w == 64 else \
+          {"rgb": torch.zeros(n, h, w, 3, dtype=torch.uint8, device=envs.device)}
+    r = timed(lambda: envs.render_into(out, camera=camera, samples=samples), warmup=5, reps=reps, inner=10)
+    rays = n * w * h * samples * samples
+    r.update(config=cfg, what="mcg_render" if camera == "sideview" else "mcg_render_mounted", camera=camera, envs=n, width=w, height=h,
+             samples=samples, output=list(out)[0], grays_per_s=rays / (r["median_ms"] * 1e-3) / 1e9)
+    envs.close()
+    return r
+
+
+def alternate(args):
+    """This build against another one, world camera: rounds x (other, this), every measurement in its own process."""
+    me = os.path.abspath(__file__)
+    res = {"alternation": True, "against": args.alternate_against, "envs": args.envs, "cases": []}
+    for k in range(args.rounds):
+        for which, lib in (("other", os.path.abspath(args.alternate_against)), ("this", None)):
+            env = dict(os.environ)
+            env.pop("MCG_LIB", None)
+            if lib:
+                env["MCG_LIB"] = lib
+            p = subprocess.run([sys.executable, me, "--world-only", "--envs", str(args.envs), "--reps", str(args.reps), "--configs", args.configs],
+                               env=env, capture_output=True, text=True, timeout=300)
+            if p.returncode != 0:
+                sys.exit(f"round {k}, {which} build: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")      # nothing more is started
+            for line in p.stdout.splitlines():
+                if line.startswith("{"):
+                    r = json.loads(line); r.update(build=which, round=k)
+                    res["cases"].append(r); print(json.dumps(r), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--configs", default="reach-joint,pnp-joint")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--alternate-against", default=None, metavar="LIB", help="another build of libmycobot_hip.so (the parent commit's)")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--world-only", action="store_true", help="the world-camera 64 x 64 cases at samples 1 and 2 alone (a child of --alternate-against)")
     args = ap.parse_args()
+    if args.alternate_against:
+        res = alternate(args)
+        write(args.out, res)
+        return
     if not torch.cuda.is_available():
         sys.exit("render_bench needs the GPU: a timing taken anywhere else says nothing")
     res = {"device": torch.cuda.get_device_name(0), "envs": args.envs, "cases": []}
     for cfg in args.configs.split(","):
-        task, ctrl = cfg.split("-")
-        name = f"MyCobot{'Reach' if task == 'reach' else 'PickAndPlace'}-Dense-{ctrl}"
-        for n, w, h, samples in ((args.envs, 64, 64, 1), (args.envs, 64, 64, 2), (args.envs, 64, 64, 4), (256, 480, 480, 1)):
-            envs = mg.make(name + "-v0", num_envs=n, seed=1)
-            envs.reset(seed=1)
-            rollout(envs, 30)
-            out = {"gray": torch.zeros(n, h, w, dtype=torch.uint8, device=envs.device)} if samples > 1 or w == 64 else \
-                  {"rgb": torch.zeros(n, h, w, 3, dtype=torch.uint8, device=envs.device)}
-            r = timed(lambda: envs.render_into(out, samples=samples), warmup=5, reps=args.reps, inner=10)
-            rays = n * w * h * samples * samples
-            r.update(config=cfg, what="mcg_render", envs=n, width=w, height=h, samples=samples, output=list(out)[0],
-                     grays_per_s=rays / (r["median_ms"] * 1e-3) / 1e9)
+        name = env_name(cfg)
+        cases = [(args.envs, 64, 64, 1, "sideview"), (args.envs, 64, 64, 2, "sideview")]
+        if not args.world_only:
+            cases += [(args.envs, 64, 64, 4, "sideview"), (256, 480, 480, 1, "sideview"),
+                      (args.envs, 64, 64, 1, "gripper_camera_rgb"), (args.envs, 64, 64, 2, "gripper_camera_rgb")]
+        for n, w, h, samples, camera in cases:
+            r = render_case(cfg, n, w, h, samples, camera, args.reps)
             res["cases"].append(r); print(json.dumps(r), flush=True)
-            envs.close()
+        if args.world_only:
+            continue
         # one step of the engine with and without pictures
         v0 = mg.make(name + "-v0", num_envs=args.envs, seed=1); v1 = mg.make(name + "-v1", num_envs=args.envs, seed=1)
         for e, what in ((v0, "step -v0"), (v1, "step -v1 (step + render + masked reset + render, samples 2)")):
@@ -77,9 +128,13 @@ def main():
             r.update(config=cfg, what=what, envs=args.envs)
             res["cases"].append(r); print(json.dumps(r), flush=True)
             e.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    write(args.out, res)
+
+
+def write(path, res):
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
             json.dump(res, f, indent=1); f.write("\n")
 
 
