@@ -261,6 +261,65 @@ int mcg_render(mcg_env* env, const mcg_scene* scene, int width, int height, int 
 int mcg_render_mounted(mcg_env* env, const mcg_scene* scene, int body, double znear, int width, int height, int samples,
                        int target_at_goal, const uint8_t* mask /* [N] device or NULL = all */, const mcg_render_out* out, void* stream);
 
+/* ---- Per-environment scenes: camera, light and colours from a device table with one row per environment.
+   A scene table is a device array double [N, MCG_SCENE_ENV_DOUBLES], row-major.  A row is the head of mcg_scene, in its order: */
+#define MCG_SCENE_ENV_DOUBLES 40
+#define MCG_SCENE_CAM_POS 0          /* [3]  in the carrier's frame: the world, or the engine body the camera rides on */
+#define MCG_SCENE_CAM_MAT 3          /* [9]  row-major carrier <- camera, as mcg_scene.cam_mat */
+#define MCG_SCENE_FOVY 12            /*      degrees */
+#define MCG_SCENE_LIGHT_DIR 13       /* [3]  unit */
+#define MCG_SCENE_LIGHT_AMBIENT 16
+#define MCG_SCENE_LIGHT_DIFFUSE 17
+#define MCG_SCENE_HEAD_AMBIENT 18
+#define MCG_SCENE_HEAD_DIFFUSE 19
+#define MCG_SCENE_RGB 20             /* [6][3] ground, table, cube, target, mesh, sky, each in [0, 1] */
+#define MCG_SCENE_PAD 38             /* [2]  zero */
+#define MCG_SCENE_RAND_CAM_SLOTS 8
+
+/* mcg_render_mounted with environment e's camera, fovy, light, shading coefficients and colours taken from row e of `scenes`; `body`,
+   `znear` and `target_half` are per call (all rows of one call describe the same named camera).  Host checks as mcg_render_mounted's
+   (those of the scene's values excepted: the rows are device memory), plus a null table or target_half (MCG_ERR_ARG); before any HIP
+   call.  The values of a row cannot be checked on the host: the kernel is safe for any bit pattern in a row -- no address and no loop
+   bound depends on one -- and a bad row gives a bad picture of that environment and nothing else. */
+int mcg_render_scenes(mcg_env* env, const double* scenes /* device [N, MCG_SCENE_ENV_DOUBLES] */, const double target_half[3], int body,
+                      double znear, int width, int height, int samples, int target_at_goal,
+                      const uint8_t* mask /* [N] device or NULL = all */, const mcg_render_out* out, void* stream);
+
+/* Ranges of mcg_scene_randomize; all doubles.  A half range h draws from [-h, h]; a scale pair draws from [lo, hi]. */
+typedef struct mcg_scene_rand {
+  double cam_pos[3];                 /* half ranges, metres, in the carrier's frame */
+  double cam_rot[3];                 /* half ranges of a rotation vector, radians */
+  double fovy_scale[2];
+  double light_tilt;                 /* largest tilt of the light's direction, radians, in [0, pi] */
+  double light_ambient_scale[2];
+  double light_diffuse_scale[2];
+  double head_scale[2];              /* one factor for both headlight terms */
+  double rgb[6];                     /* half range per colour class (ground, table, cube, target, mesh, sky), the same for its three channels */
+} mcg_scene_rand;
+
+/* Fills the rows of `scenes` (where mask is non-zero; the others are left as they are) with the base scene jittered per environment and
+   per episode.  Uniforms: Philox4x32-10 keyed as every reset draw, by (seed, global environment id, episode, draw index), stream 2
+   (0: goals, 1: mass and friction), the episode being the state's counter at the time of the call; so a table is a function of the
+   state, does not depend on how environments are split over engines, and need not be checkpointed.  Draw d gives the pair (u0, u1);
+   a mapped value is fma(hi - lo, u, lo).
+     world block (the same for every camera of an environment)
+       0      tilt = light_tilt * sqrt(u0), azimuth = 2 pi u1: light_dir = cos(tilt) d0 + sin(tilt) (cos(az) e1 + sin(az) e2),
+              e1 = normalize(x^ x d0) (y^ for x^ where |d0.x| > 0.9), e2 = d0 x e1
+       1      light_ambient scale, light_diffuse scale
+       2      headlight scale (both terms), -
+       3 + k  colour channels 2k and 2k + 1 of the row's 18 (k = 0..8): base + offset, clamped to [0, 1]
+     camera block, draw 32 + 4 * cam_slot + ...
+       0      dx, dy;  1  dz, fovy scale;  2  w_x, w_y;  3  w_z, -
+       cam_pos = base + d; cam_mat = R(w) base, R(w) = I + a K + b K^2, K = [w]x, a = sin|w| / |w|, b = (1 - cos|w|) / |w|^2
+       (a = 1, b = 1/2 below |w| = 1e-12); scales multiply the base's value.
+   A zero offset, a zero tilt and a zero rotation vector leave the base's values as they are, signed zeros included: with all half
+   ranges zero and all scales [1, 1] a row is the base scene bit for bit.  Host checks, before any HIP call (MCG_ERR_ARG):
+   null handle / base / ranges / scenes, cam_slot outside 0..7, a range negative or not finite, a scale pair with lo <= 0 or lo > hi,
+   base.fovy * fovy_scale[1] >= 180, light_tilt outside [0, pi], a base that fails mcg_render's checks of a scene. */
+int mcg_scene_randomize(mcg_env* env, const mcg_scene* base, const mcg_scene_rand* ranges, int cam_slot /* 0..7 */,
+                        const uint8_t* mask /* [N] device or NULL = all */, double* scenes /* device [N, MCG_SCENE_ENV_DOUBLES], out */,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

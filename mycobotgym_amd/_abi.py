@@ -129,12 +129,86 @@ class McgRenderOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rgb", "gray", "depth", "geom")]
 
 
+# one row of a scene table (include/mcg.h: MCG_SCENE_*): camera, light, shading coefficients and colours of one environment
+SCENE_ENV_DOUBLES = 40
+SCENE_CAM_POS, SCENE_CAM_MAT, SCENE_FOVY, SCENE_LIGHT_DIR = 0, 3, 12, 13
+SCENE_LIGHT_AMBIENT, SCENE_LIGHT_DIFFUSE, SCENE_HEAD_AMBIENT, SCENE_HEAD_DIFFUSE = 16, 17, 18, 19
+SCENE_RGB, SCENE_PAD = 20, 38
+SCENE_RAND_CAM_SLOTS = 8
+RGB_CLASSES = ("ground", "table", "cube", "target", "mesh", "sky")       # the order of a row's colours, and of mcg_scene_rand.rgb
+
+
+class McgSceneRand(C.Structure):
+    """Ranges of mcg_scene_randomize (include/mcg.h: mcg_scene_rand); ``from_dict``: missing keys mean no jitter."""
+    _fields_ = [("cam_pos", d * 3), ("cam_rot", d * 3), ("fovy_scale", d * 2), ("light_tilt", d), ("light_ambient_scale", d * 2),
+                ("light_diffuse_scale", d * 2), ("head_scale", d * 2), ("rgb", d * 6)]
+
+    @classmethod
+    def from_dict(cls, ranges: dict) -> "McgSceneRand":
+        known = {n for n, _ in cls._fields_}
+        if set(ranges) - known:
+            raise ValueError(f"unknown range(s) {sorted(set(ranges) - known)}; known: {sorted(known)}")
+        r = cls()
+        for name in ("cam_pos", "cam_rot"):       # a half range: one number for the three components, or three
+            v = np.broadcast_to(np.asarray(ranges.get(name, 0.0), dtype=np.float64), (3,))
+            for j in range(3):
+                getattr(r, name)[j] = float(v[j])
+        for name in ("fovy_scale", "light_ambient_scale", "light_diffuse_scale", "head_scale"):
+            lo, hi = ranges.get(name, (1.0, 1.0))
+            getattr(r, name)[0], getattr(r, name)[1] = float(lo), float(hi)
+        r.light_tilt = float(ranges.get("light_tilt", 0.0))
+        rgb = ranges.get("rgb", 0.0)
+        if isinstance(rgb, dict):
+            if set(rgb) - set(RGB_CLASSES):
+                raise ValueError(f"rgb: unknown colour class(es) {sorted(set(rgb) - set(RGB_CLASSES))}; known: {list(RGB_CLASSES)}")
+            rgb = [rgb.get(k, 0.0) for k in RGB_CLASSES]
+        v = np.broadcast_to(np.asarray(rgb, dtype=np.float64), (6,))
+        for j in range(6):
+            r.rgb[j] = float(v[j])
+        return r
+
+
+def scene_row(scene, camera=None) -> np.ndarray:
+    """One row of a scene table, float64 [40]: of an ``McgScene``, or of a compiled scene dict and ``camera`` (a world or body camera's
+    name, or a camera dict pos / mat / fovy).  A row is the head of ``mcg_scene`` (everything before ``target_half``) and two zeros."""
+    if not isinstance(scene, McgScene):
+        if isinstance(camera, dict):
+            cam = camera
+        elif camera in scene["cameras"]:
+            cam = scene["cameras"][camera]
+        elif camera in scene.get("body_cameras", {}):
+            cam = scene["body_cameras"][camera]
+        else:
+            raise ValueError(f"unknown camera {camera!r}")
+        scene = McgScene.from_camera(scene, cam)
+    row = np.zeros(SCENE_ENV_DOUBLES)
+    row[:SCENE_PAD] = np.frombuffer(bytes(scene), dtype=np.float64)[:SCENE_PAD]
+    return row
+
+
+def scene_from_row(row, target_half=None):
+    """Inverse of ``scene_row``: -> (camera dict pos / mat / fovy, scene dict light / headlight / rgb), the shapes the compiled scene has
+    (a body camera's pos / mat stay in its carrier's frame).  ``target_half`` is not part of a row: given, it goes into the scene dict."""
+    r = np.asarray(row, dtype=np.float64).reshape(-1)
+    if r.shape != (SCENE_ENV_DOUBLES,):
+        raise ValueError(f"a row has {SCENE_ENV_DOUBLES} doubles, got {r.shape}")
+    cam = {"pos": r[SCENE_CAM_POS:SCENE_CAM_POS + 3].tolist(), "mat": r[SCENE_CAM_MAT:SCENE_CAM_MAT + 9].reshape(3, 3).tolist(),
+           "fovy": float(r[SCENE_FOVY])}
+    scene = {"light": {"dir": r[SCENE_LIGHT_DIR:SCENE_LIGHT_DIR + 3].tolist(), "ambient": float(r[SCENE_LIGHT_AMBIENT]),
+                       "diffuse": float(r[SCENE_LIGHT_DIFFUSE])},
+             "headlight": {"ambient": float(r[SCENE_HEAD_AMBIENT]), "diffuse": float(r[SCENE_HEAD_DIFFUSE])},
+             "rgb": {k: r[SCENE_RGB + 3 * j:SCENE_RGB + 3 * j + 3].tolist() for j, k in enumerate(RGB_CLASSES)}}
+    if target_half is not None:
+        scene["target_half"] = [float(x) for x in target_half]
+    return cam, scene
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
            "mcg_action_dim", "mcg_nq", "mcg_nv", "mcg_reset", "mcg_step", "mcg_get_state", "mcg_set_state",
            "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts",
-           "mcg_render", "mcg_render_mounted")
+           "mcg_render", "mcg_render_mounted", "mcg_render_scenes", "mcg_scene_randomize")
 
 _lib = None
 
@@ -178,6 +252,11 @@ def load():
     if hasattr(L, "mcg_render_mounted"):  # absent only from older builds selected through MCG_LIB for A/B timing
         L.mcg_render_mounted.argtypes = [C.c_void_p, C.POINTER(McgScene), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.POINTER(McgRenderOut), C.c_void_p]
+    if hasattr(L, "mcg_render_scenes"):   # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_render_scenes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(d * 3), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.POINTER(McgRenderOut), C.c_void_p]
+        L.mcg_scene_randomize.argtypes = [C.c_void_p, C.POINTER(McgScene), C.POINTER(McgSceneRand), C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
     _lib = L
     return L
 

@@ -7,6 +7,7 @@
 // gfx950 only; no CPU fallback exists on purpose.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstddef>
 
 #include <cmath>
 #include <cstdio>
@@ -1360,16 +1361,19 @@ int mcg_debug_contacts(mcg_env* e, int32_t* count, int32_t* dropped, double* dat
   return MCG_OK;
 }
 
-int mcg_render_mounted(mcg_env* e, const mcg_scene* sc, int body, double znear, int width, int height, int samples, int target_at_goal,
-                       const uint8_t* mask, const mcg_render_out* out, void* stream) {
-  // host checks first: nothing below them touches HIP.  (mcg_render's texts are kept: it is this entry with body = -1, znear = 0)
-  const char* fn = (body == -1 && znear == 0.0) ? "mcg_render" : "mcg_render_mounted";
-  if (!sc || !out) return fail(MCG_ERR_ARG, "%s: null scene or output block", fn);
+// ---- the three picture entries' shared pieces (host only)
+// the checks of what is per call, in the order and with the texts mcg_render has always had; nothing here touches HIP
+static int render_call_checks(const char* fn, const mcg_render_out* out, int width, int height, int samples, int body, double znear) {
   if (!out->rgb && !out->gray && !out->depth && !out->geom) return fail(MCG_ERR_ARG, "%s: all four outputs are null", fn);
   if (width < 1 || width > 512 || height < 1 || height > 512) return fail(MCG_ERR_ARG, "%s: width and height must be in 1..512", fn);
   if (samples < 1 || samples > 4) return fail(MCG_ERR_ARG, "%s: samples must be in 1..4", fn);
   if (body < -1 || body >= NB) return fail(MCG_ERR_ARG, "%s: body must be -1 (the world) or an engine body 0..11", fn);
   if (!(std::isfinite(znear) && znear >= 0.0)) return fail(MCG_ERR_ARG, "%s: znear must be finite and not negative", fn);
+  return MCG_OK;
+}
+
+// the checks of a scene's own values
+static int scene_value_checks(const char* fn, const mcg_scene* sc) {
   if (!(sc->fovy > 0.0 && sc->fovy < 180.0)) return fail(MCG_ERR_ARG, "%s: fovy must be in (0, 180) degrees", fn);
   for (int a = 0; a < 3; a++)
     for (int b = 0; b < 3; b++) {
@@ -1378,36 +1382,105 @@ int mcg_render_mounted(mcg_env* e, const mcg_scene* sc, int body, double znear, 
       if (!(std::fabs(s - (a == b ? 1.0 : 0.0)) <= 1e-9)) return fail(MCG_ERR_ARG, "%s: cam_mat is not orthonormal to 1e-9", fn);
     }
   if (!(std::fabs(norm3(sc->light_dir) - 1.0) <= 1e-9)) return fail(MCG_ERR_ARG, "%s: light_dir is not a unit vector to 1e-9", fn);
-  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
-  if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
-  if (!e->d_faces) {       // the first picture of this engine: the face table goes to the device (a blocking copy, once)
-    HIP_OK(hipSetDevice(e->device));
-    float4* d = nullptr;
-    HIP_OK(hipMalloc(&d, e->faces_host.size() * sizeof(float)));
-    const hipError_t err = hipMemcpy(d, e->faces_host.data(), e->faces_host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (err != hipSuccess) { (void)hipFree(d); return fail(MCG_ERR_HIP, "mcg_render: %s", hipGetErrorString(err)); }
-    e->d_faces = d;
-  }
-  const bool mounted = !(body == -1 && znear == 0.0);       // the world camera without a near plane keeps its own kernel
-  RenderArgs A;
-  memset(&A, 0, sizeof(A));
-  for (int k = 0; k < 3; k++) { A.cam_pos[k] = sc->cam_pos[k]; A.light[k] = sc->light_dir[k]; A.target_half[k] = (float)sc->target_half[k]; }
-  for (int k = 0; k < 9; k++) { A.cam_mat[k] = sc->cam_mat[k]; A.cam_matf[k] = (float)sc->cam_mat[k]; }
-  A.focal = (float)(0.5 * height / std::tan(0.5 * sc->fovy * 3.14159265358979323846 / 180.0));
-  A.la = (float)sc->light_ambient; A.ld = (float)sc->light_diffuse; A.ha = (float)sc->head_ambient; A.hd = (float)sc->head_diffuse;
-  const double* rgb[6] = {sc->rgb_ground, sc->rgb_table, sc->rgb_cube, sc->rgb_target, sc->rgb_mesh, sc->rgb_sky};
-  for (int c = 0; c < 6; c++) for (int k = 0; k < 3; k++) A.rgb[c][k] = (float)(255.0 * rgb[c][k]);
+  return MCG_OK;
+}
+
+// the first picture of an engine: the face table goes to the device (a blocking copy, once)
+static int render_upload_faces(mcg_env* e) {
+  if (e->d_faces) return MCG_OK;
+  HIP_OK(hipSetDevice(e->device));
+  float4* d = nullptr;
+  HIP_OK(hipMalloc(&d, e->faces_host.size() * sizeof(float)));
+  const hipError_t err = hipMemcpy(d, e->faces_host.data(), e->faces_host.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (err != hipSuccess) { (void)hipFree(d); return fail(MCG_ERR_HIP, "mcg_render: %s", hipGetErrorString(err)); }
+  e->d_faces = d;
+  return MCG_OK;
+}
+
+// what of RenderArgs is per call: the target box, the picture, the face table, mask and outputs (A zeroed by the caller)
+static void render_call_args(RenderArgs& A, const mcg_env* e, const double* target_half, int width, int height, int samples, int target_at_goal,
+                             const uint8_t* mask, const mcg_render_out* out) {
+  for (int k = 0; k < 3; k++) A.target_half[k] = (float)target_half[k];
   A.W = width; A.H = height; A.S = samples; A.target_at_goal = target_at_goal ? 1 : 0;
   A.draw_cube = (e->cfg.has_object && !e->cfg.hidden) ? 1 : 0;       // the reference hides the cube in Reach (mycobot.py:475-481)
   A.dwords = (width % 4 == 0) && ((uintptr_t)out->rgb % 4 == 0) && ((uintptr_t)out->gray % 4 == 0) && ((uintptr_t)out->depth % 16 == 0)
              && ((uintptr_t)out->geom % 4 == 0);
   memcpy(A.foff, e->foff, sizeof(A.foff));
   A.faces = e->d_faces; A.mask = mask; A.out = *out;
+}
+
+int mcg_render_mounted(mcg_env* e, const mcg_scene* sc, int body, double znear, int width, int height, int samples, int target_at_goal,
+                       const uint8_t* mask, const mcg_render_out* out, void* stream) {
+  // host checks first: nothing below them touches HIP.  (mcg_render's texts are kept: it is this entry with body = -1, znear = 0)
+  const char* fn = (body == -1 && znear == 0.0) ? "mcg_render" : "mcg_render_mounted";
+  if (!sc || !out) return fail(MCG_ERR_ARG, "%s: null scene or output block", fn);
+  if (int rc = render_call_checks(fn, out, width, height, samples, body, znear)) return rc;
+  if (int rc = scene_value_checks(fn, sc)) return rc;
+  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
+  if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
+  if (int rc = render_upload_faces(e)) return rc;
+  const bool mounted = !(body == -1 && znear == 0.0);       // the world camera without a near plane keeps its own kernel
+  RenderArgs A;
+  memset(&A, 0, sizeof(A));
+  for (int k = 0; k < 3; k++) { A.cam_pos[k] = sc->cam_pos[k]; A.light[k] = sc->light_dir[k]; }
+  for (int k = 0; k < 9; k++) { A.cam_mat[k] = sc->cam_mat[k]; A.cam_matf[k] = (float)sc->cam_mat[k]; }
+  A.focal = (float)(0.5 * height / std::tan(0.5 * sc->fovy * 3.14159265358979323846 / 180.0));
+  A.la = (float)sc->light_ambient; A.ld = (float)sc->light_diffuse; A.ha = (float)sc->head_ambient; A.hd = (float)sc->head_diffuse;
+  const double* rgb[6] = {sc->rgb_ground, sc->rgb_table, sc->rgb_cube, sc->rgb_target, sc->rgb_mesh, sc->rgb_sky};
+  for (int c = 0; c < 6; c++) for (int k = 0; k < 3; k++) A.rgb[c][k] = (float)(255.0 * rgb[c][k]);
+  render_call_args(A, e, sc->target_half, width, height, samples, target_at_goal, mask, out);
   const size_t lds_bytes = (size_t)render_head_floats(mounted) * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;     // built-in tables: 35 KB
   if (lds_bytes > 64 * 1024) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: the face tables do not fit the 64 KB of LDS a workgroup asks for (about 3 200 faces)%s");
   const hipError_t lerr = (hipError_t)launch_render(A, mounted, body, (float)znear, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
                                                     e->view.d + (size_t)(2 * e->cfg.nq + 2 * e->cfg.nv + 7) * e->cfg.n, e->d_model);
   if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_render: launch: %s", hipGetErrorString(lerr));
+  return MCG_OK;
+}
+
+int mcg_render_scenes(mcg_env* e, const double* scenes, const double* target_half, int body, double znear, int width, int height, int samples,
+                      int target_at_goal, const uint8_t* mask, const mcg_render_out* out, void* stream) {
+  const char* fn = "mcg_render_scenes";
+  if (!scenes) return fail(MCG_ERR_ARG, "%s: null scene table", fn);
+  if (!target_half || !out) return fail(MCG_ERR_ARG, "%s: null target_half or output block", fn);
+  if (int rc = render_call_checks(fn, out, width, height, samples, body, znear)) return rc;
+  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
+  if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
+  if (int rc = render_upload_faces(e)) return rc;
+  RenderArgs A;          // camera, light and colours stay zero: the kernel takes them from the table
+  memset(&A, 0, sizeof(A));
+  render_call_args(A, e, target_half, width, height, samples, target_at_goal, mask, out);
+  const size_t lds_bytes = (size_t)RENDER_HEAD_FLOATS_SCENES * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;
+  if (lds_bytes > 64 * 1024) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: the face tables do not fit the 64 KB of LDS a workgroup asks for (about 3 200 faces)%s");
+  const hipError_t lerr = (hipError_t)launch_render_scenes(A, scenes, body, (float)znear, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
+                                                           e->view.d + (size_t)(2 * e->cfg.nq + 2 * e->cfg.nv + 7) * e->cfg.n, e->d_model);
+  if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_render_scenes: launch: %s", hipGetErrorString(lerr));
+  return MCG_OK;
+}
+
+int mcg_scene_randomize(mcg_env* e, const mcg_scene* base, const mcg_scene_rand* r, int cam_slot, const uint8_t* mask, double* scenes, void* stream) {
+  const char* fn = "mcg_scene_randomize";
+  if (!base || !r || !scenes) return fail(MCG_ERR_ARG, "%s: null base scene, ranges or scene table", fn);
+  if (cam_slot < 0 || cam_slot >= MCG_SCENE_RAND_CAM_SLOTS) return fail(MCG_ERR_ARG, "%s: cam_slot must be in 0..7", fn);
+  {
+    bool ok = std::isfinite(r->light_tilt) && r->light_tilt >= 0.0;
+    for (int k = 0; k < 3; k++) ok = ok && std::isfinite(r->cam_pos[k]) && r->cam_pos[k] >= 0.0 && std::isfinite(r->cam_rot[k]) && r->cam_rot[k] >= 0.0;
+    for (int k = 0; k < 6; k++) ok = ok && std::isfinite(r->rgb[k]) && r->rgb[k] >= 0.0;
+    if (!ok) return fail(MCG_ERR_ARG, "%s: a range is negative or not finite", fn);
+  }
+  if (!(r->light_tilt <= 3.14159265358979323846)) return fail(MCG_ERR_ARG, "%s: light_tilt must be in [0, pi]", fn);
+  const double* pairs[4] = {r->fovy_scale, r->light_ambient_scale, r->light_diffuse_scale, r->head_scale};
+  for (int k = 0; k < 4; k++)
+    if (!(std::isfinite(pairs[k][0]) && std::isfinite(pairs[k][1]) && pairs[k][0] > 0.0 && pairs[k][0] <= pairs[k][1]))
+      return fail(MCG_ERR_ARG, "%s: a scale pair needs 0 < lo <= hi, both finite", fn);
+  if (int rc = scene_value_checks(fn, base)) return rc;
+  if (!(base->fovy * r->fovy_scale[1] < 180.0)) return fail(MCG_ERR_ARG, "%s: fovy * fovy_scale[1] must stay below 180 degrees", fn);
+  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
+  SceneRandArgs P;
+  static_assert(offsetof(mcg_scene, target_half) == MCG_SCENE_PAD * sizeof(double), "a row is the head of mcg_scene");
+  memcpy(P.base, base, sizeof(P.base));
+  P.r = *r; P.seed = e->cfg.seed; P.env_id_offset = e->cfg.env_id_offset; P.cam_slot = cam_slot; P.n = e->cfg.n;
+  const hipError_t lerr = (hipError_t)launch_scene_randomize(P, e->view.i32 + e->cfg.n, mask, scenes, (hipStream_t)stream);
+  if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_scene_randomize: launch: %s", hipGetErrorString(lerr));
   return MCG_OK;
 }
 

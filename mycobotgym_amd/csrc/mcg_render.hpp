@@ -25,6 +25,11 @@
 // there, lifted into uniform registers once per wave.  It also carries the near plane.  render_kernel<false> is the world camera's
 // kernel as it was: the switch is a template parameter, so its instruction stream does not change.
 //
+// Per-environment scenes (mcg_render_scenes) are the third instantiation, render_kernel<true, true>: lane 0 reads the environment's row
+// of the scene table (40 doubles), composes the camera's world pose from it as the mounted kernel does from the call's scene, and parks
+// in the LDS head, as float32, what the rays need: the focal length in pixels, the four shading coefficients, the light's direction
+// and the six colours x 255; the waves lift the scalars into uniform registers once.  Of RenderArgs it reads what is per call.
+//
 // Visibility.  Surfaces are one-sided: a convex geom whose entry point lies behind the camera or before the near plane (depth along the
 // camera's -z below znear) is invisible along that ray, and the ray goes on to the other geoms.  So a camera inside a polytope does not
 // see it (OpenGL's back-face culling on closed convex solids): the gripper camera sits inside the flange's polytope and looks out of it.
@@ -50,6 +55,13 @@ constexpr int RENDER_CAM_MAT = RENDER_CAM + 4;
 constexpr int RENDER_HEAD_FLOATS_MOUNTED = RENDER_HEAD_FLOATS + 16;
 static_assert((RENDER_HEAD_FLOATS_MOUNTED * 4) % 16 == 0, "the face table is read as b128");
 constexpr int render_head_floats(bool mounted) { return mounted ? RENDER_HEAD_FLOATS_MOUNTED : RENDER_HEAD_FLOATS; }
+// per-environment scenes (mcg_render_scenes): the mounted head and, converted by lane 0 from the environment's row, the focal length in
+// pixels, the four shading coefficients, the light's direction in the world; the six colours take the place of the call's in RENDER_RGB
+constexpr int RENDER_SCN = RENDER_HEAD_FLOATS_MOUNTED;
+constexpr int RENDER_SCN_FOCAL = RENDER_SCN, RENDER_SCN_SHADE = RENDER_SCN + 1, RENDER_SCN_LIGHT = RENDER_SCN + 5;
+constexpr int RENDER_HEAD_FLOATS_SCENES = RENDER_HEAD_FLOATS_MOUNTED + 8;
+static_assert((RENDER_HEAD_FLOATS_SCENES * 4) % 16 == 0, "the face table is read as b128");
+constexpr int render_head_floats(bool mounted, bool scenes) { return scenes ? RENDER_HEAD_FLOATS_SCENES : render_head_floats(mounted); }
 constexpr int RENDER_TILE_BYTES = (RENDER_LANES / 64) * 3 * 256 * 4;                    // per wave: 256 pixels x (packed r g b gray, depth, geom); after the faces
 constexpr float RENDER_BOX_SLACK = 1e-6f;             // the slab test is a filter: the faces decide
 
@@ -72,6 +84,20 @@ struct RenderArgs {
 // znear, metres along the camera's -z; otherwise the world camera's kernel, which reads neither
 int launch_render(const RenderArgs& A, bool mounted, int body, float znear, int n, int nq, size_t lds_bytes, hipStream_t stream,
                   const double* qpos, const double* goal, const mcg_model* model);
+// the third instantiation: camera, fovy, light, shading coefficients and colours of environment e from row e of `scenes` (device,
+// [n, MCG_SCENE_ENV_DOUBLES]); of A it reads what is per call (target_half, the picture's size, the face table, mask, out)
+int launch_render_scenes(const RenderArgs& A, const double* scenes, int body, float znear, int n, int nq, size_t lds_bytes, hipStream_t stream,
+                         const double* qpos, const double* goal, const mcg_model* model);
+
+// mcg_scene_randomize's kernel (mcg_render.hip): one lane per environment
+struct SceneRandArgs {
+  double base[MCG_SCENE_PAD];                         // the base scene as a row
+  mcg_scene_rand r;
+  unsigned long long seed;
+  long long env_id_offset;
+  int cam_slot, n;
+};
+int launch_scene_randomize(const SceneRandArgs& P, const int32_t* episode, const uint8_t* mask, double* scenes, hipStream_t stream);
 
 #ifdef MCG_RENDER_KERNELS      // the device code: compiled in mcg_render.hip alone (see there)
 struct RayHit { float t; int id; float nl, nd; };      // distance along the (unit) ray, geom id, n.(-light), n.(-ray) of the face hit
@@ -111,7 +137,7 @@ MCG_DEV void hit_box(RayHit& best, int id, const float* o, const float* d, const
 }
 
 // tnear: the near plane as a distance along this ray (MOUNTED alone; the world camera's entry tests stay `> 0`)
-template <bool MOUNTED>
+template <bool MOUNTED, bool SCENES>
 MCG_DEV RayHit trace(const RenderArgs& A, const float* __restrict__ lds, const float* camw, const float* lightw, const float* tpos,
                      const float* table_c, const float* table_h, const float* cube_h, const float* dw, float tnear) {
   RayHit best{INFINITY, -1, 0.0f, 0.0f};
@@ -130,7 +156,7 @@ MCG_DEV RayHit trace(const RenderArgs& A, const float* __restrict__ lds, const f
     hit_box<MOUNTED>(best, 2, F + RF_O, db, F + RF_L, zero, cube_h, tnear);
   }
   hit_box<MOUNTED>(best, 3, camw, dw, lightw, tpos, A.target_half, tnear);
-  const float4* __restrict__ faces = (const float4*)(lds + render_head_floats(MOUNTED));
+  const float4* __restrict__ faces = (const float4*)(lds + render_head_floats(MOUNTED, SCENES));
   int body_at = -1;
   float db[3];
   const float* F = lds;
@@ -176,33 +202,53 @@ MCG_DEV void render_joint(const TrigC& T, int sg, const real* r, real ang, real*
   }
 }
 
-// cam: the camera's world position
-MCG_DEV void render_park(const RenderArgs& A, const real* cam, float* lds, int slot, const real* R, const real* p) {
+// cam: the camera's world position, light: the light's direction in the world
+MCG_DEV void render_park(const real* light, const real* cam, float* lds, int slot, const real* R, const real* p) {
   float* F = lds + slot * RF_STRIDE;
   const real c[3] = {cam[0] - p[0], cam[1] - p[1], cam[2] - p[2]};
   for (int k = 0; k < 9; k++) F[k] = (float)R[k];
   for (int j = 0; j < 3; j++) {
     F[RF_O + j] = (float)(R[j] * c[0] + R[3 + j] * c[1] + R[6 + j] * c[2]);
-    F[RF_L + j] = (float)(R[j] * A.light[0] + R[3 + j] * A.light[1] + R[6 + j] * A.light[2]);
+    F[RF_L + j] = (float)(R[j] * light[0] + R[3 + j] * light[1] + R[6 + j] * light[2]);
   }
   F[15] = 0.0f;
 }
 
+MCG_DEV float render_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+
 namespace {       // (internal linkage, like the other kernels: a text section of its own, placed in definition order)
-// qpos: [nq, N] (the engine's state), goal: [3, N].  MOUNTED: the camera rides on body cam_body (see the head of this file); the two last
-// arguments trail the others so that the world camera's kernel, which does not read them, finds its own where they were
-template <bool MOUNTED>
+// qpos: [nq, N] (the engine's state), goal: [3, N].  MOUNTED: the camera rides on body cam_body (see the head of this file).  SCENES (with
+// MOUNTED): camera, fovy, light, shading coefficients and colours are environment env's row of `scenes`, not A's; the row's address
+// depends on env alone and nothing read from it reaches an address or a loop bound, so any bit pattern in a row gives a bad picture of
+// that environment and nothing else.  Arguments an instantiation does not read trail the others, so that each finds its own where they
+// were.  (One kernel template, not a shared body behind three kernels: through such a wrapper the two older instantiations came out
+// with other instruction streams.)
+template <bool MOUNTED, bool SCENES>
 __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, const double* __restrict__ qpos, const double* __restrict__ goal,
-                                                              int n, int nq, const mcg_model* __restrict__ Pg, int cam_body, float cam_znear) {
+                                                              int n, int nq, const mcg_model* __restrict__ Pg, int cam_body, float cam_znear,
+                                                              const double* __restrict__ scenes) {
+  static_assert(MOUNTED || !SCENES, "per-environment scenes are built on the mounted path");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int env = blockIdx.x;
   if (env >= n) return;
   if (A.mask && A.mask[env] == 0) return;                          // workgroup-uniform
   const int tid = threadIdx.x;
-  constexpr int HEAD = render_head_floats(MOUNTED);
+  constexpr int HEAD = render_head_floats(MOUNTED, SCENES);
 
   if (tid == 0) {
     const TrigC T = load_trig();
+    real srow[SCENES ? MCG_SCENE_RGB : 1];                         // SCENES: the row's camera, fovy, light and shading coefficients
+    const real* cam_pos = A.cam_pos; const real* cam_mat = A.cam_mat; const real* light = A.light;
+    if constexpr (SCENES) {
+      const double* __restrict__ row = scenes + (size_t)env * MCG_SCENE_ENV_DOUBLES;
+      for (int k = 0; k < MCG_SCENE_RGB; k++) srow[k] = row[k];
+      cam_pos = srow + MCG_SCENE_CAM_POS; cam_mat = srow + MCG_SCENE_CAM_MAT; light = srow + MCG_SCENE_LIGHT_DIR;
+      lds[RENDER_SCN_FOCAL] = (float)(0.5 * A.H / tan(0.5 * srow[MCG_SCENE_FOVY] * 3.14159265358979323846 / 180.0));
+      for (int k = 0; k < 4; k++) lds[RENDER_SCN_SHADE + k] = (float)srow[MCG_SCENE_LIGHT_AMBIENT + k];
+      for (int k = 0; k < 3; k++) lds[RENDER_SCN_LIGHT + k] = (float)light[k];
+      for (int c = 0; c < 6; c++)
+        for (int k = 0; k < 4; k++) lds[RENDER_RGB + 4 * c + k] = k < 3 ? (float)(255.0 * row[MCG_SCENE_RGB + 3 * c + k]) : 0.0f;
+    }
     real R[9], p[3], R5[9], p5[3];
     // MOUNTED: the bodies' R, p wait as float64 where the faces will lie (lane 0 alone reads them back, before the barrier), the
     // carrier's are kept: the camera's world pose has to be known before any body's camera origin can be parked
@@ -229,20 +275,20 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
           for (int k = 0; k < 3; k++) pb[k] = p[k];
         }
       } else {
-        render_park(A, A.cam_pos, lds, i, R, p);
+        render_park(A.light, A.cam_pos, lds, i, R, p);
       } });
     static_assert(PAR[6] == 5 && PAR[7] == 6 && PAR[8] == 5 && PAR[9] == 8 && PAR[10] == 5 && PAR[11] == 5, "the chain above");
     real camd[3];                                                  // MOUNTED: the camera's world position
     if constexpr (MOUNTED) {                                       // world <- camera = (world <- body) (body <- camera); cam_body == -1: Rb, pb are the identity
       for (int k = 0; k < 3; k++) {
-        camd[k] = pb[k] + Rb[3*k] * A.cam_pos[0] + Rb[3*k+1] * A.cam_pos[1] + Rb[3*k+2] * A.cam_pos[2];
+        camd[k] = pb[k] + Rb[3*k] * cam_pos[0] + Rb[3*k+1] * cam_pos[1] + Rb[3*k+2] * cam_pos[2];
         lds[RENDER_CAM + k] = (float)camd[k];
         for (int j = 0; j < 3; j++)
-          lds[RENDER_CAM_MAT + 3*k + j] = (float)(Rb[3*k] * A.cam_mat[j] + Rb[3*k+1] * A.cam_mat[3 + j] + Rb[3*k+2] * A.cam_mat[6 + j]);
+          lds[RENDER_CAM_MAT + 3*k + j] = (float)(Rb[3*k] * cam_mat[j] + Rb[3*k+1] * cam_mat[3 + j] + Rb[3*k+2] * cam_mat[6 + j]);
       }
       lds[RENDER_CAM + 3] = 0.0f;
       for (int k = 9; k < 12; k++) lds[RENDER_CAM_MAT + k] = 0.0f;
-      for (int i = 0; i < NB; i++) render_park(A, camd, lds, i, chain + 12 * i, chain + 12 * i + 9);
+      for (int i = 0; i < NB; i++) render_park(light, camd, lds, i, chain + 12 * i, chain + 12 * i + 9);
     }
     if (A.draw_cube) {                                             // nq == 19: the free joint's position and quaternion (normalised as mj_kinematics does)
       real q[4], Rc[9], pc[3];
@@ -252,7 +298,7 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
       const bool tiny = nn < MINVAL;
       for (int k = 0; k < 4; k++) q[k] = tiny ? (k == 0 ? 1.0 : 0.0) : q[k] / nn;
       quat_to_mat(q, Rc);
-      render_park(A, MOUNTED ? camd : A.cam_pos, lds, NB, Rc, pc);
+      render_park(light, MOUNTED ? camd : A.cam_pos, lds, NB, Rc, pc);
     } else {
       for (int k = 0; k < RF_STRIDE; k++) lds[NB * RF_STRIDE + k] = 0.0f;
     }
@@ -261,7 +307,8 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
     const int m = (tid - 64) / RENDER_BOX_FLOATS, k = (tid - 64) % RENDER_BOX_FLOATS;
     lds[RENDER_FRAMES * RF_STRIDE + m * RENDER_BOX_FLOATS + k] = k < 6 ? (float)Pg->mesh_box[m][k] + (k >= 3 ? RENDER_BOX_SLACK : 0.0f) : 0.0f;
   }
-  if (tid >= 192 && tid < 192 + 24) lds[RENDER_RGB + tid - 192] = ((tid - 192) & 3) < 3 ? A.rgb[(tid - 192) >> 2][(tid - 192) & 3] : 0.0f;
+  if constexpr (!SCENES)
+    if (tid >= 192 && tid < 192 + 24) lds[RENDER_RGB + tid - 192] = ((tid - 192) & 3) < 3 ? A.rgb[(tid - 192) >> 2][(tid - 192) & 3] : 0.0f;
   __syncthreads();
   {   // the faces, with the camera folded in
     float4* lf = (float4*)(lds + HEAD);
@@ -285,7 +332,18 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
   }
   const float* const cm = MOUNTED ? cmat : A.cam_matf;
   const float camw[3] = {MOUNTED ? camm[0] : (float)A.cam_pos[0], MOUNTED ? camm[1] : (float)A.cam_pos[1], MOUNTED ? camm[2] : (float)A.cam_pos[2]};
-  const float lightw[3] = {(float)A.light[0], (float)A.light[1], (float)A.light[2]};
+  // SCENES: the focal length, the shading coefficients and the light from the head as well
+  // (read through accessors at the places of use: the two other instantiations then read A where they always did)
+  float scn[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (SCENES) for (int k = 0; k < 5; k++) scn[k] = render_uniform(lds[RENDER_SCN + k]);
+  static_assert(RENDER_SCN_FOCAL == RENDER_SCN && RENDER_SCN_SHADE == RENDER_SCN + 1, "scn[]: focal, la, ld, ha, hd");
+  auto focal = [&]() -> float { if constexpr (SCENES) return scn[0]; else return A.focal; };
+  auto la = [&]() -> float { if constexpr (SCENES) return scn[1]; else return A.la; };
+  auto ld = [&]() -> float { if constexpr (SCENES) return scn[2]; else return A.ld; };
+  auto ha = [&]() -> float { if constexpr (SCENES) return scn[3]; else return A.ha; };
+  auto hd = [&]() -> float { if constexpr (SCENES) return scn[4]; else return A.hd; };
+  const float lightw[3] = {SCENES ? render_uniform(lds[RENDER_SCN_LIGHT]) : (float)A.light[0], SCENES ? render_uniform(lds[RENDER_SCN_LIGHT + 1]) : (float)A.light[1],
+                           SCENES ? render_uniform(lds[RENDER_SCN_LIGHT + 2]) : (float)A.light[2]};
   float tpos[3], table_c[3], table_h[3], cube_h[3];
   for (int k = 0; k < 3; k++) {
     tpos[k] = (float)(A.target_at_goal ? goal[(size_t)k * n + env] : Pg->target0[k]);
@@ -317,17 +375,17 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
         const bool centre_only = s == S * S;
         const float fx = centre_only ? 0.5f : ((float)(s % S) + 0.5f) * inv_s, fy = centre_only ? 0.5f : ((float)(s / S) + 0.5f) * inv_s;
         const float u = (float)x + fx - 0.5f * (float)W, v = -((float)y + fy - 0.5f * (float)H);
-        const float rn = __frsqrt_rn(u * u + v * v + A.focal * A.focal);
-        const float dc[3] = {u * rn, v * rn, -A.focal * rn};
+        const float rn = __frsqrt_rn(u * u + v * v + focal() * focal());
+        const float dc[3] = {u * rn, v * rn, -focal() * rn};
         float dw[3];
         for (int k = 0; k < 3; k++) dw[k] = cm[3*k] * dc[0] + cm[3*k+1] * dc[1] + cm[3*k+2] * dc[2];
         // depth along the camera's -z = t * focal * rn: the near plane as a distance along this ray
-        const float tnear = MOUNTED ? cam_znear * __builtin_amdgcn_rcpf(A.focal * rn) : 0.0f;
-        const RayHit h = trace<MOUNTED>(A, lds, camw, lightw, tpos, table_c, table_h, cube_h, dw, tnear);
-        if (centre_only || S == 1) { dep1 = h.id < 0 ? INFINITY : h.t * A.focal * rn; gid1 = h.id; }
+        const float tnear = MOUNTED ? cam_znear * __builtin_amdgcn_rcpf(focal() * rn) : 0.0f;
+        const RayHit h = trace<MOUNTED, SCENES>(A, lds, camw, lightw, tpos, table_c, table_h, cube_h, dw, tnear);
+        if (centre_only || S == 1) { dep1 = h.id < 0 ? INFINITY : h.t * focal() * rn; gid1 = h.id; }
         if (!centre_only) {
           const int ci = h.id < 0 ? 5 : (h.id < 4 ? h.id : 4);
-          const float shade = h.id < 0 ? 1.0f : A.la + A.ld * fmaxf(0.0f, h.nl) + A.ha + A.hd * fmaxf(0.0f, h.nd);
+          const float shade = h.id < 0 ? 1.0f : la() + ld() * fmaxf(0.0f, h.nl) + ha() + hd() * fmaxf(0.0f, h.nd);
           const float* col = lds + RENDER_RGB + 4 * ci;
           const float r = fminf(col[0] * shade, 255.0f), g = fminf(col[1] * shade, 255.0f), b = fminf(col[2] * shade, 255.0f);
           sr += r; sg += g; sb += b;

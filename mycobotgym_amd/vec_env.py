@@ -96,6 +96,30 @@ def load_scene(path: Optional[str] = None) -> dict:
         return json.load(f)
 
 
+def validate_scenes(scenes: torch.Tensor, num_envs: Optional[int] = None) -> None:
+    """What ``mcg_render`` checks of a scene on the host, for every row of a scene table (float64 [N, 40], any device): ``cam_mat``
+    orthonormal to 1e-9, ``fovy`` in (0, 180), ``light_dir`` a unit vector to 1e-9, the colours in [0, 1], everything finite.  Raises
+    ``ValueError`` naming the first bad row.  The kernel draws any row safely; a bad one gives a bad picture of its environment."""
+    A = _abi
+    if not (isinstance(scenes, torch.Tensor) and scenes.dtype == torch.float64 and scenes.dim() == 2
+            and scenes.shape[1] == A.SCENE_ENV_DOUBLES and (num_envs is None or scenes.shape[0] == num_envs)):
+        raise ValueError(f"scenes: expected a float64 tensor [{'N' if num_envs is None else num_envs}, {A.SCENE_ENV_DOUBLES}]")
+    R = scenes[:, A.SCENE_CAM_MAT:A.SCENE_CAM_MAT + 9].reshape(-1, 3, 3)
+    eye = torch.eye(3, dtype=torch.float64, device=scenes.device)
+    fovy, light, rgb = scenes[:, A.SCENE_FOVY], scenes[:, A.SCENE_LIGHT_DIR:A.SCENE_LIGHT_DIR + 3], scenes[:, A.SCENE_RGB:A.SCENE_PAD]
+    problems = (          # (a comparison with a NaN is false: every test is written so that a NaN fails it)
+        ("a value that is not finite", ~torch.isfinite(scenes).all(dim=1)),
+        ("cam_mat not orthonormal to 1e-9", ~((R.transpose(1, 2) @ R - eye).abs().amax(dim=(1, 2)) <= 1e-9)),
+        ("fovy outside (0, 180)", ~((fovy > 0.0) & (fovy < 180.0))),
+        ("light_dir not a unit vector to 1e-9", ~((light.norm(dim=1) - 1.0).abs() <= 1e-9)),
+        ("a colour outside [0, 1]", ~((rgb >= 0.0) & (rgb <= 1.0)).all(dim=1)))
+    bad = torch.stack([b for _, b in problems])                 # [5, N]
+    if bool(bad.any()):
+        row = int(torch.nonzero(bad.any(dim=0))[0])
+        why = [text for (text, _), b in zip(problems, bad[:, row].tolist()) if b]
+        raise ValueError(f"scenes: row {row}: " + "; ".join(why))
+
+
 class MyCobotVecEnv:
     metadata = {"render_modes": ["rgb_array", "depth_array"], "render_fps": 25}      # mycobot.py:28
 
@@ -357,12 +381,18 @@ class MyCobotVecEnv:
                          f"{sorted(mounted)}")
 
     def render_into(self, out: dict, camera: str = "sideview", samples: int = 1, show_goal: bool = True,
-                    mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None, znear: Optional[float] = None):
+                    mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None, znear: Optional[float] = None,
+                    scenes: Optional[torch.Tensor] = None, validate: Optional[bool] = None):
         """Raw form of ``render``: ``out`` maps any of rgb (uint8 [N, H, W, 3]), gray (uint8 [N, H, W]), depth (float32 [N, H, W]),
         geom (int8 [N, H, W]) to contiguous device tensors of one H, W, which the kernel fills (where ``mask`` is set); enqueued on the
         current stream, not synchronised.  ``camera``: a world camera or a body camera of the scene (``gripper_camera_rgb``: it rides on
         the flange, its pose follows each environment's arm).  ``znear``: the near plane in metres, in place of the camera's own (a
-        world camera has none: 0)."""
+        world camera has none: 0).
+
+        ``scenes``: a scene table, a contiguous float64 device tensor [N, 40] (``randomize_scenes``, or rows made with
+        ``_abi.scene_row``): environment e is drawn with the camera, field of view, light and colours of row e, stated in the frame
+        ``camera`` rides in; of ``camera`` itself the carrier body and the near plane are used, of ``scene`` the target's size.
+        ``validate`` (default: True with ``scenes``): check the rows first (``validate_scenes``; it synchronises)."""
         want = {"rgb": (torch.uint8, 3), "gray": (torch.uint8, None), "depth": (torch.float32, None), "geom": (torch.int8, None)}
         hw = None
         for k, t in out.items():
@@ -385,8 +415,16 @@ class MyCobotVecEnv:
         znear = cam_znear if znear is None else float(znear)
         h, w = hw if hw is not None else (0, 0)
         mp = None if m is None else C.c_void_p(m.data_ptr())
+        if scenes is not None:
+            self._check_table(scenes, "scenes")
+            if validate is None or validate:
+                validate_scenes(scenes, self.num_envs)
         with torch.cuda.device(self.device):
-            if body < 0 and znear == 0.0:
+            if scenes is not None:
+                _abi.check(self._lib.mcg_render_scenes(self._h, C.c_void_p(scenes.data_ptr()), sc.target_half, body, znear, int(w), int(h),
+                                                       int(samples), int(bool(show_goal)), mp, C.byref(ro), self._stream()),
+                           "mcg_render_scenes")
+            elif body < 0 and znear == 0.0:
                 _abi.check(self._lib.mcg_render(self._h, C.byref(sc), int(w), int(h), int(samples), int(bool(show_goal)), mp, C.byref(ro),
                                                 self._stream()), "mcg_render")
             else:
@@ -395,11 +433,13 @@ class MyCobotVecEnv:
         return out
 
     def render(self, camera: str = "sideview", width: int = 480, height: int = 480, samples: int = 1, mode: str = "rgb_array",
-               mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None, show_goal: bool = True):
+               mask: Optional[torch.Tensor] = None, scene: Optional[dict] = None, show_goal: bool = True,
+               scenes: Optional[torch.Tensor] = None, validate: Optional[bool] = None):
         """All environments as ``camera`` sees them: ``mode="rgb_array"`` -> uint8 [N, H, W, 3], ``"depth_array"`` -> float32 [N, H, W]
         (distance along the viewing axis, +inf = sky); device tensors.  The target site is drawn at the goal, as the reference's
         ``_render_callback`` does (mycobot.py:308-311).  ``samples``: s x s rays per pixel, box-averaged; ``mask``: draw these environments
-        only (the others' images are zero); ``scene``: a compiled scene other than the built-in one (tools/compile_scene.py)."""
+        only (the others' images are zero); ``scene``: a compiled scene other than the built-in one (tools/compile_scene.py);
+        ``scenes`` / ``validate``: one scene per environment, as ``render_into`` takes it."""
         if mode not in self.metadata["render_modes"]:
             raise ValueError(f"mode must be one of {self.metadata['render_modes']}, got {mode!r}")
         n, dev = self.num_envs, self.device
@@ -407,8 +447,39 @@ class MyCobotVecEnv:
             out = {"rgb": torch.zeros(n, int(height), int(width), 3, dtype=torch.uint8, device=dev)}
         else:
             out = {"depth": torch.zeros(n, int(height), int(width), dtype=torch.float32, device=dev)}
-        self.render_into(out, camera=camera, samples=samples, show_goal=show_goal, mask=mask, scene=scene)
+        self.render_into(out, camera=camera, samples=samples, show_goal=show_goal, mask=mask, scene=scene, scenes=scenes, validate=validate)
         return out["rgb" if mode == "rgb_array" else "depth"]
+
+    def _check_table(self, t, name: str):
+        want = (self.num_envs, _abi.SCENE_ENV_DOUBLES)
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == want and t.is_contiguous()
+                and t.device == self._buf["obs"].device):
+            raise ValueError(f"{name}: expected a contiguous float64 device tensor {list(want)}")
+
+    def randomize_scenes(self, ranges: dict, camera: str = "sideview", cam_slot: int = 0, scene: Optional[dict] = None,
+                         mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A scene table, float64 [N, 40], for ``render_into(..., camera=camera, scenes=table)``: ``camera``'s base scene jittered per
+        environment and per episode (``mcg_scene_randomize``).  ``ranges``: keyed by the fields of ``mcg_scene_rand`` -- ``cam_pos`` (m) and
+        ``cam_rot`` (rad, a rotation vector): half ranges, one number or three; ``fovy_scale``, ``light_ambient_scale``,
+        ``light_diffuse_scale``, ``head_scale``: (lo, hi); ``light_tilt`` (rad); ``rgb``: a half range, one number or a dict by colour
+        class (ground, table, cube, target, mesh, sky); a missing key means no jitter.  The draw is keyed by (seed, global environment
+        id, episode, draw index), like the goals and the physics randomisation: a table is a function of the engine's state.  Light and
+        colours are the same for every ``cam_slot`` (0..7) of an environment, the camera's own jitter differs between slots.  ``mask``:
+        the rows to draw (the others of ``out`` stay as they are; without ``out`` they are the base scene's); enqueued, not synchronised."""
+        base = self._scene(camera, scene)[0]
+        rr = _abi.McgSceneRand.from_dict(ranges)
+        m = None
+        if mask is not None:
+            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            if m.shape != (self.num_envs,):
+                raise ValueError("mask must have shape (num_envs,)")
+        if out is None:
+            out = torch.as_tensor(_abi.scene_row(base), device=self.device).repeat(self.num_envs, 1).contiguous()
+        self._check_table(out, "out")
+        with torch.cuda.device(self.device):
+            _abi.check(self._lib.mcg_scene_randomize(self._h, C.byref(base), C.byref(rr), int(cam_slot), None if m is None else C.c_void_p(m.data_ptr()),
+                                                     C.c_void_p(out.data_ptr()), self._stream()), "mcg_scene_randomize")
+        return out
 
     def counters(self, clear: bool = False) -> dict:
         """Event counters of the engine (include/mcg.h: mcg_counters); synchronises the device."""
@@ -452,12 +523,20 @@ class MyCobotImgVecEnv(MyCobotVecEnv):
     The reference's ``_get_obs`` calls the renderer directly, not ``render()``: the target site is NOT moved to the goal in its observations
     and stays at its MJCF position (SURVEY D-15).  ``show_goal=True`` draws it at the goal instead.
 
+    ``visual_randomization``: None, or a dict of ranges as ``randomize_scenes`` takes it, optionally with ``"cameras": {name: overrides}``:
+    every environment is drawn with its own camera pose, field of view, light and colours, redrawn for every episode.  One scene table
+    per camera (``cam_slot`` = the camera's place in the tuple: light and colours agree between the cameras of an environment); the
+    tables are drawn after ``reset()`` and, in ``step()``, for the finished environments after their reset, so ``final_observation``
+    shows the finished episode's own scene; ``set_state`` / ``load_state_dict`` redraw them: they are a function of the state (seed,
+    episode), ``state_dict()`` does not carry them.  None: the calls made are those made without this keyword.
+
     Auto-reset: the picture of the pre-reset state is ``info["final_observation"]``, and the step kernel's own auto-reset would have
     overwritten that state.  So the engine runs with ``auto_reset=0``; a step renders, resets the finished environments with the masked
     ``mcg_reset`` (the same per-environment random streams as the in-kernel reset) and draws those again."""
 
     def __init__(self, num_envs: int, *args, camera: str = "sideview", image_size: int = 64, samples: int = 2, show_goal: bool = False,
-                 scene: Optional[dict] = None, auto_reset: bool = True, image_obs: bool = True, **kwargs):
+                 scene: Optional[dict] = None, auto_reset: bool = True, image_obs: bool = True,
+                 visual_randomization: Optional[dict] = None, **kwargs):
         if kwargs.get("reward_type", "sparse") == "reward_shaping":
             raise ValueError("the reference registers no image variant for reward_shaping (mycobotgym/__init__.py:37-39)")
         self._img_auto_reset = bool(auto_reset)
@@ -475,17 +554,47 @@ class MyCobotImgVecEnv(MyCobotVecEnv):
         # one contiguous [N, S, S] plane per camera; the observation is the [N, C, S, S] view of the planes
         self._img = torch.zeros(c, self.num_envs, s, s, dtype=torch.uint8, device=self.device).permute(1, 0, 2, 3)
         self._final_img = torch.zeros(c, self.num_envs, s, s, dtype=torch.uint8, device=self.device).permute(1, 0, 2, 3)
+        # visual randomisation: one scene table per camera (cam_slot = its place in the tuple), a function of the engine's state
+        self._vr_ranges, self._vr_tables = None, None
+        if visual_randomization is not None:
+            if len(self._cameras) > _abi.SCENE_RAND_CAM_SLOTS:
+                raise ValueError(f"visual_randomization: at most {_abi.SCENE_RAND_CAM_SLOTS} cameras")
+            common = {k: v for k, v in visual_randomization.items() if k != "cameras"}
+            per_cam = visual_randomization.get("cameras", {})
+            if set(per_cam) - set(self._cameras):
+                raise ValueError(f"visual_randomization['cameras']: {sorted(set(per_cam) - set(self._cameras))} not among {self._cameras}")
+            self._vr_ranges = [dict(common, **per_cam.get(cam, {})) for cam in self._cameras]
+            for r in self._vr_ranges:
+                _abi.McgSceneRand.from_dict(r)             # an unknown key fails here
+            self._vr_tables = [torch.as_tensor(_abi.scene_row(self._scene(cam, scene)[0]), device=self.device).repeat(self.num_envs, 1).contiguous()
+                               for cam in self._cameras]
+
+    def _redraw_scenes(self, mask: Optional[torch.Tensor] = None):
+        """The scene tables of the current episodes (where ``mask`` is set)."""
+        if self._vr_tables is None:
+            return
+        for c, cam in enumerate(self._cameras):
+            self.randomize_scenes(self._vr_ranges[c], camera=cam, cam_slot=c, scene=self._img_scene, mask=mask, out=self._vr_tables[c])
 
     def _draw(self, dst: torch.Tensor, mask: Optional[torch.Tensor] = None):
         for c, cam in enumerate(self._cameras):
-            self.render_into({"gray": dst[:, c]}, camera=cam, samples=self.samples, show_goal=self.show_goal, mask=mask,
-                             scene=self._img_scene)
+            if self._vr_tables is None:
+                self.render_into({"gray": dst[:, c]}, camera=cam, samples=self.samples, show_goal=self.show_goal, mask=mask,
+                                 scene=self._img_scene)
+            else:       # (the draw kernel's own rows: not validated)
+                self.render_into({"gray": dst[:, c]}, camera=cam, samples=self.samples, show_goal=self.show_goal, mask=mask,
+                                 scene=self._img_scene, scenes=self._vr_tables[c], validate=False)
+
+    def set_state(self, **state):
+        super().set_state(**state)
+        self._redraw_scenes()             # the tables are a function of (seed, episode): a checkpoint does not carry them
 
     def _goal_info(self, b: dict) -> dict:
         return {"achieved_goal": b["achieved_goal"], "desired_goal": b["desired_goal"]}
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None, mask: Optional[torch.Tensor] = None):
         super().reset(seed=seed, options=options, mask=mask)
+        self._redraw_scenes(mask)
         self._draw(self._img, mask)
         return self._img.clone(), self._goal_info({k: v.clone() for k, v in self._obs().items()})
 
@@ -513,6 +622,7 @@ class MyCobotImgVecEnv(MyCobotVecEnv):
             with torch.cuda.device(self.device):      # resets the finished environments only; rewrites their rows of obs / goals
                 _abi.check(self._lib.mcg_reset(self._h, C.c_void_p(m.data_ptr()), 0, C.c_uint64(0), C.byref(self._out), self._stream()),
                            "mcg_reset")
+            self._redraw_scenes(m)        # after final_img: the finished episode's last picture shows its own scene
             self._draw(self._img, m)
         reward = step_out["reward"].float() if self.reward_type == "sparse" else step_out["reward"]
         info = {"is_success": step_out["is_success"],

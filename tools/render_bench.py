@@ -8,7 +8,9 @@ Per case (64 x 64 at samples 1, 2, 4 on --envs environments; 480 x 480 on 256): 
 back-to-back launches between two events on the launch stream; reported: median and spread of the per-launch time.  The states are
 a seeded random-policy rollout with desynchronised episodes (what a training run renders), not the reset pose.  Also: one step() of
 the -v1 image engine (step + render + masked reset + render) against the -v0 state engine of the same configuration.  The camera is
-`sideview`; the 64 x 64 cases at samples 1 and 2 are measured from `gripper_camera_rgb` (the camera on the flange) as well.
+`sideview`; the 64 x 64 cases at samples 1 and 2 are measured from `gripper_camera_rgb` (the camera on the flange) as well, and both
+again with one scene per environment (mcg_render_scenes on a table drawn by mcg_scene_randomize, whose own time is a row too), and the
+-v1 step with visual_randomization.
 
 --alternate-against LIB: the world-camera case (sideview, 64 x 64, samples 1 and 2) of this build and of another build of the library
 (the parent commit's), alternated `rounds` times in one call, each measurement in a process of its own (the library is chosen through
@@ -55,16 +57,37 @@ def env_name(cfg):
     return f"MyCobot{'Reach' if task == 'reach' else 'PickAndPlace'}-Dense-{ctrl}"
 
 
-def render_case(cfg, n, w, h, samples, camera, reps):
+# the ranges of the per-environment rows: those of tests/test_gpu_scene_rand.py (the gripper camera moves less: it is 5 cm from what it sees)
+VISUAL = {"cam_pos": 0.05, "cam_rot": 0.0873, "fovy_scale": (0.9, 1.1), "light_tilt": 0.5236, "light_ambient_scale": (0.7, 1.3),
+          "light_diffuse_scale": (0.7, 1.3), "head_scale": (0.7, 1.3), "rgb": 0.1}
+VISUAL_MOUNTED = dict(VISUAL, cam_pos=0.005, cam_rot=0.0349)
+
+
+def render_case(cfg, n, w, h, samples, camera, reps, scenes=False):
     envs = mg.make(env_name(cfg) + "-v0", num_envs=n, seed=1)
     envs.reset(seed=1)
     rollout(envs, 30)
     out = {"gray": torch.zeros(n, h, w, dtype=torch.uint8, device=envs.device)} if samples > 1 or w == 64 else \
           {"rgb": torch.zeros(n, h, w, 3, dtype=torch.uint8, device=envs.device)}
-    r = timed(lambda: envs.render_into(out, camera=camera, samples=samples), warmup=5, reps=reps, inner=10)
+    more = {}
+    if scenes:       # one scene per environment; validate=False: the timing is the launch's
+        more = dict(scenes=envs.randomize_scenes(VISUAL if camera == "sideview" else VISUAL_MOUNTED, camera=camera), validate=False)
+    r = timed(lambda: envs.render_into(out, camera=camera, samples=samples, **more), warmup=5, reps=reps, inner=10)
     rays = n * w * h * samples * samples
-    r.update(config=cfg, what="mcg_render" if camera == "sideview" else "mcg_render_mounted", camera=camera, envs=n, width=w, height=h,
+    what = "mcg_render_scenes" if scenes else ("mcg_render" if camera == "sideview" else "mcg_render_mounted")
+    r.update(config=cfg, what=what, camera=camera, envs=n, width=w, height=h,
              samples=samples, output=list(out)[0], grays_per_s=rays / (r["median_ms"] * 1e-3) / 1e9)
+    envs.close()
+    return r
+
+
+def randomize_case(cfg, n, reps):
+    envs = mg.make(env_name(cfg) + "-v0", num_envs=n, seed=1)
+    envs.reset(seed=1)
+    rollout(envs, 30)
+    tab = envs.randomize_scenes(VISUAL)
+    r = timed(lambda: envs.randomize_scenes(VISUAL, out=tab), warmup=5, reps=reps, inner=10)
+    r.update(config=cfg, what="mcg_scene_randomize", camera="sideview", envs=n)
     envs.close()
     return r
 
@@ -109,18 +132,24 @@ def main():
     res = {"device": torch.cuda.get_device_name(0), "envs": args.envs, "cases": []}
     for cfg in args.configs.split(","):
         name = env_name(cfg)
-        cases = [(args.envs, 64, 64, 1, "sideview"), (args.envs, 64, 64, 2, "sideview")]
+        cases = [(args.envs, 64, 64, 1, "sideview", False), (args.envs, 64, 64, 2, "sideview", False)]
         if not args.world_only:
-            cases += [(args.envs, 64, 64, 4, "sideview"), (256, 480, 480, 1, "sideview"),
-                      (args.envs, 64, 64, 1, "gripper_camera_rgb"), (args.envs, 64, 64, 2, "gripper_camera_rgb")]
-        for n, w, h, samples, camera in cases:
-            r = render_case(cfg, n, w, h, samples, camera, args.reps)
+            cases += [(args.envs, 64, 64, 4, "sideview", False), (256, 480, 480, 1, "sideview", False),
+                      (args.envs, 64, 64, 1, "gripper_camera_rgb", False), (args.envs, 64, 64, 2, "gripper_camera_rgb", False),
+                      (args.envs, 64, 64, 1, "sideview", True), (args.envs, 64, 64, 2, "sideview", True),
+                      (args.envs, 64, 64, 1, "gripper_camera_rgb", True), (args.envs, 64, 64, 2, "gripper_camera_rgb", True)]
+        for n, w, h, samples, camera, scenes in cases:
+            r = render_case(cfg, n, w, h, samples, camera, args.reps, scenes)
             res["cases"].append(r); print(json.dumps(r), flush=True)
         if args.world_only:
             continue
+        r = randomize_case(cfg, args.envs, args.reps)
+        res["cases"].append(r); print(json.dumps(r), flush=True)
         # one step of the engine with and without pictures
         v0 = mg.make(name + "-v0", num_envs=args.envs, seed=1); v1 = mg.make(name + "-v1", num_envs=args.envs, seed=1)
-        for e, what in ((v0, "step -v0"), (v1, "step -v1 (step + render + masked reset + render, samples 2)")):
+        vr = mg.make(name + "-v1", num_envs=args.envs, seed=1, visual_randomization=VISUAL)
+        for e, what in ((v0, "step -v0"), (v1, "step -v1 (step + render + masked reset + render, samples 2)"),
+                        (vr, "step -v1 with visual_randomization (step + render + masked reset + masked draw of the table + render, samples 2)")):
             e.reset(seed=1)
             rollout(e, 30)
             a = torch.rand(args.envs, e.action_dim, device=e.device) * 2 - 1
