@@ -14,6 +14,8 @@
  *                       TimeLimit(50) from the registration mycobotgym/__init__.py:34; auto-reset as in
  *                       gymnasium.vector (info["final_observation"]) / SB3 VecEnv used by scripts/train.py:80-85
  *   mcg_compute_reward  MyCobotEnv.compute_reward on batched goals (HER)   mycobot.py:289-298, utils.py:24-26
+ *   mcg_her_start / mcg_her_add / mcg_her_sample   SB3's HerReplayBuffer as the reference configures it (n_sampled_goal = 4, strategy
+ *                       "future")   scripts/train.py:89-97
  *   mcg_get_state / mcg_set_state   direct access to data.qpos/qvel/ctrl/qacc_warmstart (set_joint_qpos etc.)
  *
  * Conventions: every pointer in the step/reset/state calls is DEVICE memory owned by the caller;
@@ -319,6 +321,77 @@ typedef struct mcg_scene_rand {
 int mcg_scene_randomize(mcg_env* env, const mcg_scene* base, const mcg_scene_rand* ranges, int cam_slot /* 0..7 */,
                         const uint8_t* mask /* [N] device or NULL = all */, double* scenes /* device [N, MCG_SCENE_ENV_DOUBLES], out */,
                         void* stream);
+
+/* ---- Hindsight replay buffer (SB3's HerReplayBuffer as scripts/train.py:89-97 uses it: goal_selection_strategy "future", on the
+   engine's N lockstep environments).  Stateless on the C side: the caller owns all device memory and passes it per call; there is no
+   handle.  The ring is time-major [capacity, N]: every environment writes slot pos = n_written % capacity on the same call, so
+   n_written is a host integer and no call synchronises.  One record per (slot, env), mcg_her_record_bytes(D, A) bytes, contiguous:
+     byte 0            double achieved[3], next_achieved[3], desired[3]     (float64: a recomputed reward is the engine's own number)
+     byte 72           float  obs[D], next_obs[D], action[A], reward
+     then              int32  t_in_ep   step index inside its episode (saturates at max_episode_steps in an over-long episode)
+                       int32  ep_len    0 while the episode is in flight (or abandoned), back-filled into all its slots when it ends
+                       uint8  terminated, 3 bytes zero
+     zero padding to a multiple of 16 bytes.
+   An episode is abandoned -- its slots keep ep_len 0 and are never sampled -- by mcg_her_start while it is in flight, or when it runs to
+   max_episode_steps transitions without a done flag (a caller error; counted in counters[1]). */
+typedef struct mcg_her_buf {        /* device pointers the caller owns, and the buffer's shape */
+  void* records;                    /* [capacity, N] records; zero before the first call; 16-byte aligned */
+  int32_t* t_run;                   /* [N]     transitions of the episode in flight */
+  float* last_obs;                  /* [N, D]  observation the next transition starts from */
+  double* last_achieved;            /* [N, 3] */
+  uint64_t* counters;               /* [2]     samples that gave up (no valid transition in 256 draws), over-long episodes */
+  int32_t n_envs, obs_dim, act_dim;
+  int32_t capacity;                 /* slots; >= 2 * max_episode_steps: an episode must not overlap itself in the ring */
+  int32_t max_episode_steps;        /* bound of every episode length, and of every loop over one */
+  int32_t reward_type;              /* MCG_REWARD_*: how a relabelled reward is recomputed */
+  double distance_threshold;
+} mcg_her_buf;
+
+typedef struct mcg_her_batch {      /* outputs of mcg_her_sample; device pointers, float32, any may be NULL.  B = batch */
+  float* obs;            /* [B, D] */
+  float* achieved;       /* [B, 3] */
+  float* desired;        /* [B, 3]  also the next observation's desired goal; relabelled in a virtual sample */
+  float* next_obs;       /* [B, D] */
+  float* next_achieved;  /* [B, 3] */
+  float* action;         /* [B, A] */
+  float* reward;         /* [B]     stored (real sample) or recomputed under the new goal (virtual sample) */
+  float* done;           /* [B]     the stored `terminated` (SB3's dones * (1 - timeouts)); not recomputed under the new goal */
+  int32_t* index;        /* [B, 3]  slot, env, slot the new goal came from (-1 in a real sample); all -1 where the sample gave up */
+} mcg_her_batch;
+
+/* All three calls enqueue on `stream` and do not synchronise.  Checked on the host before any HIP call (MCG_ERR_ARG): a null struct or
+   required pointer (every pointer of mcg_her_buf; obs and achieved_goal of `first`; actions and obs, achieved_goal, desired_goal,
+   reward, terminated, truncated, final_obs, final_achieved, final_desired of `out`), n_envs / obs_dim / act_dim / max_episode_steps /
+   batch < 1, capacity < 2 * max_episode_steps, n_virtual outside [0, batch], n_written < 0.  MCG_ERR_UNSUPPORTED: n_virtual > 0 with
+   MCG_REWARD_SHAPING (that reward depends on simulator state, as for mcg_compute_reward). */
+int64_t mcg_her_record_bytes(int obs_dim, int act_dim);      /* 0 where a dimension is < 1 */
+
+/* An episode starts in the environments of `mask` (NULL = all) from the observation a reset wrote to `first`: last_obs, last_achieved
+   and t_run = 0.  An episode that was in flight there is abandoned. */
+int mcg_her_start(const mcg_her_buf* buf, const mcg_step_out* first, const uint8_t* mask /* [N] device or NULL */, void* stream);
+
+/* One transition per environment into slot n_written % capacity; the caller then counts n_written up by one.  `out` is what mcg_step
+   wrote for `actions`.  done = truncated | terminated; where done, the engine's obs / achieved_goal / desired_goal already belong to the
+   next episode: the record's next_obs / next_achieved / desired are final_obs / final_achieved / final_desired there, and the episode's
+   length is written into its t_run + 1 slots.  float64 -> float32 by round-to-nearest-even. */
+int mcg_her_add(const mcg_her_buf* buf, int64_t n_written, const float* actions /* [N, A] device */, const mcg_step_out* out, void* stream);
+
+/* A batch by the `future` strategy; W = min(n_written, capacity), pos = n_written % capacity.  Uniforms: Philox4x32-10 with counter
+   (sample index k, (uint32)call, draw, 3 ^ ((uint32)(call >> 32) << 8)) and key `seed` (stream 3; 0-2: the reset draws), mapped to the
+   pair (u0, u1) as every reset draw is.
+     draw d = 0..255   slot s = min(W - 1, floor(u0 * W)), environment e = min(N - 1, floor(u1 * N)).  The slot's absolute time is
+                       a = n_written - 1 - ((pos - 1 - s) mod capacity).  Valid iff ep_len > 0 and a - t_in_ep >= max(0, n_written -
+                       capacity): the episode is complete and its first slot is not overwritten (an episode is overwritten from its
+                       start).  Sample k takes the first valid pair: SB3's uniform choice among the valid transitions.  After 256
+                       invalid draws it gives up: index -1, outputs zero, counters[0] counted up.
+     draw 256          samples k >= batch - n_virtual (SB3's split, real samples first) are relabelled: the future step
+                       f = min(ep_len - 1, t_in_ep + floor(u0 * (ep_len - t_in_ep))), current step included, as SB3's randint(t, len);
+                       the new goal is next_achieved of slot (s + f - t_in_ep) mod capacity, the reward mcg_compute_reward's expression
+                       on (the sample's next_achieved, the new goal) in float64.
+   t_in_ep and ep_len are clamped to [0, max_episode_steps] where they are read: no address and no loop bound depends on a record's
+   content otherwise, and a corrupt record gives a wrong sample and nothing else. */
+int mcg_her_sample(const mcg_her_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch, int n_virtual,
+                   const mcg_her_batch* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ The numeric path is the HIP library ``libmycobot_hip.so`` (C ABI in ``include/mc
 package does not need a GPU, constructing an environment does.
 """
 from .registry import REGISTRY, spec  # noqa: F401
+from .replay import HerBuffer, HerSamples  # noqa: F401
 from .vec_env import MyCobotImgVecEnv, MyCobotVecEnv, env_class, load_scene, make, validate_scenes  # noqa: F401
 
 __version__ = "0.1.0"

@@ -203,12 +203,33 @@ def scene_from_row(row, target_half=None):
     return cam, scene
 
 
+class McgHerBuf(C.Structure):
+    """The replay buffer's device memory and shape (include/mcg.h: mcg_her_buf); the caller owns every pointer."""
+    _fields_ = [("records", C.c_void_p), ("t_run", C.c_void_p), ("last_obs", C.c_void_p), ("last_achieved", C.c_void_p),
+                ("counters", C.c_void_p), ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("capacity", C.c_int32),
+                ("max_episode_steps", C.c_int32), ("reward_type", C.c_int32), ("distance_threshold", d)]
+
+
+class McgHerBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "achieved", "desired", "next_obs", "next_achieved", "action", "reward", "done", "index")]
+
+
+def her_record_dtype(obs_dim: int, act_dim: int) -> np.dtype:
+    """One record of the replay ring as a numpy structured dtype (include/mcg.h: the layout above mcg_her_buf)."""
+    fields = [("achieved", "<f8", (3,)), ("next_achieved", "<f8", (3,)), ("desired", "<f8", (3,)),
+              ("obs", "<f4", (obs_dim,)), ("next_obs", "<f4", (obs_dim,)), ("action", "<f4", (act_dim,)), ("reward", "<f4"),
+              ("t_in_ep", "<i4"), ("ep_len", "<i4"), ("terminated", "u1")]
+    used = np.dtype(fields).itemsize
+    return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
            "mcg_action_dim", "mcg_nq", "mcg_nv", "mcg_reset", "mcg_step", "mcg_get_state", "mcg_set_state",
            "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts",
-           "mcg_render", "mcg_render_mounted", "mcg_render_scenes", "mcg_scene_randomize")
+           "mcg_render", "mcg_render_mounted", "mcg_render_scenes", "mcg_scene_randomize",
+           "mcg_her_record_bytes", "mcg_her_start", "mcg_her_add", "mcg_her_sample")
 
 _lib = None
 
@@ -257,6 +278,12 @@ def load():
                                         C.c_void_p, C.POINTER(McgRenderOut), C.c_void_p]
         L.mcg_scene_randomize.argtypes = [C.c_void_p, C.POINTER(McgScene), C.POINTER(McgSceneRand), C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+    if hasattr(L, "mcg_her_sample"):      # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_her_record_bytes.argtypes = [C.c_int, C.c_int]; L.mcg_her_record_bytes.restype = C.c_int64
+        L.mcg_her_start.argtypes = [C.POINTER(McgHerBuf), C.POINTER(McgStepOut), C.c_void_p, C.c_void_p]
+        L.mcg_her_add.argtypes = [C.POINTER(McgHerBuf), C.c_int64, C.c_void_p, C.POINTER(McgStepOut), C.c_void_p]
+        L.mcg_her_sample.argtypes = [C.POINTER(McgHerBuf), C.c_int64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(McgHerBatch),
+                                     C.c_void_p]
     _lib = L
     return L
 

@@ -1,0 +1,308 @@
+"""The device-resident hindsight replay buffer (mcg_her_start / mcg_her_add / mcg_her_sample, mycobotgym_amd/replay.py) against the
+rule restated in tests/indep_her.py, and on the real engine.  Shapes: the smallest that break a wrong kernel -- 40 environments
+(neither a multiple of 64 nor of 32, several blocks of the insertion kernel), a ring of 32 slots that wraps, episodes of 1..7 steps."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests.indep_her import History, record_dtype
+
+pytestmark = pytest.mark.gpu
+
+N, D, A, CAP, MAX_STEPS, THRESHOLD = 40, 25, 7, 32, 7, 0.05
+CHECKPOINTS = (5, 31, 32, 33, 100)
+RESTART_AT, RESTARTED = 20, 5
+FIELDS = ("obs", "achieved", "desired", "next_obs", "next_achieved", "action", "reward", "done")
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_events(n_insertions=100):
+    """Step outputs from default_rng(0): ("start", obs, achieved, mask) and ("add", actions, out) events.  final_* differ from the
+    post-reset values; episode lengths are uniform in 1..7; `terminated` on a random half of the ends; before insertion 20 a masked
+    start abandons five episodes in flight.  Goals are drawn within a few centimetres, so that the sparse reward takes both values."""
+    rng = np.random.default_rng(0)
+    goal = lambda: rng.uniform(-0.03, 0.03, (N, 3))
+    events = [("start", rng.normal(size=(N, D)), goal(), None)]
+    left = rng.integers(1, MAX_STEPS + 1, N)             # steps the episode in flight still has
+    in_flight = np.zeros(N, dtype=np.int64)
+    for i in range(n_insertions):
+        if i == RESTART_AT:
+            mask = np.zeros(N, dtype=bool)
+            mask[np.flatnonzero(in_flight > 0)[:RESTARTED]] = True
+            assert mask.sum() == RESTARTED
+            events.append(("start", rng.normal(size=(N, D)), goal(), mask))
+            left[mask] = rng.integers(1, MAX_STEPS + 1, RESTARTED)
+            in_flight[mask] = 0
+        left -= 1
+        done = left == 0
+        terminated = done & (rng.random(N) < 0.5)
+        truncated = done & (~terminated | (rng.random(N) < 0.5))         # the kernel takes truncated | terminated
+        out = {"obs": rng.normal(size=(N, D)), "achieved_goal": goal(), "desired_goal": goal(), "reward": rng.normal(size=N),
+               "terminated": terminated, "truncated": truncated, "final_obs": rng.normal(size=(N, D)), "final_achieved": goal(),
+               "final_desired": goal()}
+        events.append(("add", rng.uniform(-1, 1, (N, A)).astype(np.float32), out))
+        in_flight = np.where(done, 0, in_flight + 1)
+        left[done] = rng.integers(1, MAX_STEPS + 1, int(done.sum()))
+    return tuple(events)
+
+
+@functools.lru_cache(maxsize=None)
+def rule_history(reward_type, n_insertions=100):
+    """The rule's history after every event, its ring at the checkpoints, and its batch: computed once, shared, not modified."""
+    H = History(N, D, A, CAP, MAX_STEPS, reward_type, THRESHOLD)
+    rings = {}
+    for ev in synthetic_events(n_insertions):
+        if ev[0] == "start":
+            H.start(ev[1], ev[2], ev[3])
+        else:
+            H.add(ev[1], ev[2])
+            if H.n in CHECKPOINTS:
+                rings[H.n] = H.ring()
+    return H, rings
+
+
+def apply_event(buf, ev):
+    import torch
+    dev = buf.device
+    t = lambda x: torch.as_tensor(x, device=dev)
+    if ev[0] == "start":
+        buf.start({"observation": t(ev[1]), "achieved_goal": t(ev[2]), "desired_goal": t(np.zeros((N, 3)))}, mask=None if ev[3] is None else t(ev[3]))
+        return
+    o = ev[2]
+    obs = {"observation": t(o["obs"]), "achieved_goal": t(o["achieved_goal"]), "desired_goal": t(o["desired_goal"])}
+    info = {"final_observation": {"observation": t(o["final_obs"]), "achieved_goal": t(o["final_achieved"]), "desired_goal": t(o["final_desired"])}}
+    buf.add(t(ev[1]), obs, t(o["reward"]), t(o["terminated"]), t(o["truncated"]), info)
+
+
+def make_buffer(reward_type="dense", **kw):
+    from mycobotgym_amd import HerBuffer
+    return HerBuffer(capacity=CAP, n_sampled_goal=4, seed=11, num_envs=N, obs_dim=D, act_dim=A, max_episode_steps=MAX_STEPS,
+                     reward_type=reward_type, distance_threshold=THRESHOLD, **kw)
+
+
+def device_ring(buf):
+    return buf.records().cpu().numpy().reshape(buf.capacity, buf.num_envs, -1).view(record_dtype(buf.obs_dim, buf.act_dim))[..., 0]
+
+
+def batch_arrays(b):
+    o = {"obs": b.observations["observation"], "achieved": b.observations["achieved_goal"], "desired": b.observations["desired_goal"],
+         "next_obs": b.next_observations["observation"], "next_achieved": b.next_observations["achieved_goal"], "action": b.actions,
+         "reward": b.rewards[:, 0], "done": b.dones[:, 0], "index": b.index}
+    return {k: v.cpu().numpy() for k, v in o.items()}
+
+
+def bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view({4: np.uint32, 8: np.uint64}[x.dtype.itemsize])
+
+
+def reward_bound_check(lib_reward, r32, reward_type, label):
+    """r32: the kernel's float32 rewards; lib_reward: mcg_compute_reward's float64 on the same goals.  Sparse: exactly its float32 cast.
+    Dense: the float32 cast of a float64 within 1e-15 relative of it (two translation units may contract dx dx + dy dy + dz dz
+    differently: about 1 ulp of float64 after the square root).  -> the worst |float64(r32) - float32(lib)|."""
+    ref = np.asarray(lib_reward, dtype=np.float64)
+    worst = float(np.abs(r32.astype(np.float64) - ref.astype(np.float32).astype(np.float64)).max()) if len(ref) else 0.0
+    print(f"{label}: {len(ref)} relabelled rewards, worst |kernel - float32(mcg_compute_reward)| = {worst:.3e}")
+    if reward_type == "sparse":
+        assert np.array_equal(bits(r32), bits(ref.astype(np.float32)))
+    else:
+        ok = np.zeros(len(ref), dtype=bool)
+        for f in (1.0 - 1e-15, 1.0, 1.0 + 1e-15):
+            ok |= r32 == (ref * f).astype(np.float32)
+        assert ok.all(), (label, int((~ok).sum()))
+    return worst
+
+
+@pytest.mark.parametrize("reward_type", ["dense", "sparse"])
+def test_synthetic_insertion_and_sampling_match_the_rule(built, reward_type):
+    """Records after 5, 31, 32, 33 and 100 insertions and a batch of 1000 equal the rule's bit for bit; the relabelled rewards equal
+    mcg_compute_reward's on the same float64 goals (sparse: exactly; dense: within 1e-15 relative before the float32 cast).
+    Measured on an MI355X: worst |kernel - float32(mcg_compute_reward)| = 0 in both reward types (800 relabelled rewards each)."""
+    import torch
+    H, rings = rule_history(reward_type)
+    batch = 1000
+    n_virtual = int(batch * (1 - 1 / 5))
+    want = H.sample(seed=11, call=0, batch=batch, n_virtual=n_virtual)
+    # the cap of 256 draws is a condition of the inputs, settled before the GPU is touched
+    assert want["draws"].max() <= 64, int(want["draws"].max())
+    assert (want["index"][:, 2] >= 0).sum() == n_virtual == 800
+
+    buf = make_buffer(reward_type)
+    for ev in synthetic_events():
+        apply_event(buf, ev)
+        if ev[0] == "add" and buf.n_written in CHECKPOINTS:
+            got, ref = device_ring(buf), rings[buf.n_written]
+            for name in ref.dtype.names:
+                g, r = np.ascontiguousarray(got[name]), np.ascontiguousarray(ref[name])
+                assert np.array_equal(g.view(np.uint8), r.view(np.uint8)), (buf.n_written, name)
+            assert got.tobytes() == ref.tobytes(), buf.n_written
+    assert buf.n_written == 100
+    got = batch_arrays(buf.sample(batch))
+    assert np.array_equal(got["index"], want["index"])
+    for name in FIELDS:
+        assert got[name].dtype == np.float32 and got[name].shape == want[name].shape, name
+        assert np.array_equal(bits(got[name]), bits(want[name])), name
+    # relabelled rewards against the library's own reward on the same goals
+    from mycobotgym_amd import _abi
+    virtual = want["index"][:, 2] >= 0
+    ag = torch.as_tensor(want["next_achieved64"][virtual], device=buf.device).contiguous()
+    dg = torch.as_tensor(want["goal64"][virtual], device=buf.device).contiguous()
+    out = torch.empty(len(ag), dtype=torch.float64, device=buf.device)
+    _abi.check(_abi.load().mcg_compute_reward(ag.data_ptr(), dg.data_ptr(), len(ag), {"sparse": 0, "dense": 1}[reward_type], THRESHOLD,
+                                              out.data_ptr(), None), "mcg_compute_reward")
+    torch.cuda.synchronize()
+    reward_bound_check(out.cpu().numpy(), got["reward"][virtual], reward_type, f"synthetic {reward_type}")
+    if reward_type == "sparse":
+        assert set(np.unique(got["reward"][virtual])) == {-1.0, 0.0}          # both outcomes occur
+    assert buf.counters() == {"sample_give_ups": 0, "overlong_episodes": 0}
+
+
+def test_give_up_path(built):
+    """No finished episode: every sample gives up -- index -1, zeros, counted -- as an ordinary return; check=True raises."""
+    buf = make_buffer()
+    events = [ev for ev in synthetic_events(3)]
+    never = dict(terminated=np.zeros(N, bool), truncated=np.zeros(N, bool))
+    for ev in events:
+        apply_event(buf, ev if ev[0] == "start" else ("add", ev[1], dict(ev[2], **never)))
+    assert buf.n_written == 3
+    got = batch_arrays(buf.sample(256, check=False))
+    assert (got["index"] == -1).all()
+    for name in FIELDS:
+        assert not bits(got[name]).any(), name
+    assert buf.counters() == {"sample_give_ups": 256, "overlong_episodes": 0}
+    with pytest.raises(RuntimeError, match="no valid transition"):
+        buf.sample(256)
+    assert buf.counters()["sample_give_ups"] == 512
+
+
+def test_overlong_episode_is_abandoned_inside_the_ring(built):
+    """9 insertions and no done flag at a time limit of 7: every environment's episode is counted once and abandoned, nothing of it is
+    sampled, t_run saturates, and the guard slots before and after the ring stay as they were."""
+    buf = make_buffer(guard_rows=2)
+    for g in buf.guards():
+        g.fill_(0xA5)
+    never = dict(terminated=np.zeros(N, bool), truncated=np.zeros(N, bool))
+    for ev in synthetic_events(9):
+        apply_event(buf, ev if ev[0] == "start" else ("add", ev[1], dict(ev[2], **never)))
+    assert buf.counters() == {"sample_give_ups": 0, "overlong_episodes": N}
+    ring = device_ring(buf)
+    assert (ring["ep_len"] == 0).all()
+    assert (ring["t_in_ep"][:9] == np.minimum(np.arange(9), MAX_STEPS)[:, None]).all() and (ring["t_in_ep"][9:] == 0).all()
+    assert (buf.state_dict()["t_run"].cpu().numpy() == MAX_STEPS).all()
+    got = batch_arrays(buf.sample(64, check=False))
+    assert (got["index"] == -1).all() and buf.counters()["sample_give_ups"] == 64
+    # an episode that ends after it ran over stays abandoned; the next one is stored and sampled as usual
+    ev = synthetic_events(12)
+    ends = dict(terminated=np.ones(N, bool), truncated=np.ones(N, bool))
+    apply_event(buf, ("add", ev[10][1], dict(ev[10][2], **ends)))
+    assert (device_ring(buf)["ep_len"] == 0).all()
+    apply_event(buf, ("add", ev[11][1], dict(ev[11][2], **ends)))
+    ring = device_ring(buf)
+    assert (ring["ep_len"][10] == 1).all() and (np.delete(ring["ep_len"], 10, axis=0) == 0).all()
+    got = batch_arrays(buf.sample(64))
+    assert (got["index"][:, 0] == 10).all()
+    for g in buf.guards():
+        assert bool((g == 0xA5).all())
+    assert buf.counters()["overlong_episodes"] == N
+
+
+@pytest.mark.parametrize("env_id", ["MyCobotReach-Dense-joint-v0", "MyCobotPickAndPlace-Sparse-IK-v0"])
+def test_with_the_real_engine(built, env_id):
+    """60 random-policy steps of 40 environments (time limit 7, threshold 0.05: some episodes end by success) into a ring of 32 slots.
+    Real samples are the float32 casts of what step() returned at their step; virtual samples carry the next achieved goal of their
+    future slot and the library's reward for it; the engine's state is what it is without a buffer.
+    Measured on an MI355X: worst |kernel - float32(compute_reward)| = 0 for both ids (409 relabelled rewards each); 320 episodes ended in
+    either run, none of them by success (a random policy does not come within 5 cm in 7 steps), so `dones` is 0 throughout here and its
+    1 is exercised by the synthetic inputs."""
+    import torch
+    from mycobotgym_amd import HerBuffer, make
+    kw = dict(num_envs=N, max_episode_steps=MAX_STEPS, distance_threshold=THRESHOLD, seed=3)
+    envs, twin = make(env_id, **kw), make(env_id, **kw)
+    buf = HerBuffer(envs, capacity=CAP, n_sampled_goal=4, seed=2)
+    assert (buf.num_envs, buf.obs_dim, buf.act_dim, buf.max_episode_steps) == (N, envs.obs_dim, envs.action_dim, MAX_STEPS)
+    host = lambda x: {k: host(v) for k, v in x.items()} if isinstance(x, dict) else x.cpu().numpy()
+    obs, _ = envs.reset(seed=0)
+    twin.reset(seed=0)
+    buf.start(obs)
+    first = host({k: v.clone() for k, v in obs.items()})
+    rng = np.random.default_rng(1)
+    steps = []
+    for _ in range(60):
+        a = torch.as_tensor(rng.uniform(-1, 1, (N, envs.action_dim)).astype(np.float32), device=envs.device)
+        out = envs.step(a)
+        buf.add(a, *out)
+        twin.step(a)
+        o, r, term, trunc, info = out
+        steps.append({"action": host(a), "obs": host(o), "reward": host(r), "terminated": host(term), "truncated": host(trunc),
+                      "final": host(info["final_observation"])})
+    s1, s2 = envs.get_state(), twin.get_state()
+    for k in s1:
+        assert torch.equal(s1[k], s2[k]), k
+    done_count = sum(int((s["truncated"] | s["terminated"]).sum()) for s in steps)
+    success = sum(int(s["terminated"].sum()) for s in steps)
+    print(f"{env_id}: {done_count} episodes ended, {success} of them terminated")
+    assert done_count >= N * (60 // MAX_STEPS)
+
+    batch, n = 512, buf.n_written
+    got = batch_arrays(buf.sample(batch))
+    n_virtual = int(batch * 0.8)
+    idx = got["index"]
+    assert (idx[:batch - n_virtual, 2] == -1).all() and (idx[batch - n_virtual:, 2] >= 0).all() and (idx[:, :2] >= 0).all()
+    time_of = lambda slot: n - 1 - ((n % CAP - 1 - slot) % CAP)
+    f32 = lambda x: np.asarray(x, dtype=np.float64).astype(np.float32)
+
+    def nxt(time, e, key):            # the transition's own next observation: the finished episode's last where it ended
+        s = steps[time]
+        done = s["truncated"][e] or s["terminated"][e]
+        return (s["final"] if done else s["obs"])[key][e]
+
+    goal64, nach64 = [], []
+    for k in range(batch):
+        slot, e, fslot = (int(x) for x in idx[k])
+        tm = time_of(slot)
+        prev = first if tm == 0 else steps[tm - 1]["obs"]
+        assert np.array_equal(bits(got["obs"][k]), bits(f32(prev["observation"][e]))), k
+        assert np.array_equal(bits(got["achieved"][k]), bits(f32(prev["achieved_goal"][e]))), k
+        assert np.array_equal(bits(got["next_obs"][k]), bits(f32(nxt(tm, e, "observation")))), k
+        assert np.array_equal(bits(got["next_achieved"][k]), bits(f32(nxt(tm, e, "achieved_goal")))), k
+        assert np.array_equal(bits(got["action"][k]), bits(steps[tm]["action"][e])), k
+        assert got["done"][k] == float(steps[tm]["terminated"][e]), k
+        if fslot < 0:
+            assert np.array_equal(bits(got["desired"][k]), bits(f32(nxt(tm, e, "desired_goal")))), k
+            assert bits(got["reward"][k:k + 1])[0] == bits(f32(steps[tm]["reward"][e:e + 1]))[0], k
+        else:
+            ft = time_of(fslot)
+            assert tm <= ft < n and ft - tm < MAX_STEPS, k
+            # the future slot belongs to the same episode: no episode end between the two
+            assert not any(steps[x]["truncated"][e] or steps[x]["terminated"][e] for x in range(tm, ft)), k
+            assert np.array_equal(bits(got["desired"][k]), bits(f32(nxt(ft, e, "achieved_goal")))), k
+            goal64.append(nxt(ft, e, "achieved_goal")); nach64.append(nxt(tm, e, "achieved_goal"))
+    lib = envs.compute_reward(np.array(nach64), np.array(goal64)).double().cpu().numpy()
+    reward_bound_check(lib, got["reward"][batch - n_virtual:], envs.reward_type, env_id)
+    assert buf.counters() == {"sample_give_ups": 0, "overlong_episodes": 0}
+    envs.close(); twin.close()
+
+
+def test_checkpoint(built):
+    """state_dict() into a new buffer: the next batches of both are identical; so is the next insertion."""
+    import torch
+    events = synthetic_events(40)
+    buf = make_buffer()
+    for ev in events:
+        apply_event(buf, ev)
+    buf.sample(100)                    # the call counter is part of the state
+    sd = buf.state_dict()
+    assert {k for k, v in sd.items() if isinstance(v, int)} == {"n_written", "n_sampled", "seed"} and len(sd) == 8
+    other = make_buffer()
+    other.seed = 99
+    other.load_state_dict(sd)
+    a, b = batch_arrays(buf.sample(300)), batch_arrays(other.sample(300))
+    for k in a:
+        assert np.array_equal(bits(a[k]), bits(b[k])), k
+    assert (a["index"][:, 0] >= 0).all()
+    nxt = synthetic_events(100)[len(events)]
+    assert nxt[0] == "add"
+    apply_event(buf, nxt); apply_event(other, nxt)
+    assert torch.equal(buf.records(), other.records())
+    assert torch.equal(buf.state_dict()["t_run"], other.state_dict()["t_run"])
