@@ -1466,4 +1466,13 @@ MCG_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, u
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// one block keyed by `seed` as two uniforms in [0, 1) of 53 bits each.  The counter layout is the caller's: rng_pair (mcg_hip.hip),
+// scene_pair (mcg_render.hip) and her_pair (mcg_replay.hip) each keep their own
+MCG_DEV void philox_pair(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, unsigned long long seed, real& u0, real& u1) {
+  uint32_t r[4];
+  philox4x32_10(c0, c1, c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  u0 = (real)((((unsigned long long)r[0] << 32) | r[1]) >> 11) * (1.0 / 9007199254740992.0);
+  u1 = (real)((((unsigned long long)r[2] << 32) | r[3]) >> 11) * (1.0 / 9007199254740992.0);
+}
+
 }  // namespace mcg

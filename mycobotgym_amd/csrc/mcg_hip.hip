@@ -1,4 +1,5 @@
-// mcg_hip.hip -- kernels and C ABI of the MI355X rollout engine (see include/mcg.h for the boundary).
+// mcg_hip.hip -- the MI355X rollout engine: the step, reset and state kernels with their C entries, mcg_create and the library's error buffer
+// (include/mcg.h is the boundary; pictures and replay are units of their own, mcg_render.hip and mcg_replay.hip; mcg_engine.hpp is shared).
 //
 // One environment per lane, 64-lane workgroups, struct-of-arrays state in HBM ([field][N], N fastest, so every
 // state load/store of a wave is one contiguous 512-byte row).  A whole env.step() -- controller, all physics
@@ -8,14 +9,15 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstddef>
-
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "mcg.h"
+#include "mcg_engine.hpp"
 #include "mcg_dynamics.hpp"
 #include "mcg_cube.hpp"
 #include "mcg_coop.hpp"
@@ -25,40 +27,6 @@
 using namespace mcg;
 
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, const char* a = "") { snprintf(g_err, sizeof(g_err), fmt, a); return code; }
-#define HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(MCG_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); } while (0)
-
-// ------------------------------------------------------------------------------------------- device-side views
-struct Cfg {
-  int n, has_object, controller, fetch, reward_type, frame_skip, control_steps, max_episode_steps;
-  int target_in_the_air, auto_reset, nq, nv, obs_dim, act_dim, dr_enable, block_gripper;
-  int coop_pair;         // PickAndPlace: the cooperative phase solves two environments per wave (default; MCG_COOP_PAIR=0: one per wave, the first implementation)
-  int hidden;            // Reach with reward_shaping: the cube stays in the physics as a hidden free body (mycobot.py:475-481)
-  double dr_mass[2], dr_fric[2], qpos0_cube[7];
-  double distance_threshold, height_offset, igx[3], dt, grip_center, grip_range;
-  double init_qpos[19], init_qvel[18], init_ctrl[7];
-  unsigned long long seed;
-  long long env_id_offset;
-  unsigned long long* cnt;   // device: mcg_counters (reset-cap hits, bad-state resets, contacts dropped by the cap, flagged env-sub-steps)
-};
-
-struct View {           // SoA state: field f of env i at d[f * n + i]
-  double* d; int32_t* i32; int n, nq, nv;
-  __device__ double& qpos(int k, int i) const { return d[(size_t)k * n + i]; }
-  __device__ double& qvel(int k, int i) const { return d[(size_t)(nq + k) * n + i]; }
-  __device__ double& ctrl(int k, int i) const { return d[(size_t)(nq + nv + k) * n + i]; }
-  __device__ double& warm(int k, int i) const { return d[(size_t)(nq + nv + 7 + k) * n + i]; }
-  __device__ double& qlag(int k, int i) const { return d[(size_t)(nq + 2 * nv + 7 + k) * n + i]; }
-  __device__ double& goal(int k, int i) const { return d[(size_t)(2 * nq + 2 * nv + 7 + k) * n + i]; }
-  __device__ double& epret(int i) const { return d[(size_t)(2 * nq + 2 * nv + 10) * n + i]; }
-  __device__ double& dr(int k, int i) const { return d[(size_t)(2 * nq + 2 * nv + 11 + k) * n + i]; }
-  __device__ int32_t& elapsed(int i) const { return i32[i]; }
-  __device__ int32_t& episode(int i) const { return i32[n + i]; }
-  __device__ int32_t& eplen(int i) const { return i32[2 * n + i]; }
-};
-inline int state_doubles(int nq, int nv) { return 2 * nq + 2 * nv + 13; }
 
 struct Env {            // one lane's working set
   Robot R;
@@ -74,11 +42,7 @@ MCG_DEV void count_event(const Cfg& C, int slot, bool ev) {
 // ------------------------------------------------------------------------------------------------- sampling
 MCG_DEV void rng_pair(const Cfg& C, int i, int32_t episode, uint32_t draw, uint32_t stream, real& u0, real& u1) {
   unsigned long long gid = (unsigned long long)(C.env_id_offset + i);
-  uint32_t r[4];
-  philox4x32_10((uint32_t)gid, (uint32_t)episode, draw, stream ^ ((uint32_t)(gid >> 32) << 8),
-                (uint32_t)C.seed, (uint32_t)(C.seed >> 32), r);
-  u0 = (real)((((unsigned long long)r[0] << 32) | r[1]) >> 11) * (1.0 / 9007199254740992.0);
-  u1 = (real)((((unsigned long long)r[2] << 32) | r[3]) >> 11) * (1.0 / 9007199254740992.0);
+  philox_pair((uint32_t)gid, (uint32_t)episode, draw, stream ^ ((uint32_t)(gid >> 32) << 8), C.seed, u0, u1);
 }
 
 // _sample_goal (mycobot.py:238-243) with generate_random_point_inside_rectangle (utils.py:14-21); uses draws d, d+1
@@ -984,8 +948,6 @@ __global__ void copy_state_kernel(View V, mcg_state S, int to_engine) {
 // ------------------------------------------------------------------------------------------- host checks of mcg_create
 // A caller's polytope block and model block are checked on the host before any HIP call: the kernels walk the block's own index, and
 // the broad phase trusts mesh_box, hull_rad and the GATE_* literals (mcg_cube.hpp).  On failure: false, and the reason in `why`.
-double norm3(const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
-
 bool polytope_index_ok(const double* pb, size_t np, char* why, size_t nwhy) {
   for (int m = 0; m < MCG_NMESH; m++) {
     const double* meta = pb + 8 * m;     // {V, F, E, offset, Vpad, Fpad, Epad, 0} (mycobotgym_amd/model/polytope.py: pack)
@@ -1070,24 +1032,12 @@ bool model_within_gates(const mcg_model* mm, const double* cube_half, char* why,
 
 }  // namespace
 
-#include "mcg_render.hpp"      // RenderArgs and the launch; the kernel lives in mcg_render.hip, a code object of its own
-
 // ================================================================================================== host ABI
-struct mcg_env {
-  Cfg cfg;
-  View view;
-  mcg_model* d_model;
-  double* d_poly;                 // the mesh geoms' collision tables (mcg_create: polytopes)
-  unsigned long long* d_cnt;      // mcg_counters
-  int device;
-  int num_cu;
-  float4* d_faces;     // mcg_render: the polytopes' face planes as float32 (n, d), mesh by mesh, each range padded to a multiple of four;
-  std::vector<float> faces_host;      // made at mcg_create, uploaded by the first mcg_render (an engine that never draws allocates nothing for it)
-  int foff[MCG_NMESH + 1];
-  bool render_ok;      // false: created from a caller's model that the polytope block at hand does not fit (render_why)
-  char render_why[200];
-  bool no_split;       // MCG_NO_SPLIT=1 in the environment at mcg_create: always the one-wave REACH kernels (tests, A/B timing)
-};
+static thread_local char g_err[512] = "";      // one per thread for the whole library: every unit refuses through mcg_fail (mcg_engine.hpp)
+int mcg::mcg_fail(int code, const char* fmt, ...) {
+  va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
+  return code;
+}
 
 extern "C" {
 
@@ -1095,52 +1045,48 @@ int mcg_abi_version(void) { return MCG_ABI_VERSION; }
 const char* mcg_last_error(void) { return g_err; }
 
 int mcg_default_model(int variant, mcg_model* out) {
-  if (!out || variant < 0 || variant >= MCG_NUM_MODEL_VARIANTS) return fail(MCG_ERR_ARG, "mcg_default_model: bad variant%s");
+  if (!out || variant < 0 || variant >= MCG_NUM_MODEL_VARIANTS) return mcg_fail(MCG_ERR_ARG, "mcg_default_model: bad variant");
   memcpy(out, &kDefaultModels[variant], sizeof(mcg_model));
   return MCG_OK;
 }
 
 int mcg_create(const mcg_config* c, const mcg_model* model, const double* polytopes, int64_t n_polytopes, int device, mcg_env** out) {
-  if (!c || !out) return fail(MCG_ERR_ARG, "mcg_create: null argument%s");
-  if (polytopes && n_polytopes < 8 * MCG_NMESH) return fail(MCG_ERR_ARG, "mcg_create: polytope block too short%s");
-  if (c->n_envs <= 0) return fail(MCG_ERR_ARG, "mcg_create: n_envs must be positive%s");
-  if (c->controller != MCG_CTRL_JOINT && c->controller != MCG_CTRL_IK && c->controller != MCG_CTRL_MOCAP) return fail(MCG_ERR_ARG, "mcg_create: controller must be joint, IK or mocap%s");
-  {   // the mocap controller needs the model variant with the weld (and without arm actuators), the others the one without
-    const mcg_model* mm = model ? model : &kDefaultModels[0];
-    if ((c->controller == MCG_CTRL_MOCAP) != (mm->weld_on != 0.0))
-      return fail(MCG_ERR_ARG, "mcg_create: the mocap controller goes with the mocap model variants (mcg_default_model 2 / 3), joint and IK with 0 / 1%s");
-  }
-  if (c->controller == MCG_CTRL_JOINT && c->fetch_env) return fail(MCG_ERR_ARG, "Joint controller not supported for Fetch env%s");  // mycobot.py:96
-  if (c->reward_type < MCG_REWARD_SPARSE || c->reward_type > MCG_REWARD_SHAPING) return fail(MCG_ERR_ARG, "mcg_create: bad reward_type%s");
+  const mcg_model* const m = model ? model : &kDefaultModels[0];
+  const double* const pb = polytopes ? polytopes : kDefaultPolytopes;
+  const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;      // (the defaults, resolved once)
+  if (!c || !out) return mcg_fail(MCG_ERR_ARG, "mcg_create: null argument");
+  if (polytopes && n_polytopes < 8 * MCG_NMESH) return mcg_fail(MCG_ERR_ARG, "mcg_create: polytope block too short");
+  if (c->n_envs <= 0) return mcg_fail(MCG_ERR_ARG, "mcg_create: n_envs must be positive");
+  if (c->controller != MCG_CTRL_JOINT && c->controller != MCG_CTRL_IK && c->controller != MCG_CTRL_MOCAP) return mcg_fail(MCG_ERR_ARG, "mcg_create: controller must be joint, IK or mocap");
+  // the mocap controller needs the model variant with the weld (and without arm actuators), the others the one without
+  if ((c->controller == MCG_CTRL_MOCAP) != (m->weld_on != 0.0))
+    return mcg_fail(MCG_ERR_ARG, "mcg_create: the mocap controller goes with the mocap model variants (mcg_default_model 2 / 3), joint and IK with 0 / 1");
+  if (c->controller == MCG_CTRL_JOINT && c->fetch_env) return mcg_fail(MCG_ERR_ARG, "Joint controller not supported for Fetch env");  // mycobot.py:96
+  if (c->reward_type < MCG_REWARD_SPARSE || c->reward_type > MCG_REWARD_SHAPING) return mcg_fail(MCG_ERR_ARG, "mcg_create: bad reward_type");
   {
-    const mcg_model* mm = model ? model : &kDefaultModels[0];
     bool ok = true;
-    for (int k = 0; k < 12; k++) ok = ok && (mm->limit_par[k][6] == 1.0 || mm->limit_par[k][6] == 2.0);
-    for (int k = 0; k < 3; k++) ok = ok && (mm->eq_par[k][6] == 1.0 || mm->eq_par[k][6] == 2.0);
-    if (mm->weld_on != 0.0) ok = ok && (mm->weld_par[6] == 1.0 || mm->weld_par[6] == 2.0);
-    if (!ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_create: solimp power must be 1 or 2 (the MJCF default is 2)%s");
+    for (int k = 0; k < 12; k++) ok = ok && (m->limit_par[k][6] == 1.0 || m->limit_par[k][6] == 2.0);
+    for (int k = 0; k < 3; k++) ok = ok && (m->eq_par[k][6] == 1.0 || m->eq_par[k][6] == 2.0);
+    if (m->weld_on != 0.0) ok = ok && (m->weld_par[6] == 1.0 || m->weld_par[6] == 2.0);
+    if (!ok) return mcg_fail(MCG_ERR_UNSUPPORTED, "mcg_create: solimp power must be 1 or 2 (the MJCF default is 2)");
   }
-  if (c->frame_skip <= 0 || c->control_steps <= 0 || c->max_episode_steps <= 0) return fail(MCG_ERR_ARG, "mcg_create: frame_skip, control_steps, max_episode_steps must be positive%s");
+  if (c->frame_skip <= 0 || c->control_steps <= 0 || c->max_episode_steps <= 0) return mcg_fail(MCG_ERR_ARG, "mcg_create: frame_skip, control_steps, max_episode_steps must be positive");
   const bool cube_physics = c->has_object || (c->reward_type == MCG_REWARD_SHAPING && !c->has_object);     // C.has_object below
   if (cube_physics) {     // the PickAndPlace kernels: the polytope block, its fit to the model, the broad-phase gates (host only, before any HIP call)
-    const mcg_model* mm = model ? model : &kDefaultModels[0];
-    const double* pb = polytopes ? polytopes : kDefaultPolytopes;
-    const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;
     char why[200];
-    if (!polytope_index_ok(pb, np, why, sizeof(why))) return fail(MCG_ERR_ARG, "mcg_create: inconsistent polytope block: %s", why);
-    if (!polytopes_fit_model(pb, mm, why, sizeof(why)))
-      return fail(MCG_ERR_ARG, "mcg_create: the polytope block does not fit the model (pass the block specialised with it): %s", why);
+    if (!polytope_index_ok(pb, np, why, sizeof(why))) return mcg_fail(MCG_ERR_ARG, "mcg_create: inconsistent polytope block: %s", why);
+    if (!polytopes_fit_model(pb, m, why, sizeof(why)))
+      return mcg_fail(MCG_ERR_ARG, "mcg_create: the polytope block does not fit the model (pass the block specialised with it): %s", why);
     const bool hidden = !c->has_object;
-    const double cube_half[3] = {hidden ? 0.0 : mm->cube_half[0], hidden ? 0.0 : mm->cube_half[1], hidden ? 0.0 : mm->cube_half[2]};
-    if (!model_within_gates(mm, cube_half, why, sizeof(why))) return fail(MCG_ERR_UNSUPPORTED, "mcg_create: unsupported model: %s", why);
+    const double cube_half[3] = {hidden ? 0.0 : m->cube_half[0], hidden ? 0.0 : m->cube_half[1], hidden ? 0.0 : m->cube_half[2]};
+    if (!model_within_gates(m, cube_half, why, sizeof(why))) return mcg_fail(MCG_ERR_UNSUPPORTED, "mcg_create: unsupported model: %s", why);
   }
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MCG_ERR_HIP, "mcg_create: no HIP device (this engine has no CPU path)%s");
-  if (device < 0 || device >= ndev) return fail(MCG_ERR_ARG, "mcg_create: bad device index%s");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return mcg_fail(MCG_ERR_HIP, "mcg_create: no HIP device (this engine has no CPU path)");
+  if (device < 0 || device >= ndev) return mcg_fail(MCG_ERR_ARG, "mcg_create: bad device index");
   HIP_OK(hipSetDevice(device));
   mcg_env* e = new (std::nothrow) mcg_env();
-  if (!e) return fail(MCG_ERR_ARG, "mcg_create: out of host memory%s");
-  const mcg_model* m = model ? model : &kDefaultModels[0];
+  if (!e) return mcg_fail(MCG_ERR_ARG, "mcg_create: out of host memory");
   Cfg& C = e->cfg;
   // Reach + reward_shaping: stage_rewards reads the cube's site and its pad contacts (mycobot.py:402-448), and the reference only
   // HIDES the cube in Reach (geom and site size := 0, mycobot.py:475-481) -- body, mass and free joint stay.  Those ids run the
@@ -1184,30 +1130,14 @@ int mcg_create(const mcg_config* c, const mcg_model* model, const double* polyto
   if (err == hipSuccess) err = hipMalloc(&e->view.i32, (size_t)3 * C.n * sizeof(int32_t));
   if (err == hipSuccess) err = hipMalloc(&e->d_model, sizeof(mcg_model));
   if (err == hipSuccess) err = hipMalloc(&e->d_cnt, sizeof(mcg_counters));
-  if (err == hipSuccess && C.has_object) {
-    const double* pb = polytopes ? polytopes : kDefaultPolytopes;            // checked above
-    const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;
+  if (err == hipSuccess && C.has_object) {           // (the block was checked above)
     err = hipMalloc(&e->d_poly, np * sizeof(double));
     if (err == hipSuccess) err = hipMemcpy(e->d_poly, pb, np * sizeof(double), hipMemcpyHostToDevice);
   }
-  if (err == hipSuccess) {   // mcg_render's face table.  Engines without the cube in the physics have not had their block checked above: the same two
-    // checks decide here whether they can be drawn (they run either way: their kernels collide nothing)
-    const double* pb = polytopes ? polytopes : kDefaultPolytopes;
-    const size_t np = polytopes ? (size_t)n_polytopes : (size_t)MCG_DEFAULT_POLYTOPES_LEN;
+  if (err == hipSuccess) {   // the ray caster's face table.  Engines without the cube in the physics have not had their block checked above: the same
+    // two checks decide here whether they can be drawn (they run either way: their kernels collide nothing)
     e->render_ok = C.has_object || (polytope_index_ok(pb, np, e->render_why, sizeof(e->render_why)) && polytopes_fit_model(pb, m, e->render_why, sizeof(e->render_why)));
-    if (e->render_ok) {
-      std::vector<float>& tab = e->faces_host;
-      for (int mm = 0; mm < MCG_NMESH; mm++) {
-        const double* meta = pb + 8 * mm;
-        const long long nf = (long long)meta[1], off = (long long)meta[3], vp = (long long)meta[4], fp = (long long)meta[5];
-        const double* f = pb + off + 3 * vp;                    // [4, Fpad]: nx ny nz d
-        e->foff[mm] = (int)(tab.size() / 4);
-        for (long long k = 0; k < nf; k++) for (int a = 0; a < 4; a++) tab.push_back((float)f[a * fp + k]);
-        while ((tab.size() / 4) % 4) { tab.insert(tab.end(), {0.0f, 0.0f, 0.0f, 1e30f}); }
-      }
-      e->foff[MCG_NMESH] = (int)(tab.size() / 4);
-      if (tab.empty()) tab.assign(4, 0.0f);
-    }
+    if (e->render_ok) render_face_table(e, pb);
   }
   if (err == hipSuccess) err = hipMemset(e->d_cnt, 0, sizeof(mcg_counters));
   if (err == hipSuccess) C.cnt = e->d_cnt;
@@ -1215,7 +1145,7 @@ int mcg_create(const mcg_config* c, const mcg_model* model, const double* polyto
   if (err == hipSuccess) err = hipMemset(e->view.i32, 0, (size_t)3 * C.n * sizeof(int32_t));
   if (err == hipSuccess) {          // domain-randomisation scales start at 1
     std::vector<double> ones((size_t)2 * C.n, 1.0);
-    err = hipMemcpy(e->view.d + (size_t)(2 * C.nq + 2 * C.nv + 11) * C.n, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice);
+    err = hipMemcpy(e->view.row(e->view.rows().dr), ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice);
   }
   if (err == hipSuccess) {
     mcg_model mm = *m;
@@ -1223,7 +1153,7 @@ int mcg_create(const mcg_config* c, const mcg_model* model, const double* polyto
     if (C.hidden) mm.cube_half[0] = mm.cube_half[1] = mm.cube_half[2] = 0.0;       // model.geom_size[object0] = 0
     err = hipMemcpy(e->d_model, &mm, sizeof(mcg_model), hipMemcpyHostToDevice);
   }
-  if (err != hipSuccess) { mcg_destroy(e); return fail(MCG_ERR_HIP, "mcg_create: %s", hipGetErrorString(err)); }
+  if (err != hipSuccess) { mcg_destroy(e); return mcg_fail(MCG_ERR_HIP, "mcg_create: %s", hipGetErrorString(err)); }
   *out = e;
   return MCG_OK;
 }
@@ -1263,7 +1193,7 @@ int mcg_nv(const mcg_env* e) { return e ? e->cfg.nv : -1; }
 static mcg_step_out out_or_empty(const mcg_step_out* o) { mcg_step_out z; memset(&z, 0, sizeof(z)); return o ? *o : z; }
 
 int mcg_reset(mcg_env* e, const uint8_t* mask, int reseed, uint64_t seed, const mcg_step_out* out, void* stream) {
-  if (!e) return fail(MCG_ERR_ARG, "mcg_reset: null handle%s");
+  if (!e) return mcg_fail(MCG_ERR_ARG, "mcg_reset: null handle");
   if (reseed) e->cfg.seed = seed;
   if (e->cfg.has_object) {
     dim3 grid((e->cfg.n + PNP_LANES - 1) / PNP_LANES), block(PNP_LANES);
@@ -1303,19 +1233,19 @@ static int launch_step(mcg_env* e, const float* actions, const mcg_step_out& o, 
 }
 
 int mcg_step(mcg_env* e, const float* actions, const mcg_step_out* out, void* stream) {
-  if (!e || !actions) return fail(MCG_ERR_ARG, "mcg_step: null argument%s");
-  if (launch_step(e, actions, out_or_empty(out), (hipStream_t)stream) != MCG_OK) return fail(MCG_ERR_HIP, "mcg_step: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  if (!e || !actions) return mcg_fail(MCG_ERR_ARG, "mcg_step: null argument");
+  if (launch_step(e, actions, out_or_empty(out), (hipStream_t)stream) != MCG_OK) return mcg_fail(MCG_ERR_HIP, "mcg_step: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return MCG_OK;
 }
 
 int mcg_time_steps(mcg_env* e, const float* actions, const mcg_step_out* out, int steps, void* stream, float* ms_total) {
-  if (!e || !actions || !ms_total || steps <= 0) return fail(MCG_ERR_ARG, "mcg_time_steps: bad argument%s");
+  if (!e || !actions || !ms_total || steps <= 0) return mcg_fail(MCG_ERR_ARG, "mcg_time_steps: bad argument");
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t t0, t1;
   HIP_OK(hipEventCreate(&t0)); HIP_OK(hipEventCreate(&t1));
   mcg_step_out o = out_or_empty(out);
   HIP_OK(hipEventRecord(t0, s));
-  for (int k = 0; k < steps; k++) if (launch_step(e, actions, o, s) != MCG_OK) return fail(MCG_ERR_HIP, "mcg_time_steps: launch failed%s");
+  for (int k = 0; k < steps; k++) if (launch_step(e, actions, o, s) != MCG_OK) return mcg_fail(MCG_ERR_HIP, "mcg_time_steps: launch failed");
   HIP_OK(hipEventRecord(t1, s));
   HIP_OK(hipEventSynchronize(t1));
   HIP_OK(hipEventElapsedTime(ms_total, t0, t1));
@@ -1324,7 +1254,7 @@ int mcg_time_steps(mcg_env* e, const float* actions, const mcg_step_out* out, in
 }
 
 static int copy_state(mcg_env* e, const mcg_state* s, int to_engine, void* stream) {
-  if (!e || !s) return fail(MCG_ERR_ARG, "mcg_get/set_state: null argument%s");
+  if (!e || !s) return mcg_fail(MCG_ERR_ARG, "mcg_get/set_state: null argument");
   dim3 grid((e->cfg.n + 255) / 256), block(256);
   hipLaunchKernelGGL(copy_state_kernel, grid, block, 0, (hipStream_t)stream, e->view, *s, to_engine);
   HIP_OK(hipGetLastError());
@@ -1332,7 +1262,7 @@ static int copy_state(mcg_env* e, const mcg_state* s, int to_engine, void* strea
 }
 int mcg_get_state(mcg_env* e, const mcg_state* dst, void* stream) { return copy_state(e, dst, 0, stream); }
 uint64_t mcg_get_seed(const mcg_env* e) { return e ? (uint64_t)e->cfg.seed : 0; }
-int mcg_set_seed(mcg_env* e, uint64_t seed) { if (!e) return fail(MCG_ERR_ARG, "mcg_set_seed: null handle%s"); e->cfg.seed = seed; return MCG_OK; }
+int mcg_set_seed(mcg_env* e, uint64_t seed) { if (!e) return mcg_fail(MCG_ERR_ARG, "mcg_set_seed: null handle"); e->cfg.seed = seed; return MCG_OK; }
 int mcg_set_state(mcg_env* e, const mcg_state* src, void* stream) { return copy_state(e, src, 1, stream); }
 
 #ifdef MCG_COOP_DEBUG
@@ -1344,7 +1274,7 @@ extern "C" int mcg_debug_coop_dump(double* out, int clear) {
 #endif
 
 int mcg_get_counters(mcg_env* e, mcg_counters* out, int clear) {
-  if (!e || !out) return fail(MCG_ERR_ARG, "mcg_get_counters: null argument%s");
+  if (!e || !out) return mcg_fail(MCG_ERR_ARG, "mcg_get_counters: null argument");
   HIP_OK(hipSetDevice(e->device));
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemcpy(out, e->d_cnt, sizeof(mcg_counters), hipMemcpyDeviceToHost));
@@ -1353,146 +1283,18 @@ int mcg_get_counters(mcg_env* e, mcg_counters* out, int clear) {
 }
 
 int mcg_debug_contacts(mcg_env* e, int32_t* count, int32_t* dropped, double* data, void* stream) {
-  if (!e || !count || !data) return fail(MCG_ERR_ARG, "mcg_debug_contacts: null argument%s");
-  if (!e->cfg.has_object) return fail(MCG_ERR_UNSUPPORTED, "mcg_debug_contacts: Reach has no collision pass%s");
+  if (!e || !count || !data) return mcg_fail(MCG_ERR_ARG, "mcg_debug_contacts: null argument");
+  if (!e->cfg.has_object) return mcg_fail(MCG_ERR_UNSUPPORTED, "mcg_debug_contacts: Reach has no collision pass");
   dim3 grid((e->cfg.n + PNP_LANES - 1) / PNP_LANES), block(64);
   hipLaunchKernelGGL(contacts_pnp_kernel, grid, block, 0, (hipStream_t)stream, e->cfg, e->view, e->d_model, e->d_poly, count, dropped, data);
   HIP_OK(hipGetLastError());
   return MCG_OK;
 }
 
-// ---- the three picture entries' shared pieces (host only)
-// the checks of what is per call, in the order and with the texts mcg_render has always had; nothing here touches HIP
-static int render_call_checks(const char* fn, const mcg_render_out* out, int width, int height, int samples, int body, double znear) {
-  if (!out->rgb && !out->gray && !out->depth && !out->geom) return fail(MCG_ERR_ARG, "%s: all four outputs are null", fn);
-  if (width < 1 || width > 512 || height < 1 || height > 512) return fail(MCG_ERR_ARG, "%s: width and height must be in 1..512", fn);
-  if (samples < 1 || samples > 4) return fail(MCG_ERR_ARG, "%s: samples must be in 1..4", fn);
-  if (body < -1 || body >= NB) return fail(MCG_ERR_ARG, "%s: body must be -1 (the world) or an engine body 0..11", fn);
-  if (!(std::isfinite(znear) && znear >= 0.0)) return fail(MCG_ERR_ARG, "%s: znear must be finite and not negative", fn);
-  return MCG_OK;
-}
-
-// the checks of a scene's own values
-static int scene_value_checks(const char* fn, const mcg_scene* sc) {
-  if (!(sc->fovy > 0.0 && sc->fovy < 180.0)) return fail(MCG_ERR_ARG, "%s: fovy must be in (0, 180) degrees", fn);
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) {
-      double s = 0;
-      for (int k = 0; k < 3; k++) s += sc->cam_mat[3 * k + a] * sc->cam_mat[3 * k + b];
-      if (!(std::fabs(s - (a == b ? 1.0 : 0.0)) <= 1e-9)) return fail(MCG_ERR_ARG, "%s: cam_mat is not orthonormal to 1e-9", fn);
-    }
-  if (!(std::fabs(norm3(sc->light_dir) - 1.0) <= 1e-9)) return fail(MCG_ERR_ARG, "%s: light_dir is not a unit vector to 1e-9", fn);
-  return MCG_OK;
-}
-
-// the first picture of an engine: the face table goes to the device (a blocking copy, once)
-static int render_upload_faces(mcg_env* e) {
-  if (e->d_faces) return MCG_OK;
-  HIP_OK(hipSetDevice(e->device));
-  float4* d = nullptr;
-  HIP_OK(hipMalloc(&d, e->faces_host.size() * sizeof(float)));
-  const hipError_t err = hipMemcpy(d, e->faces_host.data(), e->faces_host.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (err != hipSuccess) { (void)hipFree(d); return fail(MCG_ERR_HIP, "mcg_render: %s", hipGetErrorString(err)); }
-  e->d_faces = d;
-  return MCG_OK;
-}
-
-// what of RenderArgs is per call: the target box, the picture, the face table, mask and outputs (A zeroed by the caller)
-static void render_call_args(RenderArgs& A, const mcg_env* e, const double* target_half, int width, int height, int samples, int target_at_goal,
-                             const uint8_t* mask, const mcg_render_out* out) {
-  for (int k = 0; k < 3; k++) A.target_half[k] = (float)target_half[k];
-  A.W = width; A.H = height; A.S = samples; A.target_at_goal = target_at_goal ? 1 : 0;
-  A.draw_cube = (e->cfg.has_object && !e->cfg.hidden) ? 1 : 0;       // the reference hides the cube in Reach (mycobot.py:475-481)
-  A.dwords = (width % 4 == 0) && ((uintptr_t)out->rgb % 4 == 0) && ((uintptr_t)out->gray % 4 == 0) && ((uintptr_t)out->depth % 16 == 0)
-             && ((uintptr_t)out->geom % 4 == 0);
-  memcpy(A.foff, e->foff, sizeof(A.foff));
-  A.faces = e->d_faces; A.mask = mask; A.out = *out;
-}
-
-int mcg_render_mounted(mcg_env* e, const mcg_scene* sc, int body, double znear, int width, int height, int samples, int target_at_goal,
-                       const uint8_t* mask, const mcg_render_out* out, void* stream) {
-  // host checks first: nothing below them touches HIP.  (mcg_render's texts are kept: it is this entry with body = -1, znear = 0)
-  const char* fn = (body == -1 && znear == 0.0) ? "mcg_render" : "mcg_render_mounted";
-  if (!sc || !out) return fail(MCG_ERR_ARG, "%s: null scene or output block", fn);
-  if (int rc = render_call_checks(fn, out, width, height, samples, body, znear)) return rc;
-  if (int rc = scene_value_checks(fn, sc)) return rc;
-  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
-  if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
-  if (int rc = render_upload_faces(e)) return rc;
-  const bool mounted = !(body == -1 && znear == 0.0);       // the world camera without a near plane keeps its own kernel
-  RenderArgs A;
-  memset(&A, 0, sizeof(A));
-  for (int k = 0; k < 3; k++) { A.cam_pos[k] = sc->cam_pos[k]; A.light[k] = sc->light_dir[k]; }
-  for (int k = 0; k < 9; k++) { A.cam_mat[k] = sc->cam_mat[k]; A.cam_matf[k] = (float)sc->cam_mat[k]; }
-  A.focal = (float)(0.5 * height / std::tan(0.5 * sc->fovy * 3.14159265358979323846 / 180.0));
-  A.la = (float)sc->light_ambient; A.ld = (float)sc->light_diffuse; A.ha = (float)sc->head_ambient; A.hd = (float)sc->head_diffuse;
-  const double* rgb[6] = {sc->rgb_ground, sc->rgb_table, sc->rgb_cube, sc->rgb_target, sc->rgb_mesh, sc->rgb_sky};
-  for (int c = 0; c < 6; c++) for (int k = 0; k < 3; k++) A.rgb[c][k] = (float)(255.0 * rgb[c][k]);
-  render_call_args(A, e, sc->target_half, width, height, samples, target_at_goal, mask, out);
-  const size_t lds_bytes = (size_t)render_head_floats(mounted) * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;     // built-in tables: 35 KB
-  if (lds_bytes > 64 * 1024) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: the face tables do not fit the 64 KB of LDS a workgroup asks for (about 3 200 faces)%s");
-  const hipError_t lerr = (hipError_t)launch_render(A, mounted, body, (float)znear, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
-                                                    e->view.d + (size_t)(2 * e->cfg.nq + 2 * e->cfg.nv + 7) * e->cfg.n, e->d_model);
-  if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_render: launch: %s", hipGetErrorString(lerr));
-  return MCG_OK;
-}
-
-int mcg_render_scenes(mcg_env* e, const double* scenes, const double* target_half, int body, double znear, int width, int height, int samples,
-                      int target_at_goal, const uint8_t* mask, const mcg_render_out* out, void* stream) {
-  const char* fn = "mcg_render_scenes";
-  if (!scenes) return fail(MCG_ERR_ARG, "%s: null scene table", fn);
-  if (!target_half || !out) return fail(MCG_ERR_ARG, "%s: null target_half or output block", fn);
-  if (int rc = render_call_checks(fn, out, width, height, samples, body, znear)) return rc;
-  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
-  if (!e->render_ok) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: this engine's model came without the polytope block specialised with it: %s", e->render_why);
-  if (int rc = render_upload_faces(e)) return rc;
-  RenderArgs A;          // camera, light and colours stay zero: the kernel takes them from the table
-  memset(&A, 0, sizeof(A));
-  render_call_args(A, e, target_half, width, height, samples, target_at_goal, mask, out);
-  const size_t lds_bytes = (size_t)RENDER_HEAD_FLOATS_SCENES * sizeof(float) + (size_t)e->foff[MCG_NMESH] * sizeof(float4) + RENDER_TILE_BYTES;
-  if (lds_bytes > 64 * 1024) return fail(MCG_ERR_UNSUPPORTED, "mcg_render: the face tables do not fit the 64 KB of LDS a workgroup asks for (about 3 200 faces)%s");
-  const hipError_t lerr = (hipError_t)launch_render_scenes(A, scenes, body, (float)znear, e->cfg.n, e->cfg.nq, lds_bytes, (hipStream_t)stream, e->view.d,
-                                                           e->view.d + (size_t)(2 * e->cfg.nq + 2 * e->cfg.nv + 7) * e->cfg.n, e->d_model);
-  if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_render_scenes: launch: %s", hipGetErrorString(lerr));
-  return MCG_OK;
-}
-
-int mcg_scene_randomize(mcg_env* e, const mcg_scene* base, const mcg_scene_rand* r, int cam_slot, const uint8_t* mask, double* scenes, void* stream) {
-  const char* fn = "mcg_scene_randomize";
-  if (!base || !r || !scenes) return fail(MCG_ERR_ARG, "%s: null base scene, ranges or scene table", fn);
-  if (cam_slot < 0 || cam_slot >= MCG_SCENE_RAND_CAM_SLOTS) return fail(MCG_ERR_ARG, "%s: cam_slot must be in 0..7", fn);
-  {
-    bool ok = std::isfinite(r->light_tilt) && r->light_tilt >= 0.0;
-    for (int k = 0; k < 3; k++) ok = ok && std::isfinite(r->cam_pos[k]) && r->cam_pos[k] >= 0.0 && std::isfinite(r->cam_rot[k]) && r->cam_rot[k] >= 0.0;
-    for (int k = 0; k < 6; k++) ok = ok && std::isfinite(r->rgb[k]) && r->rgb[k] >= 0.0;
-    if (!ok) return fail(MCG_ERR_ARG, "%s: a range is negative or not finite", fn);
-  }
-  if (!(r->light_tilt <= 3.14159265358979323846)) return fail(MCG_ERR_ARG, "%s: light_tilt must be in [0, pi]", fn);
-  const double* pairs[4] = {r->fovy_scale, r->light_ambient_scale, r->light_diffuse_scale, r->head_scale};
-  for (int k = 0; k < 4; k++)
-    if (!(std::isfinite(pairs[k][0]) && std::isfinite(pairs[k][1]) && pairs[k][0] > 0.0 && pairs[k][0] <= pairs[k][1]))
-      return fail(MCG_ERR_ARG, "%s: a scale pair needs 0 < lo <= hi, both finite", fn);
-  if (int rc = scene_value_checks(fn, base)) return rc;
-  if (!(base->fovy * r->fovy_scale[1] < 180.0)) return fail(MCG_ERR_ARG, "%s: fovy * fovy_scale[1] must stay below 180 degrees", fn);
-  if (!e) return fail(MCG_ERR_ARG, "%s: null handle", fn);
-  SceneRandArgs P;
-  static_assert(offsetof(mcg_scene, target_half) == MCG_SCENE_PAD * sizeof(double), "a row is the head of mcg_scene");
-  memcpy(P.base, base, sizeof(P.base));
-  P.r = *r; P.seed = e->cfg.seed; P.env_id_offset = e->cfg.env_id_offset; P.cam_slot = cam_slot; P.n = e->cfg.n;
-  const hipError_t lerr = (hipError_t)launch_scene_randomize(P, e->view.i32 + e->cfg.n, mask, scenes, (hipStream_t)stream);
-  if (lerr != hipSuccess) return fail(MCG_ERR_HIP, "mcg_scene_randomize: launch: %s", hipGetErrorString(lerr));
-  return MCG_OK;
-}
-
-int mcg_render(mcg_env* e, const mcg_scene* sc, int width, int height, int samples, int target_at_goal, const uint8_t* mask,
-               const mcg_render_out* out, void* stream) {
-  return mcg_render_mounted(e, sc, -1, 0.0, width, height, samples, target_at_goal, mask, out, stream);
-}
-
 int mcg_compute_reward(const double* achieved, const double* desired, int n, int reward_type, double threshold,
                        double* out, void* stream) {
-  if (!achieved || !desired || !out || n < 0) return fail(MCG_ERR_ARG, "mcg_compute_reward: bad argument%s");
-  if (reward_type != MCG_REWARD_SPARSE && reward_type != MCG_REWARD_DENSE) return fail(MCG_ERR_UNSUPPORTED, "mcg_compute_reward: reward_shaping needs simulator state%s");
+  if (!achieved || !desired || !out || n < 0) return mcg_fail(MCG_ERR_ARG, "mcg_compute_reward: bad argument");
+  if (reward_type != MCG_REWARD_SPARSE && reward_type != MCG_REWARD_DENSE) return mcg_fail(MCG_ERR_UNSUPPORTED, "mcg_compute_reward: reward_shaping needs simulator state");
   if (n == 0) return MCG_OK;
   hipLaunchKernelGGL(reward_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, achieved, desired, n, reward_type, threshold, out);
   HIP_OK(hipGetLastError());

@@ -1,5 +1,5 @@
 // mcg_render.hpp -- the picture of an environment: a ray caster over the engine's own state (mcg_render; MyCobotImgEnv / render(),
-// mycobot.py:308-311, 517-545).
+// mycobot.py:308-311, 517-545).  The kernel; mcg_render.hip, which alone includes this file, holds the entries that launch it.
 //
 // The scene is the ground plane, three boxes (table, cube, target site) and the fourteen mesh geoms as their collision polytopes (face
 // planes n.x <= d in the frame of the body a mesh rides on: the tables the mesh collision uses, within 1 mm of the convex hulls).  A ray
@@ -54,14 +54,13 @@ constexpr int RENDER_CAM = RENDER_HEAD_FLOATS;        // a mounted camera's head
 constexpr int RENDER_CAM_MAT = RENDER_CAM + 4;
 constexpr int RENDER_HEAD_FLOATS_MOUNTED = RENDER_HEAD_FLOATS + 16;
 static_assert((RENDER_HEAD_FLOATS_MOUNTED * 4) % 16 == 0, "the face table is read as b128");
-constexpr int render_head_floats(bool mounted) { return mounted ? RENDER_HEAD_FLOATS_MOUNTED : RENDER_HEAD_FLOATS; }
 // per-environment scenes (mcg_render_scenes): the mounted head and, converted by lane 0 from the environment's row, the focal length in
 // pixels, the four shading coefficients, the light's direction in the world; the six colours take the place of the call's in RENDER_RGB
 constexpr int RENDER_SCN = RENDER_HEAD_FLOATS_MOUNTED;
 constexpr int RENDER_SCN_FOCAL = RENDER_SCN, RENDER_SCN_SHADE = RENDER_SCN + 1, RENDER_SCN_LIGHT = RENDER_SCN + 5;
 constexpr int RENDER_HEAD_FLOATS_SCENES = RENDER_HEAD_FLOATS_MOUNTED + 8;
 static_assert((RENDER_HEAD_FLOATS_SCENES * 4) % 16 == 0, "the face table is read as b128");
-constexpr int render_head_floats(bool mounted, bool scenes) { return scenes ? RENDER_HEAD_FLOATS_SCENES : render_head_floats(mounted); }
+constexpr int render_head_floats(bool mounted, bool scenes) { return scenes ? RENDER_HEAD_FLOATS_SCENES : (mounted ? RENDER_HEAD_FLOATS_MOUNTED : RENDER_HEAD_FLOATS); }
 constexpr int RENDER_TILE_BYTES = (RENDER_LANES / 64) * 3 * 256 * 4;                    // per wave: 256 pixels x (packed r g b gray, depth, geom); after the faces
 constexpr float RENDER_BOX_SLACK = 1e-6f;             // the slab test is a filter: the faces decide
 
@@ -79,27 +78,6 @@ struct RenderArgs {
   mcg_render_out out;
 };
 
-// the launch (mcg_render.hip): 0, or the hipError_t of the launch
-// mounted: render_kernel<true>, with A.cam_pos / A.cam_mat stated in the frame of engine body `body` (-1: the world) and the near plane
-// znear, metres along the camera's -z; otherwise the world camera's kernel, which reads neither
-int launch_render(const RenderArgs& A, bool mounted, int body, float znear, int n, int nq, size_t lds_bytes, hipStream_t stream,
-                  const double* qpos, const double* goal, const mcg_model* model);
-// the third instantiation: camera, fovy, light, shading coefficients and colours of environment e from row e of `scenes` (device,
-// [n, MCG_SCENE_ENV_DOUBLES]); of A it reads what is per call (target_half, the picture's size, the face table, mask, out)
-int launch_render_scenes(const RenderArgs& A, const double* scenes, int body, float znear, int n, int nq, size_t lds_bytes, hipStream_t stream,
-                         const double* qpos, const double* goal, const mcg_model* model);
-
-// mcg_scene_randomize's kernel (mcg_render.hip): one lane per environment
-struct SceneRandArgs {
-  double base[MCG_SCENE_PAD];                         // the base scene as a row
-  mcg_scene_rand r;
-  unsigned long long seed;
-  long long env_id_offset;
-  int cam_slot, n;
-};
-int launch_scene_randomize(const SceneRandArgs& P, const int32_t* episode, const uint8_t* mask, double* scenes, hipStream_t stream);
-
-#ifdef MCG_RENDER_KERNELS      // the device code: compiled in mcg_render.hip alone (see there)
 struct RayHit { float t; int id; float nl, nd; };      // distance along the (unit) ray, geom id, n.(-light), n.(-ray) of the face hit
 
 // slab test of the ray o + t d against the box |x - c| <= h; on a hit (the ray enters from outside, in front of the camera): tin and the
@@ -434,5 +412,4 @@ __global__ __launch_bounds__(RENDER_LANES) void render_kernel(RenderArgs A, cons
 }
 
 }  // namespace
-#endif  // MCG_RENDER_KERNELS
 }  // namespace mcg

@@ -1,24 +1,19 @@
 // mcg_replay.hip -- the hindsight replay buffer (include/mcg.h: mcg_her_*): insertion and `future`-strategy sampling on the device.
 //
 // A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives: the step kernels' code object stays laid
-// out as it is without this file.  The C side is stateless: every call gets the caller's device pointers in an mcg_her_buf.
+// out as it is without this file.  Kernels and C entries are both here.  The C side is stateless: every call gets the caller's device
+// pointers in an mcg_her_buf; of mcg_engine.hpp it uses the error reporting alone.
 //
 // A record is read and written as 4-byte words (the nine float64 goals, words 0-17, as 8-byte pairs); W_* below name the words.
-#include <cstdio>
 #include <hip/hip_runtime.h>
 
 #include "mcg.h"
-#include "mcg_dynamics.hpp"      // philox4x32_10
+#include "mcg_engine.hpp"        // mcg_fail
+#include "mcg_dynamics.hpp"      // philox_pair
 
 using namespace mcg;
 
 namespace {
-
-// mcg_last_error() hands out mcg_hip.hip's thread-local message buffer (512 bytes); this unit's refusals are written into it
-int fail(int code, const char* fmt, const char* a = "") {
-  snprintf(const_cast<char*>(mcg_last_error()), 512, fmt, a);
-  return code;
-}
 
 constexpr int GOAL_WORDS = 18;          // achieved[3], next_achieved[3], desired[3] as doubles
 constexpr int HER_STREAM = 3;           // Philox stream of the sampling draws (0: goals, 1: mass and friction, 2: pictures)
@@ -135,10 +130,7 @@ __global__ __launch_bounds__(ADD_LANES) void her_add_kernel(Her B, int pos, int 
 
 // ----------------------------------------------------------------------------------------------------------- sample
 MCG_DEV void her_pair(unsigned long long seed, unsigned long long call, uint32_t k, uint32_t draw, double& u0, double& u1) {
-  uint32_t r[4];
-  philox4x32_10(k, (uint32_t)call, draw, (uint32_t)HER_STREAM ^ ((uint32_t)(call >> 32) << 8), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-  u0 = (double)((((unsigned long long)r[0] << 32) | r[1]) >> 11) * (1.0 / 9007199254740992.0);
-  u1 = (double)((((unsigned long long)r[2] << 32) | r[3]) >> 11) * (1.0 / 9007199254740992.0);
+  philox_pair(k, (uint32_t)call, draw, (uint32_t)HER_STREAM ^ ((uint32_t)(call >> 32) << 8), seed, u0, u1);
 }
 
 struct Batch { float *obs, *ach, *des, *nobs, *nach, *act, *rew, *done; int32_t* index; };
@@ -243,13 +235,13 @@ __global__ __launch_bounds__(SAMPLE_LANES) void her_sample_kernel(Her B, long lo
 }
 
 int check_buf(const mcg_her_buf* b, const char* who) {
-  if (!b) return fail(MCG_ERR_ARG, "%s: null mcg_her_buf", who);
-  if (!b->records || !b->t_run || !b->last_obs || !b->last_achieved || !b->counters) return fail(MCG_ERR_ARG, "%s: null pointer in mcg_her_buf", who);
-  if (b->n_envs < 1 || b->obs_dim < 1 || b->act_dim < 1) return fail(MCG_ERR_ARG, "%s: n_envs, obs_dim and act_dim must be >= 1", who);
-  if (b->max_episode_steps < 1) return fail(MCG_ERR_ARG, "%s: max_episode_steps must be >= 1", who);
+  if (!b) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_her_buf", who);
+  if (!b->records || !b->t_run || !b->last_obs || !b->last_achieved || !b->counters) return mcg_fail(MCG_ERR_ARG, "%s: null pointer in mcg_her_buf", who);
+  if (b->n_envs < 1 || b->obs_dim < 1 || b->act_dim < 1) return mcg_fail(MCG_ERR_ARG, "%s: n_envs, obs_dim and act_dim must be >= 1", who);
+  if (b->max_episode_steps < 1) return mcg_fail(MCG_ERR_ARG, "%s: max_episode_steps must be >= 1", who);
   if ((long long)b->capacity < 2ll * b->max_episode_steps)
-    return fail(MCG_ERR_ARG, "%s: capacity < 2 * max_episode_steps (an episode must not overlap itself in the ring)", who);
-  if (((uintptr_t)b->records & 15) != 0) return fail(MCG_ERR_ARG, "%s: records is not 16-byte aligned", who);
+    return mcg_fail(MCG_ERR_ARG, "%s: capacity < 2 * max_episode_steps (an episode must not overlap itself in the ring)", who);
+  if (((uintptr_t)b->records & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: records is not 16-byte aligned", who);
   return MCG_OK;
 }
 
@@ -264,7 +256,7 @@ Her view(const mcg_her_buf* b) {
 
 int launched() {
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MCG_OK : fail(MCG_ERR_HIP, "mcg_her kernel launch: %s", hipGetErrorString(e));
+  return e == hipSuccess ? MCG_OK : mcg_fail(MCG_ERR_HIP, "mcg_her kernel launch: %s", hipGetErrorString(e));
 }
 
 }  // namespace
@@ -278,8 +270,8 @@ int64_t mcg_her_record_bytes(int obs_dim, int act_dim) {
 
 int mcg_her_start(const mcg_her_buf* buf, const mcg_step_out* first, const uint8_t* mask, void* stream) {
   if (const int rc = check_buf(buf, "mcg_her_start")) return rc;
-  if (!first) return fail(MCG_ERR_ARG, "mcg_her_start: null mcg_step_out");
-  if (!first->obs || !first->achieved_goal) return fail(MCG_ERR_ARG, "mcg_her_start: obs and achieved_goal of the reset's output are required");
+  if (!first) return mcg_fail(MCG_ERR_ARG, "mcg_her_start: null mcg_step_out");
+  if (!first->obs || !first->achieved_goal) return mcg_fail(MCG_ERR_ARG, "mcg_her_start: obs and achieved_goal of the reset's output are required");
   const Her B = view(buf);
   const long long total = (long long)B.n * (B.L.D + 4);
   hipLaunchKernelGGL(her_start_kernel, dim3((unsigned)((total + ADD_LANES - 1) / ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
@@ -289,12 +281,12 @@ int mcg_her_start(const mcg_her_buf* buf, const mcg_step_out* first, const uint8
 
 int mcg_her_add(const mcg_her_buf* buf, int64_t n_written, const float* actions, const mcg_step_out* out, void* stream) {
   if (const int rc = check_buf(buf, "mcg_her_add")) return rc;
-  if (n_written < 0) return fail(MCG_ERR_ARG, "mcg_her_add: n_written < 0");
-  if (!actions) return fail(MCG_ERR_ARG, "mcg_her_add: null actions");
-  if (!out) return fail(MCG_ERR_ARG, "mcg_her_add: null mcg_step_out");
+  if (n_written < 0) return mcg_fail(MCG_ERR_ARG, "mcg_her_add: n_written < 0");
+  if (!actions) return mcg_fail(MCG_ERR_ARG, "mcg_her_add: null actions");
+  if (!out) return mcg_fail(MCG_ERR_ARG, "mcg_her_add: null mcg_step_out");
   if (!out->obs || !out->achieved_goal || !out->desired_goal || !out->reward || !out->terminated || !out->truncated || !out->final_obs ||
       !out->final_achieved || !out->final_desired)
-    return fail(MCG_ERR_ARG, "mcg_her_add: obs, achieved_goal, desired_goal, reward, terminated, truncated and the three final_* of the step's output are required");
+    return mcg_fail(MCG_ERR_ARG, "mcg_her_add: obs, achieved_goal, desired_goal, reward, terminated, truncated and the three final_* of the step's output are required");
   const Her B = view(buf);
   const int elems = 9 + (B.L.words - GOAL_WORDS);
   int epb = ADD_LANES / elems;
@@ -307,12 +299,12 @@ int mcg_her_add(const mcg_her_buf* buf, int64_t n_written, const float* actions,
 int mcg_her_sample(const mcg_her_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch, int n_virtual,
                    const mcg_her_batch* out, void* stream) {
   if (const int rc = check_buf(buf, "mcg_her_sample")) return rc;
-  if (n_written < 0) return fail(MCG_ERR_ARG, "mcg_her_sample: n_written < 0");
-  if (batch < 1) return fail(MCG_ERR_ARG, "mcg_her_sample: batch must be >= 1");
-  if (n_virtual < 0 || n_virtual > batch) return fail(MCG_ERR_ARG, "mcg_her_sample: n_virtual outside [0, batch]");
-  if (!out) return fail(MCG_ERR_ARG, "mcg_her_sample: null mcg_her_batch");
+  if (n_written < 0) return mcg_fail(MCG_ERR_ARG, "mcg_her_sample: n_written < 0");
+  if (batch < 1) return mcg_fail(MCG_ERR_ARG, "mcg_her_sample: batch must be >= 1");
+  if (n_virtual < 0 || n_virtual > batch) return mcg_fail(MCG_ERR_ARG, "mcg_her_sample: n_virtual outside [0, batch]");
+  if (!out) return mcg_fail(MCG_ERR_ARG, "mcg_her_sample: null mcg_her_batch");
   if (n_virtual > 0 && buf->reward_type != MCG_REWARD_SPARSE && buf->reward_type != MCG_REWARD_DENSE)
-    return fail(MCG_ERR_UNSUPPORTED, "mcg_her_sample: relabelling needs a reward that depends on the goals alone (sparse or dense); reward_shaping depends on simulator state");
+    return mcg_fail(MCG_ERR_UNSUPPORTED, "mcg_her_sample: relabelling needs a reward that depends on the goals alone (sparse or dense); reward_shaping depends on simulator state");
   const Her B = view(buf);
   const Batch O = {out->obs, out->achieved, out->desired, out->next_obs, out->next_achieved, out->action, out->reward, out->done, out->index};
   hipLaunchKernelGGL(her_sample_kernel, dim3((unsigned)((batch + SAMPLES_PER_BLOCK - 1) / SAMPLES_PER_BLOCK)), dim3(SAMPLE_LANES), 0,
