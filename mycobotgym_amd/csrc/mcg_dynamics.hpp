@@ -42,7 +42,7 @@ enum { ST_LOAD = 0, ST_CTRL, ST_TRIG, ST_RNE, ST_ACT, ST_CRB, ST_ROWS, ST_G0, ST
        ST_COUPLED, ST_CUBE_FIN, ST_POST, ST_N_BUILD, ST_N_FACTOR, ST_N_SOLVE, ST_N_CHECK, ST_E_RHS, ST_R_AX5, ST_R_CONNECT, ST_R_LIMITS, ST_C_MASK, ST_C_ASSEMBLE, ST_C_SCHUR, ST_C_SOLVE, ST_C_CHECK, ST_C_LS, ST_W2_WAIT1, ST_W2_COLLIDE, ST_W2_CUBE, ST_W2_WAIT2, ST_W1_WAIT, ST_A_ENTRY, ST_A_G, ST_A_TWIST, ST_A_LOOP, ST_A_MAP, ST_A_STORE,
        ST_CO_SETUP, ST_CO_ROWS, ST_CO_H0, ST_CO_RESID, ST_CO_ASM, ST_CO_FACTOR, ST_CO_SOLVE, ST_CO_CHECK, ST_CO_LS, ST_CO_OUT, ST_CO_IDLE,
        ST_X_S1C, ST_X_NUMBERS, ST_X_S2, ST_S_S1B, ST_S_MESH, ST_S_S1C, ST_S_NUMBERS,
-       ST_M_S2B, ST_H_S1, ST_H_CRB, ST_H_S2, ST_H_FACTOR, ST_H_S3, ST_Q_S1, ST_Q_BIAS, ST_Q_S2, ST_Q_COLS, ST_Q_S3, ST_COUNT,
+       ST_M_S3, ST_H_S1, ST_H_CRB, ST_H_S2, ST_H_FACTOR, ST_H_S3, ST_Q_S1, ST_Q_BIAS, ST_Q_S2, ST_Q_COLS, ST_Q_S3, ST_COUNT,
        CN_SUBSTEP = 0, CN_NEWTON_IT, CN_LINESEARCH, CN_CUBE_IT, CN_CUBE_LS, CN_COUPLED, CN_COUPLED_IT, CN_COUPLED_LS, CN_CONTACTS, CN_COOP_ROWS, CN_COOP_LSEVAL, CN_COOP_LONG, CN_COOP_CAP, CN_COOP_12, CN_G_FAILED, CN_G_LIM, CN_G_STAT, CN_G_CUBE, CN_G_MISSING, CN_G_EXTRA, CN_G_EQ1, CN_G_EQ2, CN_G_EQ2N1, CN_MP_PAIRS, CN_MP_HITS, CN_MP_FACE, CN_MP_EXIT_B, CN_MP_EXIT_P, CN_MP_EXIT_E, CN_MP_KIND_E, CN_MP_KIND_P, CN_MP_CUBE, CN_COUNT };
 #ifdef MCG_STAGE_CLOCKS
 __device__ unsigned long long g_stage_clocks[ST_COUNT + CN_COUNT];      // stage clocks, then event counts (summed over waves)
@@ -398,10 +398,20 @@ constexpr int LDS_SLOTS = 2 * (NB * (NB + 1) / 2);
 // two-wave variant (SplitA / helper_substep): factor of M + hB, its reciprocal pivots, and q published for the helper wave
 constexpr int LDS_FAC = LDS_SLOTS, LDS_FDINV = LDS_FAC + NB * (NB + 1) / 2, LDS_QB = LDS_FDINV + NB, LDS_QDB = LDS_QB + NB;
 constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM + NB, LDS_IKT = LDS_QLAG + 6;      // LDS_WARM: qacc_warmstart parked between sub-steps; LDS_QLAG: q of the last forward pass; LDS_IKT: the IK controller's six ctrl increments of a control step, handed from the RNE wave to the main wave (two slots spare)
-// The columns z6 = H^-1 e_6, z8 = H^-1 e_8 of the closed-form limit solve, handed from the RNE wave to the main wave between S2 and S2b
-// (SplitMain::limit_cols).  z6 lives in the warm-start slots: only the general iteration reads those, a sub-step that takes S2b never
-// runs it, and the Euler step after S3 writes them again.  z8 has slots of its own.
-constexpr int LDS_Z6 = LDS_WARM, LDS_Z8 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_Z8 + NB;
+// The hand-over of the remote solve (SplitMain::solve_remote: the RNE wave solves the constraint system).  In EVERY sub-step the main wave
+// parks its eight actuation forces (RACT: dofs 0..5, 6, 8 -- the other four are exactly zero) as soon as it has them and the constraint
+// part of g0 (RG0, 12) likewise, and reads them back after S2 if it solves itself: neither stays in registers across the rows and the
+// assembly of H_eq.  In a remote sub-step it adds D, aref, sign of the limit rows 6 and 8 (RLIM, 6) before S2, and the RNE wave leaves
+// the acceleration a in RA (12) before S3.  Lifetimes of the slots borrowed:
+//   RLIM, RA in WARM: only the general iteration reads the warm start, a remote sub-step never runs it, and the Euler step after S3 writes
+//                     the slots again (with a: what the RNE wave left there, or zero in a lane that was reset) before the next sub-step
+//                     could fall back and read them; the RNE wave reads RLIM before it writes RA;
+//   RACT = IKT:       the IK increments are live between the control-step barriers C1 and C2 only, the sub-steps run after C2;
+//   RG0:              slots of its own.
+constexpr int LDS_RLIM = LDS_WARM, LDS_RA = LDS_WARM, LDS_RACT = LDS_IKT, LDS_RG0 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_RG0 + NB;
+constexpr int RACT_DOF[8] = {0, 1, 2, 3, 4, 5, 6, 8};                       // the dofs an actuator drives
+static_assert(LDS_RA + NB == LDS_QLAG && LDS_RACT >= LDS_QLAG + 6 && LDS_RACT + 8 <= LDS_RG0,
+              "the remote solve's hand-over must stay inside the warm-start and IK-increment slots (the lagged q between them is live)");
 static_assert(LDS_SLOTS_SPLIT * 64 * sizeof(real) <= 160 * 1024, "the split Reach kernel's LDS exceeds the 160 KB of a gfx950 workgroup");
 // The sines and cosines of a sub-step, each evaluated by one of the three waves (SplitMain::trig_once), are exchanged between S1 and S1t in the
 // FACTOR slots: the main wave's last read of the factor (after S3) comes before it reaches the next S1, and the helper's next write comes
@@ -653,11 +663,10 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // Three-wave variant (Reach, grids of at most one workgroup per CU, where 3 of the 4 SIMDs of a CU would idle): the workgroup
 // has two more waves over the same 64 environments.  The HELPER wave computes what depends on the joint angles alone -- M by
 // the composite rigid body pass, then the L^T D L factor of M + hB for the Euler step; the RNE wave computes the bias forces;
-// the main wave does actuation and constraint rows meanwhile, then H_eq, the Newton solve and the Euler step.  Three workgroup
-// barriers per sub-step, four when the wave's only limit rows are the gear joints':
+// the main wave does actuation and constraint rows meanwhile, then H_eq, the Newton solve and the Euler step.  The same workgroup
+// barriers in every sub-step, for every wave (S1t: see trig_once):
 //   S1  q(t), qd(t) are published in LDS      (the other waves may read them)
-//   S2  M(t) and passive - bias are in LDS    (main wave: g0, H_eq, Newton solve)
-//   S2b the columns z6, z8 are in LDS         (main wave: the closed-form limit solve; see limit_cols)
+//   S2  M(t) and passive - bias are in LDS    (main wave: g0, H_eq, Newton solve; remote sub-step: the RNE wave does, see solve_remote)
 //   S3  the factor of M + hB is in LDS        (main wave: a' = a - h (M + hB)^-1 (B a), which equals (M + hB)^-1 M a)
 // A split policy says which pieces other waves provide and where the exchange slots are.
 // early_heq: the J^T D J part of H_eq is assembled (and the constraint part of g0 formed) BEFORE barrier S2, while the main wave
@@ -666,20 +675,25 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // read it; only the rare general iteration does -- but in registers it stays live through the factorisation, the kernel's register peak.
 // With it the Euler step also re-reads q(t), qd(t) from the slots they were published in for the other waves (QB, QDB) instead of
 // carrying them through the solve, and the lagged configuration (q of this forward pass, for observations and IK) goes to slots QLAG.
-// limit_cols: when the only violated limit rows of the wave are the gear joints' (6, 8: every fresh episode starts on them), the RNE
-// wave, idle after S2, factors the same H_eq and solves for the closed-form solve's two columns z6, z8 while the main wave factors and
-// solves for abar; a fourth barrier, S2b, hands them over.  Every wave decides from the q slots whether to take S2b (gear_rows_only).
+// solve_remote (round 7; it replaces round 5's limit_cols, where both waves factored the same H and a fourth barrier, S2b, handed the
+// columns z6, z8 over): in a sub-step where no lane of the wave violates a limit row other than the gear joints' (6, 8: every fresh
+// episode starts on them) -- no limit row at all included -- the RNE wave, whose registers are empty after S2 and which holds
+// passive - bias already, does the whole constraint solve: H = H_eq + M built and factored once, solved for abar, z6, z8, the closed-form
+// limit solve, and the acceleration a left in LDS before S3.  The main wave parks what only it has before S2 (slots LDS_RG0 / LDS_RACT /
+// LDS_RLIM) and does nothing between S2 and S3.  The main wave decides from the limit signs it holds, the RNE wave from the q slots with
+// the same compares (no_other_rows); the helper wave does not need to know.  Any other violated row: the main wave solves as without the
+// flag and the RNE wave goes straight to S3.
 // trig_once (round 6): the sub-step's twelve sines and cosines are evaluated once instead of once per wave: after S1 the main wave takes
 // joints 0..3, the helper 4..7, the RNE wave 8..11, and a barrier S1t hands all twenty-four to every wave through the slots LDS_SN /
 // LDS_CS (trig_exchange).
-struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, limit_cols = false,
+struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, solve_remote = false,
                                        trig_once = false;
                  static constexpr int QB = 0, QDB = 0, FS = 0, WARM = 0, QLAG = 0; };
-struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, limit_cols = true,
+struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, solve_remote = true,
                                          trig_once = true;
                    static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
-// The IK and mocap kernels keep the three barriers: measured with S2b, both were ~1 % slower (profiles/r05/ab_quick_all_controllers.log).
-struct SplitMainNoCols : SplitMain { static constexpr bool limit_cols = false; };
+// The main wave solves in every sub-step (which controller's kernel takes which policy: step_reach_kernel, and DESIGN.md section 5).
+struct SplitMainLocal : SplitMain { static constexpr bool solve_remote = false; };
 struct SplitMainOwnTrig : SplitMain { static constexpr bool trig_once = false; };      // every wave its own twelve (round 5), for A/B builds
 
 // A wave's share of the exchange (trig_once): joints FIRST .. FIRST + 3 (`q_of(i)`: the wave's copy of q_i), stored, then -- S1t -- all
@@ -695,7 +709,7 @@ MCG_DEV void trig_exchange(const LS MS, QF q_of, real* sn, real* cs) {
 }
 
 // H_eq + M (the equality rows' system, from LDS) plus D on the diagonal of the limit rows in act_.  One function for every wave that
-// factors it: the RNE wave's columns (limit_cols) must come from the very same L and dinv as the main wave's solve.
+// factors it: the RNE wave's remote solve (solve_remote) must give the very same L and dinv as the main wave's.
 template <class SPL, class LS>
 MCG_DEV void build_H(const LS MS, real* H, const bool* act_, const real* Dl) {
   static_for<NB>([&](auto I) { constexpr int i = I;
@@ -707,18 +721,20 @@ MCG_DEV void build_H(const LS MS, real* H, const bool* act_, const real* Dl) {
   static_for<10>([&](auto I) { constexpr int j = I; H[tri(j, j)] += act_[j] ? Dl[j] : 0.0; });
 }
 
-// Barrier S2b is taken by a wave (all three of the workgroup: they cover the same lanes and read the same q) when some lane has a
-// violated limit row on a gear joint and no lane one on any other joint.  Same compares as the limit rows of robot_substep.
+// A sub-step is remote (solve_remote) when no lane of the wave has a violated limit row on a joint other than the gear joints 6 and 8.
+// The RNE wave's side of that decision, from the q slots (the waves of a workgroup cover the same lanes and read the same q): the same
+// compares as the limit rows of robot_substep, from which the main wave decides.
 template <class SPL, class LS>
-MCG_DEV bool gear_rows_only(ModelPtr Pm, const LS MS) {
+MCG_DEV bool no_other_rows(ModelPtr Pm, const LS MS) {
   real jr[10][2];
-  { ModelPtr Q = launder(Pm); static_for<10>([&](auto I) { constexpr int j = I; jr[j][0] = Q->jnt_range[j][0]; jr[j][1] = Q->jnt_range[j][1]; }); }
-  bool gear = false, other = false;
+  { ModelPtr Q = launder(Pm); static_for<10>([&](auto I) { constexpr int j = I; if constexpr (j != 6 && j != 8) { jr[j][0] = Q->jnt_range[j][0]; jr[j][1] = Q->jnt_range[j][1]; } }); }
+  bool other = false;
   static_for<10>([&](auto I) { constexpr int j = I;
-    const real q = MS.ld(SPL::QB + j);
-    const bool v = (q - jr[j][0] < 0) || (jr[j][1] - q < 0);
-    if constexpr (j == 6 || j == 8) gear = gear || v; else other = other || v; });
-  return __any(gear) && !__any(other);
+    if constexpr (j != 6 && j != 8) {
+      const real q = MS.ld(SPL::QB + j);
+      other = other || (q - jr[j][0] < 0) || (jr[j][1] - q < 0);
+    } });
+  return !__any(other);
 }
 
 // The closed-form solve's 2 x 2 complementarity problem over the limit rows in slots 0 and 1 (e0 / e1: the slot holds a row), enumerated
@@ -740,6 +756,25 @@ MCG_DEV void limit_pair(bool e0, bool e1, real D0, real D1, real s0, real s1, re
   nu0 = cB ? b0 : nu0;  nu1 = cB ? b1 : nu1;
   nu0 = cN ? 0.0 : nu0; nu1 = cN ? 0.0 : nu1;
   f0 = s0 * nu0; f1 = s1 * nu1;
+}
+
+// The closed-form solve when the only limit rows are the gear joints' (remote sub-step): x = abar on entry, a on return; z6 = H^-1 e_6,
+// z8 = H^-1 e_8; D, aref, sign of rows 6 and 8 (sign 0: no row).  The rows sit in slots 0 / 1 as in the direct solve of robot_substep.
+MCG_DEV void gear_rows_solve(real* x, const real* z6, const real* z8, real Dl6, real arefl6, real sgl6, real Dl8, real arefl8, real sgl8) {
+  const bool v6 = sgl6 != 0, v8 = sgl8 != 0, both = v6 && v8;
+  const real D0 = v6 ? Dl6 : (v8 ? Dl8 : 1.0), D1 = both ? Dl8 : 1.0;
+  const real ar0 = v6 ? arefl6 : arefl8, ar1 = both ? arefl8 : 0.0;
+  const real s0 = v6 ? sgl6 : sgl8, s1 = both ? sgl8 : 0.0;
+  const real xa0 = v6 ? x[6] : (v8 ? x[8] : 0.0), xa1 = both ? x[8] : 0.0;
+  real W00 = v6 ? z6[6] : (v8 ? z8[8] : 0.0), W01 = both ? z6[8] : 0.0;
+  const real W11 = both ? z8[8] : 0.0;
+  W01 *= s0 * s1;
+  const real rb0 = s0 * xa0 - ar0, rb1 = s1 * xa1 - ar1;
+  real f0, f1;
+  limit_pair(v6 || v8, both, D0, D1, s0, s1, rb0, rb1, W00, W01, W11, f0, f1);
+  // slot 0 is row 6 where row 6 is violated, else row 8; the other column enters with a zero force (finite z: exactly x)
+  const real g6 = v6 ? f0 : 0.0, g8 = v6 ? f1 : f0;
+  static_for<NB>([&](auto I) { constexpr int i = I; x[i] = fma(-z8[i], g8, fma(-z6[i], g6, x[i])); });
 }
 
 // COMMIT = false: the new q / qd / qacc_warmstart go to *next and S stays as it was (speculative sub-step of the two-wave
@@ -786,6 +821,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     fs[6] += c0 * f; fs[8] += c1 * f;
   }
   static_for<NB>([&](auto I) { constexpr int i = I; pin(fs[i]); });
+  if constexpr (SPL::solve_remote) static_for<8>([&](auto K) { constexpr int k = K; MS.st(LDS_RACT + k, fs[RACT_DOF[k]]); });      // read back after S2, by this wave or the RNE wave
   MCG_FENCE();
 
   MCG_TICK(ST_ACT);
@@ -979,6 +1015,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   if constexpr (WLD::enabled)
     static_for<6>([&](auto Rr) { constexpr int r = Rr; const real da = Dw[r / 3] * arefw[r];
       static_for<6>([&](auto I) { constexpr int j = I; g0[j] = fma(Jw[r][j], da, g0[j]); }); });
+  if constexpr (SPL::solve_remote) static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RG0 + i, g0[i]); });      // the constraint part, parked (see LDS_RG0)
   if constexpr (SPL::early_heq) assemble_heq(std::false_type{});      // J^T D J only: M is not there yet
 #if MCG_DUP == 3        // critical-path probe: the robot wave's assembly twice (same numbers to the same slots)
   if constexpr (SPL::early_heq && SPL::mesh_split) { MCG_FENCE(); static_for<2>([&](auto Sd) { constexpr int sd = Sd; pin(Dc[sd]); }); assemble_heq(std::false_type{}); }
@@ -987,6 +1024,24 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   // phase and solver numbers.  When the workgroup HAS a mesh phase (some lane's candidate mask is set: the same masks every wave reads)
   // this wave runs its whole solve now, under it, and passes S1c / S2 when it is done; when it has none the solve stays behind S2, where
   // it runs beside the cube wave's own solve as before.
+  // solve_remote: the RNE wave has the two parts of g0 apart (RG0, RACT: parked above) and forms g0c + (actuation + (passive - bias)),
+  // the association of the sums below; a remote sub-step adds the gear rows' numbers
+  bool remote = false;                                             // wave-uniform
+  if constexpr (SPL::solve_remote) {
+    static_assert(!CPL::enabled && !SPL::mesh_split && SPL::rne_remote && SPL::factor_remote && SPL::early_heq && SPL::warm_lds,
+                  "the remote solve replaces the direct solve of the three-wave Reach kernel; a coupled solve would skip it");
+    bool other = false;
+    static_for<10>([&](auto I) { constexpr int j = I; if constexpr (j != 6 && j != 8) other = other || (sgl[j] != 0); });
+    remote = !__any(other);
+    if (remote) {
+#ifdef MCG_STAGE_CLOCKS      // counted here for the RNE wave's solve, in the slots of the direct solve
+      MCG_COUNT(CN_NEWTON_IT);
+      if (__any(sgl[6] != 0 || sgl[8] != 0)) MCG_COUNT(CN_LINESEARCH);
+#endif
+      static_for<2>([&](auto Sd) { constexpr int j = 6 + 2 * Sd;
+        MS.st(LDS_RLIM + 3 * Sd, Dl[j]); MS.st(LDS_RLIM + 3 * Sd + 1, arefl[j]); MS.st(LDS_RLIM + 3 * Sd + 2, sgl[j]); });
+    }
+  }
   bool ahead = false;
   if constexpr (SPL::enabled) {
     if constexpr (SPL::mesh_split) {
@@ -994,9 +1049,15 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
       ahead = __any(MS.ld(SPL::MASK0) != 0.0 || MS.ld(SPL::MASK0 + 1) != 0.0 || MS.ld(SPL::MASK0 + 2) != 0.0);
       if (!ahead) { __syncthreads(); __syncthreads(); }             // S1c, S2
     } else __syncthreads();                                         // S2: M and passive - bias are in LDS
-    if constexpr (SPL::rne_remote) static_for<NB>([&](auto I) { constexpr int i = I; fs[i] += MS.ld(SPL::FS + i); });
+    if constexpr (SPL::solve_remote) {
+      if (!remote) {                                                // this wave solves: its parked parts back, summed as below
+        static_for<NB>([&](auto I) { constexpr int i = I; fs[i] = 0; g0[i] = MS.ld(LDS_RG0 + i); });
+        static_for<8>([&](auto K) { constexpr int k = K; fs[RACT_DOF[k]] = MS.ld(LDS_RACT + k); });
+        static_for<NB>([&](auto I) { constexpr int i = I; fs[i] += MS.ld(SPL::FS + i); });
+      }
+    } else if constexpr (SPL::rne_remote) static_for<NB>([&](auto I) { constexpr int i = I; fs[i] += MS.ld(SPL::FS + i); });
   }
-  static_for<NB>([&](auto I) { constexpr int i = I; g0[i] += fs[i]; });
+  static_for<NB>([&](auto I) { constexpr int i = I; g0[i] += fs[i]; });      // (remote: not read again)
   if constexpr (CPL::publishes) CP->publish(g0, Dl, arefl, sgl, S.qd, S.warm, !ahead);
   if constexpr (!SPL::early_heq) assemble_heq(std::true_type{});
   auto build_H = [&](real* H, const bool* act_) { mcg::build_H<SPL>(MS, H, act_, Dl); };
@@ -1014,7 +1075,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     static_for<NB>([&](auto I) { constexpr int i = I; a[i] = S.warm[i]; });
     static_for<10>([&](auto I) { constexpr int j = I; act[j] = (sgl[j] != 0) && (sgl[j] * a[j] - arefl[j] < 0); });
   }
-  bool conv = false;
+  bool conv = remote;                                  // remote sub-step: neither solve below runs, a arrives after S3
   if constexpr (CPL::enabled) {
     if (__any(CP->any_pad)) {     // wave-uniform: every lane of the wave takes the coupled path (same minimiser)
       MCG_TICK(ST_G0);
@@ -1037,14 +1098,6 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     static_for<10>([&](auto I) { constexpr int j = I;
       const bool v = sgl[j] != 0;
       j1 = (v && nviol == 1) ? j : j1; j0 = (v && nviol == 0) ? j : j0; nviol += v ? 1 : 0; });
-    static_assert(!(SPL::limit_cols && CPL::enabled), "S2b is taken inside the direct solve, which a coupled solve would skip");
-    bool cols = false;                                       // barrier S2b (see gear_rows_only: the other waves decide from the q slots)
-    if constexpr (SPL::limit_cols) {
-      bool gear = false, other = false;
-      static_for<10>([&](auto I) { constexpr int j = I;
-        if constexpr (j == 6 || j == 8) gear = gear || (sgl[j] != 0); else other = other || (sgl[j] != 0); });
-      cols = __any(gear) && !__any(other);
-    }
     if (!conv && !__any(nviol > 2)) {                        // wave-uniform (conv is wave-uniform here)
       MCG_COUNT(CN_NEWTON_IT);
       real L[NB * (NB + 1) / 2], dinv[NB], x[NB];
@@ -1060,28 +1113,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
       ldl_solve<PAT_H>(L, dinv, x);
       MCG_TICK_PIN(x, NB);
       MCG_TICK(ST_N_SOLVE);
-      if (cols) {                                            // wave-uniform: only rows 6 and 8, in slots 0 / 1 as below
-        MCG_COUNT(CN_LINESEARCH);
-        MCG_TICK(ST_N_CHECK);
-        __syncthreads();                                     // S2b: the RNE wave's columns z6, z8 are in LDS
-        MCG_TICK(ST_M_S2B);
-        real z6[NB], z8[NB];
-        static_for<NB>([&](auto I) { constexpr int i = I; z6[i] = MS.ld(LDS_Z6 + i); z8[i] = MS.ld(LDS_Z8 + i); });
-        const bool v6 = sgl[6] != 0, v8 = sgl[8] != 0, both = v6 && v8;
-        const real D0 = v6 ? Dl[6] : (v8 ? Dl[8] : 1.0), D1 = both ? Dl[8] : 1.0;
-        const real ar0 = v6 ? arefl[6] : arefl[8], ar1 = both ? arefl[8] : 0.0;
-        const real s0 = v6 ? sgl[6] : sgl[8], s1 = both ? sgl[8] : 0.0;
-        const real xa0 = v6 ? x[6] : (v8 ? x[8] : 0.0), xa1 = both ? x[8] : 0.0;
-        real W00 = v6 ? z6[6] : (v8 ? z8[8] : 0.0), W01 = both ? z6[8] : 0.0;
-        const real W11 = both ? z8[8] : 0.0;
-        W01 *= s0 * s1;
-        const real rb0 = s0 * xa0 - ar0, rb1 = s1 * xa1 - ar1;
-        real f0, f1;
-        limit_pair(v6 || v8, both, D0, D1, s0, s1, rb0, rb1, W00, W01, W11, f0, f1);
-        // slot 0 is row 6 where row 6 is violated, else row 8; the other column enters with a zero force (finite z: exactly x)
-        const real g6 = v6 ? f0 : 0.0, g8 = v6 ? f1 : f0;
-        static_for<NB>([&](auto I) { constexpr int i = I; x[i] = fma(-z8[i], g8, fma(-z6[i], g6, x[i])); });
-      } else if (__any(nviol > 0)) {
+      if (__any(nviol > 0)) {
         MCG_COUNT(CN_LINESEARCH);                            // counted in the old line search's slot: "sub-steps with limit rows"
         real D0 = 1, D1 = 1, ar0 = 0, ar1 = 0, s0 = 0, s1 = 0, xa0 = 0, xa1 = 0;
         static_for<10>([&](auto I) { constexpr int j = I;
@@ -1189,11 +1221,20 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   // ---- constraint forces -> qfrc_constraint; P10 implicit-damping Euler                  (mj_Euler, mj_advance)
   real rhs[NB];
   if constexpr (SPL::factor_remote) {
-    __syncthreads();                                                // S3: the helper's factor of M + hB is in LDS
+    real damp[NB];
+    if constexpr (SPL::solve_remote) {      // a remote sub-step only waits here: the damping's batch of s_loads flies during the wait
+      if (remote) { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; damp[i] = Q->body[i].damping; }); }
+    }
+    __syncthreads();                                                // S3: the helper's factor of M + hB is in LDS (remote: and the RNE wave's a)
+    MCG_TICK(ST_M_S3);
+    if constexpr (SPL::solve_remote) { if (remote) static_for<NB>([&](auto I) { constexpr int i = I; a[i] = MS.ld(LDS_RA + i); }); }
     real Lf[NB * (NB + 1) / 2], dinv[NB];
     static_for<NB>([&](auto I) { constexpr int i = I; dinv[i] = MS.ld(LDS_FDINV + i);
       static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) Lf[tri(i, j)] = MS.ld(LDS_FAC + tri(i, j)); }); });
-    { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = Q->body[i].damping * a[i]; }); }      // one batch of s_loads
+    if constexpr (SPL::solve_remote) {
+      if (!remote) { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; damp[i] = Q->body[i].damping; }); }
+      static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = damp[i] * a[i]; });
+    } else { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = Q->body[i].damping * a[i]; }); }      // one batch of s_loads
     ldl_solve<PAT_M>(Lf, dinv, rhs);
     static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = fma(-h, rhs[i], a[i]); });
   } else {
@@ -1249,8 +1290,6 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
   real cs[NB], sn[NB];
   side_trig<SPL, 4>(MS, sn, cs);
   crb_to_lds(Pm, cs, sn, MS);
-  bool cols = false;
-  if constexpr (SPL::limit_cols) cols = gear_rows_only<SPL>(Pm, MS);
   static_assert(!SPL::mesh_split, "the four-wave PickAndPlace kernel drives its side waves itself: helper_pre / rne_pre");
   (void)side;
   MCG_TICK(ST_H_CRB);
@@ -1266,7 +1305,6 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
     static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_FDINV + i, dinv[i]);
       static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) MS.st(LDS_FAC + tri(i, j), Mh[tri(i, j)]); }); });
     MCG_TICK(ST_H_FACTOR);
-    if (cols) __syncthreads();                                      // S2b (wave-uniform)
     __syncthreads();                                                // S3
     MCG_TICK(ST_H_S3);
   }
@@ -1282,27 +1320,40 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   static_for<NB>([&](auto I) { constexpr int i = I; qd[i] = MS.ld(SPL::QDB + i); });
   rne_bias(Pm, cs, sn, qd, fs);
   static_for<NB>([&](auto I) { constexpr int i = I; MS.st(SPL::FS + i, fs[i]); });
-  bool cols = false;
-  if constexpr (SPL::limit_cols) cols = gear_rows_only<SPL>(Pm, MS);
+  bool remote = false;
+  if constexpr (SPL::solve_remote) {
+    remote = no_other_rows<SPL>(Pm, MS);
+    static_for<NB>([&](auto I) { constexpr int i = I; pin(fs[i]); });      // the sum below takes passive - bias as the main wave reads it
+    MCG_FENCE();                                                           // from LDS: rounded, no product of rne_bias contracted into the add
+  }
   static_assert(!SPL::mesh_split, "the four-wave PickAndPlace kernel drives its side waves itself: helper_pre / rne_pre");
   (void)side;
   MCG_TICK(ST_Q_BIAS);
   __syncthreads();                                                  // S2
   MCG_TICK(ST_Q_S2);
-  if constexpr (SPL::limit_cols) {
-    if (cols) {                                                     // wave-uniform
-      // the main wave's H_eq + M (no limit row active), factored by the same code: the same L and dinv to the bit
-      real L[NB * (NB + 1) / 2], dinv[NB], z[NB];
+  if constexpr (SPL::solve_remote) {
+    if (remote) {                                                   // wave-uniform: the whole constraint solve (see SplitMain)
+      // H_eq + M with no limit row active, x = g0, factor, solve: the direct solve of robot_substep, by the same functions in the same order
+      real L[NB * (NB + 1) / 2], dinv[NB], x[NB];
       const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
       const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       build_H<SPL>(MS, L, none, zero);
+      static_for<NB>([&](auto I) { constexpr int i = I; x[i] = 0.0; });                       // the actuation forces: zero but for RACT_DOF
+      static_for<8>([&](auto K) { constexpr int k = K; x[RACT_DOF[k]] = MS.ld(LDS_RACT + k); });
+      static_for<NB>([&](auto I) { constexpr int i = I; x[i] = MS.ld(LDS_RG0 + i) + (x[i] + fs[i]); });
       ldl_factor<PAT_H>(L, dinv);
-      ldl_solve_unit<PAT_H, 6>(L, dinv, z);
-      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_Z6 + i, z[i]); });
-      ldl_solve_unit<PAT_H, 8>(L, dinv, z);
-      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_Z8 + i, z[i]); });
+      ldl_solve<PAT_H>(L, dinv, x);
+      const real Dl6 = MS.ld(LDS_RLIM), arefl6 = MS.ld(LDS_RLIM + 1), sgl6 = MS.ld(LDS_RLIM + 2);
+      const real Dl8 = MS.ld(LDS_RLIM + 3), arefl8 = MS.ld(LDS_RLIM + 4), sgl8 = MS.ld(LDS_RLIM + 5);
+      if (__any(sgl6 != 0 || sgl8 != 0)) {                          // wave-uniform: a gear row in some lane
+        real z6[NB], z8[NB];
+        ldl_solve_unit<PAT_H, 6>(L, dinv, z6);
+        ldl_solve_unit<PAT_H, 8>(L, dinv, z8);
+        static_for<NB>([&](auto I) { constexpr int i = I; pin(z6[i]); pin(z8[i]); });      // as values read back from LDS: nothing contracted into them
+        gear_rows_solve(x, z6, z8, Dl6, arefl6, sgl6, Dl8, arefl8, sgl8);
+      }
+      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RA + i, x[i]); });
       MCG_TICK(ST_Q_COLS);
-      __syncthreads();                                              // S2b
     }
   }
   if constexpr (SPL::factor_remote) __syncthreads();                // S3

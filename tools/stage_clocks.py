@@ -29,9 +29,9 @@ NAMES = ["load", "controller", "sincos", "rne", "actuation", "crb->M", "rows: we
          "coop: gradient + LDL", "coop: solves + transpose", "coop: consistency check", "coop: line search", "coop: hand back", "coop: idle at S5",
          "cube wave: waiting at S1c", "cube wave: flags + solver numbers", "cube wave: waiting at S2", "M / RNE waves: waiting at S1b", "M / RNE waves: mesh phase",
          "M / RNE waves: waiting at S1c", "M / RNE waves: solver numbers",
-         "main wave: waiting at S2b", "helper wave: waiting for q (S1)", "helper wave: CRB -> M", "helper wave: waiting at S2",
-         "helper wave: factor M+hB", "helper wave: waiting at S2b / S3", "RNE wave: waiting for q (S1)", "RNE wave: bias forces",
-         "RNE wave: waiting at S2", "RNE wave: H, factor, columns z6 z8", "RNE wave: waiting at S2b / S3"]
+         "main wave: waiting at S3", "helper wave: waiting for q (S1)", "helper wave: CRB -> M", "helper wave: waiting at S2",
+         "helper wave: factor M+hB", "helper wave: waiting at S3", "RNE wave: waiting for q (S1)", "RNE wave: bias forces",
+         "RNE wave: waiting at S2", "RNE wave: remote constraint solve", "RNE wave: waiting at S3"]
 if "--legacy" in sys.argv: NAMES = NAMES[:58]
 COUNTS = ["robot sub-steps", "robot Newton iterations", "robot line searches", "cube Newton iterations", "cube line searches",
           "coupled solves", "coupled Newton iterations", "coupled line searches", "wave-max contacts (per collision pass)",
