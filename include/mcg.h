@@ -16,6 +16,8 @@
  *   mcg_compute_reward  MyCobotEnv.compute_reward on batched goals (HER)   mycobot.py:289-298, utils.py:24-26
  *   mcg_her_start / mcg_her_add / mcg_her_sample   SB3's HerReplayBuffer as the reference configures it (n_sampled_goal = 4, strategy
  *                       "future")   scripts/train.py:89-97
+ *   mcg_rollout_start / mcg_rollout_add / mcg_rollout_gae / mcg_rollout_gather   SB3's RolloutBuffer as PPO / A2C use it (n_steps,
+ *                       gamma, gae_lambda)   scripts/train.py:99-101
  *   mcg_get_state / mcg_set_state   direct access to data.qpos/qvel/ctrl/qacc_warmstart (set_joint_qpos etc.)
  *
  * Conventions: every pointer in the step/reset/state calls is DEVICE memory owned by the caller;
@@ -392,6 +394,84 @@ int mcg_her_add(const mcg_her_buf* buf, int64_t n_written, const float* actions 
    content otherwise, and a corrupt record gives a wrong sample and nothing else. */
 int mcg_her_sample(const mcg_her_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch, int n_virtual,
                    const mcg_her_batch* out, void* stream);
+
+/* ---- On-policy rollout buffer (SB3's RolloutBuffer as scripts/train.py:99-101 configures PPO / A2C with n_steps, on the engine's N
+   lockstep environments): storage, the time-limit bootstrap, the advantage recursion (GAE) and the shuffled minibatch gather.
+   Stateless on the C side, as mcg_her_*: the caller owns all device memory and passes it per call; there is no handle.  T = n_steps,
+   N = n_envs; everything is time-major [T, N], as SB3's [buffer_size, n_envs], and the write position is a host integer.
+   One record per (step, env), mcg_rollout_record_bytes(D, A) bytes, contiguous, float32 throughout:
+     byte 0            float obs[D], achieved[3], desired[3]     the observation the action was taken from
+     then              float action[A], log_prob
+     zero padding to a multiple of 16 bytes.
+   These fields are only ever read by the gather, so a sample is one contiguous run.  What the recursion reads or writes lies in planes
+   [T, N] of their own (lane = environment, rows coalesced). */
+typedef struct mcg_rollout_buf {    /* device pointers the caller owns (all required), and the buffer's shape */
+  void* records;                    /* [T, N] records; 16-byte aligned */
+  float* reward;                    /* [T, N]  the step's reward, plus gamma * final_values where the time limit ended the episode */
+  float* value;                     /* [T, N]  the policy's value estimate of the observation the action was taken from */
+  uint8_t* episode_start;           /* [T, N]  1 where that observation is the first of its episode */
+  float* advantage;                 /* [T, N]  written by mcg_rollout_gae */
+  float* returns;                   /* [T, N]  advantage + value */
+  float* last_obs;                  /* [N, D]  observation the next transition starts from */
+  float* last_goals;                /* [N, 6]  its achieved and desired goal */
+  uint8_t* last_start;              /* [N]     1 where it is the first of its episode */
+  int32_t n_envs, obs_dim, act_dim, n_steps;
+  double gamma, gae_lambda;         /* in [0, 1] */
+} mcg_rollout_buf;
+
+typedef struct mcg_rollout_batch {  /* outputs of mcg_rollout_gather; device pointers, any may be NULL (not all).  B = count */
+  float* obs;            /* [B, D] */
+  float* achieved;       /* [B, 3] */
+  float* desired;        /* [B, 3] */
+  float* action;         /* [B, A] */
+  float* old_value;      /* [B] */
+  float* old_log_prob;   /* [B] */
+  float* advantage;      /* [B] */
+  float* returns;        /* [B] */
+  int32_t* index;        /* [B]     flat index of the sample in SB3's swap_and_flatten order, env * T + step */
+} mcg_rollout_batch;
+
+/* All calls enqueue on `stream` and do not synchronise.  Checked on the host before any HIP call (MCG_ERR_ARG): a null struct or a null
+   pointer in it; n_envs / obs_dim / act_dim / n_steps < 1; n_steps * n_envs >= 2^31; records not 16-byte aligned; gamma or gae_lambda
+   not finite or outside [0, 1]; pos outside [0, n_steps); first < 0, count < 1 or first + count > n_steps * n_envs; a null actions /
+   values / log_probs / last_values; a null mcg_step_out or mcg_rollout_batch; obs, achieved_goal, desired_goal of `first`; those and
+   reward, terminated, truncated of `out`; all nine outputs of a batch null. */
+int64_t mcg_rollout_record_bytes(int obs_dim, int act_dim);      /* 0 where a dimension is < 1 */
+
+/* The environments of `mask` (NULL = all) continue from the observation a reset wrote to `first`: last_obs, last_goals, and
+   last_start = 1.  float64 -> float32 by round-to-nearest-even. */
+int mcg_rollout_start(const mcg_rollout_buf* buf, const mcg_step_out* first, const uint8_t* mask /* [N] device or NULL */, void* stream);
+
+/* Step `pos` of the rollout; `out` is what mcg_step wrote for `actions`.  The record's obs / achieved / desired come from last_obs /
+   last_goals, episode_start[pos] from last_start; action, log_prob and value are stored as given.  The reward is SB3's collect_rollouts
+   bootstrap [RECALL: on_policy_algorithm.py; SB3 is not installed next to the reference]: r = (float)out.reward, and where
+   truncated & !terminated (TimeLimit.truncated, as sb3_adapter.py states it) and final_values != NULL, r = r + (float)gamma *
+   final_values[e], the product rounded before the sum.  Afterwards last_obs / last_goals are out.obs / achieved_goal / desired_goal
+   (which already belong to the next episode where this one ended) and last_start = truncated | terminated.  final_obs is not read. */
+int mcg_rollout_add(const mcg_rollout_buf* buf, int pos, const float* actions /* [N, A] device */, const float* values /* [N] */,
+                    const float* log_probs /* [N] */, const float* final_values /* [N]: value of final_obs; or NULL */,
+                    const mcg_step_out* out, void* stream);
+
+/* SB3's compute_returns_and_advantage [RECALL: buffers.py] over the T stored steps, every operation in float32, rounded one by one
+   (nothing fused), in this order: g32 = (float)gamma, c32 = (float)(gamma * gae_lambda) (the product in double), last = 0, and for
+   t = T-1 .. 0, with start_next = episode_start[t+1], vn = value[t+1] (t = T-1: last_start, last_values):
+     nnt   = 1.0f - (float)start_next
+     delta = (reward[t] + (g32 * vn) * nnt) - value[t]
+     last  = delta + (c32 * nnt) * last
+     advantage[t] = last;  returns[t] = last + value[t] */
+int mcg_rollout_gae(const mcg_rollout_buf* buf, const float* last_values /* [N] device */, void* stream);
+
+/* Samples k = first .. first + count - 1 of epoch `epoch`'s permutation of the M = T * N stored transitions, into rows 0 .. count - 1 of
+   the outputs.  A transition's flat index is i = env * T + step (SB3's swap_and_flatten).  The permutation is computed per sample, with
+   no index array and no sort: a 4-round balanced Feistel network on b bits with cycle walking.
+     b, h              b = the smallest even number >= 2 with 2^b >= M; h = b / 2; a value x splits into L = x >> h, R = x & (2^h - 1)
+     round r = 0..3    (L, R) -> (R, L ^ F_r(R)),  F_r(R) = w0 & (2^h - 1), w0 = word 0 of Philox4x32-10 with counter
+                       (R, (uint32)epoch, r, 4 ^ ((uint32)(epoch >> 32) << 8)) and key `seed` (stream 4; 0-2: the reset draws, 3: HER)
+     walk              x = k; x = (L << h) | R after the four rounds; repeated until x < M: sample k is transition x.
+   The network is a bijection of [0, 2^b), so the walk from a k < M comes back below M (a cycle closes) and the map k -> x is a
+   bijection of [0, M); 2^b < 4 M, so a walk takes fewer than 4 passes in expectation.  No address depends on stored content. */
+int mcg_rollout_gather(const mcg_rollout_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
+                       const mcg_rollout_batch* out, void* stream);
 
 #ifdef __cplusplus
 }

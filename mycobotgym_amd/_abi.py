@@ -223,13 +223,32 @@ def her_record_dtype(obs_dim: int, act_dim: int) -> np.dtype:
     return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
 
 
+class McgRolloutBuf(C.Structure):
+    """The rollout buffer's device memory, shape and discounting (include/mcg.h: mcg_rollout_buf); the caller owns every pointer."""
+    _fields_ = ([(n, C.c_void_p) for n in ("records", "reward", "value", "episode_start", "advantage", "returns", "last_obs", "last_goals",
+                                           "last_start")]
+                + [("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_steps", C.c_int32), ("gamma", d), ("gae_lambda", d)])
+
+
+class McgRolloutBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "achieved", "desired", "action", "old_value", "old_log_prob", "advantage", "returns", "index")]
+
+
+def rollout_record_dtype(obs_dim: int, act_dim: int) -> np.dtype:
+    """One record of the rollout buffer as a numpy structured dtype (include/mcg.h: the layout above mcg_rollout_buf)."""
+    fields = [("obs", "<f4", (obs_dim,)), ("achieved", "<f4", (3,)), ("desired", "<f4", (3,)), ("action", "<f4", (act_dim,)), ("log_prob", "<f4")]
+    used = np.dtype(fields).itemsize
+    return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
            "mcg_action_dim", "mcg_nq", "mcg_nv", "mcg_reset", "mcg_step", "mcg_get_state", "mcg_set_state",
            "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts",
            "mcg_render", "mcg_render_mounted", "mcg_render_scenes", "mcg_scene_randomize",
-           "mcg_her_record_bytes", "mcg_her_start", "mcg_her_add", "mcg_her_sample")
+           "mcg_her_record_bytes", "mcg_her_start", "mcg_her_add", "mcg_her_sample",
+           "mcg_rollout_record_bytes", "mcg_rollout_start", "mcg_rollout_add", "mcg_rollout_gae", "mcg_rollout_gather")
 
 _lib = None
 
@@ -284,6 +303,14 @@ def load():
         L.mcg_her_add.argtypes = [C.POINTER(McgHerBuf), C.c_int64, C.c_void_p, C.POINTER(McgStepOut), C.c_void_p]
         L.mcg_her_sample.argtypes = [C.POINTER(McgHerBuf), C.c_int64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(McgHerBatch),
                                      C.c_void_p]
+    if hasattr(L, "mcg_rollout_gather"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_rollout_record_bytes.argtypes = [C.c_int, C.c_int]; L.mcg_rollout_record_bytes.restype = C.c_int64
+        L.mcg_rollout_start.argtypes = [C.POINTER(McgRolloutBuf), C.POINTER(McgStepOut), C.c_void_p, C.c_void_p]
+        L.mcg_rollout_add.argtypes = [C.POINTER(McgRolloutBuf), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(McgStepOut),
+                                      C.c_void_p]
+        L.mcg_rollout_gae.argtypes = [C.POINTER(McgRolloutBuf), C.c_void_p, C.c_void_p]
+        L.mcg_rollout_gather.argtypes = [C.POINTER(McgRolloutBuf), C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(McgRolloutBatch),
+                                         C.c_void_p]
     _lib = L
     return L
 
