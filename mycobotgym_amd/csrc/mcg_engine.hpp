@@ -1,4 +1,4 @@
-// mcg_engine.hpp -- what mcg_hip.hip, mcg_render.hip and mcg_replay.hip share on the host side: error reporting, the layout of an engine's
+// mcg_engine.hpp -- what mcg_hip.hip, mcg_render.hip and, through mcg_buffer.hpp, mcg_replay.hip and mcg_rollout.hip share on the host side: error reporting, the layout of an engine's
 // state, its two kernel-parameter views (Cfg, View) and the handle behind the C ABI (mcg_env).  Internal: include/mcg.h is the boundary.
 #pragma once
 

@@ -8,8 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mcg.h"
-#include "mcg_engine.hpp"        // mcg_fail
-#include "mcg_dynamics.hpp"      // philox_pair
+#include "mcg_buffer.hpp"        // what the rollout buffer has too: launched, record_bytes, carry, copy_phase; philox_pair
 
 using namespace mcg;
 
@@ -19,9 +18,6 @@ constexpr int GOAL_WORDS = 18;          // achieved[3], next_achieved[3], desire
 constexpr int HER_STREAM = 3;           // Philox stream of the sampling draws (0: goals, 1: mass and friction, 2: pictures)
 constexpr int HER_MAX_DRAWS = 256;      // rejection draws per sample; draw HER_MAX_DRAWS picks the future step
 constexpr int ADD_LANES = 256;
-constexpr int SAMPLE_LANES = 256;
-constexpr int SPW = 16;                 // samples per wave: the index phase runs on lanes 0..SPW-1, the copy phase on all 64
-constexpr int SAMPLES_PER_BLOCK = SPW * (SAMPLE_LANES / 64);
 
 struct Layout {                          // word indices inside a record
   int D, A, w_nobs, w_act, w_rew, w_t, w_len, w_term, words;
@@ -31,7 +27,7 @@ Layout layout(int D, int A) {
   L.D = D; L.A = A;
   L.w_nobs = GOAL_WORDS + D; L.w_act = L.w_nobs + D; L.w_rew = L.w_act + A;
   L.w_t = L.w_rew + 1; L.w_len = L.w_rew + 2; L.w_term = L.w_rew + 3;
-  L.words = (L.w_term + 1 + 3) / 4 * 4;
+  L.words = padded_words(L.w_term + 1);
   return L;
 }
 
@@ -92,8 +88,7 @@ __global__ __launch_bounds__(ADD_LANES) void her_add_kernel(Her B, int pos, int 
     uint32_t bits = 0;
     if (w < L.w_nobs) {
       const size_t a = (size_t)e * L.D + (w - GOAL_WORDS);
-      bits = __float_as_uint(B.last_obs[a]);
-      B.last_obs[a] = (float)O.obs[a];
+      bits = carry(B.last_obs[a], O.obs[a]);
     } else if (w < L.w_act) {
       const size_t a = (size_t)e * L.D + (w - L.w_nobs);
       bits = __float_as_uint((float)(done ? O.final_obs[a] : O.obs[a]));
@@ -199,39 +194,27 @@ __global__ __launch_bounds__(SAMPLE_LANES) void her_sample_kernel(Her B, long lo
     if (is_virtual) fs = slot;
   }
   if (lane < SPW && k < batch && O.index) { O.index[(size_t)k * 3] = s; O.index[(size_t)k * 3 + 1] = e; O.index[(size_t)k * 3 + 2] = fs; }
-  // ---- copy phase: lane = 8 bytes of a record (a float64 goal, or two words); four samples' loads in flight
-  const int pairs = L.words / 2;
-  for (int i0 = 0; i0 < SPW && k0 + i0 < batch; i0 += 4) {
-    for (int p0 = 0; p0 < pairs; p0 += 64) {
-      const int p = p0 + lane;
-      uint2 v[4]; const uint32_t* rec[4]; const uint32_t* frec[4]; int kk[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int si = __builtin_amdgcn_readlane(s, i0 + u), ei = __builtin_amdgcn_readlane(e, i0 + u), fi = __builtin_amdgcn_readlane(fs, i0 + u);
-        kk[u] = k0 + i0 + u;
-        rec[u] = si >= 0 ? record(B, si, ei) : nullptr;
-        frec[u] = fi >= 0 ? record(B, fi, ei) : nullptr;
-        v[u] = make_uint2(0u, 0u);
-        if (kk[u] < batch && rec[u] && p < pairs) {
-          // a virtual sample's desired goal (pairs 6-8) is the future record's next_achieved (pairs 3-5)
-          const uint32_t* src = (frec[u] && p >= 6 && p < 9) ? frec[u] + 2 * (p - 3) : rec[u] + 2 * p;
-          v[u] = *reinterpret_cast<const uint2*>(src);
-        }
+  // ---- copy phase
+  const uint32_t* rec[4]; const uint32_t* frec[4];                      // of the four samples in flight
+  copy_phase(lane, k0, batch, L.words / 2,
+    [&](int u, int i, int p) {
+      const int si = __builtin_amdgcn_readlane(s, i), ei = __builtin_amdgcn_readlane(e, i), fi = __builtin_amdgcn_readlane(fs, i);
+      rec[u] = si >= 0 ? record(B, si, ei) : nullptr;
+      frec[u] = fi >= 0 ? record(B, fi, ei) : nullptr;
+      if (!rec[u]) return rec[u];
+      // a virtual sample's desired goal (pairs 6-8) is the future record's next_achieved (pairs 3-5)
+      return (frec[u] && p >= 6 && p < 9) ? frec[u] + 2 * (p - 3) : rec[u] + 2 * p;
+    },
+    [&](int u, int row, int p, uint2 v) {
+      if (p < 9) {                       // a float64 goal
+        const double g = __longlong_as_double((long long)(((unsigned long long)v.y << 32) | v.x));
+        float* dst = p < 3 ? O.ach : (p < 6 ? O.nach : O.des);
+        if (dst) dst[(size_t)row * 3 + p % 3] = (float)g;
+      } else {
+        emit_word(B, O, row, 2 * p, v.x, frec[u] != nullptr, rec[u], frec[u]);
+        emit_word(B, O, row, 2 * p + 1, v.y, frec[u] != nullptr, rec[u], frec[u]);
       }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        if (!(kk[u] < batch && p < pairs)) continue;
-        if (p < 9) {
-          const double g = rec[u] ? __longlong_as_double((long long)(((unsigned long long)v[u].y << 32) | v[u].x)) : 0.0;
-          float* dst = p < 3 ? O.ach : (p < 6 ? O.nach : O.des);
-          if (dst) dst[(size_t)kk[u] * 3 + p % 3] = (float)g;
-        } else {
-          emit_word(B, O, kk[u], 2 * p, v[u].x, frec[u] != nullptr, rec[u], frec[u]);
-          emit_word(B, O, kk[u], 2 * p + 1, v[u].y, frec[u] != nullptr, rec[u], frec[u]);
-        }
-      }
-    }
-  }
+    });
 }
 
 int check_buf(const mcg_her_buf* b, const char* who) {
@@ -254,18 +237,12 @@ Her view(const mcg_her_buf* b) {
   return B;
 }
 
-int launched() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MCG_OK : mcg_fail(MCG_ERR_HIP, "mcg_her kernel launch: %s", hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t mcg_her_record_bytes(int obs_dim, int act_dim) {
-  if (obs_dim < 1 || act_dim < 1) return 0;
-  return (int64_t)layout(obs_dim, act_dim).words * 4;
+  return record_bytes(obs_dim, act_dim, layout(obs_dim, act_dim).words);
 }
 
 int mcg_her_start(const mcg_her_buf* buf, const mcg_step_out* first, const uint8_t* mask, void* stream) {
@@ -274,9 +251,9 @@ int mcg_her_start(const mcg_her_buf* buf, const mcg_step_out* first, const uint8
   if (!first->obs || !first->achieved_goal) return mcg_fail(MCG_ERR_ARG, "mcg_her_start: obs and achieved_goal of the reset's output are required");
   const Her B = view(buf);
   const long long total = (long long)B.n * (B.L.D + 4);
-  hipLaunchKernelGGL(her_start_kernel, dim3((unsigned)((total + ADD_LANES - 1) / ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(her_start_kernel, dim3(blocks(total, ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
                      B, first->obs, first->achieved_goal, mask);
-  return launched();
+  return launched("mcg_her");
 }
 
 int mcg_her_add(const mcg_her_buf* buf, int64_t n_written, const float* actions, const mcg_step_out* out, void* stream) {
@@ -291,9 +268,9 @@ int mcg_her_add(const mcg_her_buf* buf, int64_t n_written, const float* actions,
   const int elems = 9 + (B.L.words - GOAL_WORDS);
   int epb = ADD_LANES / elems;
   epb = epb < 1 ? 1 : (epb > ADD_MAX_EPB ? ADD_MAX_EPB : epb);
-  hipLaunchKernelGGL(her_add_kernel, dim3((unsigned)((B.n + epb - 1) / epb)), dim3(ADD_LANES), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(her_add_kernel, dim3(blocks(B.n, epb)), dim3(ADD_LANES), 0, (hipStream_t)stream,
                      B, (int)(n_written % B.cap), epb, actions, *out);
-  return launched();
+  return launched("mcg_her");
 }
 
 int mcg_her_sample(const mcg_her_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch, int n_virtual,
@@ -307,9 +284,9 @@ int mcg_her_sample(const mcg_her_buf* buf, int64_t n_written, uint64_t seed, uin
     return mcg_fail(MCG_ERR_UNSUPPORTED, "mcg_her_sample: relabelling needs a reward that depends on the goals alone (sparse or dense); reward_shaping depends on simulator state");
   const Her B = view(buf);
   const Batch O = {out->obs, out->achieved, out->desired, out->next_obs, out->next_achieved, out->action, out->reward, out->done, out->index};
-  hipLaunchKernelGGL(her_sample_kernel, dim3((unsigned)((batch + SAMPLES_PER_BLOCK - 1) / SAMPLES_PER_BLOCK)), dim3(SAMPLE_LANES), 0,
+  hipLaunchKernelGGL(her_sample_kernel, dim3(blocks(batch, SAMPLES_PER_BLOCK)), dim3(SAMPLE_LANES), 0,
                      (hipStream_t)stream, B, (long long)n_written, (unsigned long long)seed, (unsigned long long)call, batch, n_virtual, O);
-  return launched();
+  return launched("mcg_her");
 }
 
 }  // extern "C"

@@ -11,8 +11,7 @@
 #include <cmath>
 
 #include "mcg.h"
-#include "mcg_engine.hpp"        // mcg_fail
-#include "mcg_dynamics.hpp"      // philox4x32_10
+#include "mcg_buffer.hpp"        // what the replay buffer has too: launched, record_bytes, carry, copy_phase; philox4x32_10
 
 using namespace mcg;
 
@@ -22,9 +21,6 @@ constexpr int ROLLOUT_STREAM = 4;       // Philox stream of the permutation (0: 
 constexpr int FEISTEL_ROUNDS = 4;
 constexpr int ADD_LANES = 256;
 constexpr int GAE_LANES = 64;           // lane = environment and nothing is shared: one wave per block spreads 8192 environments over 128 CUs
-constexpr int GATHER_LANES = 256;
-constexpr int SPW = 16;                 // samples per wave: the index phase runs on lanes 0..SPW-1, the copy phase on all 64
-constexpr int SAMPLES_PER_BLOCK = SPW * (GATHER_LANES / 64);
 
 struct Layout {                          // word indices inside a record: obs at 0
   int D, A, w_ach, w_des, w_act, w_logp, words;
@@ -33,7 +29,7 @@ Layout layout(int D, int A) {
   Layout L;
   L.D = D; L.A = A;
   L.w_ach = D; L.w_des = D + 3; L.w_act = D + 6; L.w_logp = L.w_act + A;
-  L.words = (L.w_logp + 1 + 3) / 4 * 4;
+  L.words = padded_words(L.w_logp + 1);
   return L;
 }
 
@@ -88,12 +84,10 @@ __global__ __launch_bounds__(ADD_LANES) void rollout_add_kernel(Roll B, int pos,
   uint32_t bits = 0;
   if (w < L.w_ach) {
     const size_t a = (size_t)e * L.D + w;
-    bits = __float_as_uint(B.last_obs[a]);
-    B.last_obs[a] = (float)O.obs[a];
+    bits = carry(B.last_obs[a], O.obs[a]);
   } else if (w < L.w_act) {
     const int c = w - L.w_ach;           // 0..2 achieved, 3..5 desired
-    bits = __float_as_uint(B.last_goals[e * 6 + c]);
-    B.last_goals[e * 6 + c] = (float)(c < 3 ? O.achieved_goal[e * 3 + c] : O.desired_goal[e * 3 + (c - 3)]);
+    bits = carry(B.last_goals[e * 6 + c], c < 3 ? O.achieved_goal[e * 3 + c] : O.desired_goal[e * 3 + (c - 3)]);
   } else if (w < L.w_logp) {
     bits = __float_as_uint(actions[(size_t)e * L.A + (w - L.w_act)]);
   } else if (w == L.w_logp) {
@@ -145,11 +139,11 @@ MCG_DEV void emit_word(const Layout& L, const Batch& O, int j, int w, uint32_t b
   else if (w == L.w_logp) { if (O.logp) O.logp[j] = f; }
 }
 
-__global__ __launch_bounds__(GATHER_LANES) void rollout_gather_kernel(Roll B, unsigned long long seed, unsigned long long epoch, int first,
+__global__ __launch_bounds__(SAMPLE_LANES) void rollout_gather_kernel(Roll B, unsigned long long seed, unsigned long long epoch, int first,
                                                                       int count, int h, Batch O) {
   const Layout& L = B.L;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j0 = (blockIdx.x * (GATHER_LANES / 64) + wave) * SPW;       // wave-uniform; first output row of this wave
+  const int j0 = (blockIdx.x * (SAMPLE_LANES / 64) + wave) * SPW;       // wave-uniform; first output row of this wave
   if (j0 >= count) return;
   // ---- index phase: lane i < SPW walks position first + j0 + i through the Feistel network until it lands below M
   const uint32_t M = (uint32_t)B.n * (uint32_t)B.T;                     // < 2^31 (host check)
@@ -179,27 +173,13 @@ __global__ __launch_bounds__(GATHER_LANES) void rollout_gather_kernel(Roll B, un
     if (O.ret) O.ret[j] = g;
     if (O.index) O.index[j] = (int32_t)x;
   }
-  // ---- copy phase: lane = 8 bytes of a record; four samples' loads in flight
-  const int pairs = L.words / 2;
-  for (int i0 = 0; i0 < SPW && j0 + i0 < count; i0 += 4) {
-    for (int p0 = 0; p0 < pairs; p0 += 64) {
-      const int p = p0 + lane;
-      uint2 v[4]; int jj[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int si = __builtin_amdgcn_readlane(src, i0 + u);
-        jj[u] = j0 + i0 + u;
-        v[u] = make_uint2(0u, 0u);
-        if (jj[u] < count && p < pairs) v[u] = *reinterpret_cast<const uint2*>(B.rec + (size_t)si * L.words + 2 * p);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        if (!(jj[u] < count && p < pairs)) continue;
-        emit_word(L, O, jj[u], 2 * p, v[u].x);
-        emit_word(L, O, jj[u], 2 * p + 1, v[u].y);
-      }
-    }
-  }
+  // ---- copy phase
+  copy_phase(lane, j0, count, L.words / 2,
+    [&](int, int i, int p) { return B.rec + (size_t)__builtin_amdgcn_readlane(src, i) * L.words + 2 * p; },
+    [&](int, int row, int p, uint2 v) {
+      emit_word(L, O, row, 2 * p, v.x);
+      emit_word(L, O, row, 2 * p + 1, v.y);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
@@ -228,18 +208,12 @@ Roll view(const mcg_rollout_buf* b) {
   return B;
 }
 
-int launched() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MCG_OK : mcg_fail(MCG_ERR_HIP, "mcg_rollout kernel launch: %s", hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t mcg_rollout_record_bytes(int obs_dim, int act_dim) {
-  if (obs_dim < 1 || act_dim < 1) return 0;
-  return (int64_t)layout(obs_dim, act_dim).words * 4;
+  return record_bytes(obs_dim, act_dim, layout(obs_dim, act_dim).words);
 }
 
 int mcg_rollout_start(const mcg_rollout_buf* buf, const mcg_step_out* first, const uint8_t* mask, void* stream) {
@@ -249,9 +223,9 @@ int mcg_rollout_start(const mcg_rollout_buf* buf, const mcg_step_out* first, con
     return mcg_fail(MCG_ERR_ARG, "mcg_rollout_start: obs, achieved_goal and desired_goal of the reset's output are required");
   const Roll B = view(buf);
   const long long total = (long long)B.n * (B.L.D + 7);
-  hipLaunchKernelGGL(rollout_start_kernel, dim3((unsigned)((total + ADD_LANES - 1) / ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rollout_start_kernel, dim3(blocks(total, ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
                      B, first->obs, first->achieved_goal, first->desired_goal, mask);
-  return launched();
+  return launched("mcg_rollout");
 }
 
 int mcg_rollout_add(const mcg_rollout_buf* buf, int pos, const float* actions, const float* values, const float* log_probs,
@@ -266,18 +240,18 @@ int mcg_rollout_add(const mcg_rollout_buf* buf, int pos, const float* actions, c
     return mcg_fail(MCG_ERR_ARG, "mcg_rollout_add: obs, achieved_goal, desired_goal, reward, terminated and truncated of the step's output are required");
   const Roll B = view(buf);
   const long long total = (long long)B.n * (B.L.words + 1);
-  hipLaunchKernelGGL(rollout_add_kernel, dim3((unsigned)((total + ADD_LANES - 1) / ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rollout_add_kernel, dim3(blocks(total, ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream,
                      B, pos, actions, values, log_probs, final_values, *out);
-  return launched();
+  return launched("mcg_rollout");
 }
 
 int mcg_rollout_gae(const mcg_rollout_buf* buf, const float* last_values, void* stream) {
   if (const int rc = check_buf(buf, "mcg_rollout_gae")) return rc;
   if (!last_values) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_gae: null last_values");
   const Roll B = view(buf);
-  hipLaunchKernelGGL(rollout_gae_kernel, dim3((unsigned)((B.n + GAE_LANES - 1) / GAE_LANES)), dim3(GAE_LANES), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rollout_gae_kernel, dim3(blocks(B.n, GAE_LANES)), dim3(GAE_LANES), 0, (hipStream_t)stream,
                      B, last_values);
-  return launched();
+  return launched("mcg_rollout");
 }
 
 int mcg_rollout_gather(const mcg_rollout_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
@@ -295,9 +269,9 @@ int mcg_rollout_gather(const mcg_rollout_buf* buf, uint64_t seed, uint64_t epoch
   while ((1ll << b) < M) b += 2;         // the smallest even b >= 2 with 2^b >= M; M < 2^31, so b <= 32
   const Roll B = view(buf);
   const Batch O = {out->obs, out->achieved, out->desired, out->action, out->old_value, out->old_log_prob, out->advantage, out->returns, out->index};
-  hipLaunchKernelGGL(rollout_gather_kernel, dim3((unsigned)((count + SAMPLES_PER_BLOCK - 1) / SAMPLES_PER_BLOCK)), dim3(GATHER_LANES), 0,
+  hipLaunchKernelGGL(rollout_gather_kernel, dim3(blocks(count, SAMPLES_PER_BLOCK)), dim3(SAMPLE_LANES), 0,
                      (hipStream_t)stream, B, (unsigned long long)seed, (unsigned long long)epoch, (int)first, (int)count, b / 2, O);
-  return launched();
+  return launched("mcg_rollout");
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@ from typing import Optional
 import torch
 
 from . import _abi
+from ._devbuf import DeviceBuffer, _ptr
 
 _REWARDS = {"sparse": _abi.REWARD_SPARSE, "dense": _abi.REWARD_DENSE, "reward_shaping": _abi.REWARD_SHAPING}
 
@@ -28,36 +29,25 @@ _REWARDS = {"sparse": _abi.REWARD_SPARSE, "dense": _abi.REWARD_DENSE, "reward_sh
 HerSamples = namedtuple("HerSamples", ["observations", "actions", "next_observations", "dones", "rewards", "index"])
 
 
-class HerBuffer:
+class HerBuffer(DeviceBuffer):
+    _FROM_ENVS = (("num_envs", "num_envs"), ("obs_dim", "obs_dim"), ("act_dim", "action_dim"), ("max_episode_steps", "max_episode_steps"),
+                  ("reward_type", "reward_type"), ("distance_threshold", "distance_threshold"))
+    _NO_IMAGES = "the -v1 image ids carry no goals in their observation: hindsight relabelling has nothing to act on"
+    _HOST_STATE = ("n_written", "n_sampled", "seed")
+
     def __init__(self, envs=None, capacity: int = 1000, n_sampled_goal: int = 4, seed: int = 0, *, num_envs: Optional[int] = None,
                  obs_dim: Optional[int] = None, act_dim: Optional[int] = None, max_episode_steps: Optional[int] = None,
                  reward_type: Optional[str] = None, distance_threshold: Optional[float] = None, device=None, guard_rows: int = 0):
         """``envs``: a ``MyCobotVecEnv`` to take the dimensions, reward type, threshold, time limit and device from; or give them
         by keyword.  ``capacity``: slots of the ring (transitions per environment), at least twice the time limit.
         ``guard_rows``: spare slots allocated before and after the ring, which no call may touch (``guards()``; tests)."""
-        if envs is not None:
-            from .vec_env import MyCobotImgVecEnv
-            if isinstance(envs, MyCobotImgVecEnv):
-                raise ValueError("the -v1 image ids carry no goals in their observation: hindsight relabelling has nothing to act on")
-            num_envs = envs.num_envs if num_envs is None else num_envs
-            obs_dim = envs.obs_dim if obs_dim is None else obs_dim
-            act_dim = envs.action_dim if act_dim is None else act_dim
-            max_episode_steps = envs.max_episode_steps if max_episode_steps is None else max_episode_steps
-            reward_type = envs.reward_type if reward_type is None else reward_type
-            distance_threshold = envs.distance_threshold if distance_threshold is None else distance_threshold
-            device = envs.device if device is None else device
-        missing = [k for k, v in (("num_envs", num_envs), ("obs_dim", obs_dim), ("act_dim", act_dim), ("max_episode_steps", max_episode_steps),
-                                  ("reward_type", reward_type), ("distance_threshold", distance_threshold)) if v is None]
-        if missing:
-            raise ValueError(f"HerBuffer needs envs= or {', '.join(missing)}")
+        num_envs, obs_dim, act_dim, max_episode_steps, reward_type, distance_threshold = self._resolve(envs, device, dict(
+            num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim, max_episode_steps=max_episode_steps, reward_type=reward_type,
+            distance_threshold=distance_threshold))
         if reward_type not in _REWARDS:
             raise ValueError(f"unknown reward_type {reward_type!r}")
         if n_sampled_goal < 0:
             raise ValueError("n_sampled_goal must be >= 0")
-        self.device = torch.device("cuda:0" if device is None else device)
-        if self.device.type != "cuda":
-            raise _abi.McgError("HerBuffer lives on an AMD GPU only (device='cuda:N'); there is no CPU path")
-        self._lib = _abi.load()
         self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
         self.capacity, self.max_episode_steps = int(capacity), int(max_episode_steps)
         self.reward_type, self.distance_threshold = reward_type, float(distance_threshold)
@@ -82,25 +72,6 @@ class HerBuffer:
                                     act_dim=self.act_dim, capacity=self.capacity, max_episode_steps=self.max_episode_steps,
                                     reward_type=_REWARDS[reward_type], distance_threshold=self.distance_threshold)
 
-    # ------------------------------------------------------------------------------------------------------ plumbing
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _dev(self, x, dtype, shape, name):
-        t = torch.as_tensor(x, device=self.device)
-        if t.dtype != dtype:
-            t = t.to(dtype)
-        t = t.contiguous()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-        return t
-
-    def _goal_obs(self, obs, name):
-        n, D = self.num_envs, self.obs_dim
-        return (self._dev(obs["observation"], torch.float64, (n, D), name + "['observation']"),
-                self._dev(obs["achieved_goal"], torch.float64, (n, 3), name + "['achieved_goal']"),
-                self._dev(obs["desired_goal"], torch.float64, (n, 3), name + "['desired_goal']"))
-
     # ----------------------------------------------------------------------------------------------------- insertion
     def start(self, obs, mask=None):
         """An episode starts from ``obs`` (what ``reset`` returned) in the environments of ``mask`` (None: all); an episode that was in
@@ -108,26 +79,14 @@ class HerBuffer:
         o, ag, _ = self._goal_obs(obs, "obs")
         m = None if mask is None else self._dev(mask, torch.uint8, (self.num_envs,), "mask")
         first = _abi.McgStepOut(obs=o.data_ptr(), achieved_goal=ag.data_ptr())
-        with torch.cuda.device(self.device):
-            _abi.check(self._lib.mcg_her_start(C.byref(self._cbuf), C.byref(first), None if m is None else C.c_void_p(m.data_ptr()),
-                                               self._stream()), "mcg_her_start")
+        self._call("mcg_her_start", C.byref(first), _ptr(m))
 
     def add(self, actions, obs, reward, terminated, truncated, info):
         """One transition per environment: ``buf.add(a, *envs.step(a))``.  Where an episode ended, the transition's next observation and
         goal are ``info["final_observation"]`` (``obs`` already belongs to the next episode there)."""
-        n = self.num_envs
-        a = self._dev(actions, torch.float32, (n, self.act_dim), "actions")
-        o, ag, dg = self._goal_obs(obs, "obs")
-        fo, fa, fd = self._goal_obs(info["final_observation"], "info['final_observation']")
-        r = self._dev(reward, torch.float64, (n,), "reward")           # (the sparse reward comes back as float32: one small cast)
-        term = self._dev(terminated, torch.bool, (n,), "terminated")
-        trunc = self._dev(truncated, torch.bool, (n,), "truncated")
-        out = _abi.McgStepOut(obs=o.data_ptr(), achieved_goal=ag.data_ptr(), desired_goal=dg.data_ptr(), reward=r.data_ptr(),
-                              terminated=term.data_ptr(), truncated=trunc.data_ptr(), final_obs=fo.data_ptr(),
-                              final_achieved=fa.data_ptr(), final_desired=fd.data_ptr())
-        with torch.cuda.device(self.device):
-            _abi.check(self._lib.mcg_her_add(C.byref(self._cbuf), self.n_written, C.c_void_p(a.data_ptr()), C.byref(out), self._stream()),
-                       "mcg_her_add")
+        a = self._dev(actions, torch.float32, (self.num_envs, self.act_dim), "actions")
+        out, _alive = self._step_out(obs, reward, terminated, truncated, info["final_observation"])
+        self._call("mcg_her_add", self.n_written, _ptr(a), C.byref(out))
         self.n_written += 1
 
     # ------------------------------------------------------------------------------------------------------ sampling
@@ -148,9 +107,7 @@ class HerBuffer:
              "index": torch.empty(rows, 3, dtype=torch.int32, device=dev)}
         out = _abi.McgHerBatch(**{k: v.data_ptr() for k, v in t.items()})
         before = self.counters()["sample_give_ups"] if check else 0
-        with torch.cuda.device(self.device):
-            _abi.check(self._lib.mcg_her_sample(C.byref(self._cbuf), self.n_written, C.c_uint64(self.seed), C.c_uint64(self.n_sampled), B,
-                                                self.n_virtual(B), C.byref(out), self._stream()), "mcg_her_sample")
+        self._call("mcg_her_sample", self.n_written, C.c_uint64(self.seed), C.c_uint64(self.n_sampled), B, self.n_virtual(B), C.byref(out))
         self.n_sampled += 1
         if check:
             gave_up = self.counters()["sample_give_ups"] - before
@@ -163,33 +120,13 @@ class HerBuffer:
             next_observations={"observation": t["next_obs"], "achieved_goal": t["next_achieved"], "desired_goal": t["desired"]},
             dones=t["done"], rewards=t["reward"], index=t["index"])
 
-    # --------------------------------------------------------------------------------------------- counters, checkpoints
+    # --------------------------------------------------------------------------------------------- counters, storage
     def counters(self) -> dict:
         """``sample_give_ups``: samples that found no valid transition; ``overlong_episodes``: episodes that ran to ``max_episode_steps``
         transitions without a done flag and were abandoned.  Synchronises."""
         c = self._t["counters"].cpu().tolist()
         return {"sample_give_ups": c[0] & (2 ** 64 - 1), "overlong_episodes": c[1] & (2 ** 64 - 1)}
 
-    def records(self) -> torch.Tensor:
-        """The ring, uint8 [capacity, N, record_bytes] (a view; ``_abi.her_record_dtype`` names the fields of a record)."""
-        return self._t["records"]
-
     def guards(self):
         """The ``guard_rows`` slots before and after the ring."""
         return self._alloc[:self._guard], self._alloc[self._guard + self.capacity:]
-
-    def state_dict(self) -> dict:
-        """The five device tensors (cloned) and the three host integers: everything a new ``HerBuffer`` of the same shape needs to
-        draw the batches this one would."""
-        sd = {k: v.clone() for k, v in self._t.items()}
-        sd.update(n_written=self.n_written, n_sampled=self.n_sampled, seed=self.seed)
-        return sd
-
-    def load_state_dict(self, sd: dict):
-        for k, v in self._t.items():
-            src = torch.as_tensor(sd[k], device=self.device)
-            if src.shape != v.shape or src.dtype != v.dtype:
-                raise ValueError(f"{k}: expected {v.dtype} {tuple(v.shape)}, got {src.dtype} {tuple(src.shape)}")
-            v.copy_(src)
-        self.n_written, self.n_sampled = int(sd["n_written"]), int(sd["n_sampled"])
-        self.seed = int(sd["seed"]) & (2 ** 64 - 1)

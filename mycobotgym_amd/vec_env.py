@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _devbuf
 from .registry import MAX_EPISODE_STEPS, spec as _spec
 from .spaces import Box, Dict, batch_box
 
@@ -242,8 +242,7 @@ class MyCobotVecEnv:
         self._needs_reset = True
 
     # ------------------------------------------------------------------------------------------- Gymnasium API
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    _stream = _devbuf.DeviceBuffer._stream
 
     def _obs(self):
         b = self._buf

@@ -214,3 +214,9 @@ def assert_within_oracle_sensitivity(e_hip, e_twin, what="", factor=10.0):
     print(f"\n{what} quantiles (median p90 p99 | max): hip-vs-oracle " + " ".join(f"{x:.2e}" for x in qh) + f" | {e_hip.max():.2e};  "
           "oracle-vs-oracle+1e-14 " + " ".join(f"{x:.2e}" for x in qt) + f" | {e_twin.max():.2e}")
     assert np.all(qh <= factor * qt + 1e-13), (what, qh, qt)
+
+
+def bits(x):
+    """The array's own bits as unsigned integers of its item size: what a bit-for-bit comparison compares (nan payloads and -0 included)."""
+    x = np.ascontiguousarray(x)
+    return x.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[x.dtype.itemsize])

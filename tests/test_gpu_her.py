@@ -6,6 +6,7 @@ import functools
 import numpy as np
 import pytest
 
+from tests.common import bits
 from tests.indep_her import History, record_dtype
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ FIELDS = ("obs", "achieved", "desired", "next_obs", "next_achieved", "action", "
 
 
 @functools.lru_cache(maxsize=None)
-def synthetic_events(n_insertions=100):
+def synthetic_events(n_insertions=100, D=D, A=A):
     """Step outputs from default_rng(0): ("start", obs, achieved, mask) and ("add", actions, out) events.  final_* differ from the
     post-reset values; episode lengths are uniform in 1..7; `terminated` on a random half of the ends; before insertion 20 a masked
     start abandons five episodes in flight.  Goals are drawn within a few centimetres, so that the sparse reward takes both values."""
@@ -48,11 +49,11 @@ def synthetic_events(n_insertions=100):
 
 
 @functools.lru_cache(maxsize=None)
-def rule_history(reward_type, n_insertions=100):
+def rule_history(reward_type, n_insertions=100, D=D, A=A):
     """The rule's history after every event, its ring at the checkpoints, and its batch: computed once, shared, not modified."""
     H = History(N, D, A, CAP, MAX_STEPS, reward_type, THRESHOLD)
     rings = {}
-    for ev in synthetic_events(n_insertions):
+    for ev in synthetic_events(n_insertions, D, A):
         if ev[0] == "start":
             H.start(ev[1], ev[2], ev[3])
         else:
@@ -75,7 +76,7 @@ def apply_event(buf, ev):
     buf.add(t(ev[1]), obs, t(o["reward"]), t(o["terminated"]), t(o["truncated"]), info)
 
 
-def make_buffer(reward_type="dense", **kw):
+def make_buffer(reward_type="dense", D=D, A=A, **kw):
     from mycobotgym_amd import HerBuffer
     return HerBuffer(capacity=CAP, n_sampled_goal=4, seed=11, num_envs=N, obs_dim=D, act_dim=A, max_episode_steps=MAX_STEPS,
                      reward_type=reward_type, distance_threshold=THRESHOLD, **kw)
@@ -90,11 +91,6 @@ def batch_arrays(b):
          "next_obs": b.next_observations["observation"], "next_achieved": b.next_observations["achieved_goal"], "action": b.actions,
          "reward": b.rewards[:, 0], "done": b.dones[:, 0], "index": b.index}
     return {k: v.cpu().numpy() for k, v in o.items()}
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({4: np.uint32, 8: np.uint64}[x.dtype.itemsize])
 
 
 def reward_bound_check(lib_reward, r32, reward_type, label):
@@ -114,22 +110,20 @@ def reward_bound_check(lib_reward, r32, reward_type, label):
     return worst
 
 
-@pytest.mark.parametrize("reward_type", ["dense", "sparse"])
-def test_synthetic_insertion_and_sampling_match_the_rule(built, reward_type):
-    """Records after 5, 31, 32, 33 and 100 insertions and a batch of 1000 equal the rule's bit for bit; the relabelled rewards equal
-    mcg_compute_reward's on the same float64 goals (sparse: exactly; dense: within 1e-15 relative before the float32 cast).
-    Measured on an MI355X: worst |kernel - float32(mcg_compute_reward)| = 0 in both reward types (800 relabelled rewards each)."""
+def run_against_rule(reward_type, batch, D=D, A=A):
+    """100 insertions and one batch against the rule, with two guard slots around the ring -> how many of the batch are relabelled."""
     import torch
-    H, rings = rule_history(reward_type)
-    batch = 1000
+    H, rings = rule_history(reward_type, 100, D, A)
     n_virtual = int(batch * (1 - 1 / 5))
     want = H.sample(seed=11, call=0, batch=batch, n_virtual=n_virtual)
     # the cap of 256 draws is a condition of the inputs, settled before the GPU is touched
     assert want["draws"].max() <= 64, int(want["draws"].max())
-    assert (want["index"][:, 2] >= 0).sum() == n_virtual == 800
+    assert (want["index"][:, 2] >= 0).sum() == n_virtual
 
-    buf = make_buffer(reward_type)
-    for ev in synthetic_events():
+    buf = make_buffer(reward_type, D, A, guard_rows=2)
+    for g in buf.guards():
+        g.fill_(0xA5)
+    for ev in synthetic_events(100, D, A):
         apply_event(buf, ev)
         if ev[0] == "add" and buf.n_written in CHECKPOINTS:
             got, ref = device_ring(buf), rings[buf.n_written]
@@ -156,6 +150,24 @@ def test_synthetic_insertion_and_sampling_match_the_rule(built, reward_type):
     if reward_type == "sparse":
         assert set(np.unique(got["reward"][virtual])) == {-1.0, 0.0}          # both outcomes occur
     assert buf.counters() == {"sample_give_ups": 0, "overlong_episodes": 0}
+    for g in buf.guards():
+        assert bool((g == 0xA5).all())
+    return n_virtual
+
+
+@pytest.mark.parametrize("reward_type", ["dense", "sparse"])
+def test_synthetic_insertion_and_sampling_match_the_rule(built, reward_type):
+    """Records after 5, 31, 32, 33 and 100 insertions and a batch of 1000 equal the rule's bit for bit; the relabelled rewards equal
+    mcg_compute_reward's on the same float64 goals (sparse: exactly; dense: within 1e-15 relative before the float32 cast).
+    Measured on an MI355X: worst |kernel - float32(mcg_compute_reward)| = 0 in both reward types (800 relabelled rewards each)."""
+    assert run_against_rule(reward_type, 1000) == 800
+
+
+def test_record_of_66_pairs_takes_two_passes_of_the_copy_phase(built):
+    """D = 51, A = 7: a record of 131 words padded to 132, 66 pairs -- the smallest at which the copy phase's loop over pairs goes
+    round twice, the second pass with two lanes.  The same checks as above on one batch of 64, dense."""
+    assert record_dtype(51, 7).itemsize == 66 * 8
+    assert run_against_rule("dense", 64, D=51, A=7) == 51
 
 
 def test_give_up_path(built):

@@ -7,6 +7,7 @@ import functools
 import numpy as np
 import pytest
 
+from tests.common import bits
 from tests.indep_rollout import PERM_SEED, Rollout, record_dtype
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ PLANES = ("reward", "value", "episode_start", "advantage", "returns")
 
 
 @functools.lru_cache(maxsize=None)
-def synthetic_events(n=N, steps=T, rollouts=2, restart_at=RESTART_AT, poison=False):
+def synthetic_events(n=N, steps=T, rollouts=2, restart_at=RESTART_AT, poison=False, D=D, A=A):
     """Step outputs from default_rng(0): ("start", obs, achieved, desired, mask), ("add", actions, values, log_probs, final_values, out)
     and ("finish", last_values) events, `rollouts` rollouts of `steps` steps.  final_* differ from the post-reset values (the buffer must
     not read them); episode lengths are uniform in 1..7; `terminated` on a random half of the ends; before step `restart_at` a masked
@@ -59,12 +60,12 @@ def minibatches(M, batch):
 
 
 @functools.lru_cache(maxsize=None)
-def rule_snapshots(n=N, steps=T, rollouts=2, restart_at=RESTART_AT, with_final_values=True, batch=64, poison=False):
+def rule_snapshots(n=N, steps=T, rollouts=2, restart_at=RESTART_AT, with_final_values=True, batch=64, poison=False, D=D, A=A):
     """The rule on the events: after every finish its records, planes, carried state and the epoch's minibatches.  Computed once,
     shared, not modified."""
     R = Rollout(n, D, A, steps, GAMMA, LAMBDA)
     snaps = []
-    for ev in synthetic_events(n, steps, rollouts, restart_at, poison):
+    for ev in synthetic_events(n, steps, rollouts, restart_at, poison, D, A):
         if ev[0] == "start":
             R.start(ev[1], ev[2], ev[3], ev[4])
         elif ev[0] == "add":
@@ -93,7 +94,7 @@ def apply_event(buf, ev, with_final_values=True):
         buf.finish(t(ev[1]))
 
 
-def make_buffer(n=N, steps=T, **kw):
+def make_buffer(n=N, steps=T, D=D, A=A, **kw):
     from mycobotgym_amd import RolloutBuffer
     buf = RolloutBuffer(n_steps=steps, gamma=GAMMA, gae_lambda=LAMBDA, seed=PERM_SEED, num_envs=n, obs_dim=D, act_dim=A, **kw)
     for pair in buf.guards().values():
@@ -106,11 +107,6 @@ def guards_intact(buf):
     return all(bool((g == 0xA5).all()) for pair in buf.guards().values() for g in pair)
 
 
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[x.dtype.itemsize])
-
-
 def batch_arrays(b):
     o = {"obs": b.observations["observation"], "achieved": b.observations["achieved_goal"], "desired": b.observations["desired_goal"],
          "action": b.actions, "old_value": b.old_values, "old_log_prob": b.old_log_prob, "advantage": b.advantages, "returns": b.returns,
@@ -120,7 +116,7 @@ def batch_arrays(b):
 
 def assert_state_equals(buf, snap, skip_envs=()):
     keep = np.array([e not in skip_envs for e in range(buf.num_envs)])
-    got = buf.records().cpu().numpy().reshape(buf.n_steps, buf.num_envs, -1).view(record_dtype(D, A))[..., 0]
+    got = buf.records().cpu().numpy().reshape(buf.n_steps, buf.num_envs, -1).view(record_dtype(buf.obs_dim, buf.act_dim))[..., 0]
     for name in snap["records"].dtype.names:
         assert np.array_equal(bits(got[name]), bits(snap["records"][name])), name
     assert got.tobytes() == snap["records"].tobytes()
@@ -149,15 +145,15 @@ def assert_epoch_equals(buf, snap, batch, skip_fields=()):
     return got
 
 
-def run_against_rule(n, steps, rollouts, restart_at, with_final_values, batch):
-    snaps = rule_snapshots(n, steps, rollouts, restart_at, with_final_values, batch)
+def run_against_rule(n, steps, rollouts, restart_at, with_final_values, batch, D=D, A=A):
+    snaps = rule_snapshots(n, steps, rollouts, restart_at, with_final_values, batch, False, D, A)
     # the walk's length is a condition of the inputs, settled before the GPU is touched
     longest = max(int(b["passes"].max()) for s in snaps for b in s["batches"])
     print(f"(T, N) = ({steps}, {n}): longest walk {longest} passes")
     assert longest <= 64
-    buf = make_buffer(n, steps, guard_rows=2)
+    buf = make_buffer(n, steps, D, A, guard_rows=2)
     done = 0
-    for ev in synthetic_events(n, steps, rollouts, restart_at):
+    for ev in synthetic_events(n, steps, rollouts, restart_at, False, D, A):
         apply_event(buf, ev, with_final_values)
         if ev[0] == "finish":
             assert_state_equals(buf, snaps[done])
@@ -192,6 +188,15 @@ def test_no_walk_and_degenerate_shapes(built, steps, n):
     snaps = run_against_rule(n, steps, 2, None, True, 64)
     if steps * n == 256:
         assert all(int(b["passes"].max()) == 1 for s in snaps for b in s["batches"])
+
+
+def test_record_of_66_pairs_takes_two_passes_of_the_copy_phase(built):
+    """D = 116, A = 7: a record of 130 words padded to 132, 66 pairs -- the smallest at which the copy phase's loop over pairs goes
+    round twice, the second pass with two lanes.  One rollout of 3 steps of 11 environments (a masked start before step 1), one epoch
+    of get(16): two minibatches of 16 and one of 1."""
+    assert record_dtype(116, 7).itemsize == 66 * 8
+    snaps = run_against_rule(11, 3, 1, 1, True, 16, D=116, A=7)
+    assert [len(b["index"]) for b in snaps[0]["batches"]] == [16, 16, 1]
 
 
 def test_non_finite_policy_outputs(built):

@@ -23,27 +23,11 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import mycobotgym_amd as mg  # noqa: E402
-
-
-def timed(fn, warmup, reps, inner):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b) / inner)
-    ms = np.asarray(ms)
-    return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()), "reps": reps, "inner": inner}
+from _timing import timed  # noqa: E402
 
 
 def rollout(envs, steps, seed=0):

@@ -29,27 +29,12 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import mycobotgym_amd as mg  # noqa: E402
+from _timing import timed  # noqa: E402
 from mycobotgym_amd import _abi  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0          # bench.py's
 ENV_ID = "MyCobotPickAndPlace-Sparse-joint-v0"
 ROUNDS = 6                      # rejection rounds of the PyTorch formulation (fixed: it may not look at the device to stop early)
-
-
-def timed(fn, warmup, reps, inner):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b) / inner)
-    ms = np.asarray(ms)
-    return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()), "reps": reps, "inner": inner}
 
 
 def filled(args):

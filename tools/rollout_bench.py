@@ -29,33 +29,17 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import mycobotgym_amd as mg  # noqa: E402
+from _timing import timed  # noqa: E402
 from mycobotgym_amd import _abi  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0          # bench.py's
 ENV_ID = "MyCobotReach-Dense-joint-v0"
 GAMMA, LAMBDA = 0.99, 0.95
 PATHS = ("add", "add_raw", "gae", "get", "torch_add", "torch_gae", "torch_get", "step")
-
-
-def timed(fn, warmup, reps, inner):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b) / inner)
-    ms = np.asarray(ms)
-    return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()), "reps": reps, "inner": inner}
 
 
 def rollout(envs, n_steps, seed, buf=None):
