@@ -151,7 +151,8 @@ def make_pair(n, device="cuda:0", table=None, **kw):
 
 
 def step_errors(envs, ora, actions):
-    """Step both; per-env max abs error over observation / achieved goal / reward, plus the oracle outputs."""
+    """Step both; per-env max abs error over observation / achieved goal / reward, whether terminated, truncated, is_success and the
+    finished episodes' lengths all agree, plus the oracle outputs."""
     import torch
     obs, rew, term, trunc, info = envs.step(torch.as_tensor(actions))
     o = ora.step(actions)
@@ -162,6 +163,10 @@ def step_errors(envs, ora, actions):
     assert np.array_equal(obs["desired_goal"].cpu().numpy(), o["desired"]), "desired_goal differs (reset draws)"
     flags_equal = (np.array_equal(term.cpu().numpy(), o["terminated"].astype(bool))
                    and np.array_equal(trunc.cpu().numpy(), o["truncated"].astype(bool)))
+    # is_success, and the finished episodes' length (Monitor's "l"), are integers: they agree exactly whenever the flags do
+    done = o["terminated"].astype(bool) | o["truncated"].astype(bool)
+    flags_equal = (flags_equal and np.array_equal(info["is_success"].cpu().numpy(), o["is_success"].astype(bool))
+                   and np.array_equal(info["episode"]["l"].cpu().numpy()[done], o["ep_length"][done]))
     return e, flags_equal, o
 
 

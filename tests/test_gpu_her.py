@@ -219,17 +219,11 @@ def test_overlong_episode_is_abandoned_inside_the_ring(built):
     assert buf.counters()["overlong_episodes"] == N
 
 
-@pytest.mark.parametrize("env_id", ["MyCobotReach-Dense-joint-v0", "MyCobotPickAndPlace-Sparse-IK-v0"])
-def test_with_the_real_engine(built, env_id):
-    """60 random-policy steps of 40 environments (time limit 7, threshold 0.05: some episodes end by success) into a ring of 32 slots.
-    Real samples are the float32 casts of what step() returned at their step; virtual samples carry the next achieved goal of their
-    future slot and the library's reward for it; the engine's state is what it is without a buffer.
-    Measured on an MI355X: worst |kernel - float32(compute_reward)| = 0 for both ids (409 relabelled rewards each); 320 episodes ended in
-    either run, none of them by success (a random policy does not come within 5 cm in 7 steps), so `dones` is 0 throughout here and its
-    1 is exercised by the synthetic inputs."""
+def real_engine_run(env_id, threshold):
+    """The checks of test_with_the_real_engine at one distance threshold -> the steps' host copies, the batch and the counts."""
     import torch
     from mycobotgym_amd import HerBuffer, make
-    kw = dict(num_envs=N, max_episode_steps=MAX_STEPS, distance_threshold=THRESHOLD, seed=3)
+    kw = dict(num_envs=N, max_episode_steps=MAX_STEPS, distance_threshold=threshold, seed=3)
     envs, twin = make(env_id, **kw), make(env_id, **kw)
     buf = HerBuffer(envs, capacity=CAP, n_sampled_goal=4, seed=2)
     assert (buf.num_envs, buf.obs_dim, buf.act_dim, buf.max_episode_steps) == (N, envs.obs_dim, envs.action_dim, MAX_STEPS)
@@ -294,6 +288,54 @@ def test_with_the_real_engine(built, env_id):
     reward_bound_check(lib, got["reward"][batch - n_virtual:], envs.reward_type, env_id)
     assert buf.counters() == {"sample_give_ups": 0, "overlong_episodes": 0}
     envs.close(); twin.close()
+    return {"steps": steps, "got": got, "done_count": done_count, "success": success, "n_virtual": n_virtual, "time_of": time_of}
+
+
+@pytest.mark.parametrize("env_id", ["MyCobotReach-Dense-joint-v0", "MyCobotPickAndPlace-Sparse-IK-v0"])
+def test_with_the_real_engine(built, env_id):
+    """60 random-policy steps of 40 environments (time limit 7, threshold 0.05: some episodes end by success) into a ring of 32 slots.
+    Real samples are the float32 casts of what step() returned at their step; virtual samples carry the next achieved goal of their
+    future slot and the library's reward for it; the engine's state is what it is without a buffer.
+    Measured on an MI355X: worst |kernel - float32(compute_reward)| = 0 for both ids (409 relabelled rewards each); 320 episodes ended in
+    either run, none of them by success (a random policy does not come within 5 cm in 7 steps), so `dones` is 0 throughout here and its
+    1 is exercised by the synthetic inputs."""
+    real_engine_run(env_id, THRESHOLD)
+
+
+# threshold per id: the smallest at which the CPU oracle's replay of this very run (seed 3, reset seed 0, default_rng(1) actions, 60 steps of
+# 40 environments, time limit 7) ends at least 10 episodes by success and 10 by the time limit alone.  PickAndPlace: 0.12 of
+# {0.08, 0.1, 0.12, 0.15} (0.08, 0.1: no success).  Reach: the oracle's run has no success ending at any of the four, nor at 0.2 and
+# 0.25 (a random joint policy does not bring the gripper that close within 7 steps); the list continued in steps of 0.05 gives 0.3.
+SUCCESS_THRESHOLD = {"MyCobotReach-Dense-joint-v0": 0.3, "MyCobotPickAndPlace-Sparse-IK-v0": 0.12}
+
+
+@pytest.mark.parametrize("env_id", list(SUCCESS_THRESHOLD))
+def test_with_the_real_engine_and_success_endings(built, env_id):
+    """test_with_the_real_engine's run and checks at a threshold at which episodes end both ways, so that `terminated` from the step
+    kernel's tail reaches the buffer: samples with done = 1, and goals relabelled inside episodes that success ended before the time
+    limit.  The CPU oracle's replay of the run: Reach (0.3) 22 episodes ended by success and 308 by the time limit alone, PickAndPlace
+    (0.12) 67 and 319; asserted here: at least 5 of each kind (half the oracle's floor of 10: the physics is chaotic, the engine's
+    counts differ).  Measured on an MI355X: the oracle's counts exactly (22 / 308 and 67 / 319: episodes of at most 7 steps leave the chaos
+    no room); 4 and 14 of the 512 samples carry done = 1, 11 and 12 relabelled samples lie in episodes that success ended early."""
+    r = real_engine_run(env_id, SUCCESS_THRESHOLD[env_id])
+    steps, got, time_of = r["steps"], r["got"], r["time_of"]
+    by_success = r["success"]
+    by_limit = sum(int((s["truncated"] & ~s["terminated"]).sum()) for s in steps)
+    done_samples = int((got["done"] == 1.0).sum())
+    early = 0            # relabelled samples of episodes that success ended before the time limit
+    batch = len(got["index"])
+    for k in range(batch - r["n_virtual"], batch):
+        slot, e, _ = (int(x) for x in got["index"][k])
+        tm = time_of(slot)
+        end = next(x for x in range(tm, len(steps)) if steps[x]["truncated"][e] or steps[x]["terminated"][e])
+        start = tm
+        while start > 0 and not (steps[start - 1]["truncated"][e] or steps[start - 1]["terminated"][e]):
+            start -= 1
+        early += int(steps[end]["terminated"][e] and end - start + 1 < MAX_STEPS)
+    print(f"{env_id} at threshold {SUCCESS_THRESHOLD[env_id]}: {by_success} episodes ended by success, {by_limit} by the time limit alone; "
+          f"{done_samples} of {batch} samples carry done = 1, {early} relabelled samples lie in episodes that ended early")
+    assert by_success >= 5 and by_limit >= 5
+    assert done_samples >= 1 and early >= 1
 
 
 def test_checkpoint(built):

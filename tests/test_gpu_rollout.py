@@ -259,16 +259,16 @@ def test_image_ids_are_refused(built):
     envs.close()
 
 
-@pytest.mark.parametrize("env_id", ["MyCobotReach-Dense-joint-v0", "MyCobotPickAndPlace-Sparse-IK-v0"])
-def test_with_the_real_engine(built, env_id):
-    """Two rollouts of 16 steps of 40 environments (time limit 7) under a fixed linear policy.  Every gathered sample is the float32 cast
-    of what reset / step returned at its (step, env); the reward plane is the recalled bootstrap rule on the host copies of reward,
-    terminated, truncated and final_values; advantages and returns equal the rule's on those inputs bit for bit; the engine's state
-    is what it is without a buffer.  Measured on an MI355X: 160 episodes ended in either run (the time limit's 40 * 4)."""
+def real_engine_run(env_id, threshold=None, action_seed=None):
+    """The checks of test_with_the_real_engine; threshold: a distance threshold other than the default; action_seed: actions from
+    default_rng(action_seed) on the host in place of the policy's -> rows ended by the time limit alone, rows ended by success."""
     import torch
     from mycobotgym_amd import RolloutBuffer, make
     steps = 16
     kw = dict(num_envs=N, max_episode_steps=MAX_STEPS, seed=3)
+    if threshold is not None:
+        kw["distance_threshold"] = threshold
+    rng = np.random.default_rng(action_seed) if action_seed is not None else None
     envs, twin = make(env_id, **kw), make(env_id, **kw)
     buf = RolloutBuffer(envs, n_steps=steps, gamma=GAMMA, gae_lambda=LAMBDA, seed=PERM_SEED, guard_rows=1)
     Do, Aa = envs.obs_dim, envs.action_dim
@@ -291,11 +291,13 @@ def test_with_the_real_engine(built, env_id):
     R = Rollout(N, Do, Aa, steps, GAMMA, LAMBDA)
     first = host(obs)
     R.start(first["observation"], first["achieved_goal"], first["desired_goal"])
-    prev, ended = first, 0
+    prev, ended, boot_rows, both_rows = first, 0, 0, 0
     for rollout in range(2):
         log = []
         for _ in range(steps):
             a, v, lp = policy(obs)
+            if rng is not None:      # seeded host actions, which the CPU oracle can replay
+                a = torch.as_tensor(rng.uniform(-1, 1, (N, Aa)).astype(np.float32), device=envs.device)
             obs, r, term, trunc, info = envs.step(a)
             fv = policy(info["final_observation"])[1]
             buf.add(a, v, lp, obs, r, term, trunc, info, final_values=fv)
@@ -308,6 +310,7 @@ def test_with_the_real_engine(built, env_id):
             log.append(s)
             prev = s["obs"]
             ended += int((s["truncated"] | s["terminated"]).sum())
+            boot_rows += int((s["truncated"] & ~s["terminated"]).sum()); both_rows += int((s["truncated"] & s["terminated"]).sum())
         lv = policy(obs)[1]
         buf.finish(lv)
         R.finish(host(lv))
@@ -345,6 +348,37 @@ def test_with_the_real_engine(built, env_id):
     assert ended >= N * (2 * steps // MAX_STEPS)          # true by the time limit alone
     assert guards_intact(buf)
     envs.close(); twin.close()
+    return boot_rows, both_rows
+
+
+@pytest.mark.parametrize("env_id", ["MyCobotReach-Dense-joint-v0", "MyCobotPickAndPlace-Sparse-IK-v0"])
+def test_with_the_real_engine(built, env_id):
+    """Two rollouts of 16 steps of 40 environments (time limit 7) under a fixed linear policy.  Every gathered sample is the float32 cast
+    of what reset / step returned at its (step, env); the reward plane is the recalled bootstrap rule on the host copies of reward,
+    terminated, truncated and final_values; advantages and returns equal the rule's on those inputs bit for bit; the engine's state
+    is what it is without a buffer.  Measured on an MI355X: 160 episodes ended in either run (the time limit's 40 * 4)."""
+    real_engine_run(env_id)
+
+
+# threshold per id: the smallest at which the CPU oracle's replay of this very run (seed 3, reset seed 0, default_rng(1) actions, 32 steps of
+# 40 environments, time limit 7) ends at least 10 episodes by success and 10 by the time limit alone.  PickAndPlace: 0.12 of
+# {0.08, 0.1, 0.12, 0.15} (0.08, 0.1: no success).  Reach: the oracle's run has no success ending at any of the four, nor at 0.2 and
+# 0.25, and 9 at 0.3 (a random joint policy does not bring the gripper closer within 7 steps); the list continued in steps of 0.05
+# gives 0.35.
+SUCCESS_THRESHOLD = {"MyCobotReach-Dense-joint-v0": 0.35, "MyCobotPickAndPlace-Sparse-IK-v0": 0.12}
+
+
+@pytest.mark.parametrize("env_id", list(SUCCESS_THRESHOLD))
+def test_with_the_real_engine_and_success_endings(built, env_id):
+    """test_with_the_real_engine's checks on a run in which episodes end both ways, so that `terminated & truncated` from the step
+    kernel's tail reaches the buffer: rows without the bootstrap next to time-limit rows with it (the reward plane is asserted row by
+    row against the recalled rule, the advantages against tests/indep_rollout.py).  Actions are seeded host draws, so that the CPU
+    oracle can replay the run: Reach (0.35) 63 episodes ended by success and 143 by the time limit alone, PickAndPlace (0.12) 34 and
+    160; asserted here: at least 5 of each kind (half the oracle's floor of 10: the physics is chaotic, the engine's counts differ).
+    Measured on an MI355X: the oracle's counts exactly, 63 / 143 and 34 / 160."""
+    boot_rows, both_rows = real_engine_run(env_id, SUCCESS_THRESHOLD[env_id], action_seed=1)
+    print(f"{env_id} at threshold {SUCCESS_THRESHOLD[env_id]}: {both_rows} rows ended by success (no bootstrap), {boot_rows} by the time limit alone")
+    assert both_rows >= 5 and boot_rows >= 5
 
 
 def test_checkpoint(built):
