@@ -18,6 +18,8 @@
  *                       "future")   scripts/train.py:89-97
  *   mcg_rollout_start / mcg_rollout_add / mcg_rollout_gae / mcg_rollout_gather   SB3's RolloutBuffer as PPO / A2C use it (n_steps,
  *                       gamma, gae_lambda)   scripts/train.py:99-101
+ *   mcg_rollout_img_start / _add / _gae / _carry / _gather   the same RolloutBuffer on the uint8 pictures MyCobotImgEnv observes
+ *                       (PPO / A2C on the -v1 ids)   scripts/train.py:99-101, mycobot.py:517-545
  *   mcg_get_state / mcg_set_state   direct access to data.qpos/qvel/ctrl/qacc_warmstart (set_joint_qpos etc.)
  *
  * Conventions: every pointer in the step/reset/state calls is DEVICE memory owned by the caller;
@@ -472,6 +474,80 @@ int mcg_rollout_gae(const mcg_rollout_buf* buf, const float* last_values /* [N] 
    bijection of [0, M); 2^b < 4 M, so a walk takes fewer than 4 passes in expectation.  No address depends on stored content. */
 int mcg_rollout_gather(const mcg_rollout_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
                        const mcg_rollout_batch* out, void* stream);
+
+/* ---- On-policy rollout buffer of pictures (the same SB3 RolloutBuffer, scripts/train.py:99-101, on what MyCobotImgEnv observes: the
+   uint8 picture [C, S, S] alone).  Stateless as mcg_rollout_*; T = n_steps, N = n_envs, time-major, the write position a host integer.
+   Pu = C * S * S bytes of a picture, channel-major as the environment holds it; P = Pu rounded up to a multiple of 16.
+     pixels   uint8 [T + 1, N, P]: row t holds the picture the action of step t was taken from, row T the picture the next rollout
+              continues from; bytes Pu .. P - 1 of every picture that a call writes are zero.  There is no carried last observation:
+              mcg_rollout_img_start writes row `pos`, mcg_rollout_img_add(pos) writes the step's picture into row pos + 1, and
+              mcg_rollout_img_carry copies row T (the write position) to row 0 between two rollouts.  An insertion reads and writes each pixel once.
+     records  one per (step, env), mcg_rollout_img_record_bytes(A) bytes: float action[A], log_prob; zero padding to a multiple of 16.
+     planes   reward, value, episode_start, advantage, returns [T, N] and last_start [N]: those of mcg_rollout_buf, by the same rules.
+   A picture is passed as a base pointer and two strides in bytes: channel c of environment e is the S * S contiguous bytes at
+   img + e * env_stride + c * chan_stride (the environment's [C, N, S, S] buffer: env_stride = S * S, chan_stride = N * S * S; a
+   contiguous [N, C, S, S] tensor: env_stride = C * S * S, chan_stride = S * S).  It is read with 16-byte loads where img, both strides
+   and S * S are multiples of 16, with 4-byte loads where they are multiples of 4, and byte by byte otherwise; the choice is made on
+   the host, and every store to `pixels` is 16 bytes wide. */
+typedef struct mcg_rollout_img_buf {  /* device pointers the caller owns (all required), and the buffer's shape */
+  uint8_t* pixels;                  /* [T + 1, N, P]; 16-byte aligned */
+  void* records;                    /* [T, N] records; 16-byte aligned */
+  float* reward;                    /* [T, N]  as mcg_rollout_buf's */
+  float* value;                     /* [T, N] */
+  uint8_t* episode_start;           /* [T, N]  1 where the picture of row t is the first of its episode */
+  float* advantage;                 /* [T, N]  written by mcg_rollout_img_gae */
+  float* returns;                   /* [T, N] */
+  uint8_t* last_start;              /* [N]     1 where the picture to continue from is the first of its episode */
+  int32_t n_envs, channels, size, act_dim, n_steps;      /* channels <= 8, size <= 512 */
+  double gamma, gae_lambda;         /* in [0, 1] */
+} mcg_rollout_img_buf;
+
+typedef struct mcg_rollout_img_batch {  /* outputs of mcg_rollout_img_gather; device pointers, any may be NULL (not all).  B = count */
+  uint8_t* pix;          /* [B, Pu]  the picture as stored (no padding between rows) */
+  float* pix_f32;        /* [B, Pu]  byte / 255 in float32, correctly rounded: bit for bit (float)b / 255.0f, SB3's obs.float() / 255 */
+  float* action;         /* [B, A] */
+  float* old_value;      /* [B] */
+  float* old_log_prob;   /* [B] */
+  float* advantage;      /* [B] */
+  float* returns;        /* [B] */
+  int32_t* index;        /* [B]     env * T + step, as mcg_rollout_batch's */
+} mcg_rollout_img_batch;
+
+/* All calls enqueue on `stream` and do not synchronise.  Checked on the host before any HIP call (MCG_ERR_ARG): a null struct or a null
+   pointer in it; n_envs / channels / size / act_dim / n_steps < 1; channels > 8; size > 512; n_steps * n_envs >= 2^31; pixels or records
+   not 16-byte aligned; gamma or gae_lambda not finite or outside [0, 1]; pos outside [0, n_steps) (mcg_rollout_img_start and
+   mcg_rollout_img_carry: outside [0, n_steps]); first < 0, count < 1 or first + count > n_steps * n_envs; a null img / actions / values / log_probs / reward /
+   terminated / truncated / last_values; a negative stride, or a channel stride below S * S while channels > 1; a null
+   mcg_rollout_img_batch or all eight outputs of a batch null. */
+int64_t mcg_rollout_img_record_bytes(int act_dim);               /* 0 where act_dim < 1 */
+
+/* The environments of `mask` (NULL = all) continue from the picture a reset returned: it is written to row `pos` of pixels (the write
+   position: 0 at the start of a rollout, n_steps after a full one, before the carry), and last_start = 1. */
+int mcg_rollout_img_start(const mcg_rollout_img_buf* buf, int pos, const uint8_t* img, int64_t env_stride, int64_t chan_stride,
+                          const uint8_t* mask /* [N] device or NULL */, void* stream);
+
+/* Step `pos` of the rollout, one launch.  `img` is the picture the step returned (after an auto-reset: the next episode's first; the
+   finished episode's last picture is never read) and goes to row pos + 1 of pixels; `reward` (float64), `terminated` and `truncated`
+   are mcg_step_out's.  The record takes action and log_prob as given, its padding zeros.  The plane row is mcg_rollout_add's: value
+   as given, episode_start[pos] = last_start, then last_start = truncated | terminated, and the reward r = (float)reward, and where
+   truncated & !terminated and final_values != NULL, r = r + (float)gamma * final_values[e], the product rounded before the sum. */
+int mcg_rollout_img_add(const mcg_rollout_img_buf* buf, int pos, const float* actions /* [N, A] device */, const float* values /* [N] */,
+                        const float* log_probs /* [N] */, const float* final_values /* [N] or NULL */, const uint8_t* img,
+                        int64_t env_stride, int64_t chan_stride, const double* reward /* [N] */, const uint8_t* terminated /* [N] */,
+                        const uint8_t* truncated /* [N] */, void* stream);
+
+/* mcg_rollout_gae's recursion on this buffer's planes: the same kernel, operation for operation. */
+int mcg_rollout_img_gae(const mcg_rollout_img_buf* buf, const float* last_values /* [N] device */, void* stream);
+
+/* Row `pos` of pixels (the write position: n_steps after a full rollout) to row 0, one launch: the picture the next rollout continues
+   from; last_start stays as it is.  pos = 0: nothing to do, no launch. */
+int mcg_rollout_img_carry(const mcg_rollout_img_buf* buf, int pos, void* stream);
+
+/* Samples k = first .. first + count - 1 of epoch `epoch`, by the permutation of mcg_rollout_gather exactly (one implementation of
+   the walk serves both): equal (seed, epoch, T, N) give equal `index`.  Sample k, transition x = env * T + step, takes the picture of
+   row `step`, environment env.  All byte offsets are 64-bit; no address and no loop bound depends on stored content. */
+int mcg_rollout_img_gather(const mcg_rollout_img_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
+                           const mcg_rollout_img_batch* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -241,6 +241,24 @@ def rollout_record_dtype(obs_dim: int, act_dim: int) -> np.dtype:
     return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
 
 
+class McgRolloutImgBuf(C.Structure):
+    """The picture rollout buffer's device memory, shape and discounting (include/mcg.h: mcg_rollout_img_buf); the caller owns every pointer."""
+    _fields_ = ([(n, C.c_void_p) for n in ("pixels", "records", "reward", "value", "episode_start", "advantage", "returns", "last_start")]
+                + [("n_envs", C.c_int32), ("channels", C.c_int32), ("size", C.c_int32), ("act_dim", C.c_int32), ("n_steps", C.c_int32),
+                   ("gamma", d), ("gae_lambda", d)])
+
+
+class McgRolloutImgBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pix", "pix_f32", "action", "old_value", "old_log_prob", "advantage", "returns", "index")]
+
+
+def rollout_img_record_dtype(act_dim: int) -> np.dtype:
+    """One record of the picture rollout buffer as a numpy structured dtype (include/mcg.h: the layout above mcg_rollout_img_buf)."""
+    fields = [("action", "<f4", (act_dim,)), ("log_prob", "<f4")]
+    used = np.dtype(fields).itemsize
+    return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -248,7 +266,9 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_compute_reward", "mcg_time_steps", "mcg_get_seed", "mcg_set_seed", "mcg_get_counters", "mcg_debug_contacts",
            "mcg_render", "mcg_render_mounted", "mcg_render_scenes", "mcg_scene_randomize",
            "mcg_her_record_bytes", "mcg_her_start", "mcg_her_add", "mcg_her_sample",
-           "mcg_rollout_record_bytes", "mcg_rollout_start", "mcg_rollout_add", "mcg_rollout_gae", "mcg_rollout_gather")
+           "mcg_rollout_record_bytes", "mcg_rollout_start", "mcg_rollout_add", "mcg_rollout_gae", "mcg_rollout_gather",
+           "mcg_rollout_img_record_bytes", "mcg_rollout_img_start", "mcg_rollout_img_add", "mcg_rollout_img_gae", "mcg_rollout_img_carry",
+           "mcg_rollout_img_gather")
 
 _lib = None
 
@@ -311,6 +331,15 @@ def load():
         L.mcg_rollout_gae.argtypes = [C.POINTER(McgRolloutBuf), C.c_void_p, C.c_void_p]
         L.mcg_rollout_gather.argtypes = [C.POINTER(McgRolloutBuf), C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(McgRolloutBatch),
                                          C.c_void_p]
+    if hasattr(L, "mcg_rollout_img_gather"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        img = C.POINTER(McgRolloutImgBuf)
+        L.mcg_rollout_img_record_bytes.argtypes = [C.c_int]; L.mcg_rollout_img_record_bytes.restype = C.c_int64
+        L.mcg_rollout_img_start.argtypes = [img, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcg_rollout_img_add.argtypes = [img, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcg_rollout_img_gae.argtypes = [img, C.c_void_p, C.c_void_p]
+        L.mcg_rollout_img_carry.argtypes = [img, C.c_int, C.c_void_p]
+        L.mcg_rollout_img_gather.argtypes = [img, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(McgRolloutImgBatch), C.c_void_p]
     _lib = L
     return L
 

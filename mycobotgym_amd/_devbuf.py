@@ -18,16 +18,18 @@ def _ptr(t):
 
 class DeviceBuffer:
     """A subclass sets ``_FROM_ENVS`` (constructor keyword, attribute of a ``MyCobotVecEnv`` to take it from), ``_NO_IMAGES`` (why it
-    refuses the -v1 image ids) and ``_HOST_STATE`` (the host fields of ``state_dict()``), fills ``self._t`` (name -> device tensor,
-    the pointers of the struct) and ``self._cbuf`` (the struct), and keeps ``num_envs``, ``obs_dim`` and ``seed``."""
+    refuses the -v1 image ids; a buffer of pictures sets ``_IMAGES = True`` and ``_NO_STATES``, why it refuses the -v0 ids) and
+    ``_HOST_STATE`` (the host fields of ``state_dict()``), fills ``self._t`` (name -> device tensor, the pointers of the struct) and
+    ``self._cbuf`` (the struct), and keeps ``num_envs``, ``obs_dim`` (with ``_goal_obs``) and ``seed``."""
+    _IMAGES = False
 
     def _resolve(self, envs, device, given: dict):
         """Sets ``device`` and loads the library -> the values of ``_FROM_ENVS``'s keywords in its order, each as ``given`` or else
         from ``envs`` (the device likewise)."""
         if envs is not None:
             from .vec_env import MyCobotImgVecEnv
-            if isinstance(envs, MyCobotImgVecEnv):
-                raise ValueError(self._NO_IMAGES)
+            if isinstance(envs, MyCobotImgVecEnv) != self._IMAGES:
+                raise ValueError(self._NO_STATES if self._IMAGES else self._NO_IMAGES)
             given = {k: getattr(envs, attr) if given[k] is None else given[k] for k, attr in self._FROM_ENVS}
             device = envs.device if device is None else device
         missing = [k for k, _ in self._FROM_ENVS if given[k] is None]
@@ -75,8 +77,8 @@ class DeviceBuffer:
 
     # ------------------------------------------------------------------------------------------- storage, checkpoints
     def records(self) -> torch.Tensor:
-        """The records, uint8 [capacity or n_steps, N, record_bytes] (a view; ``_abi.her_record_dtype`` or
-        ``_abi.rollout_record_dtype`` names the fields of a record)."""
+        """The records, uint8 [capacity or n_steps, N, record_bytes] (a view; ``_abi.her_record_dtype``, ``_abi.rollout_record_dtype``
+        or ``_abi.rollout_img_record_dtype`` names the fields of a record)."""
         return self._t["records"]
 
     def state_dict(self) -> dict:

@@ -1,5 +1,6 @@
-// mcg_rollout.hip -- the on-policy rollout buffer (include/mcg.h: mcg_rollout_*): insertion with the time-limit bootstrap, the advantage
-// recursion (GAE) and the shuffled minibatch gather on the device.
+// mcg_rollout.hip -- the on-policy rollout buffers (include/mcg.h: mcg_rollout_* for state observations, mcg_rollout_img_* for pictures):
+// insertion with the time-limit bootstrap, the advantage recursion (GAE) and the shuffled minibatch gather on the device.  The plane
+// row, the recursion and the permutation exist once and serve both.
 //
 // A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives: the step, render and replay kernels' code
 // objects stay laid out as they are without this file.  Kernels and C entries are both here.  The C side is stateless: every call gets
@@ -55,6 +56,22 @@ __global__ __launch_bounds__(ADD_LANES) void rollout_start_kernel(Roll B, const 
 }
 
 // -------------------------------------------------------------------------------------------------------------- add
+// The plane row of environment e at `at` = pos * N + e, and the one writer of last_start: one lane per environment (both buffers).
+MCG_DEV void plane_row(const Roll& B, size_t at, int e, const float* __restrict__ values, const float* __restrict__ final_values,
+                       const double* __restrict__ reward, const uint8_t* __restrict__ terminated, const uint8_t* __restrict__ truncated) {
+#pragma clang fp contract(off)
+  const bool term = terminated[e] != 0, trunc = truncated[e] != 0;
+  float r = (float)reward[e];
+  if (final_values && trunc && !term) {            // [RECALL] SB3 collect_rollouts: rewards[idx] += gamma * terminal_value
+    const float boot = B.g32 * final_values[e];
+    r = r + boot;
+  }
+  B.rew[at] = r;
+  B.val[at] = values[e];
+  B.start[at] = B.last_start[e];
+  B.last_start[e] = (term || trunc) ? 1 : 0;
+}
+
 // Lane = one word of one environment's record, and one more lane per environment for the plane row; environments are neighbours in
 // a step's row, so the grid writes one contiguous run.  Every element of last_obs / last_goals / last_start has one lane, which reads
 // it and then overwrites it.
@@ -68,17 +85,8 @@ __global__ __launch_bounds__(ADD_LANES) void rollout_add_kernel(Roll B, int pos,
   if (x >= (long long)B.n * elems) return;
   const int e = (int)(x / elems), w = (int)(x % elems);
   const size_t at = (size_t)pos * B.n + e;
-  if (w == L.words) {                    // the plane row, and the one writer of last_start
-    const bool term = O.terminated[e] != 0, trunc = O.truncated[e] != 0;
-    float r = (float)O.reward[e];
-    if (final_values && trunc && !term) {          // [RECALL] SB3 collect_rollouts: rewards[idx] += gamma * terminal_value
-      const float boot = B.g32 * final_values[e];
-      r = r + boot;
-    }
-    B.rew[at] = r;
-    B.val[at] = values[e];
-    B.start[at] = B.last_start[e];
-    B.last_start[e] = (term || trunc) ? 1 : 0;
+  if (w == L.words) {
+    plane_row(B, at, e, values, final_values, O.reward, O.terminated, O.truncated);
     return;
   }
   uint32_t bits = 0;
@@ -127,6 +135,28 @@ __global__ __launch_bounds__(GAE_LANES) void rollout_gae_kernel(Roll B, const fl
 }
 
 // ----------------------------------------------------------------------------------------------------------- gather
+// The index phase of both gathers, one lane per sample: position `k` of the epoch (on the lanes with `mine`; the others ride along)
+// walks through the Feistel network until it lands below M -> the transition's flat index i = env * T + step.
+MCG_DEV uint32_t walk(bool mine, uint32_t k, uint32_t M, int h, unsigned long long seed, unsigned long long epoch) {
+  const uint32_t half = (1u << h) - 1u;
+  const uint32_t c1 = (uint32_t)epoch, c3 = (uint32_t)ROLLOUT_STREAM ^ ((uint32_t)(epoch >> 32) << 8);
+  uint32_t x = mine ? k : 0u;
+  bool need = mine;
+  do {                                   // wave-uniform, per-lane effects predicated on `need`; ends because a bijection's cycles close
+    uint32_t Lh = x >> h, Rh = x & half;
+#pragma unroll
+    for (int r = 0; r < FEISTEL_ROUNDS; r++) {
+      uint32_t w[4];
+      philox4x32_10(Rh, c1, (uint32_t)r, c3, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+      const uint32_t nr = Lh ^ (w[0] & half);
+      Lh = Rh; Rh = nr;
+    }
+    if (need) x = (Lh << h) | Rh;
+    need = need && x >= M;
+  } while (__any(need));
+  return x;
+}
+
 struct Batch { float *obs, *ach, *des, *act, *val, *logp, *adv, *ret; int32_t* index; };
 
 // one 4-byte word of a record to its place in row j of the outputs
@@ -147,24 +177,9 @@ __global__ __launch_bounds__(SAMPLE_LANES) void rollout_gather_kernel(Roll B, un
   if (j0 >= count) return;
   // ---- index phase: lane i < SPW walks position first + j0 + i through the Feistel network until it lands below M
   const uint32_t M = (uint32_t)B.n * (uint32_t)B.T;                     // < 2^31 (host check)
-  const uint32_t half = (1u << h) - 1u;
-  const uint32_t c1 = (uint32_t)epoch, c3 = (uint32_t)ROLLOUT_STREAM ^ ((uint32_t)(epoch >> 32) << 8);
   const int j = j0 + lane;
   const bool mine = lane < SPW && j < count;
-  uint32_t x = mine ? (uint32_t)first + (uint32_t)j : 0u;
-  bool need = mine;
-  do {                                   // wave-uniform, per-lane effects predicated on `need`; ends because a bijection's cycles close
-    uint32_t Lh = x >> h, Rh = x & half;
-#pragma unroll
-    for (int r = 0; r < FEISTEL_ROUNDS; r++) {
-      uint32_t w[4];
-      philox4x32_10(Rh, c1, (uint32_t)r, c3, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-      const uint32_t nr = Lh ^ (w[0] & half);
-      Lh = Rh; Rh = nr;
-    }
-    if (need) x = (Lh << h) | Rh;
-    need = need && x >= M;
-  } while (__any(need));
+  const uint32_t x = walk(mine, (uint32_t)first + (uint32_t)j, M, h, seed, epoch);
   const int src = (int)((size_t)(x % (uint32_t)B.T) * B.n + x / (uint32_t)B.T);      // row of i = e * T + t in the [T, N] planes; < M
   if (mine) {                            // the three plane words of a sample: scattered 4-byte loads
     const float v = B.val[src], a = B.adv[src], g = B.ret[src];
@@ -206,6 +221,235 @@ Roll view(const mcg_rollout_buf* b) {
   B.g32 = (float)b->gamma; B.c32 = (float)(b->gamma * b->gae_lambda);
   B.L = layout(b->obs_dim, b->act_dim);
   return B;
+}
+
+
+// ================================================================================================ the picture buffer
+// mcg_rollout_img_*: the planes, the recursion and the permutation are the ones above (plane_row, rollout_gae_kernel, walk); what is
+// new is data movement, and every kernel here is judged by bytes per second.  A picture is X.P bytes (a multiple of 16) in `pixels`,
+// so every access to `pixels` is one aligned 16-byte word per lane, 1 KiB contiguous per wave instruction.
+constexpr int IMG_FLIGHT = 8;           // loads a lane of the gather issues before its first store
+
+struct Pix {                            // the pixel plane and the record of mcg_rollout_img_buf as the kernels see them
+  uint8_t* px;
+  int Pu, P, SS;                        // bytes of a picture, of its padded row, of one channel
+  int A, rw;                            // action words and words of a record (padded: a multiple of 4)
+};
+struct Src { const uint8_t* img; long long es, cs; };      // a picture as the caller holds it: base, environment and channel stride in bytes
+
+// Bytes b .. b + 15 (b a multiple of 16) of environment e's picture, channel-major; bytes from Pu on are zeros.  W is the width of a
+// load: it divides the base address, both strides and S * S (the host's choice), so no load is misaligned or straddles two channels.
+template <int W>
+MCG_DEV uint4 load_chunk(const Pix& X, const Src& S, int e, int b) {
+  const uint8_t* base = S.img + (long long)e * S.es;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if constexpr (W == 16) {
+    if (b >= X.Pu) return make_uint4(0u, 0u, 0u, 0u);
+    const int c = b / X.SS;
+    return *reinterpret_cast<const uint4*>(base + (long long)c * S.cs + (b - c * X.SS));
+  } else if constexpr (W == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int bb = b + 4 * k, c = bb / X.SS;
+      if (bb < X.Pu) w[k] = *reinterpret_cast<const uint32_t*>(base + (long long)c * S.cs + (bb - c * X.SS));
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const int bb = b + k, c = bb / X.SS;
+      if (bb < X.Pu) w[k >> 2] |= (uint32_t)base[(long long)c * S.cs + (bb - c * X.SS)] << (8 * (k & 3));
+    }
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// Lane = 16 bytes of row `row` of pixels, environments neighbours: the grid writes one contiguous run.  One more lane per
+// environment, after the pixels, sets last_start.
+template <int W>
+__global__ __launch_bounds__(ADD_LANES) void img_start_kernel(Roll B, Pix X, int row, Src S, const uint8_t* __restrict__ mask) {
+  const int c16 = X.P >> 4;
+  const long long x = (long long)blockIdx.x * ADD_LANES + threadIdx.x, npix = (long long)B.n * c16;
+  if (x >= npix + B.n) return;
+  const int e = x < npix ? (int)(x / c16) : (int)(x - npix);
+  if (mask && mask[e] == 0) return;
+  if (x < npix) {
+    const int q = (int)(x % c16);
+    reinterpret_cast<uint4*>(X.px + ((size_t)row * B.n + e) * X.P)[q] = load_chunk<W>(X, S, e, q * 16);
+  } else {
+    B.last_start[e] = 1;
+  }
+}
+
+// The same run into row pos + 1; after the pixels, per environment, one lane per 16 bytes of its record and one for its plane row.
+template <int W>
+__global__ __launch_bounds__(ADD_LANES) void img_add_kernel(Roll B, Pix X, int pos, Src S, const float* __restrict__ actions,
+                                                            const float* __restrict__ values, const float* __restrict__ log_probs,
+                                                            const float* __restrict__ final_values, const double* __restrict__ reward,
+                                                            const uint8_t* __restrict__ terminated, const uint8_t* __restrict__ truncated) {
+  const int c16 = X.P >> 4, r16 = X.rw >> 2;
+  const long long x = (long long)blockIdx.x * ADD_LANES + threadIdx.x, npix = (long long)B.n * c16;
+  if (x < npix) {
+    const int e = (int)(x / c16), q = (int)(x % c16);
+    reinterpret_cast<uint4*>(X.px + ((size_t)(pos + 1) * B.n + e) * X.P)[q] = load_chunk<W>(X, S, e, q * 16);
+    return;
+  }
+  const long long y = x - npix;
+  if (y >= (long long)B.n * (r16 + 1)) return;
+  const int e = (int)(y / (r16 + 1)), q = (int)(y % (r16 + 1));
+  const size_t at = (size_t)pos * B.n + e;
+  if (q == r16) {
+    plane_row(B, at, e, values, final_values, reward, terminated, truncated);
+    return;
+  }
+  uint32_t w[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {          // action[A], log_prob, zeros
+    const int i = 4 * q + k;
+    w[k] = i < X.A ? __float_as_uint(actions[(size_t)e * X.A + i]) : i == X.A ? __float_as_uint(log_probs[e]) : 0u;
+  }
+  reinterpret_cast<uint4*>(B.rec)[at * r16 + q] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// Row `row` (> 0) of pixels to row 0: lane = 16 bytes.
+__global__ __launch_bounds__(ADD_LANES) void img_carry_kernel(Roll B, Pix X, int row) {
+  const long long x = (long long)blockIdx.x * ADD_LANES + threadIdx.x, n16 = (long long)B.n * (X.P >> 4);
+  if (x >= n16) return;
+  uint4* to = reinterpret_cast<uint4*>(X.px);
+  to[x] = to[(size_t)row * n16 + x];
+}
+
+struct ImgBatch { uint8_t* pix; float *pix_f32, *act, *val, *logp, *adv, *ret; int32_t* index; };
+
+// A copy loop of the gather: the wave's sample has `per` units (a unit: what one lane loads at once), lane = unit, so a wave instruction
+// covers 64 consecutive units.  A lane issues IMG_FLIGHT loads before its first store.
+//   load(q)      unit q of the sample's picture
+//   emit(q, v)   to its place in the sample's row of the output
+template <class V, class Load, class Emit>
+MCG_DEV void each_unit(int lane, int per, Load load, Emit emit) {
+  for (int q0 = 0; q0 < per; q0 += 64 * IMG_FLIGHT) {
+    V v[IMG_FLIGHT];
+#pragma unroll
+    for (int u = 0; u < IMG_FLIGHT; u++)
+      if (q0 + 64 * u + lane < per) v[u] = load(q0 + 64 * u + lane);
+#pragma unroll
+    for (int u = 0; u < IMG_FLIGHT; u++)
+      if (q0 + 64 * u + lane < per) emit(q0 + 64 * u + lane, v[u]);
+  }
+}
+
+// One sample per wave, four per block: a minibatch of 4096 is 4096 waves, four on every SIMD of the chip, each with its sample's
+// 4 KB or more in flight (measured against 2 and 4 samples per wave, which share a walk but leave the chip a half or a quarter as many
+// waves to hide the loads behind: DESIGN.md section 13).  The index phase is rollout_gather_kernel's with every lane of the wave on
+// the wave's one sample, so the picture's row needs no broadcast.
+// ALIGN: what divides Pu and the output pointers (the host's choice): 16 -- the u8 rows are stored as 16-byte words, 4 -- as 4-byte
+// words, 1 -- as bytes; the normalised picture is one float4 per lane from 4 source bytes (ALIGN >= 4: a wave's store instruction
+// covers 1 KiB contiguous) or one float per lane.
+template <int ALIGN>
+__global__ __launch_bounds__(SAMPLE_LANES) void img_gather_kernel(Roll B, Pix X, unsigned long long seed, unsigned long long epoch,
+                                                                  int first, int count, int h, ImgBatch O) {
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * (SAMPLE_LANES / 64) + (threadIdx.x >> 6);   // wave-uniform; the output row of this wave
+  if (j >= count) return;
+  // ---- index phase
+  const uint32_t M = (uint32_t)B.n * (uint32_t)B.T;                     // < 2^31 (host check)
+  const uint32_t x = walk(true, (uint32_t)first + (uint32_t)j, M, h, seed, epoch);
+  const size_t src = (size_t)(x % (uint32_t)B.T) * B.n + x / (uint32_t)B.T;          // row in the [T, N] planes; < M
+  if (lane == 0) {                       // the sample's plane words
+    const float v = B.val[src], a = B.adv[src], g = B.ret[src];
+    if (O.val) O.val[j] = v;
+    if (O.adv) O.adv[j] = a;
+    if (O.ret) O.ret[j] = g;
+    if (O.index) O.index[j] = (int32_t)x;
+  }
+  const uint32_t* rec = B.rec + src * X.rw;          // and its record: action[A], log_prob
+  if (O.act)
+    for (int w = lane; w < X.A; w += 64) O.act[(size_t)j * X.A + w] = __uint_as_float(rec[w]);
+  if (O.logp && lane == 0) O.logp[j] = __uint_as_float(rec[X.A]);
+  // ---- copy phase
+  const uint8_t* from = X.px + src * X.P;
+  if (O.pix) {
+    uint8_t* row = O.pix + (size_t)j * X.Pu;
+    each_unit<uint4>(lane, X.P >> 4,
+      [&](int q) { return reinterpret_cast<const uint4*>(from)[q]; },
+      [&](int q, uint4 v) {
+        uint8_t* to = row + 16 * q;
+        if constexpr (ALIGN == 16) {
+          *reinterpret_cast<uint4*>(to) = v;
+        } else if constexpr (ALIGN == 4) {
+          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            if (16 * q + 4 * k < X.Pu) reinterpret_cast<uint32_t*>(to)[k] = w[k];
+        } else {
+          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int k = 0; k < 16; k++)
+            if (16 * q + k < X.Pu) to[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+        }
+      });
+  }
+  if (O.pix_f32) {                       // byte / 255: the correctly rounded float32 quotient (IEEE division, nothing reciprocal)
+    float* row = O.pix_f32 + (size_t)j * X.Pu;
+    if constexpr (ALIGN >= 4) {
+      each_unit<uint32_t>(lane, X.Pu >> 2,
+        [&](int q) { return reinterpret_cast<const uint32_t*>(from)[q]; },
+        [&](int q, uint32_t v) {
+          reinterpret_cast<float4*>(row)[q] = make_float4((float)(v & 255u) / 255.0f, (float)((v >> 8) & 255u) / 255.0f,
+                                                          (float)((v >> 16) & 255u) / 255.0f, (float)(v >> 24) / 255.0f);
+        });
+    } else {
+      each_unit<uint8_t>(lane, X.Pu, [&](int q) { return from[q]; }, [&](int q, uint8_t v) { row[q] = (float)v / 255.0f; });
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------- host side, pictures
+int check_img(const mcg_rollout_img_buf* b, const char* who) {
+  if (!b) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_rollout_img_buf", who);
+  if (!b->pixels || !b->records || !b->reward || !b->value || !b->episode_start || !b->advantage || !b->returns || !b->last_start)
+    return mcg_fail(MCG_ERR_ARG, "%s: null pointer in mcg_rollout_img_buf", who);
+  if (b->n_envs < 1 || b->channels < 1 || b->size < 1 || b->act_dim < 1 || b->n_steps < 1)
+    return mcg_fail(MCG_ERR_ARG, "%s: n_envs, channels, size, act_dim and n_steps must be >= 1", who);
+  if (b->channels > 8) return mcg_fail(MCG_ERR_ARG, "%s: channels must be <= 8", who);
+  if (b->size > 512) return mcg_fail(MCG_ERR_ARG, "%s: size must be <= 512", who);
+  if ((long long)b->n_steps * b->n_envs >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: n_steps * n_envs must be below 2^31", who);
+  if (((uintptr_t)b->pixels & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: pixels is not 16-byte aligned", who);
+  if (((uintptr_t)b->records & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: records is not 16-byte aligned", who);
+  if (!std::isfinite(b->gamma) || !std::isfinite(b->gae_lambda) || b->gamma < 0.0 || b->gamma > 1.0 || b->gae_lambda < 0.0 ||
+      b->gae_lambda > 1.0)
+    return mcg_fail(MCG_ERR_ARG, "%s: gamma and gae_lambda must be finite and in [0, 1]", who);
+  return MCG_OK;
+}
+
+int check_src(const mcg_rollout_img_buf* b, const uint8_t* img, int64_t env_stride, int64_t chan_stride, const char* who) {
+  if (!img) return mcg_fail(MCG_ERR_ARG, "%s: null img", who);
+  if (env_stride < 0 || chan_stride < 0) return mcg_fail(MCG_ERR_ARG, "%s: a stride is negative", who);
+  if (b->channels > 1 && chan_stride < (int64_t)b->size * b->size)
+    return mcg_fail(MCG_ERR_ARG, "%s: chan_stride is below size * size", who);
+  return MCG_OK;
+}
+
+// the widest load that the picture's base, strides and channel size allow
+int load_width(const mcg_rollout_img_buf* b, const uint8_t* img, int64_t env_stride, int64_t chan_stride) {
+  const uint64_t all = (uint64_t)(uintptr_t)img | (uint64_t)env_stride | (b->channels > 1 ? (uint64_t)chan_stride : 0u) |
+                       (uint64_t)((int64_t)b->size * b->size);
+  return (all & 15) == 0 ? 16 : (all & 3) == 0 ? 4 : 1;
+}
+
+Roll planes(const mcg_rollout_img_buf* b) {
+  Roll B = {};
+  B.rec = static_cast<uint32_t*>(b->records); B.rew = b->reward; B.val = b->value; B.adv = b->advantage; B.ret = b->returns;
+  B.start = b->episode_start; B.last_start = b->last_start;
+  B.n = b->n_envs; B.T = b->n_steps;
+  B.g32 = (float)b->gamma; B.c32 = (float)(b->gamma * b->gae_lambda);
+  return B;
+}
+
+Pix pixels(const mcg_rollout_img_buf* b) {
+  Pix X;
+  X.px = b->pixels; X.SS = b->size * b->size; X.Pu = b->channels * X.SS; X.P = (X.Pu + 15) / 16 * 16;      // Pu <= 8 * 512 * 512
+  X.A = b->act_dim; X.rw = padded_words(b->act_dim + 1);
+  return X;
 }
 
 }  // namespace
@@ -272,6 +516,102 @@ int mcg_rollout_gather(const mcg_rollout_buf* buf, uint64_t seed, uint64_t epoch
   hipLaunchKernelGGL(rollout_gather_kernel, dim3(blocks(count, SAMPLES_PER_BLOCK)), dim3(SAMPLE_LANES), 0,
                      (hipStream_t)stream, B, (unsigned long long)seed, (unsigned long long)epoch, (int)first, (int)count, b / 2, O);
   return launched("mcg_rollout");
+}
+
+int64_t mcg_rollout_img_record_bytes(int act_dim) { return act_dim < 1 ? 0 : (int64_t)padded_words(act_dim + 1) * 4; }
+
+int mcg_rollout_img_start(const mcg_rollout_img_buf* buf, int pos, const uint8_t* img, int64_t env_stride, int64_t chan_stride,
+                          const uint8_t* mask, void* stream) {
+  if (const int rc = check_img(buf, "mcg_rollout_img_start")) return rc;
+  if (pos < 0 || pos > buf->n_steps) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_start: pos outside [0, n_steps]");
+  if (const int rc = check_src(buf, img, env_stride, chan_stride, "mcg_rollout_img_start")) return rc;
+  const Roll B = planes(buf);
+  const Pix X = pixels(buf);
+  const Src S = {img, (long long)env_stride, (long long)chan_stride};
+  const dim3 grid(blocks((long long)B.n * (X.P / 16) + B.n, ADD_LANES)), block(ADD_LANES);
+  switch (load_width(buf, img, env_stride, chan_stride)) {
+    case 16: hipLaunchKernelGGL(img_start_kernel<16>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, mask); break;
+    case 4: hipLaunchKernelGGL(img_start_kernel<4>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, mask); break;
+    default: hipLaunchKernelGGL(img_start_kernel<1>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, mask);
+  }
+  return launched("mcg_rollout_img");
+}
+
+int mcg_rollout_img_add(const mcg_rollout_img_buf* buf, int pos, const float* actions, const float* values, const float* log_probs,
+                        const float* final_values, const uint8_t* img, int64_t env_stride, int64_t chan_stride, const double* reward,
+                        const uint8_t* terminated, const uint8_t* truncated, void* stream) {
+  if (const int rc = check_img(buf, "mcg_rollout_img_add")) return rc;
+  if (pos < 0 || pos >= buf->n_steps) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: pos outside [0, n_steps)");
+  if (!actions) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: null actions");
+  if (!values) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: null values");
+  if (!log_probs) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: null log_probs");
+  if (!reward || !terminated || !truncated)
+    return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: reward, terminated and truncated of the step's output are required");
+  if (const int rc = check_src(buf, img, env_stride, chan_stride, "mcg_rollout_img_add")) return rc;
+  const Roll B = planes(buf);
+  const Pix X = pixels(buf);
+  const Src S = {img, (long long)env_stride, (long long)chan_stride};
+  const dim3 grid(blocks((long long)B.n * (X.P / 16) + (long long)B.n * (X.rw / 4 + 1), ADD_LANES)), block(ADD_LANES);
+#define MCG_IMG_ADD(W) hipLaunchKernelGGL(img_add_kernel<W>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, actions, values, \
+                                          log_probs, final_values, reward, terminated, truncated)
+  switch (load_width(buf, img, env_stride, chan_stride)) {
+    case 16: MCG_IMG_ADD(16); break;
+    case 4: MCG_IMG_ADD(4); break;
+    default: MCG_IMG_ADD(1);
+  }
+#undef MCG_IMG_ADD
+  return launched("mcg_rollout_img");
+}
+
+int mcg_rollout_img_gae(const mcg_rollout_img_buf* buf, const float* last_values, void* stream) {
+  if (const int rc = check_img(buf, "mcg_rollout_img_gae")) return rc;
+  if (!last_values) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_gae: null last_values");
+  const Roll B = planes(buf);
+  hipLaunchKernelGGL(rollout_gae_kernel, dim3(blocks(B.n, GAE_LANES)), dim3(GAE_LANES), 0, (hipStream_t)stream, B, last_values);
+  return launched("mcg_rollout_img");
+}
+
+int mcg_rollout_img_carry(const mcg_rollout_img_buf* buf, int pos, void* stream) {
+  if (const int rc = check_img(buf, "mcg_rollout_img_carry")) return rc;
+  if (pos < 0 || pos > buf->n_steps) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_carry: pos outside [0, n_steps]");
+  if (pos == 0) return MCG_OK;           // the picture to continue from is in row 0 already
+  const Roll B = planes(buf);
+  const Pix X = pixels(buf);
+  hipLaunchKernelGGL(img_carry_kernel, dim3(blocks((long long)B.n * (X.P / 16), ADD_LANES)), dim3(ADD_LANES), 0, (hipStream_t)stream, B, X,
+                     pos);
+  return launched("mcg_rollout_img");
+}
+
+int mcg_rollout_img_gather(const mcg_rollout_img_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
+                           const mcg_rollout_img_batch* out, void* stream) {
+  if (const int rc = check_img(buf, "mcg_rollout_img_gather")) return rc;
+  const int64_t M = (int64_t)buf->n_steps * buf->n_envs;
+  if (first < 0) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_gather: first < 0");
+  if (count < 1) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_gather: count must be >= 1");
+  if (first > M || count > M - first) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_gather: first + count > n_steps * n_envs");
+  if (!out) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_gather: null mcg_rollout_img_batch");
+  if (!out->pix && !out->pix_f32 && !out->action && !out->old_value && !out->old_log_prob && !out->advantage && !out->returns &&
+      !out->index)
+    return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_gather: all outputs are null");
+  int b = 2;
+  while ((1ll << b) < M) b += 2;         // as mcg_rollout_gather
+  const Roll B = planes(buf);
+  const Pix X = pixels(buf);
+  const ImgBatch O = {out->pix, out->pix_f32, out->action, out->old_value, out->old_log_prob, out->advantage, out->returns, out->index};
+  // what divides the rows of both picture outputs: pix rows are Pu bytes apart, pix_f32 rows 4 Pu
+  const uint64_t all = (uint64_t)X.Pu | (uint64_t)(uintptr_t)out->pix;
+  const bool f16 = ((uintptr_t)out->pix_f32 & 15) == 0;
+  const int align = (all & 15) == 0 && f16 ? 16 : (all & 3) == 0 && f16 ? 4 : 1;
+  const dim3 grid(blocks(count, SAMPLE_LANES / 64)), block(SAMPLE_LANES);
+#define MCG_IMG_GATHER(AL) hipLaunchKernelGGL(img_gather_kernel<AL>, grid, block, 0, (hipStream_t)stream, B, X, (unsigned long long)seed, \
+                                              (unsigned long long)epoch, (int)first, (int)count, b / 2, O)
+  switch (align) {
+    case 16: MCG_IMG_GATHER(16); break;
+    case 4: MCG_IMG_GATHER(4); break;
+    default: MCG_IMG_GATHER(1);
+  }
+#undef MCG_IMG_GATHER
+  return launched("mcg_rollout_img");
 }
 
 }  // extern "C"

@@ -16,7 +16,8 @@ the engine's N lockstep environments: time-major ``[n_steps, N]`` storage, one l
 
 This file owns the device memory (PyTorch tensors) and three host integers (``pos``, ``epoch``, ``seed``); the C side keeps no state
 and no call synchronises.  No CPU or PyTorch fallback: the kernels are the only implementation.  Advantages are not normalised here
-(PPO does that per minibatch).
+(PPO does that per minibatch).  The -v1 picture ids have ``ImageRolloutBuffer`` (rollout_img.py); what the two share is
+``_OnPolicyBuffer`` below.
 """
 from __future__ import annotations
 
@@ -36,11 +37,84 @@ _PLANES = (("reward", torch.float32), ("value", torch.float32), ("episode_start"
            ("returns", torch.float32))
 
 
-class RolloutBuffer(DeviceBuffer):
+class _OnPolicyBuffer(DeviceBuffer):
+    """What ``RolloutBuffer`` and ``ImageRolloutBuffer`` share: the host state, the order of calls, the planes and their guards.  A
+    subclass sets ``_ENTRY`` (the prefix of its C entries), fills ``self._alloc`` (name -> tensor with its guard rows) and implements
+    ``start``, ``add`` and ``gather``."""
+    _HOST_STATE = ("pos", "epoch", "seed", "finished")
+
+    def _host_state(self, n_steps, gamma, gae_lambda, seed, guard_rows):
+        self.n_steps, self.gamma, self.gae_lambda = int(n_steps), float(gamma), float(gae_lambda)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.pos = 0                 # steps of the rollout in flight
+        self.epoch = 0               # get() calls so far: the `epoch` word of the permutation
+        self.finished = False        # finish() has run on the rollout in flight
+        self._guard = int(guard_rows)
+
+    def _per_env(self, x, name):
+        """float32 [N]; a trailing axis of one (a value head's [N, 1]) is dropped."""
+        t = torch.as_tensor(x, device=self.device)
+        if t.dim() == 2 and t.shape[1] == 1:
+            t = t[:, 0]
+        return self._dev(t.detach(), torch.float32, (self.num_envs,), name)
+
+    def _policy_outputs(self, actions, values, log_probs, final_values):
+        """What ``add`` takes from the policy, as the C side takes it; refuses a full buffer."""
+        if self.pos >= self.n_steps:
+            raise ValueError(f"{type(self).__name__}.add: the buffer is full ({self.n_steps} steps); finish(), get() and reset() come first")
+        a = self._dev(torch.as_tensor(actions, device=self.device).detach(), torch.float32, (self.num_envs, self.act_dim), "actions")
+        fv = None if final_values is None else self._per_env(final_values, "final_values")
+        return a, self._per_env(values, "values"), self._per_env(log_probs, "log_probs"), fv
+
+    @property
+    def full(self) -> bool:
+        return self.pos >= self.n_steps
+
+    def finish(self, last_values):
+        """Advantages and returns of the full rollout (GAE); ``last_values``: the value estimate of the current observation, float [N]."""
+        if not self.full:
+            raise ValueError(f"{type(self).__name__}.finish: the rollout has {self.pos} of {self.n_steps} steps")
+        lv = self._per_env(last_values, "last_values")
+        self._call(self._ENTRY + "_gae", _ptr(lv))
+        self.finished = True
+
+    def get(self, batch_size: Optional[int] = None, **how):
+        """One epoch: the ``n_steps * N`` transitions in a fresh random order, in minibatches of ``batch_size`` (None: one batch; the
+        last one may be short), each a ``RolloutSamples`` of device tensors from one launch.  Every call is a new epoch.  ``how``:
+        ``gather``'s keywords."""
+        if not self.full:
+            raise ValueError(f"{type(self).__name__}.get: the rollout has {self.pos} of {self.n_steps} steps")
+        if not self.finished:
+            raise ValueError(f"{type(self).__name__}.get: finish(last_values) comes first")
+        M = self.n_steps * self.num_envs
+        B = M if batch_size is None else int(batch_size)
+        if B < 1:
+            raise ValueError("batch_size must be >= 1")
+        epoch = self.epoch
+        self.epoch += 1
+        return (self.gather(epoch, first, min(B, M - first), **how) for first in range(0, M, B))
+
+    def reset(self):
+        """The next rollout starts at step 0.  The observation to continue from and its episode-start flag carry over: episodes go
+        on across rollouts."""
+        self.pos = 0
+        self.finished = False
+
+    def planes(self) -> dict:
+        """reward, value, episode_start, advantage, returns: [n_steps, N] views."""
+        return {k: self._t[k] for k, _ in _PLANES}
+
+    def guards(self) -> dict:
+        """Per allocation (the records, the five planes, and a picture buffer's pixels): the ``guard_rows`` rows before and after it."""
+        g = self._guard
+        return {k: (v[:g], v[v.shape[0] - g:]) for k, v in self._alloc.items()}
+
+
+class RolloutBuffer(_OnPolicyBuffer):
+    _ENTRY = "mcg_rollout"
     _FROM_ENVS = (("num_envs", "num_envs"), ("obs_dim", "obs_dim"), ("act_dim", "action_dim"))
     _NO_IMAGES = ("the -v1 image ids observe uint8 pictures: RolloutBuffer stores float32 state observations with their "
                   "goals; picture records are not supported")
-    _HOST_STATE = ("pos", "epoch", "seed", "finished")
 
     def __init__(self, envs=None, n_steps: int = 64, gamma: float = 0.99, gae_lambda: float = 0.95, seed: int = 0, *,
                  num_envs: Optional[int] = None, obs_dim: Optional[int] = None, act_dim: Optional[int] = None, device=None,
@@ -48,14 +122,10 @@ class RolloutBuffer(DeviceBuffer):
         """``envs``: a ``MyCobotVecEnv`` to take the dimensions and device from; or give them by keyword.  ``guard_rows``: spare rows
         allocated before and after the records and every plane, which no call may touch (``guards()``; tests)."""
         num_envs, obs_dim, act_dim = self._resolve(envs, device, dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim))
-        self.num_envs, self.obs_dim, self.act_dim, self.n_steps = int(num_envs), int(obs_dim), int(act_dim), int(n_steps)
-        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.pos = 0                 # steps of the rollout in flight
-        self.epoch = 0               # get() calls so far: the `epoch` word of the permutation
-        self.finished = False        # finish() has run on the rollout in flight
+        self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
+        self._host_state(n_steps, gamma, gae_lambda, seed, guard_rows)
         self.record_bytes = int(self._lib.mcg_rollout_record_bytes(self.obs_dim, self.act_dim))
-        self._guard = g = int(guard_rows)
+        g = self._guard
         n, D, T, dev = max(self.num_envs, 1), max(self.obs_dim, 1), max(self.n_steps, 1), self.device
         # (a refused shape still gets small tensors: the C side refuses it with its own message at the first call)
         self._alloc = {"records": torch.zeros(T + 2 * g, n, max(self.record_bytes, 16), dtype=torch.uint8, device=dev)}
@@ -66,14 +136,6 @@ class RolloutBuffer(DeviceBuffer):
                        last_start=torch.zeros(n, dtype=torch.uint8, device=dev))
         self._cbuf = _abi.McgRolloutBuf(**{k: v.data_ptr() for k, v in self._t.items()}, n_envs=self.num_envs, obs_dim=self.obs_dim,
                                         act_dim=self.act_dim, n_steps=self.n_steps, gamma=self.gamma, gae_lambda=self.gae_lambda)
-
-    # ------------------------------------------------------------------------------------------------------ plumbing
-    def _per_env(self, x, name):
-        """float32 [N]; a trailing axis of one (a value head's [N, 1]) is dropped."""
-        t = torch.as_tensor(x, device=self.device)
-        if t.dim() == 2 and t.shape[1] == 1:
-            t = t[:, 0]
-        return self._dev(t.detach(), torch.float32, (self.num_envs,), name)
 
     # ----------------------------------------------------------------------------------------------------- insertion
     def start(self, obs, mask=None):
@@ -87,44 +149,13 @@ class RolloutBuffer(DeviceBuffer):
         """One step per environment: ``buf.add(a, v, logp, *envs.step(a))``.  ``final_values``: the value estimate of
         ``info["final_observation"]``, float [N]; where the time limit alone ended an episode, ``gamma`` times it is added to the
         reward (SB3's bootstrap); None: no bootstrap.  ``info`` itself is not read."""
-        if self.pos >= self.n_steps:
-            raise ValueError(f"RolloutBuffer.add: the buffer is full ({self.n_steps} steps); finish(), get() and reset() come first")
-        a = self._dev(torch.as_tensor(actions, device=self.device).detach(), torch.float32, (self.num_envs, self.act_dim), "actions")
-        v, lp = self._per_env(values, "values"), self._per_env(log_probs, "log_probs")
-        fv = None if final_values is None else self._per_env(final_values, "final_values")
+        a, v, lp, fv = self._policy_outputs(actions, values, log_probs, final_values)
         out, _alive = self._step_out(obs, reward, terminated, truncated)
         self._call("mcg_rollout_add", self.pos, _ptr(a), _ptr(v), _ptr(lp), _ptr(fv), C.byref(out))
         self.pos += 1
         self.finished = False
 
-    # ------------------------------------------------------------------------------------- advantages and minibatches
-    @property
-    def full(self) -> bool:
-        return self.pos >= self.n_steps
-
-    def finish(self, last_values):
-        """Advantages and returns of the full rollout (GAE); ``last_values``: the value estimate of the current observation, float [N]."""
-        if not self.full:
-            raise ValueError(f"RolloutBuffer.finish: the rollout has {self.pos} of {self.n_steps} steps")
-        lv = self._per_env(last_values, "last_values")
-        self._call("mcg_rollout_gae", _ptr(lv))
-        self.finished = True
-
-    def get(self, batch_size: Optional[int] = None):
-        """One epoch: the ``n_steps * N`` transitions in a fresh random order, in minibatches of ``batch_size`` (None: one batch; the
-        last one may be short), each a ``RolloutSamples`` of float32 device tensors from one launch.  Every call is a new epoch."""
-        if not self.full:
-            raise ValueError(f"RolloutBuffer.get: the rollout has {self.pos} of {self.n_steps} steps")
-        if not self.finished:
-            raise ValueError("RolloutBuffer.get: finish(last_values) comes first")
-        M = self.n_steps * self.num_envs
-        B = M if batch_size is None else int(batch_size)
-        if B < 1:
-            raise ValueError("batch_size must be >= 1")
-        epoch = self.epoch
-        self.epoch += 1
-        return (self.gather(epoch, first, min(B, M - first)) for first in range(0, M, B))
-
+    # ---------------------------------------------------------------------------------------------------- minibatches
     def gather(self, epoch: int, first: int, count: int) -> RolloutSamples:
         """Samples ``first .. first + count - 1`` of epoch ``epoch``'s permutation (what ``get`` yields, one minibatch at a time)."""
         D, A, dev = self.obs_dim, self.act_dim, self.device
@@ -139,19 +170,3 @@ class RolloutBuffer(DeviceBuffer):
         return RolloutSamples(observations={"observation": t["obs"], "achieved_goal": t["achieved"], "desired_goal": t["desired"]},
                               actions=t["action"], old_values=t["old_value"], old_log_prob=t["old_log_prob"],
                               advantages=t["advantage"], returns=t["returns"], index=t["index"])
-
-    def reset(self):
-        """The next rollout starts at step 0.  The observation to continue from and its episode-start flag carry over: episodes go
-        on across rollouts."""
-        self.pos = 0
-        self.finished = False
-
-    # ------------------------------------------------------------------------------------------------------- storage
-    def planes(self) -> dict:
-        """reward, value, episode_start, advantage, returns: [n_steps, N] views."""
-        return {k: self._t[k] for k, _ in _PLANES}
-
-    def guards(self) -> dict:
-        """Per allocation (records and the five planes): the ``guard_rows`` rows before and after it."""
-        g, T = self._guard, max(self.n_steps, 1)
-        return {k: (v[:g], v[g + T:]) for k, v in self._alloc.items()}

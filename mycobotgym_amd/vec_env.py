@@ -568,6 +568,11 @@ class MyCobotImgVecEnv(MyCobotVecEnv):
             self._vr_tables = [torch.as_tensor(_abi.scene_row(self._scene(cam, scene)[0]), device=self.device).repeat(self.num_envs, 1).contiguous()
                                for cam in self._cameras]
 
+    @property
+    def channels(self) -> int:
+        """Channels of the observation: one per camera."""
+        return len(self._cameras)
+
     def _redraw_scenes(self, mask: Optional[torch.Tensor] = None):
         """The scene tables of the current episodes (where ``mask`` is set)."""
         if self._vr_tables is None:
