@@ -20,6 +20,8 @@
  *                       gamma, gae_lambda)   scripts/train.py:99-101
  *   mcg_rollout_img_start / _add / _gae / _carry / _gather   the same RolloutBuffer on the uint8 pictures MyCobotImgEnv observes
  *                       (PPO / A2C on the -v1 ids)   scripts/train.py:99-101, mycobot.py:517-545
+ *   mcg_replay_img_start / _add / _sample   SB3's ReplayBuffer as SAC / TD3 / DDPG use it (scripts/train.py:62, 102-104) on the same
+ *                       pictures, every picture stored once and a time-limit end kept apart from a termination
  *   mcg_get_state / mcg_set_state   direct access to data.qpos/qvel/ctrl/qacc_warmstart (set_joint_qpos etc.)
  *
  * Conventions: every pointer in the step/reset/state calls is DEVICE memory owned by the caller;
@@ -548,6 +550,80 @@ int mcg_rollout_img_carry(const mcg_rollout_img_buf* buf, int pos, void* stream)
    row `step`, environment env.  All byte offsets are 64-bit; no address and no loop bound depends on stored content. */
 int mcg_rollout_img_gather(const mcg_rollout_img_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
                            const mcg_rollout_img_batch* out, void* stream);
+
+/* ---- Off-policy replay buffer of pictures (SB3's ReplayBuffer, which SAC, TD3 and DDPG train from, scripts/train.py:62, 102-104, on
+   what MyCobotImgEnv observes: the uint8 picture [C, S, S] alone).  Stateless as mcg_her_* and mcg_rollout_img_*: the caller owns all
+   device memory and passes it per call.  N = n_envs, K = capacity (transitions kept per environment), R = K + 1 rows,
+   Tm = max_episode_steps, F = ceil(K / Tm) + 1 final rows; Pu, P and the way a picture is passed (base, env_stride, chan_stride; the
+   three load widths) are mcg_rollout_img_*'s.  n_written is a host integer: the absolute time a of the next transition.
+     pixels      uint8 [R, N, P]: row a % R holds the picture the action of transition a was taken from, row (a + 1) % R the picture the
+                 step returned (after an auto-reset: the next episode's first).  Every picture is stored once; the next picture of a
+                 slot is the following row.  Bytes Pu .. P - 1 of every picture that a call writes are zero.
+     finals      uint8 [F, N, P] and final_time int64 [F, N] (the caller sets every final_time to -1 before the first call): where the
+                 time limit alone ended an episode (truncated & !terminated, mcg_rollout_add's definition), the finished episode's
+                 last picture goes to row (a / Tm) % F of finals and final_time there becomes a.  The engine sets `truncated` by the
+                 time limit at elapsed >= Tm only and every reset zeroes elapsed, so two time-limit ends of one environment are at
+                 least Tm steps apart and their a / Tm differ; the K newest transitions span at most ceil(K / Tm) + 1 values of
+                 a / Tm: no final picture of a stored transition is overwritten.  A caller who breaks this (set_state(elapsed=...))
+                 is caught by the stamp, not by a wrong picture.
+     records     one per (row, env), mcg_replay_img_record_bytes(A) bytes: float action[A], float reward (the step's float64 rounded
+                 to nearest even), uint32 flags, zeros to a multiple of 16.  Flags: 1 TERMINATED, 2 TIMEOUT (truncated &
+                 !terminated), 4 NO_NEXT (a start in mid-episode overwrote the next picture: never sampled).
+     counters    uint64 [2]: samples that gave up; timeout samples whose final picture had been overwritten. */
+typedef struct mcg_replay_img_buf {   /* device pointers the caller owns (all required), and the buffer's shape */
+  uint8_t* pixels;                  /* [K + 1, N, P]; 16-byte aligned */
+  uint8_t* finals;                  /* [F, N, P]; 16-byte aligned */
+  int64_t* final_time;              /* [F, N]; -1 before the first call */
+  void* records;                    /* [K + 1, N] records; 16-byte aligned */
+  uint64_t* counters;               /* [2] */
+  int32_t n_envs, channels, size, act_dim, capacity, max_episode_steps;      /* channels <= 8, size <= 512 */
+} mcg_replay_img_buf;
+
+typedef struct mcg_replay_img_batch { /* outputs of mcg_replay_img_sample; device pointers, any may be NULL (not all).  B = batch */
+  uint8_t* pix;          /* [B, Pu]  the picture the action was taken from, as stored (no padding between rows) */
+  uint8_t* next_pix;     /* [B, Pu]  the picture the step led to */
+  float* pix_f32;        /* [B, Pu]  byte / 255 in float32, correctly rounded: bit for bit (float)b / 255.0f, SB3's obs.float() / 255 */
+  float* next_pix_f32;   /* [B, Pu] */
+  float* action;         /* [B, A] */
+  float* reward;         /* [B] */
+  float* done;           /* [B]     1.0 where the transition ended its episode for good (SB3's dones * (1 - timeouts)) */
+  int32_t* index;        /* [B, 3]  row, env, source of the next picture (0: pixels, 1: finals); -1, -1, -1 where the sample gave up */
+} mcg_replay_img_batch;
+
+/* All calls enqueue on `stream` and do not synchronise.  Checked on the host before any HIP call (MCG_ERR_ARG), each with its own
+   message: a null struct or a null pointer in it; n_envs / channels / size / act_dim / capacity / max_episode_steps < 1; channels > 8;
+   size > 512; (capacity + 1) * n_envs >= 2^31; pixels, finals or records not 16-byte aligned; n_written < 0 (mcg_replay_img_sample:
+   n_written == 0, the buffer is empty); batch < 1; a null img / final_img / actions / reward / terminated / truncated; a negative
+   stride, or a channel stride below S * S while channels > 1; a null mcg_replay_img_batch or all eight outputs of a batch null. */
+int64_t mcg_replay_img_record_bytes(int act_dim);                /* 0 where act_dim < 1 */
+
+/* The environments of `mask` (NULL = all) continue from the picture a reset returned: it is written to row n_written % R.  Where
+   n_written >= 1, the record of transition n_written - 1 gets NO_NEXT unless it carries TERMINATED or TIMEOUT: a reset after an
+   episode's end loses nothing, a reset in mid-episode loses that transition's next picture, so it is never sampled. */
+int mcg_replay_img_start(const mcg_replay_img_buf* buf, int64_t n_written, const uint8_t* img, int64_t env_stride, int64_t chan_stride,
+                         const uint8_t* mask /* [N] device or NULL */, void* stream);
+
+/* Transition a = n_written of every environment, one launch; the caller then counts n_written up.  `img` is the picture the step
+   returned and goes to row (a + 1) % R; the record of row a % R takes action, (float)reward and the flags; where TIMEOUT, `final_img`
+   (the finished episode's last picture, info["final_observation"]; its own strides) goes to row (a / Tm) % F of finals and
+   final_time there becomes a.  Every pixel is read once and written once. */
+int mcg_replay_img_add(const mcg_replay_img_buf* buf, int64_t n_written, const float* actions /* [N, A] device */, const uint8_t* img,
+                       int64_t env_stride, int64_t chan_stride, const uint8_t* final_img, int64_t final_env_stride,
+                       int64_t final_chan_stride, const double* reward /* [N] */, const uint8_t* terminated /* [N] */,
+                       const uint8_t* truncated /* [N] */, void* stream);
+
+/* `batch` transitions, uniform over the W = min(n_written, K) newest of every environment that still have their next picture (SB3's
+   uniform choice over stored transitions).  Uniforms are Philox4x32-10 exactly as mcg_her_sample takes them, on stream 5: counter
+   (k, (uint32)call, draw, 5 ^ ((uint32)(call >> 32) << 8)), key `seed`.  Draw d = 0 .. 255 of sample k: j = min(W - 1, floor(u0 W)),
+   a = n_written - W + j, e = min(N - 1, floor(u1 N)); the draw is valid iff the record of (a % R, e) has no NO_NEXT; the first valid
+   draw is taken; after 256 invalid draws the sample gives up: index -1, outputs zeros, counters[0] counted.
+   The picture is row a % R.  The next picture is row (a / Tm) % F of finals where the record has TIMEOUT and final_time there == a,
+   and row (a + 1) % R of pixels otherwise.  done = 1.0 where TERMINATED, and where TIMEOUT with another stamp (counters[1] counted;
+   another episode's picture is never handed out as the successor: the transition is treated as terminal), else 0.0.  Where
+   TERMINATED, the next picture is the post-reset picture of row (a + 1) % R: its weight in a TD target is zero.
+   No address and no loop bound depends on stored content beyond the two flag tests and the stamp compare; all byte offsets are 64-bit. */
+int mcg_replay_img_sample(const mcg_replay_img_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch,
+                          const mcg_replay_img_batch* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ package does not need a GPU, constructing an environment does.
 """
 from .registry import REGISTRY, spec  # noqa: F401
 from .replay import HerBuffer, HerSamples  # noqa: F401
+from .replay_img import ImageReplayBuffer, ReplaySamples  # noqa: F401
 from .rollout import RolloutBuffer, RolloutSamples  # noqa: F401
 from .rollout_img import ImageRolloutBuffer  # noqa: F401
 from .vec_env import MyCobotImgVecEnv, MyCobotVecEnv, env_class, load_scene, make, validate_scenes  # noqa: F401

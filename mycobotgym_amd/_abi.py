@@ -259,6 +259,26 @@ def rollout_img_record_dtype(act_dim: int) -> np.dtype:
     return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
 
 
+class McgReplayImgBuf(C.Structure):
+    """The picture replay buffer's device memory and shape (include/mcg.h: mcg_replay_img_buf); the caller owns every pointer."""
+    _fields_ = ([(n, C.c_void_p) for n in ("pixels", "finals", "final_time", "records", "counters")]
+                + [(n, C.c_int32) for n in ("n_envs", "channels", "size", "act_dim", "capacity", "max_episode_steps")])
+
+
+class McgReplayImgBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pix", "next_pix", "pix_f32", "next_pix_f32", "action", "reward", "done", "index")]
+
+
+REPLAY_IMG_TERMINATED, REPLAY_IMG_TIMEOUT, REPLAY_IMG_NO_NEXT = 1, 2, 4      # a record's flags
+
+
+def replay_img_record_dtype(act_dim: int) -> np.dtype:
+    """One record of the picture replay buffer as a numpy structured dtype (include/mcg.h: the layout above mcg_replay_img_buf)."""
+    fields = [("action", "<f4", (act_dim,)), ("reward", "<f4"), ("flags", "<u4")]
+    used = np.dtype(fields).itemsize
+    return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -268,7 +288,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_her_record_bytes", "mcg_her_start", "mcg_her_add", "mcg_her_sample",
            "mcg_rollout_record_bytes", "mcg_rollout_start", "mcg_rollout_add", "mcg_rollout_gae", "mcg_rollout_gather",
            "mcg_rollout_img_record_bytes", "mcg_rollout_img_start", "mcg_rollout_img_add", "mcg_rollout_img_gae", "mcg_rollout_img_carry",
-           "mcg_rollout_img_gather")
+           "mcg_rollout_img_gather",
+           "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample")
 
 _lib = None
 
@@ -340,6 +361,13 @@ def load():
         L.mcg_rollout_img_gae.argtypes = [img, C.c_void_p, C.c_void_p]
         L.mcg_rollout_img_carry.argtypes = [img, C.c_int, C.c_void_p]
         L.mcg_rollout_img_gather.argtypes = [img, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(McgRolloutImgBatch), C.c_void_p]
+    if hasattr(L, "mcg_replay_img_sample"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        rimg = C.POINTER(McgReplayImgBuf)
+        L.mcg_replay_img_record_bytes.argtypes = [C.c_int]; L.mcg_replay_img_record_bytes.restype = C.c_int64
+        L.mcg_replay_img_start.argtypes = [rimg, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcg_replay_img_add.argtypes = [rimg, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcg_replay_img_sample.argtypes = [rimg, C.c_int64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(McgReplayImgBatch), C.c_void_p]
     _lib = L
     return L
 

@@ -1,4 +1,4 @@
-"""What ``HerBuffer`` (replay.py) and ``RolloutBuffer`` (rollout.py) share: a buffer whose memory is PyTorch tensors on one AMD GPU and
+"""What ``HerBuffer`` (replay.py), ``RolloutBuffer`` (rollout.py) and the two buffers of pictures (rollout_img.py, replay_img.py) share: a buffer whose memory is PyTorch tensors on one AMD GPU and
 whose every operation is one call of a stateless C entry that takes the buffer's struct first and the current stream last."""
 from __future__ import annotations
 
@@ -58,6 +58,20 @@ class DeviceBuffer:
             raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
 
+    def _picture(self, img, name):
+        """uint8 [N, C, S, S] whose [S, S] planes are contiguous -> (the tensor, its environment and channel strides in bytes).  The
+        environment's own layout (the [N, C, S, S] view of a [C, N, S, S] buffer) and a contiguous tensor pass without a copy.  (A
+        buffer of pictures: it keeps ``channels`` and ``image_size``.)"""
+        t = torch.as_tensor(img, device=self.device)
+        shape = (self.num_envs, self.channels, self.image_size, self.image_size)
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{name}: expected uint8 pictures, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+        if not t[0, 0].is_contiguous() or (self.channels > 1 and t.stride(1) < self.image_size ** 2):
+            t = t.contiguous()
+        return t, t.stride(0), t.stride(1)
+
     def _goal_obs(self, obs, name):
         n, D = self.num_envs, self.obs_dim
         return (self._dev(obs["observation"], torch.float64, (n, D), name + "['observation']"),
@@ -77,8 +91,9 @@ class DeviceBuffer:
 
     # ------------------------------------------------------------------------------------------- storage, checkpoints
     def records(self) -> torch.Tensor:
-        """The records, uint8 [capacity or n_steps, N, record_bytes] (a view; ``_abi.her_record_dtype``, ``_abi.rollout_record_dtype``
-        or ``_abi.rollout_img_record_dtype`` names the fields of a record)."""
+        """The records, uint8 [capacity or n_steps, N, record_bytes] (a view; ``_abi.her_record_dtype``, ``_abi.rollout_record_dtype``,
+        ``_abi.rollout_img_record_dtype`` or ``_abi.replay_img_record_dtype`` names the fields of a record; ``ImageReplayBuffer``:
+        capacity + 1 rows)."""
         return self._t["records"]
 
     def state_dict(self) -> dict:

@@ -11,7 +11,8 @@ ROOT = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, "csrc", "mcg_hip.hip")
 SRC_RENDER = os.path.join(_HERE, "csrc", "mcg_render.hip")      # the ray caster: a code object of its own (see the file)
 SRC_REPLAY = os.path.join(_HERE, "csrc", "mcg_replay.hip")      # the hindsight replay buffer: likewise
-SRC_ROLLOUT = os.path.join(_HERE, "csrc", "mcg_rollout.hip")    # the on-policy rollout buffer: likewise
+SRC_ROLLOUT = os.path.join(_HERE, "csrc", "mcg_rollout.hip")    # the on-policy rollout buffers: likewise
+SRC_REPLAY_IMG = os.path.join(_HERE, "csrc", "mcg_replay_img.hip")      # the off-policy replay buffer of pictures: likewise
 DEPS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*"))) + [os.path.join(ROOT, "include", "mcg.h")]      # every source and header
 OUT = os.path.join(_HERE, "libmycobot_hip.so")
 
@@ -37,7 +38,8 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     if not force and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in DEPS):
         return OUT
     cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-shared",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(_HERE, "csrc"), SRC, SRC_RENDER, SRC_REPLAY, SRC_ROLLOUT, "-o", OUT]
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(_HERE, "csrc"), SRC, SRC_RENDER, SRC_REPLAY, SRC_ROLLOUT, SRC_REPLAY_IMG,
+           "-o", OUT]
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -1,4 +1,4 @@
-// mcg_buffer.hpp -- what mcg_replay.hip and mcg_rollout.hip share: the launch check, the size of a record, the carry of the last
+// mcg_buffer.hpp -- what mcg_replay.hip, mcg_rollout.hip and mcg_replay_img.hip share: the launch check, the size of a record, the carry of the last
 // observation, and the copy phase of the two kernels that hand out samples.  Each file's own rule stays in that file.
 #pragma once
 
@@ -15,7 +15,7 @@ constexpr int SAMPLES_PER_BLOCK = SPW * (SAMPLE_LANES / 64);
 
 inline unsigned blocks(long long total, int per_block) { return (unsigned)((total + per_block - 1) / per_block); }
 
-// `what`: "mcg_her" or "mcg_rollout"
+// `what`: "mcg_her", "mcg_rollout", "mcg_rollout_img" or "mcg_replay_img"
 inline int launched(const char* what) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MCG_OK : mcg_fail(MCG_ERR_HIP, "%s kernel launch: %s", what, hipGetErrorString(e));

@@ -13,6 +13,7 @@
 
 #include "mcg.h"
 #include "mcg_buffer.hpp"        // what the replay buffer has too: launched, record_bytes, carry, copy_phase; philox4x32_10
+#include "mcg_pixels.hpp"        // what the picture replay buffer has too: Pix, Src, load_chunk, each_unit, the output rows' stores
 
 using namespace mcg;
 
@@ -227,42 +228,7 @@ Roll view(const mcg_rollout_buf* b) {
 // ================================================================================================ the picture buffer
 // mcg_rollout_img_*: the planes, the recursion and the permutation are the ones above (plane_row, rollout_gae_kernel, walk); what is
 // new is data movement, and every kernel here is judged by bytes per second.  A picture is X.P bytes (a multiple of 16) in `pixels`,
-// so every access to `pixels` is one aligned 16-byte word per lane, 1 KiB contiguous per wave instruction.
-constexpr int IMG_FLIGHT = 8;           // loads a lane of the gather issues before its first store
-
-struct Pix {                            // the pixel plane and the record of mcg_rollout_img_buf as the kernels see them
-  uint8_t* px;
-  int Pu, P, SS;                        // bytes of a picture, of its padded row, of one channel
-  int A, rw;                            // action words and words of a record (padded: a multiple of 4)
-};
-struct Src { const uint8_t* img; long long es, cs; };      // a picture as the caller holds it: base, environment and channel stride in bytes
-
-// Bytes b .. b + 15 (b a multiple of 16) of environment e's picture, channel-major; bytes from Pu on are zeros.  W is the width of a
-// load: it divides the base address, both strides and S * S (the host's choice), so no load is misaligned or straddles two channels.
-template <int W>
-MCG_DEV uint4 load_chunk(const Pix& X, const Src& S, int e, int b) {
-  const uint8_t* base = S.img + (long long)e * S.es;
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-  if constexpr (W == 16) {
-    if (b >= X.Pu) return make_uint4(0u, 0u, 0u, 0u);
-    const int c = b / X.SS;
-    return *reinterpret_cast<const uint4*>(base + (long long)c * S.cs + (b - c * X.SS));
-  } else if constexpr (W == 4) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int bb = b + 4 * k, c = bb / X.SS;
-      if (bb < X.Pu) w[k] = *reinterpret_cast<const uint32_t*>(base + (long long)c * S.cs + (bb - c * X.SS));
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const int bb = b + k, c = bb / X.SS;
-      if (bb < X.Pu) w[k >> 2] |= (uint32_t)base[(long long)c * S.cs + (bb - c * X.SS)] << (8 * (k & 3));
-    }
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
+// so every access to `pixels` is one aligned 16-byte word per lane, 1 KiB contiguous per wave instruction (mcg_pixels.hpp).
 // Lane = 16 bytes of row `row` of pixels, environments neighbours: the grid writes one contiguous run.  One more lane per
 // environment, after the pixels, sets last_start.
 template <int W>
@@ -320,23 +286,6 @@ __global__ __launch_bounds__(ADD_LANES) void img_carry_kernel(Roll B, Pix X, int
 
 struct ImgBatch { uint8_t* pix; float *pix_f32, *act, *val, *logp, *adv, *ret; int32_t* index; };
 
-// A copy loop of the gather: the wave's sample has `per` units (a unit: what one lane loads at once), lane = unit, so a wave instruction
-// covers 64 consecutive units.  A lane issues IMG_FLIGHT loads before its first store.
-//   load(q)      unit q of the sample's picture
-//   emit(q, v)   to its place in the sample's row of the output
-template <class V, class Load, class Emit>
-MCG_DEV void each_unit(int lane, int per, Load load, Emit emit) {
-  for (int q0 = 0; q0 < per; q0 += 64 * IMG_FLIGHT) {
-    V v[IMG_FLIGHT];
-#pragma unroll
-    for (int u = 0; u < IMG_FLIGHT; u++)
-      if (q0 + 64 * u + lane < per) v[u] = load(q0 + 64 * u + lane);
-#pragma unroll
-    for (int u = 0; u < IMG_FLIGHT; u++)
-      if (q0 + 64 * u + lane < per) emit(q0 + 64 * u + lane, v[u]);
-  }
-}
-
 // One sample per wave, four per block: a minibatch of 4096 is 4096 waves, four on every SIMD of the chip, each with its sample's
 // 4 KB or more in flight (measured against 2 and 4 samples per wave, which share a walk but leave the chip a half or a quarter as many
 // waves to hide the loads behind: DESIGN.md section 13).  The index phase is rollout_gather_kernel's with every lane of the wave on
@@ -371,32 +320,14 @@ __global__ __launch_bounds__(SAMPLE_LANES) void img_gather_kernel(Roll B, Pix X,
     uint8_t* row = O.pix + (size_t)j * X.Pu;
     each_unit<uint4>(lane, X.P >> 4,
       [&](int q) { return reinterpret_cast<const uint4*>(from)[q]; },
-      [&](int q, uint4 v) {
-        uint8_t* to = row + 16 * q;
-        if constexpr (ALIGN == 16) {
-          *reinterpret_cast<uint4*>(to) = v;
-        } else if constexpr (ALIGN == 4) {
-          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            if (16 * q + 4 * k < X.Pu) reinterpret_cast<uint32_t*>(to)[k] = w[k];
-        } else {
-          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int k = 0; k < 16; k++)
-            if (16 * q + k < X.Pu) to[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-        }
-      });
+      [&](int q, uint4 v) { store_u8<ALIGN>(row, X.Pu, q, v); });
   }
   if (O.pix_f32) {                       // byte / 255: the correctly rounded float32 quotient (IEEE division, nothing reciprocal)
     float* row = O.pix_f32 + (size_t)j * X.Pu;
     if constexpr (ALIGN >= 4) {
       each_unit<uint32_t>(lane, X.Pu >> 2,
         [&](int q) { return reinterpret_cast<const uint32_t*>(from)[q]; },
-        [&](int q, uint32_t v) {
-          reinterpret_cast<float4*>(row)[q] = make_float4((float)(v & 255u) / 255.0f, (float)((v >> 8) & 255u) / 255.0f,
-                                                          (float)((v >> 16) & 255u) / 255.0f, (float)(v >> 24) / 255.0f);
-        });
+        [&](int q, uint32_t v) { reinterpret_cast<float4*>(row)[q] = quotient_255(v); });
     } else {
       each_unit<uint8_t>(lane, X.Pu, [&](int q) { return from[q]; }, [&](int q, uint8_t v) { row[q] = (float)v / 255.0f; });
     }
@@ -419,21 +350,6 @@ int check_img(const mcg_rollout_img_buf* b, const char* who) {
       b->gae_lambda > 1.0)
     return mcg_fail(MCG_ERR_ARG, "%s: gamma and gae_lambda must be finite and in [0, 1]", who);
   return MCG_OK;
-}
-
-int check_src(const mcg_rollout_img_buf* b, const uint8_t* img, int64_t env_stride, int64_t chan_stride, const char* who) {
-  if (!img) return mcg_fail(MCG_ERR_ARG, "%s: null img", who);
-  if (env_stride < 0 || chan_stride < 0) return mcg_fail(MCG_ERR_ARG, "%s: a stride is negative", who);
-  if (b->channels > 1 && chan_stride < (int64_t)b->size * b->size)
-    return mcg_fail(MCG_ERR_ARG, "%s: chan_stride is below size * size", who);
-  return MCG_OK;
-}
-
-// the widest load that the picture's base, strides and channel size allow
-int load_width(const mcg_rollout_img_buf* b, const uint8_t* img, int64_t env_stride, int64_t chan_stride) {
-  const uint64_t all = (uint64_t)(uintptr_t)img | (uint64_t)env_stride | (b->channels > 1 ? (uint64_t)chan_stride : 0u) |
-                       (uint64_t)((int64_t)b->size * b->size);
-  return (all & 15) == 0 ? 16 : (all & 3) == 0 ? 4 : 1;
 }
 
 Roll planes(const mcg_rollout_img_buf* b) {
@@ -524,12 +440,12 @@ int mcg_rollout_img_start(const mcg_rollout_img_buf* buf, int pos, const uint8_t
                           const uint8_t* mask, void* stream) {
   if (const int rc = check_img(buf, "mcg_rollout_img_start")) return rc;
   if (pos < 0 || pos > buf->n_steps) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_start: pos outside [0, n_steps]");
-  if (const int rc = check_src(buf, img, env_stride, chan_stride, "mcg_rollout_img_start")) return rc;
+  if (const int rc = check_src(buf->channels, buf->size, img, env_stride, chan_stride, "mcg_rollout_img_start", "img")) return rc;
   const Roll B = planes(buf);
   const Pix X = pixels(buf);
   const Src S = {img, (long long)env_stride, (long long)chan_stride};
   const dim3 grid(blocks((long long)B.n * (X.P / 16) + B.n, ADD_LANES)), block(ADD_LANES);
-  switch (load_width(buf, img, env_stride, chan_stride)) {
+  switch (load_width(buf->channels, buf->size, img, env_stride, chan_stride)) {
     case 16: hipLaunchKernelGGL(img_start_kernel<16>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, mask); break;
     case 4: hipLaunchKernelGGL(img_start_kernel<4>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, mask); break;
     default: hipLaunchKernelGGL(img_start_kernel<1>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, mask);
@@ -547,14 +463,14 @@ int mcg_rollout_img_add(const mcg_rollout_img_buf* buf, int pos, const float* ac
   if (!log_probs) return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: null log_probs");
   if (!reward || !terminated || !truncated)
     return mcg_fail(MCG_ERR_ARG, "mcg_rollout_img_add: reward, terminated and truncated of the step's output are required");
-  if (const int rc = check_src(buf, img, env_stride, chan_stride, "mcg_rollout_img_add")) return rc;
+  if (const int rc = check_src(buf->channels, buf->size, img, env_stride, chan_stride, "mcg_rollout_img_add", "img")) return rc;
   const Roll B = planes(buf);
   const Pix X = pixels(buf);
   const Src S = {img, (long long)env_stride, (long long)chan_stride};
   const dim3 grid(blocks((long long)B.n * (X.P / 16) + (long long)B.n * (X.rw / 4 + 1), ADD_LANES)), block(ADD_LANES);
 #define MCG_IMG_ADD(W) hipLaunchKernelGGL(img_add_kernel<W>, grid, block, 0, (hipStream_t)stream, B, X, pos, S, actions, values, \
                                           log_probs, final_values, reward, terminated, truncated)
-  switch (load_width(buf, img, env_stride, chan_stride)) {
+  switch (load_width(buf->channels, buf->size, img, env_stride, chan_stride)) {
     case 16: MCG_IMG_ADD(16); break;
     case 4: MCG_IMG_ADD(4); break;
     default: MCG_IMG_ADD(1);
@@ -598,10 +514,7 @@ int mcg_rollout_img_gather(const mcg_rollout_img_buf* buf, uint64_t seed, uint64
   const Roll B = planes(buf);
   const Pix X = pixels(buf);
   const ImgBatch O = {out->pix, out->pix_f32, out->action, out->old_value, out->old_log_prob, out->advantage, out->returns, out->index};
-  // what divides the rows of both picture outputs: pix rows are Pu bytes apart, pix_f32 rows 4 Pu
-  const uint64_t all = (uint64_t)X.Pu | (uint64_t)(uintptr_t)out->pix;
-  const bool f16 = ((uintptr_t)out->pix_f32 & 15) == 0;
-  const int align = (all & 15) == 0 && f16 ? 16 : (all & 3) == 0 && f16 ? 4 : 1;
+  const int align = store_align(X.Pu, (uint64_t)(uintptr_t)out->pix, (uint64_t)(uintptr_t)out->pix_f32);
   const dim3 grid(blocks(count, SAMPLE_LANES / 64)), block(SAMPLE_LANES);
 #define MCG_IMG_GATHER(AL) hipLaunchKernelGGL(img_gather_kernel<AL>, grid, block, 0, (hipStream_t)stream, B, X, (unsigned long long)seed, \
                                               (unsigned long long)epoch, (int)first, (int)count, b / 2, O)

@@ -60,19 +60,6 @@ class ImageRolloutBuffer(_OnPolicyBuffer):
                                            size=self.image_size, act_dim=self.act_dim, n_steps=self.n_steps, gamma=self.gamma,
                                            gae_lambda=self.gae_lambda)
 
-    def _picture(self, img, name):
-        """uint8 [N, C, S, S] whose [S, S] planes are contiguous -> (the tensor, its environment and channel strides in bytes).  The
-        environment's own layout (the [N, C, S, S] view of a [C, N, S, S] buffer) and a contiguous tensor pass without a copy."""
-        t = torch.as_tensor(img, device=self.device)
-        shape = (self.num_envs, self.channels, self.image_size, self.image_size)
-        if t.dtype != torch.uint8:
-            raise ValueError(f"{name}: expected uint8 pictures, got {t.dtype}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-        if not t[0, 0].is_contiguous() or (self.channels > 1 and t.stride(1) < self.image_size ** 2):
-            t = t.contiguous()
-        return t, t.stride(0), t.stride(1)
-
     # ----------------------------------------------------------------------------------------------------- insertion
     def start(self, img, mask=None):
         """The environments of ``mask`` (None: all) continue from ``img`` (what ``reset`` returned), as the first step of an episode."""
