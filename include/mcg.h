@@ -22,6 +22,8 @@
  *                       (PPO / A2C on the -v1 ids)   scripts/train.py:99-101, mycobot.py:517-545
  *   mcg_replay_img_start / _add / _sample   SB3's ReplayBuffer as SAC / TD3 / DDPG use it (scripts/train.py:62, 102-104) on the same
  *                       pictures, every picture stored once and a time-limit end kept apart from a termination
+ *   mcg_replay_img_sample_stacked, mcg_frame_stack_push   SB3's VecFrameStack on those pictures: stacks rebuilt from the single-frame
+ *                       ring when a batch is sampled, and the stack a policy acts on, updated in one launch per step
  *   mcg_get_state / mcg_set_state   direct access to data.qpos/qvel/ctrl/qacc_warmstart (set_joint_qpos etc.)
  *
  * Conventions: every pointer in the step/reset/state calls is DEVICE memory owned by the caller;
@@ -624,6 +626,51 @@ int mcg_replay_img_add(const mcg_replay_img_buf* buf, int64_t n_written, const f
    No address and no loop bound depends on stored content beyond the two flag tests and the stamp compare; all byte offsets are 64-bit. */
 int mcg_replay_img_sample(const mcg_replay_img_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch,
                           const mcg_replay_img_batch* out, void* stream);
+
+/* ---- Frame stacking for the pictures (SB3's VecFrameStack, channels first: StackedObservations).  A frame is a whole stored picture of
+   C channels, Pu = C * S * S bytes; a stack of k = frame_stack frames is [k * C, S, S], k * Pu bytes: slot s is channels
+   s * C .. s * C + C - 1, slot k - 1 the newest.  After a reset the slots older than the episode are zeros.
+
+   mcg_replay_img_sample with `observations` and `next_observations` as stacks, rebuilt from the single-frame ring: the k - 1 frames
+   before row a are the k - 1 rows before it, so nothing is stored k times.  The struct, mcg_replay_img_start and mcg_replay_img_add
+   are unchanged; a caller who wants K sampleable transitions passes capacity = K + k - 1 (R = K + k rows), and the entry samples over
+   the W = min(n_written, capacity - (k - 1)) newest: every sampleable transition keeps its whole history in the ring, and none of the
+   k - 1 older rows is ever a sample.  The rows of pix / next_pix / pix_f32 / next_pix_f32 of the batch are k * Pu long here.
+     episode start   the picture of time t is the first of its episode iff t == 0 or the record of transition t - 1 carries any of
+                     TERMINATED, TIMEOUT, NO_NEXT.
+     stack(t)        slot k - 1 - i is the picture of time t - i (row (t - i) % R) for i = 0 .. d - 1, where d - 1 is the number of
+                     steps one can walk back from t without crossing an episode start, capped at k - 1; older slots are zeros.
+     a sample        the draws, the give-up, done, action, reward, index and both counters are mcg_replay_img_sample's, with W as
+                     above.  pix = stack(a).  next_pix = stack(a + 1) -- after TERMINATED, and after a TIMEOUT whose final picture
+                     was overwritten (done = 1, counters[1]), that is zeros and the next episode's first picture -- but where the
+                     record has TIMEOUT and the stamp equals a: stack(a) shifted down one slot with the final picture in slot k - 1
+                     (SB3's stacked terminal_observation).
+   Every byte of the outputs given is written, the zero slots as zeros.  frame_stack == 1 gives mcg_replay_img_sample's outputs bit for
+   bit.  No address and no loop bound depends on stored content beyond the two flag tests and the stamp compare of
+   mcg_replay_img_sample and the walk back: the flags of the k - 1 <= 7 records before the sample's (their rows depend on the draw
+   alone) are tested up to the first episode start.  All byte offsets are 64-bit.  Refused (MCG_ERR_ARG) beyond what mcg_replay_img_sample refuses: frame_stack outside [1, 8];
+   capacity - (frame_stack - 1) < 1. */
+int mcg_replay_img_sample_stacked(const mcg_replay_img_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch, int frame_stack,
+                                  const mcg_replay_img_batch* out, void* stream);
+
+/* The act-time half, SB3's StackedObservations.update with done = terminated | truncated; stateless, one launch on `stream`, no
+   synchronisation.  `stack` is the caller's uint8 [N, k * Pu], contiguous, updated in place; `final_stack` (NULL: none; then final_img
+   is not read) has the same shape.  `img` and `final_img` are pictures as mcg_rollout_img_* takes them (base, env_stride, chan_stride;
+   the three load widths; the stacks are read and written at the narrowest width that they and the pictures allow).
+     mask == NULL   a step.  final_stack[e] = the old stack shifted down one slot, then final_img[e] in the newest slot, for every
+                    environment; stack[e] = the old stack shifted down one slot, the older slots zeros where done[e], then img[e] in
+                    the newest slot.
+     mask != NULL   a reset.  Where mask[e]: the older slots of stack[e] are zeros, its newest slot is img[e], and final_stack[e] as
+                    above if given; the other environments are left as they are.  `done` is not read and may be NULL.
+   A lane owns one 16-byte position of one environment's frame; it loads slots 1 .. k - 1, img and final_img at that position and only
+   then stores, so the shift in place has no hazard between lanes, and every byte is read once and written once per output.
+   Checked on the host before any HIP call (MCG_ERR_ARG), each with its own message: a null stack; n_envs / channels / size < 1;
+   channels > 8; size > 512; frame_stack outside [1, 8]; n_envs * ceil(Pu / 16) >= 2^31; final_stack == stack; done and mask both null;
+   a null img (final_img, where final_stack is given); a negative stride, or a channel stride below S * S while channels > 1. */
+int mcg_frame_stack_push(uint8_t* stack, uint8_t* final_stack, int n_envs, int channels, int size, int frame_stack, const uint8_t* img,
+                         int64_t env_stride, int64_t chan_stride, const uint8_t* final_img, int64_t final_env_stride,
+                         int64_t final_chan_stride, const uint8_t* done /* [N] device */, const uint8_t* mask /* [N] device or NULL */,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
 The numeric path is the HIP library ``libmycobot_hip.so`` (C ABI in ``include/mcg.h``); importing the
 package does not need a GPU, constructing an environment does.
 """
+from .frame_stack import FrameStack  # noqa: F401
 from .registry import REGISTRY, spec  # noqa: F401
 from .replay import HerBuffer, HerSamples  # noqa: F401
 from .replay_img import ImageReplayBuffer, ReplaySamples  # noqa: F401

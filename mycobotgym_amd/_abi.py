@@ -289,7 +289,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_rollout_record_bytes", "mcg_rollout_start", "mcg_rollout_add", "mcg_rollout_gae", "mcg_rollout_gather",
            "mcg_rollout_img_record_bytes", "mcg_rollout_img_start", "mcg_rollout_img_add", "mcg_rollout_img_gae", "mcg_rollout_img_carry",
            "mcg_rollout_img_gather",
-           "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample")
+           "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample",
+           "mcg_replay_img_sample_stacked", "mcg_frame_stack_push")
 
 _lib = None
 
@@ -368,6 +369,11 @@ def load():
         L.mcg_replay_img_add.argtypes = [rimg, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcg_replay_img_sample.argtypes = [rimg, C.c_int64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(McgReplayImgBatch), C.c_void_p]
+    if hasattr(L, "mcg_frame_stack_push"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_replay_img_sample_stacked.argtypes = [C.POINTER(McgReplayImgBuf), C.c_int64, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
+                                                    C.POINTER(McgReplayImgBatch), C.c_void_p]
+        L.mcg_frame_stack_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -18,7 +18,8 @@ def _ptr(t):
 
 class DeviceBuffer:
     """A subclass sets ``_FROM_ENVS`` (constructor keyword, attribute of a ``MyCobotVecEnv`` to take it from), ``_NO_IMAGES`` (why it
-    refuses the -v1 image ids; a buffer of pictures sets ``_IMAGES = True`` and ``_NO_STATES``, why it refuses the -v0 ids) and
+    refuses the -v1 image ids and a ``FrameStack`` around them; a buffer of pictures sets ``_IMAGES = True`` and ``_NO_STATES``, why it
+    refuses the -v0 ids) and
     ``_HOST_STATE`` (the host fields of ``state_dict()``), fills ``self._t`` (name -> device tensor, the pointers of the struct) and
     ``self._cbuf`` (the struct), and keeps ``num_envs``, ``obs_dim`` (with ``_goal_obs``) and ``seed``."""
     _IMAGES = False
@@ -27,8 +28,9 @@ class DeviceBuffer:
         """Sets ``device`` and loads the library -> the values of ``_FROM_ENVS``'s keywords in its order, each as ``given`` or else
         from ``envs`` (the device likewise)."""
         if envs is not None:
+            from .frame_stack import FrameStack
             from .vec_env import MyCobotImgVecEnv
-            if isinstance(envs, MyCobotImgVecEnv) != self._IMAGES:
+            if isinstance(envs, (MyCobotImgVecEnv, FrameStack)) != self._IMAGES:      # (a FrameStack's `channels` is k * C: wide storage)
                 raise ValueError(self._NO_STATES if self._IMAGES else self._NO_IMAGES)
             given = {k: getattr(envs, attr) if given[k] is None else given[k] for k, attr in self._FROM_ENVS}
             device = envs.device if device is None else device

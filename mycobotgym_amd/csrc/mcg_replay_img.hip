@@ -188,6 +188,151 @@ __global__ __launch_bounds__(SAMPLE_LANES) void replay_img_sample_kernel(Ring B,
   }
 }
 
+// --------------------------------------------------------------------------------------------------- sample, stacked
+// Unit q of a sample of `per` units per picture -> the picture j = q / per it belongs to and its place p = q - j * per in it.  `inv`
+// is 1.0f / per; q / per <= 9, so the float quotient is off by one at the most, and the two compares settle it.
+MCG_DEV void picture_of(int q, int per, float inv, int& j, int& p) {
+  j = (int)((float)q * inv);
+  if (j * per > q) j--;
+  else if ((j + 1) * per <= q) j++;
+  p = q - j * per;
+}
+
+// replay_img_sample_kernel on stacks of ks frames: one sample per wave, the same draws (over Wn = min(n_written, K - (ks - 1))), then
+// the depth of the stack: the flags of the ks - 1 <= 7 records before the sample's, walked back to the first episode start.  Every
+// lane reads them, so the index phase stays wave-uniform.  The copy phase has ks + 1 source pictures: j = 0 .. ks - 1 is time
+// a - (ks - 1 - j), the picture of slot j of the stack, a zero picture where it lies before the episode's start; j = ks is the
+// successor or the final picture.  Each is loaded once and stored twice: into slot j of `observations` (j < ks) and into slot j - 1 of
+// `next_observations` (j >= 1), which takes zeros from j < ks where the next stack starts an episode.  They go through one copy loop
+// as (ks + 1) * per units with IMG_FLIGHT loads in flight per lane; every byte of both outputs is written.
+template <int ALIGN>
+__global__ __launch_bounds__(SAMPLE_LANES) void replay_img_sample_stacked_kernel(Ring B, Pix X, long long n_written, int Wn, uint32_t base,
+                                                                                 unsigned long long seed, unsigned long long call,
+                                                                                 int batch, int ks, Batch O) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * (SAMPLE_LANES / 64) + (threadIdx.x >> 6);   // wave-uniform; the output row of this wave
+  if (k >= batch) return;
+  // ---- index phase: the first draw whose record still has its next picture
+  const uint32_t c1 = (uint32_t)call, c3 = (uint32_t)REPLAY_IMG_STREAM ^ ((uint32_t)(call >> 32) << 8);
+  int j = 0, e = 0, row = 0;
+  uint32_t flags = NO_NEXT;
+  for (int d = 0; d < MAX_DRAWS && (flags & NO_NEXT) != 0; d++) {
+    double u0, u1;
+    philox_pair((uint32_t)k, c1, (uint32_t)d, c3, seed, u0, u1);
+    j = (int)floor(u0 * (double)Wn); j = j > Wn - 1 ? Wn - 1 : j;
+    e = (int)floor(u1 * (double)B.n); e = e > B.n - 1 ? B.n - 1 : e;
+    row = (int)((base + (uint32_t)j) % (uint32_t)B.R);                  // (n_written - Wn + j) % R; base < R, j < R: no overflow
+    flags = B.rec[((size_t)row * B.n + e) * X.rw + X.A + 1];
+  }
+  const bool ok = (flags & NO_NEXT) == 0;
+  const long long a = n_written - Wn + j;                               // the transition's absolute time
+  // the depth: pictures a - depth + 1 .. a belong to the sample's episode.  The ks - 1 records before the sample's and the stamp are
+  // loaded together, before any is tested (their rows do not depend on stored content; a - i >= n_written - R + 1 for i < ks: the rows
+  // are live, and a row of a time before 0 is read and not used), so the index phase waits for memory twice, not ks + 1 times.
+  uint32_t before[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++) {
+    const int r = row - (i + 1) < 0 ? row - (i + 1) + B.R : row - (i + 1);                  // i + 1 < ks <= R - 1
+    before[i] = i + 1 < ks ? B.rec[((size_t)r * B.n + e) * X.rw + X.A + 1] : NO_NEXT;
+  }
+  const int frow = (int)((a / B.Tm) % B.F);
+  const long long stamp = B.ftime[(size_t)frow * B.n + e];
+  int depth = 1;
+#pragma unroll
+  for (int i = 0; i < 7; i++)           // picture a - i is no episode start: a - i > 0 and the record of transition a - i - 1 ended nothing
+    if (depth == i + 1 && i + 1 < ks && a - i > 0 && (before[i] & (TERMINATED | TIMEOUT | NO_NEXT)) == 0) depth = i + 2;
+  int nrow = row + 1 == B.R ? 0 : row + 1, from_finals = 0;
+  float done = (flags & TERMINATED) != 0 ? 1.0f : 0.0f;
+  bool lost = false;
+  if (ok && (flags & TIMEOUT) != 0) {
+    if (stamp == a) { nrow = frow; from_finals = 1; }
+    else { done = 1.0f; lost = true; }   // the final picture was overwritten: a terminal transition, never another episode's picture
+  }
+  // the next stack keeps the older frames unless picture a + 1 starts an episode: the final picture belongs to the sample's own
+  const bool keep = ok && ((flags & (TERMINATED | TIMEOUT)) == 0 || from_finals != 0);
+  const uint32_t* rec = B.rec + ((size_t)row * B.n + e) * X.rw;
+  if (O.act)
+    for (int w = lane; w < X.A; w += 64) O.act[(size_t)k * X.A + w] = ok ? __uint_as_float(rec[w]) : 0.0f;
+  if (lane == 0) {
+    if (O.rew) O.rew[k] = ok ? __uint_as_float(rec[X.A]) : 0.0f;
+    if (O.done) O.done[k] = ok ? done : 0.0f;
+    if (O.index) {
+      O.index[(size_t)k * 3] = ok ? row : -1; O.index[(size_t)k * 3 + 1] = ok ? e : -1; O.index[(size_t)k * 3 + 2] = ok ? from_finals : -1;
+    }
+    if (!ok) atomicAdd(B.cnt, 1ull);
+    if (lost) atomicAdd(B.cnt + 1, 1ull);
+  }
+  // ---- copy phase
+  const uint8_t* succ = (from_finals ? B.fin : X.px) + ((size_t)nrow * B.n + e) * X.P;
+  // source picture s (nullptr: zeros).  ks - 1 - s < R: capacity >= ks, the host's check
+  auto source = [&](int s) -> const uint8_t* {
+    if (!ok) return nullptr;
+    if (s == ks) return succ;
+    const int back = ks - 1 - s;
+    if (back >= depth) return nullptr;
+    const int r = row - back < 0 ? row - back + B.R : row - back;
+    return X.px + ((size_t)r * B.n + e) * X.P;
+  };
+  const size_t out_row = (size_t)k * ks * X.Pu;                        // a row of an output: ks pictures
+  if (O.pix || O.npix) {
+    const int per = X.P >> 4;
+    const float inv = 1.0f / (float)per;
+    each_unit<uint4>(lane, (ks + 1) * per,
+      [&](int q) {
+        int s, p;
+        picture_of(q, per, inv, s, p);
+        const uint8_t* from = source(s);
+        if (!from || !(s < ks ? (O.pix || (O.npix && s >= 1 && keep)) : O.npix != nullptr)) return make_uint4(0u, 0u, 0u, 0u);
+        return reinterpret_cast<const uint4*>(from)[p];
+      },
+      [&](int q, uint4 v) {
+        int s, p;
+        picture_of(q, per, inv, s, p);
+        if (O.pix && s < ks) store_u8<ALIGN>(O.pix + out_row + (size_t)s * X.Pu, X.Pu, p, v);
+        if (O.npix && s >= 1)
+          store_u8<ALIGN>(O.npix + out_row + (size_t)(s - 1) * X.Pu, X.Pu, p, s == ks || keep ? v : make_uint4(0u, 0u, 0u, 0u));
+      });
+  }
+  if (O.pix_f32 || O.npix_f32) {
+    if constexpr (ALIGN >= 4) {
+      const int per = X.Pu >> 2;
+      const float inv = 1.0f / (float)per;
+      each_unit<uint32_t>(lane, (ks + 1) * per,
+        [&](int q) {
+          int s, p;
+          picture_of(q, per, inv, s, p);
+          const uint8_t* from = source(s);
+          if (!from || !(s < ks ? (O.pix_f32 || (O.npix_f32 && s >= 1 && keep)) : O.npix_f32 != nullptr)) return 0u;
+          return reinterpret_cast<const uint32_t*>(from)[p];
+        },
+        [&](int q, uint32_t v) {
+          int s, p;
+          picture_of(q, per, inv, s, p);
+          if (O.pix_f32 && s < ks) reinterpret_cast<float4*>(O.pix_f32 + out_row + (size_t)s * X.Pu)[p] = quotient_255(v);
+          if (O.npix_f32 && s >= 1)
+            reinterpret_cast<float4*>(O.npix_f32 + out_row + (size_t)(s - 1) * X.Pu)[p] = quotient_255(s == ks || keep ? v : 0u);
+        });
+    } else {
+      const int per = X.Pu;
+      const float inv = 1.0f / (float)per;
+      each_unit<uint8_t>(lane, (ks + 1) * per,
+        [&](int q) {
+          int s, p;
+          picture_of(q, per, inv, s, p);
+          const uint8_t* from = source(s);
+          if (!from || !(s < ks ? (O.pix_f32 || (O.npix_f32 && s >= 1 && keep)) : O.npix_f32 != nullptr)) return (uint8_t)0;
+          return from[p];
+        },
+        [&](int q, uint8_t v) {
+          int s, p;
+          picture_of(q, per, inv, s, p);
+          if (O.pix_f32 && s < ks) O.pix_f32[out_row + (size_t)s * X.Pu + p] = (float)v / 255.0f;
+          if (O.npix_f32 && s >= 1) O.npix_f32[out_row + (size_t)(s - 1) * X.Pu + p] = (float)(s == ks || keep ? v : (uint8_t)0) / 255.0f;
+        });
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------- host side
 int check_buf(const mcg_replay_img_buf* b, const char* who) {
   if (!b) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_replay_img_buf", who);
@@ -296,6 +441,40 @@ int mcg_replay_img_sample(const mcg_replay_img_buf* buf, int64_t n_written, uint
   const dim3 grid(blocks(batch, SAMPLE_LANES / 64)), block(SAMPLE_LANES);
 #define MCG_REPLAY_IMG_SAMPLE(AL) hipLaunchKernelGGL(replay_img_sample_kernel<AL>, grid, block, 0, (hipStream_t)stream, B, X, \
                                                      (long long)n_written, Wn, base, (unsigned long long)seed, (unsigned long long)call, batch, O)
+  switch (align) {
+    case 16: MCG_REPLAY_IMG_SAMPLE(16); break;
+    case 4: MCG_REPLAY_IMG_SAMPLE(4); break;
+    default: MCG_REPLAY_IMG_SAMPLE(1);
+  }
+#undef MCG_REPLAY_IMG_SAMPLE
+  return launched("mcg_replay_img");
+}
+
+int mcg_replay_img_sample_stacked(const mcg_replay_img_buf* buf, int64_t n_written, uint64_t seed, uint64_t call, int batch, int frame_stack,
+                                  const mcg_replay_img_batch* out, void* stream) {
+  const char* who = "mcg_replay_img_sample_stacked";
+  if (const int rc = check_buf(buf, who)) return rc;
+  if (frame_stack < 1 || frame_stack > 8) return mcg_fail(MCG_ERR_ARG, "%s: frame_stack must be in [1, 8]", who);
+  if (buf->capacity - (frame_stack - 1) < 1)
+    return mcg_fail(MCG_ERR_ARG, "%s: capacity - (frame_stack - 1) must be >= 1: no transition keeps its whole stack in the ring", who);
+  if (n_written < 0) return mcg_fail(MCG_ERR_ARG, "%s: n_written < 0", who);
+  if (n_written == 0) return mcg_fail(MCG_ERR_ARG, "%s: the buffer is empty (n_written == 0)", who);
+  if (batch < 1) return mcg_fail(MCG_ERR_ARG, "%s: batch must be >= 1", who);
+  if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_replay_img_batch", who);
+  if (!out->pix && !out->next_pix && !out->pix_f32 && !out->next_pix_f32 && !out->action && !out->reward && !out->done && !out->index)
+    return mcg_fail(MCG_ERR_ARG, "%s: all outputs are null", who);
+  const Ring B = ring(buf);
+  const Pix X = pixels(buf);
+  const int window = buf->capacity - (frame_stack - 1);                  // the rows older than it hold history alone
+  const int Wn = (int)(n_written < window ? n_written : window);
+  const uint32_t base = (uint32_t)((n_written - Wn) % B.R);
+  const Batch O = {out->pix, out->next_pix, out->pix_f32, out->next_pix_f32, out->action, out->reward, out->done, out->index};
+  const int align = store_align(X.Pu, (uint64_t)(uintptr_t)out->pix | (uint64_t)(uintptr_t)out->next_pix,
+                                (uint64_t)(uintptr_t)out->pix_f32 | (uint64_t)(uintptr_t)out->next_pix_f32);
+  const dim3 grid(blocks(batch, SAMPLE_LANES / 64)), block(SAMPLE_LANES);
+#define MCG_REPLAY_IMG_SAMPLE(AL) hipLaunchKernelGGL(replay_img_sample_stacked_kernel<AL>, grid, block, 0, (hipStream_t)stream, B, X, \
+                                                     (long long)n_written, Wn, base, (unsigned long long)seed, (unsigned long long)call, batch, \
+                                                     frame_stack, O)
   switch (align) {
     case 16: MCG_REPLAY_IMG_SAMPLE(16); break;
     case 4: MCG_REPLAY_IMG_SAMPLE(4); break;
