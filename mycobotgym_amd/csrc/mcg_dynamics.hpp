@@ -42,7 +42,7 @@ enum { ST_LOAD = 0, ST_CTRL, ST_TRIG, ST_RNE, ST_ACT, ST_CRB, ST_ROWS, ST_G0, ST
        ST_COUPLED, ST_CUBE_FIN, ST_POST, ST_N_BUILD, ST_N_FACTOR, ST_N_SOLVE, ST_N_CHECK, ST_E_RHS, ST_R_AX5, ST_R_CONNECT, ST_R_LIMITS, ST_C_MASK, ST_C_ASSEMBLE, ST_C_SCHUR, ST_C_SOLVE, ST_C_CHECK, ST_C_LS, ST_W2_WAIT1, ST_W2_COLLIDE, ST_W2_CUBE, ST_W2_WAIT2, ST_W1_WAIT, ST_A_ENTRY, ST_A_G, ST_A_TWIST, ST_A_LOOP, ST_A_MAP, ST_A_STORE,
        ST_CO_SETUP, ST_CO_ROWS, ST_CO_H0, ST_CO_RESID, ST_CO_ASM, ST_CO_FACTOR, ST_CO_SOLVE, ST_CO_CHECK, ST_CO_LS, ST_CO_OUT, ST_CO_IDLE,
        ST_X_S1C, ST_X_NUMBERS, ST_X_S2, ST_S_S1B, ST_S_MESH, ST_S_S1C, ST_S_NUMBERS,
-       ST_M_S3, ST_H_S1, ST_H_CRB, ST_H_S2, ST_H_FACTOR, ST_H_S3, ST_Q_S1, ST_Q_BIAS, ST_Q_S2, ST_Q_COLS, ST_Q_S3, ST_COUNT,
+       ST_M_S3, ST_H_S1, ST_H_CRB, ST_H_S2, ST_H_FACTOR, ST_H_S3, ST_Q_S1, ST_Q_BIAS, ST_Q_S2, ST_Q_COLS, ST_Q_S3, ST_M_FACTOR, ST_H_COLS, ST_M_GEAR, ST_COUNT,
        CN_SUBSTEP = 0, CN_NEWTON_IT, CN_LINESEARCH, CN_CUBE_IT, CN_CUBE_LS, CN_COUPLED, CN_COUPLED_IT, CN_COUPLED_LS, CN_CONTACTS, CN_COOP_ROWS, CN_COOP_LSEVAL, CN_COOP_LONG, CN_COOP_CAP, CN_COOP_12, CN_G_FAILED, CN_G_LIM, CN_G_STAT, CN_G_CUBE, CN_G_MISSING, CN_G_EXTRA, CN_G_EQ1, CN_G_EQ2, CN_G_EQ2N1, CN_MP_PAIRS, CN_MP_HITS, CN_MP_FACE, CN_MP_EXIT_B, CN_MP_EXIT_P, CN_MP_EXIT_E, CN_MP_KIND_E, CN_MP_KIND_P, CN_MP_CUBE, CN_COUNT };
 #ifdef MCG_STAGE_CLOCKS
 __device__ unsigned long long g_stage_clocks[ST_COUNT + CN_COUNT];      // stage clocks, then event counts (summed over waves)
@@ -408,6 +408,7 @@ constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM
 //                     could fall back and read them; the RNE wave reads RLIM before it writes RA;
 //   RACT = IKT:       the IK increments are live between the control-step barriers C1 and C2 only, the sub-steps run after C2;
 //   RG0:              slots of its own.
+// (helper_cols: RLIM is not used, the main wave keeps the six numbers and finishes the gear rows itself; RA then holds abar.)
 constexpr int LDS_RLIM = LDS_WARM, LDS_RA = LDS_WARM, LDS_RACT = LDS_IKT, LDS_RG0 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_RG0 + NB;
 constexpr int RACT_DOF[8] = {0, 1, 2, 3, 4, 5, 6, 8};                       // the dofs an actuator drives
 static_assert(LDS_RA + NB == LDS_QLAG && LDS_RACT >= LDS_QLAG + 6 && LDS_RACT + 8 <= LDS_RG0,
@@ -418,6 +419,12 @@ static_assert(LDS_SLOTS_SPLIT * 64 * sizeof(real) <= 160 * 1024, "the split Reac
 // after the next S2, by which every wave has read its sines and cosines -- the two uses never overlap.
 constexpr int LDS_SN = LDS_FAC, LDS_CS = LDS_SN + NB;
 static_assert(LDS_SN >= LDS_FAC && LDS_CS + NB <= LDS_FDINV + NB && LDS_FDINV + NB == LDS_QB, "the sine / cosine exchange must lie inside the factor slots");
+// The gear rows' columns z6 = H^-1 e_6, z8 = H^-1 e_8 (SplitMainCols::helper_cols: the helper wave solves them between S2 and S3, the main
+// wave reads them after S3).  Under that policy the main wave factors M + hB itself and nobody writes the factor slots, so the columns
+// take 24 of them, behind the sine / cosine exchange: written after S2 and read before the next S1, they never meet it either.
+constexpr int LDS_Z6 = LDS_CS + NB, LDS_Z8 = LDS_Z6 + NB;
+static_assert(LDS_Z6 == LDS_FAC + 24 && LDS_Z6 >= LDS_SN + NB && LDS_Z6 >= LDS_CS + NB && LDS_Z8 == LDS_Z6 + NB && LDS_Z8 + NB <= LDS_QB,
+              "the gear rows' columns must lie inside the factor slots, clear of the sine / cosine exchange and of the published q");
 // The lane's LDS column.  The pointer carries the LDS address space explicitly: passed through structs as a generic
 // pointer the accesses degrade to flat_load/flat_store with 64-bit address arithmetic instead of ds_read/ds_write
 // with immediate offsets.
@@ -668,6 +675,7 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 //   S1  q(t), qd(t) are published in LDS      (the other waves may read them)
 //   S2  M(t) and passive - bias are in LDS    (main wave: g0, H_eq, Newton solve; remote sub-step: the RNE wave does, see solve_remote)
 //   S3  the factor of M + hB is in LDS        (main wave: a' = a - h (M + hB)^-1 (B a), which equals (M + hB)^-1 M a)
+//       (helper_cols: abar and the gear rows' columns are; the main wave has factored M + hB itself meanwhile)
 // A split policy says which pieces other waves provide and where the exchange slots are.
 // early_heq: the J^T D J part of H_eq is assembled (and the constraint part of g0 formed) BEFORE barrier S2, while the main wave
 // would otherwise wait for M; build_H then adds M on the fly.
@@ -683,17 +691,24 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // LDS_RLIM) and does nothing between S2 and S3.  The main wave decides from the limit signs it holds, the RNE wave from the q slots with
 // the same compares (no_other_rows); the helper wave does not need to know.  Any other violated row: the main wave solves as without the
 // flag and the RNE wave goes straight to S3.
+// helper_cols (round 8, on top of solve_remote): the serial stretch after S2 is spread over all three waves.  The helper wave solves the
+// gear rows' columns z6, z8 from its own factor of H (no limit row active: the RNE wave's H), in EVERY sub-step, into the slots LDS_Z6 /
+// LDS_Z8; the RNE wave's remote solve ends at abar; the main wave factors M + hB itself between S2 and S3 (after its own solve in a
+// sub-step that is not remote) and keeps the factor in registers, and after S3 a remote sub-step reads abar, finishes the gear rows
+// from the columns (gear_rows_solve, from D / aref / sign it kept in registers) and takes the Euler step.  Nothing is handed over in
+// the factor slots or through LDS_RLIM any more.
 // trig_once (round 6): the sub-step's twelve sines and cosines are evaluated once instead of once per wave: after S1 the main wave takes
 // joints 0..3, the helper 4..7, the RNE wave 8..11, and a barrier S1t hands all twenty-four to every wave through the slots LDS_SN /
 // LDS_CS (trig_exchange).
 struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, solve_remote = false,
-                                       trig_once = false;
+                                       trig_once = false, helper_cols = false;
                  static constexpr int QB = 0, QDB = 0, FS = 0, WARM = 0, QLAG = 0; };
 struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, solve_remote = true,
-                                         trig_once = true;
+                                         trig_once = true, helper_cols = false;
                    static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
 // The main wave solves in every sub-step (which controller's kernel takes which policy: step_reach_kernel, and DESIGN.md section 5).
 struct SplitMainLocal : SplitMain { static constexpr bool solve_remote = false; };
+struct SplitMainCols : SplitMain { static constexpr bool helper_cols = true; };        // the joint controller's kernel (round 8)
 struct SplitMainOwnTrig : SplitMain { static constexpr bool trig_once = false; };      // every wave its own twelve (round 5), for A/B builds
 
 // A wave's share of the exchange (trig_once): joints FIRST .. FIRST + 3 (`q_of(i)`: the wave's copy of q_i), stored, then -- S1t -- all
@@ -775,6 +790,16 @@ MCG_DEV void gear_rows_solve(real* x, const real* z6, const real* z8, real Dl6, 
   // slot 0 is row 6 where row 6 is violated, else row 8; the other column enters with a zero force (finite z: exactly x)
   const real g6 = v6 ? f0 : 0.0, g8 = v6 ? f1 : f0;
   static_for<NB>([&](auto I) { constexpr int i = I; x[i] = fma(-z8[i], g8, fma(-z6[i], g6, x[i])); });
+}
+
+// The L^T D L factor of M + hB for the Euler step, from M in LDS (after S2); damp returns the twelve damping coefficients.  One function for
+// the helper wave (helper_substep) and the main wave (helper_cols).
+template <class LS>
+MCG_DEV void factor_m_hb(ModelPtr Pm, const LS MS, real h, real* Mh, real* dinv, real* damp) {
+  static_for<NB>([&](auto I) { constexpr int i = I;
+    static_for<i + 1>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) Mh[tri(i, j)] = MS.ld(LDS_M + tri(i, j)); }); });
+  { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; damp[i] = Q->body[i].damping; Mh[tri(i, i)] = fma(h, damp[i], Mh[tri(i, i)]); }); }
+  ldl_factor<PAT_M>(Mh, dinv);
 }
 
 // COMMIT = false: the new q / qd / qacc_warmstart go to *next and S stays as it was (speculative sub-step of the two-wave
@@ -1038,6 +1063,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
       MCG_COUNT(CN_NEWTON_IT);
       if (__any(sgl[6] != 0 || sgl[8] != 0)) MCG_COUNT(CN_LINESEARCH);
 #endif
+      if constexpr (!SPL::helper_cols)                              // (helper_cols: this wave finishes the gear rows itself, after S3)
       static_for<2>([&](auto Sd) { constexpr int j = 6 + 2 * Sd;
         MS.st(LDS_RLIM + 3 * Sd, Dl[j]); MS.st(LDS_RLIM + 3 * Sd + 1, arefl[j]); MS.st(LDS_RLIM + 3 * Sd + 2, sgl[j]); });
     }
@@ -1220,7 +1246,33 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   MCG_TICK(ST_NEWTON);
   // ---- constraint forces -> qfrc_constraint; P10 implicit-damping Euler                  (mj_Euler, mj_advance)
   real rhs[NB];
-  if constexpr (SPL::factor_remote) {
+  real q_pre[NB], qd_pre[NB];                                         // helper_cols: q(t), qd(t) back from their slots before S3
+  if constexpr (SPL::helper_cols) {
+    static_assert(SPL::solve_remote && SPL::factor_remote, "helper_cols moves pieces of the remote solve and of the remote factor");
+    real Lf[NB * (NB + 1) / 2], dinv[NB], damp[NB];
+    factor_m_hb(Pm, MS, h, Lf, dinv, damp);                         // remote: beside the other waves' solves; else after this wave's own
+    // what the integration below needs besides a: read (and the lagged q parked) while this wave has slack before S3, not after it
+    static_for<NB>([&](auto I) { constexpr int i = I; q_pre[i] = MS.ld(SPL::QB + i); qd_pre[i] = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_pre[i]); });
+    static_for<NB>([&](auto I) { constexpr int i = I; pin(dinv[i]);         // the factor exists BEFORE S3: unpinned, its arithmetic sinks below
+      static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) pin(Lf[tri(i, j)]); }); });      // the barrier towards its use
+    MCG_FENCE();
+    MCG_TICK(ST_M_FACTOR);
+    __syncthreads();                                                // S3: remote: the RNE wave's abar and the helper's columns are in LDS
+    MCG_TICK(ST_M_S3);
+    if (remote) {
+      static_for<NB>([&](auto I) { constexpr int i = I; a[i] = MS.ld(LDS_RA + i); });
+      if (__any(sgl[6] != 0 || sgl[8] != 0)) {                      // wave-uniform: a gear row in some lane
+        real z6[NB], z8[NB];
+        static_for<NB>([&](auto I) { constexpr int i = I; z6[i] = MS.ld(LDS_Z6 + i); z8[i] = MS.ld(LDS_Z8 + i); });
+        gear_rows_solve(a, z6, z8, Dl[6], arefl[6], sgl[6], Dl[8], arefl[8], sgl[8]);
+      }
+      MCG_TICK_PIN(a, NB);
+      MCG_TICK(ST_M_GEAR);
+    }
+    static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = damp[i] * a[i]; });
+    ldl_solve<PAT_M>(Lf, dinv, rhs);
+    static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = fma(-h, rhs[i], a[i]); });
+  } else if constexpr (SPL::factor_remote) {
     real damp[NB];
     if constexpr (SPL::solve_remote) {      // a remote sub-step only waits here: the damping's batch of s_loads flies during the wait
       if (remote) { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; damp[i] = Q->body[i].damping; }); }
@@ -1245,7 +1297,8 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   bool bad = false;
   static_for<NB>([&](auto I) { constexpr int i = I;
     real q_old, qd_old;
-    if constexpr (SPL::warm_lds && !CPL::enabled) { q_old = MS.ld(SPL::QB + i); qd_old = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_old); }
+    if constexpr (SPL::helper_cols) { q_old = q_pre[i]; qd_old = qd_pre[i]; }
+    else if constexpr (SPL::warm_lds && !CPL::enabled) { q_old = MS.ld(SPL::QB + i); qd_old = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_old); }
     else { q_old = S.q[i]; qd_old = S.qd[i]; }
     qdn[i] = fma(h, rhs[i], qd_old); qn[i] = fma(h, qdn[i], q_old);
     if constexpr (COMMIT) bad = bad || bad_value(qn[i]) || bad_value(qdn[i]) || bad_value(a[i]); });
@@ -1295,13 +1348,24 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
   MCG_TICK(ST_H_CRB);
   __syncthreads();                                                  // S2
   MCG_TICK(ST_H_S2);
-  if constexpr (SPL::factor_remote) {
+  if constexpr (SPL::helper_cols) {
+    // In every sub-step, remote or not (no predicate: this wave cannot disagree with another about anything): H_eq + M with no limit row
+    // active, factored, and the two unit solves -- the functions the RNE wave's solve calls, in the same order, so the very same L and dinv.
+    real L[NB * (NB + 1) / 2], dinv[NB], z6[NB], z8[NB];
+    const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
+    const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    build_H<SPL>(MS, L, none, zero);
+    ldl_factor<PAT_H>(L, dinv);
+    ldl_solve_unit<PAT_H, 6>(L, dinv, z6);
+    ldl_solve_unit<PAT_H, 8>(L, dinv, z8);
+    static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_Z6 + i, z6[i]); MS.st(LDS_Z8 + i, z8[i]); });
+    MCG_TICK(ST_H_COLS);
+    __syncthreads();                                                // S3
+    MCG_TICK(ST_H_S3);
+  } else if constexpr (SPL::factor_remote) {
     const real h = launder(Pm)->timestep;
-    real Mh[NB * (NB + 1) / 2], dinv[NB];
-    static_for<NB>([&](auto I) { constexpr int i = I;
-      static_for<i + 1>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) Mh[tri(i, j)] = MS.ld(LDS_M + tri(i, j)); }); });
-    { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; Mh[tri(i, i)] = fma(h, Q->body[i].damping, Mh[tri(i, i)]); }); }
-    ldl_factor<PAT_M>(Mh, dinv);
+    real Mh[NB * (NB + 1) / 2], dinv[NB], damp[NB];
+    factor_m_hb(Pm, MS, h, Mh, dinv, damp);
     static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_FDINV + i, dinv[i]);
       static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) MS.st(LDS_FAC + tri(i, j), Mh[tri(i, j)]); }); });
     MCG_TICK(ST_H_FACTOR);
@@ -1343,6 +1407,7 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
       static_for<NB>([&](auto I) { constexpr int i = I; x[i] = MS.ld(LDS_RG0 + i) + (x[i] + fs[i]); });
       ldl_factor<PAT_H>(L, dinv);
       ldl_solve<PAT_H>(L, dinv, x);
+      if constexpr (!SPL::helper_cols) {                            // (helper_cols: the solve ends at abar, the main wave finishes the gear rows)
       const real Dl6 = MS.ld(LDS_RLIM), arefl6 = MS.ld(LDS_RLIM + 1), sgl6 = MS.ld(LDS_RLIM + 2);
       const real Dl8 = MS.ld(LDS_RLIM + 3), arefl8 = MS.ld(LDS_RLIM + 4), sgl8 = MS.ld(LDS_RLIM + 5);
       if (__any(sgl6 != 0 || sgl8 != 0)) {                          // wave-uniform: a gear row in some lane
@@ -1351,6 +1416,7 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
         ldl_solve_unit<PAT_H, 8>(L, dinv, z8);
         static_for<NB>([&](auto I) { constexpr int i = I; pin(z6[i]); pin(z8[i]); });      // as values read back from LDS: nothing contracted into them
         gear_rows_solve(x, z6, z8, Dl6, arefl6, sgl6, Dl8, arefl8, sgl8);
+      }
       }
       static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RA + i, x[i]); });
       MCG_TICK(ST_Q_COLS);

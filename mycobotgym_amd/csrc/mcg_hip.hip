@@ -160,13 +160,19 @@ MCG_DEV void mocap_target(const Cfg& C, ModelPtr P, const real* qlag6, const flo
 #ifndef MCG_SOLVE_REMOTE_CTRLS
 #define MCG_SOLVE_REMOTE_CTRLS (1 << MCG_CTRL_JOINT)
 #endif
+// Of those, the controllers whose helper wave solves the gear rows' columns while the main wave factors M + hB (SplitMainCols::helper_cols,
+// round 8); 0 builds round 7's kernels.
+#ifndef MCG_HELPER_COLS_CTRLS
+#define MCG_HELPER_COLS_CTRLS (1 << MCG_CTRL_JOINT)
+#endif
 
 // SPLIT: three waves per 64 environments (see SplitMain in mcg_dynamics.hpp): launched when the grid has at most one workgroup
 // per CU, where the extra waves run on SIMDs that would idle.  160 KB of LDS per workgroup (LDS_SLOTS_SPLIT).
 template <int CONTROLLER, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, View V, const mcg_model* __restrict__ Pg,
                                                                       const float* __restrict__ actions, mcg_step_out O) {
-  typedef std::conditional_t<SPLIT, std::conditional_t<(MCG_SOLVE_REMOTE_CTRLS >> CONTROLLER) & 1, SplitMain, SplitMainLocal>, NoSplit> Split;
+  typedef std::conditional_t<SPLIT, std::conditional_t<(MCG_SOLVE_REMOTE_CTRLS >> CONTROLLER) & 1,
+                                                      std::conditional_t<(MCG_HELPER_COLS_CTRLS >> CONTROLLER) & 1, SplitMainCols, SplitMain>, SplitMainLocal>, NoSplit> Split;
   __shared__ real lds[SPLIT ? LDS_SLOTS_SPLIT : LDS_SLOTS][64];
   const int lane = threadIdx.x & 63;
   const LaneScratch MS(&lds[0][lane]);
@@ -486,7 +492,7 @@ constexpr int PNP_SLOTS_DUAL = PNP_SLOTS_LDS;
 static_assert(PNP_SLOTS_DUAL * PNP_LANES * 8 <= 160 * 1024, "LDS of a CU");
 // robot-side split of the four-wave PickAndPlace kernel: M from the helper wave, passive - bias from the RNE wave, the constraint
 // part of H_eq assembled before barrier S2; the Euler step stays with M a (no room for the factor in LDS)
-struct SplitPnp { static constexpr bool enabled = true, rne_remote = true, factor_remote = false, early_heq = true, warm_lds = false, mesh_split = true, solve_remote = false, trig_once = false;
+struct SplitPnp { static constexpr bool enabled = true, rne_remote = true, factor_remote = false, early_heq = true, warm_lds = false, mesh_split = true, solve_remote = false, trig_once = false, helper_cols = false;
                   static constexpr int QB = XCH_Q, QDB = XCH_QD, FS = XCH_FS, WARM = 0, QLAG = 0, MASK0 = MP_MASK; };
 
 MCG_DEV bool flag_coupled(real f) { return (((int)f) & 2) != 0; }       // XCH_FLAG: bit 1 = the environment goes to the cooperative solve,

@@ -9,6 +9,7 @@ Lane 0 of every wave accumulates s_memtime deltas per stage; the table is the su
     --reach CTRL   Reach with controller CTRL (joint, IK, mocap) only
     --desync       desynchronised episodes (per-env random initial elapsed in [0, 50), as bench.py)
     --legacy       a library built before the helper / RNE wave stages of the split Reach kernel existed (shorter table)
+    --r07          a library built before round 8's stages (main wave's factor, helper's columns, main wave's gear rows) existed
 """
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -31,8 +32,10 @@ NAMES = ["load", "controller", "sincos", "rne", "actuation", "crb->M", "rows: we
          "M / RNE waves: waiting at S1c", "M / RNE waves: solver numbers",
          "main wave: waiting at S3", "helper wave: waiting for q (S1)", "helper wave: CRB -> M", "helper wave: waiting at S2",
          "helper wave: factor M+hB", "helper wave: waiting at S3", "RNE wave: waiting for q (S1)", "RNE wave: bias forces",
-         "RNE wave: waiting at S2", "RNE wave: remote constraint solve", "RNE wave: waiting at S3"]
+         "RNE wave: waiting at S2", "RNE wave: remote constraint solve", "RNE wave: waiting at S3",
+         "main wave: factor M+hB (S2 -> S3)", "helper wave: gear columns z6, z8", "main wave: abar, gear rows (after S3)"]
 if "--legacy" in sys.argv: NAMES = NAMES[:58]
+if "--r07" in sys.argv: NAMES = NAMES[:69]
 COUNTS = ["robot sub-steps", "robot Newton iterations", "robot line searches", "cube Newton iterations", "cube line searches",
           "coupled solves", "coupled Newton iterations", "coupled line searches", "wave-max contacts (per collision pass)",
           "coop active rows (sum over iterations)", "coop line-search evaluations", "coop solves whose carried active set was confirmed at once", "coop solves at the 50-iteration cap", "coop solves that started from a carried active set",
