@@ -200,11 +200,20 @@ def compare_step(envs, ora, actions, keys=("obs", "achieved", "desired", "reward
     return err
 
 
-def twin_errors(twin, state, actions, o_ref, prng, eps=1e-14):
+def twin_errors(twin, state, actions, o_ref, prng, eps=1e-14, cols=None):
     """The oracle's own sensitivity: a second oracle steps from `state` (the reference's state before its step) with qpos
-    perturbed by +-eps; returns its per-env max abs observation difference from the reference's outputs `o_ref`."""
+    perturbed by +-eps; returns its per-env max abs observation difference from the reference's outputs `o_ref`.
+
+    `cols` (an index or slice of qpos columns, e.g. slice(0, 12) for the robot's joints): perturb only these.  A cube at its reset height
+    sits at distance ~0 from the table top, so +-1e-14 on its z switches its four table contacts on or off and the twin differs by
+    g h^2 = 3.9e-5 after ONE sub-step: a property of the resting cube, not of the controller under test, which would inflate any bound taken
+    relative to the twin.  The default perturbs every column, as before."""
     s = dict(state)
-    s["qpos"] = state["qpos"] + eps * np.sign(prng.normal(size=state["qpos"].shape))
+    p = eps * np.sign(prng.normal(size=state["qpos"].shape))
+    if cols is not None:
+        keep = np.zeros(state["qpos"].shape[1], bool); keep[cols] = True
+        p[:, ~keep] = 0.0
+    s["qpos"] = state["qpos"] + p
     twin.set_state(**s)
     ot = twin.step(actions)
     return np.abs(ot["obs"] - o_ref["obs"]).max(axis=1)
