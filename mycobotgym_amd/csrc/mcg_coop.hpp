@@ -65,9 +65,9 @@ static_assert(4 * COOP_WS_DOUBLES <= 96 * PNP_LANES, "cooperative workspace exce
 constexpr int COOP_NV = 18, COOP_WIN = 16, COOP_WSTRIDE = 20;          // window: 16 active rows x (D, D aref, J[18])
 static_assert(COOP_WIN * COOP_WSTRIDE <= COOP_WS_DOUBLES && COOP_NV * COOP_NV + COOP_NV <= COOP_WS_DOUBLES, "window / matrix buffer");
 constexpr int COOP_ROWS = 10 + 6 * MAXCON, COOP_SETS = (COOP_ROWS + PNP_LANES - 1) / PNP_LANES;      // limits first, then the contacts
-#ifndef MCG_COOP_FULL_STEPS
-#define MCG_COOP_FULL_STEPS 1
-#endif
+// A consistent candidate is the minimiser; the first COOP_FULL_STEPS iterations step to their candidate x anyway, without a line search
+// (swept 0..3 in round 3, DESIGN.md: within 2 %).
+constexpr int COOP_FULL_STEPS = 1;
 
 // ---- cross-lane helpers (32 active lanes = two DPP rows of 16)
 MCG_DEV real coop_rdlane(real v, int l) {
@@ -109,9 +109,6 @@ MCG_DEV void coop_lds_sync() {         // LDS traffic between lanes of one wave:
 // of the (strictly convex) problem; a wrong guess costs one iteration and the iteration carries on from its candidate as before.
 MCG_DEV unsigned coop_sig_step(unsigned sig, int type) { return sig * 31u + (unsigned)type + 1u; }
 MCG_DEV real coop_pack(unsigned hi, unsigned lo) { return __hiloint2double((int)hi, (int)lo); }
-#ifndef MCG_COOP_GUESS
-#define MCG_COOP_GUESS 1
-#endif
 
 // Stage clocks of the cooperative solve (-DMCG_STAGE_CLOCKS): accumulated in registers, added to the global table once per coop_phase
 // (one atomic per tick from a thousand waves would itself be the largest stage).
@@ -250,7 +247,7 @@ MCG_DEV void coop_solve(ModelPtr Pm, LdsPtr lds0, int e, LdsPtr ws, int ncon, Co
   sig |= 0x80000000u;
   unsigned guess[COOP_SETS]; bool have_guess;
   { const real p0 = ME.ld(XCH_ACT0), p1 = ME.ld(XCH_ACT1);
-    have_guess = MCG_COOP_GUESS && NSETS <= 3 && (unsigned)__double2hiint(p0) == sig;
+    have_guess = NSETS <= 3 &&(unsigned)__double2hiint(p0) == sig;
     guess[0] = (unsigned)__double2loint(p0); guess[1] = (unsigned)__double2hiint(p1); guess[2] = (unsigned)__double2loint(p1); guess[3] = 0u; }
   unsigned fin[COOP_SETS] = {0u, 0u, 0u, 0u}; bool conv = false;
   COOP_COUNT(7, have_guess ? 1 : 0);
@@ -450,7 +447,7 @@ MCG_DEV void coop_solve(ModelPtr Pm, LdsPtr lds0, int e, LdsPtr ws, int ncon, Co
     const bool dbt = blockIdx.x == 0 && g_coop_dbg_done[e] == 0 && it < 8 && threadIdx.x % 64 == 0;
     if (dbt) { double* o = g_coop_dbg + e * 512 + 400 + it * 8; o[0] = __popc(act[0]) + (NSETS > 1 ? __popc(act[1 % NSETS]) : 0); o[1] = same; o[2] = 0; o[3] = -1; }
 #endif
-    if (same || it < MCG_COOP_FULL_STEPS) {           // uniform.  A consistent candidate is the minimiser; the first iterations step to x anyway
+    if (same || it < COOP_FULL_STEPS) {               // uniform
       al = xl;
       if (same) { _Pragma("unroll") for (int s = 0; s < NSETS; s++) fin[s] = act[s]; conv = true; break; }
       continue;
@@ -587,7 +584,7 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
   sig |= 0x80000000u;
   unsigned guess[2]; bool have_guess;                            // (per half)
   { const real p0 = ME.ld(XCH_ACT0), p1 = ME.ld(XCH_ACT1);
-    have_guess = MCG_COOP_GUESS && (unsigned)__double2hiint(p0) == sig;
+    have_guess = (unsigned)__double2hiint(p0) == sig;
     guess[0] = (unsigned)__double2loint(p0); guess[1] = (unsigned)__double2hiint(p1); }
   unsigned fin[2] = {0u, 0u}; bool conv = false;
   static_assert(NSETS <= 2, "the pair solve carries two sets of rows");
@@ -836,7 +833,7 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
     const bool same = sel(up, sameB, sameA);
     COOP_TICK(ST_CO_CHECK);
     COOP_COUNT(5, __popcll(__ballot(hl == 0 && have && use_guess && same)));
-    const bool full = same || it < MCG_COOP_FULL_STEPS;
+    const bool full = same || it < COOP_FULL_STEPS;
     const bool need = !done && !full;                // this half wants a line search
 #ifdef MCG_COOP_DEBUG
     const bool dbt = blockIdx.x == 0 && have && !done && g_coop_dbg_done[e] == 0 && it < 8 && hl == 0;

@@ -15,9 +15,6 @@
 // Numbers (offsets, inertias, gains, solver parameters) come from the mcg_model block in device memory; its
 // reads are wave-uniform and become scalar loads.
 #pragma once
-#ifndef MCG_DUP
-#define MCG_DUP 0       // development probes of the four-wave kernel's critical path: a stage executed twice (1 cube wave's solver numbers, 2 M / RNE
-#endif                  // waves' arm meshes, 3 robot wave's H_eq assembly) -- a stage off the critical path costs nothing when doubled
 
 #include <type_traits>
 #include <hip/hip_runtime.h>
@@ -395,31 +392,30 @@ struct Robot {
 constexpr int LDS_M = 0;                              // packed lower triangle of M                     (78 slots)
 constexpr int LDS_HEQ = NB * (NB + 1) / 2;            // H_eq = M + J^T D J over the equality (and weld) rows  (78 slots)
 constexpr int LDS_SLOTS = 2 * (NB * (NB + 1) / 2);
-// two-wave variant (SplitA / helper_substep): factor of M + hB, its reciprocal pivots, and q published for the helper wave
+// three-wave Reach kernel (SplitMainLocal / helper_substep): factor of M + hB, its reciprocal pivots, and q, qd published for the side waves
 constexpr int LDS_FAC = LDS_SLOTS, LDS_FDINV = LDS_FAC + NB * (NB + 1) / 2, LDS_QB = LDS_FDINV + NB, LDS_QDB = LDS_QB + NB;
 constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM + NB, LDS_IKT = LDS_QLAG + 6;      // LDS_WARM: qacc_warmstart parked between sub-steps; LDS_QLAG: q of the last forward pass; LDS_IKT: the IK controller's six ctrl increments of a control step, handed from the RNE wave to the main wave (two slots spare)
-// The hand-over of the remote solve (SplitMain::solve_remote: the RNE wave solves the constraint system).  In EVERY sub-step the main wave
+// The hand-over of the remote solve (SplitMainCols: the RNE wave solves the equality rows' system).  In EVERY sub-step the main wave
 // parks its eight actuation forces (RACT: dofs 0..5, 6, 8 -- the other four are exactly zero) as soon as it has them and the constraint
 // part of g0 (RG0, 12) likewise, and reads them back after S2 if it solves itself: neither stays in registers across the rows and the
-// assembly of H_eq.  In a remote sub-step it adds D, aref, sign of the limit rows 6 and 8 (RLIM, 6) before S2, and the RNE wave leaves
-// the acceleration a in RA (12) before S3.  Lifetimes of the slots borrowed:
-//   RLIM, RA in WARM: only the general iteration reads the warm start, a remote sub-step never runs it, and the Euler step after S3 writes
-//                     the slots again (with a: what the RNE wave left there, or zero in a lane that was reset) before the next sub-step
-//                     could fall back and read them; the RNE wave reads RLIM before it writes RA;
+// assembly of H_eq.  In a remote sub-step the RNE wave leaves abar in RA (12) before S3; the main wave keeps D, aref, sign of the limit
+// rows 6 and 8 in registers and finishes the gear rows itself.  Lifetimes of the slots borrowed:
+//   RA in WARM:       only the general iteration reads the warm start, a remote sub-step never runs it, and the Euler step after S3 writes
+//                     the slots again (with a: from what the RNE wave left there, or zero in a lane that was reset) before the next
+//                     sub-step could fall back and read them;
 //   RACT = IKT:       the IK increments are live between the control-step barriers C1 and C2 only, the sub-steps run after C2;
 //   RG0:              slots of its own.
-// (helper_cols: RLIM is not used, the main wave keeps the six numbers and finishes the gear rows itself; RA then holds abar.)
-constexpr int LDS_RLIM = LDS_WARM, LDS_RA = LDS_WARM, LDS_RACT = LDS_IKT, LDS_RG0 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_RG0 + NB;
+constexpr int LDS_RA = LDS_WARM, LDS_RACT = LDS_IKT, LDS_RG0 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_RG0 + NB;
 constexpr int RACT_DOF[8] = {0, 1, 2, 3, 4, 5, 6, 8};                       // the dofs an actuator drives
 static_assert(LDS_RA + NB == LDS_QLAG && LDS_RACT >= LDS_QLAG + 6 && LDS_RACT + 8 <= LDS_RG0,
               "the remote solve's hand-over must stay inside the warm-start and IK-increment slots (the lagged q between them is live)");
 static_assert(LDS_SLOTS_SPLIT * 64 * sizeof(real) <= 160 * 1024, "the split Reach kernel's LDS exceeds the 160 KB of a gfx950 workgroup");
-// The sines and cosines of a sub-step, each evaluated by one of the three waves (SplitMain::trig_once), are exchanged between S1 and S1t in the
+// The sines and cosines of a sub-step, each evaluated by one of the three waves (trig_exchange), are exchanged between S1 and S1t in the
 // FACTOR slots: the main wave's last read of the factor (after S3) comes before it reaches the next S1, and the helper's next write comes
 // after the next S2, by which every wave has read its sines and cosines -- the two uses never overlap.
 constexpr int LDS_SN = LDS_FAC, LDS_CS = LDS_SN + NB;
 static_assert(LDS_SN >= LDS_FAC && LDS_CS + NB <= LDS_FDINV + NB && LDS_FDINV + NB == LDS_QB, "the sine / cosine exchange must lie inside the factor slots");
-// The gear rows' columns z6 = H^-1 e_6, z8 = H^-1 e_8 (SplitMainCols::helper_cols: the helper wave solves them between S2 and S3, the main
+// The gear rows' columns z6 = H^-1 e_6, z8 = H^-1 e_8 (SplitMainCols::cols: the helper wave solves them between S2 and S3, the main
 // wave reads them after S3).  Under that policy the main wave factors M + hB itself and nobody writes the factor slots, so the columns
 // take 24 of them, behind the sine / cosine exchange: written after S2 and read before the next S1, they never meet it either.
 constexpr int LDS_Z6 = LDS_CS + NB, LDS_Z8 = LDS_Z6 + NB;
@@ -434,11 +430,7 @@ static_assert(LDS_Z6 == LDS_FAC + 24 && LDS_Z6 >= LDS_SN + NB && LDS_Z6 >= LDS_C
 template <class A, class B> MCG_DEV std::common_type_t<A, B> sel(bool c, A a, B b) { return c ? a : b; }
 template <class T> MCG_DEV T sel3(int idx, T a, T b, T c) { return idx == 0 ? a : (idx == 1 ? b : c); }
 
-#ifdef MCG_GENERIC_LDS
-typedef real* LdsPtr;
-#else
 typedef __attribute__((address_space(3))) real* LdsPtr;
-#endif
 template <int STRIDE>
 struct LaneScratchT {
   LdsPtr base;
@@ -450,12 +442,10 @@ struct LaneScratchT {
 typedef LaneScratchT<64> LaneScratch;
 
 // One physics sub-step (mj_step) of the 12-dof robot.  `qlag` receives the positions the forward pass used.
-// Coupling hook: PickAndPlace passes an object that, when a finger pad touches the cube, solves the robot and cube
-// accelerations together (the Euler step needs no constraint force: M a carries it).  Reach passes NoCoupling (compiled out).
-struct NoCoupling { static constexpr bool enabled = false, publishes = false; };
-struct NoSideWork { MCG_DEV void operator()(const real*, const real*) const {} };      // what a helper / RNE wave does after its own share
-// A hook with `publishes` (and not `enabled`) is handed the Newton system's smooth right-hand side and the limit rows once they are
-// complete: the four-wave PickAndPlace kernel parks them in LDS for the cooperative coupled solve (mcg_coop.hpp).
+// Coupling hook: a hook with `publishes` is handed the Newton system's smooth right-hand side and the limit rows once they are
+// complete: the four-wave PickAndPlace kernel parks them in LDS for the cooperative coupled solve (mcg_coop.hpp), which solves the
+// robot and cube accelerations together when a finger pad touches the cube.  Reach passes NoCoupling (compiled out).
+struct NoCoupling { static constexpr bool publishes = false; };
 
 // Mocap weld (mocap controller, mycobot.py:172-189; mocap.xml:15-20): six equality rows pull gripper_tcp to the mocap
 // body's pose.  NoWeld compiles the rows out (joint / IK controllers).
@@ -671,47 +661,43 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // has two more waves over the same 64 environments.  The HELPER wave computes what depends on the joint angles alone -- M by
 // the composite rigid body pass, then the L^T D L factor of M + hB for the Euler step; the RNE wave computes the bias forces;
 // the main wave does actuation and constraint rows meanwhile, then H_eq, the Newton solve and the Euler step.  The same workgroup
-// barriers in every sub-step, for every wave (S1t: see trig_once):
+// barriers in every sub-step, for every wave:
 //   S1  q(t), qd(t) are published in LDS      (the other waves may read them)
-//   S2  M(t) and passive - bias are in LDS    (main wave: g0, H_eq, Newton solve; remote sub-step: the RNE wave does, see solve_remote)
+//   S1t the sub-step's twelve sines and cosines are: each wave has evaluated four of them (trig_exchange)
+//   S2  M(t) and passive - bias are in LDS    (main wave: g0, H_eq, Newton solve; cols, remote sub-step: the RNE wave does)
 //   S3  the factor of M + hB is in LDS        (main wave: a' = a - h (M + hB)^-1 (B a), which equals (M + hB)^-1 M a)
-//       (helper_cols: abar and the gear rows' columns are; the main wave has factored M + hB itself meanwhile)
-// A split policy says which pieces other waves provide and where the exchange slots are.
-// early_heq: the J^T D J part of H_eq is assembled (and the constraint part of g0 formed) BEFORE barrier S2, while the main wave
-// would otherwise wait for M; build_H then adds M on the fly.
-// warm_lds: qacc_warmstart lives in LDS slots WARM.. between sub-steps instead of in registers.  The closed-form limit solve does not
+//       (cols: abar and the gear rows' columns are; the main wave has factored M + hB itself meanwhile)
+// A split policy says which pieces other waves provide and where the exchange slots are.  Four policies exist:
+//   NoSplit         one wave does everything (grids of more than one workgroup per CU; MCG_NO_SPLIT).
+//   SplitMainLocal  the three-wave Reach kernel of the IK and mocap controllers: the main wave solves in every sub-step.
+//   SplitMainCols   the three-wave Reach kernel of the joint controller: remote solve and helper columns (cols, below).
+//   SplitPnp        the robot wave of the four-wave PickAndPlace kernel (mcg_hip.hip).
+// enabled: M and passive - bias come from other waves through LDS (barriers S1, S2); the J^T D J part of H_eq is assembled (and the
+// constraint part of g0 formed) BEFORE barrier S2, while this wave would otherwise wait for M; build_H then adds M on the fly.
+// reach: the three-wave Reach kernel.  The sines and cosines go through the exchange; the factor of M + hB comes from another wave
+// (barrier S3); qacc_warmstart lives in LDS slots WARM.. between sub-steps instead of in registers.  The closed-form limit solve does not
 // read it; only the rare general iteration does -- but in registers it stays live through the factorisation, the kernel's register peak.
 // With it the Euler step also re-reads q(t), qd(t) from the slots they were published in for the other waves (QB, QDB) instead of
 // carrying them through the solve, and the lagged configuration (q of this forward pass, for observations and IK) goes to slots QLAG.
-// solve_remote (round 7; it replaces round 5's limit_cols, where both waves factored the same H and a fourth barrier, S2b, handed the
-// columns z6, z8 over): in a sub-step where no lane of the wave violates a limit row other than the gear joints' (6, 8: every fresh
-// episode starts on them) -- no limit row at all included -- the RNE wave, whose registers are empty after S2 and which holds
-// passive - bias already, does the whole constraint solve: H = H_eq + M built and factored once, solved for abar, z6, z8, the closed-form
-// limit solve, and the acceleration a left in LDS before S3.  The main wave parks what only it has before S2 (slots LDS_RG0 / LDS_RACT /
-// LDS_RLIM) and does nothing between S2 and S3.  The main wave decides from the limit signs it holds, the RNE wave from the q slots with
-// the same compares (no_other_rows); the helper wave does not need to know.  Any other violated row: the main wave solves as without the
-// flag and the RNE wave goes straight to S3.
-// helper_cols (round 8, on top of solve_remote): the serial stretch after S2 is spread over all three waves.  The helper wave solves the
-// gear rows' columns z6, z8 from its own factor of H (no limit row active: the RNE wave's H), in EVERY sub-step, into the slots LDS_Z6 /
-// LDS_Z8; the RNE wave's remote solve ends at abar; the main wave factors M + hB itself between S2 and S3 (after its own solve in a
-// sub-step that is not remote) and keeps the factor in registers, and after S3 a remote sub-step reads abar, finishes the gear rows
-// from the columns (gear_rows_solve, from D / aref / sign it kept in registers) and takes the Euler step.  Nothing is handed over in
-// the factor slots or through LDS_RLIM any more.
-// trig_once (round 6): the sub-step's twelve sines and cosines are evaluated once instead of once per wave: after S1 the main wave takes
-// joints 0..3, the helper 4..7, the RNE wave 8..11, and a barrier S1t hands all twenty-four to every wave through the slots LDS_SN /
-// LDS_CS (trig_exchange).
-struct NoSplit { static constexpr bool enabled = false, rne_remote = false, factor_remote = false, early_heq = false, warm_lds = false, mesh_split = false, solve_remote = false,
-                                       trig_once = false, helper_cols = false;
-                 static constexpr int QB = 0, QDB = 0, FS = 0, WARM = 0, QLAG = 0; };
-struct SplitMain { static constexpr bool enabled = true, rne_remote = true, factor_remote = true, early_heq = true, warm_lds = true, mesh_split = false, solve_remote = true,
-                                         trig_once = true, helper_cols = false;
-                   static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
-// The main wave solves in every sub-step (which controller's kernel takes which policy: step_reach_kernel, and DESIGN.md section 5).
-struct SplitMainLocal : SplitMain { static constexpr bool solve_remote = false; };
-struct SplitMainCols : SplitMain { static constexpr bool helper_cols = true; };        // the joint controller's kernel (round 8)
-struct SplitMainOwnTrig : SplitMain { static constexpr bool trig_once = false; };      // every wave its own twelve (round 5), for A/B builds
+// mesh_split: the other waves run a mesh phase between the barriers S1b, S1c and S2 (see robot_substep).
+// cols (on top of reach): in a sub-step where no lane of the wave violates a limit row other than the gear joints' (6, 8: every fresh
+// episode starts on them) -- no limit row at all included -- the sub-step is REMOTE: the RNE wave, whose registers are empty after S2 and
+// which holds passive - bias already, builds H = H_eq + M, factors it once and solves for abar, left in LDS_RA before S3.  The main wave
+// parks what only it has before S2 (slots LDS_RG0 / LDS_RACT) and decides from the limit signs it holds, the RNE wave from the q slots
+// with the same compares (no_other_rows); the helper wave does not need to know.  Any other violated row: the main wave solves as
+// SplitMainLocal's does and the RNE wave goes straight to S3.  In EVERY sub-step the helper wave solves the gear rows' columns z6, z8
+// from its own factor of H (no limit row active: the RNE wave's H) into the slots LDS_Z6 / LDS_Z8, and the main wave factors M + hB
+// itself between S2 and S3 (after its own solve in a sub-step that is not remote) and keeps the factor in registers; after S3 a remote
+// sub-step reads abar, finishes the gear rows from the columns (gear_rows_solve, from D / aref / sign it kept in registers) and takes
+// the Euler step.  Nothing is handed over in the factor slots.
+// History: round 5 split the limit solve's columns behind a fourth barrier, S2b; round 6 added the sine / cosine
+// exchange; round 7 moved the whole solve to the RNE wave (kept for the joint controller only); round 8 added the helper columns.
+struct NoSplit { static constexpr bool enabled = false, reach = false, mesh_split = false, cols = false; };
+struct SplitMainLocal { static constexpr bool enabled = true, reach = true, mesh_split = false, cols = false;
+                        static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
+struct SplitMainCols : SplitMainLocal { static constexpr bool cols = true; };
 
-// A wave's share of the exchange (trig_once): joints FIRST .. FIRST + 3 (`q_of(i)`: the wave's copy of q_i), stored, then -- S1t -- all
+// A wave's share of the exchange (reach): joints FIRST .. FIRST + 3 (`q_of(i)`: the wave's copy of q_i), stored, then -- S1t -- all
 // twenty-four read back.  sincos_cw is explicit fma's throughout: the same bits whichever wave evaluates it.
 template <int FIRST, class LS, class QF>
 MCG_DEV void trig_exchange(const LS MS, QF q_of, real* sn, real* cs) {
@@ -724,19 +710,19 @@ MCG_DEV void trig_exchange(const LS MS, QF q_of, real* sn, real* cs) {
 }
 
 // H_eq + M (the equality rows' system, from LDS) plus D on the diagonal of the limit rows in act_.  One function for every wave that
-// factors it: the RNE wave's remote solve (solve_remote) must give the very same L and dinv as the main wave's.
+// factors it: the RNE wave's remote solve (cols) must give the very same L and dinv as the main wave's.
 template <class SPL, class LS>
 MCG_DEV void build_H(const LS MS, real* H, const bool* act_, const real* Dl) {
   static_for<NB>([&](auto I) { constexpr int i = I;
     static_for<i + 1>([&](auto Jj) { constexpr int j = Jj;
       if constexpr (PAT_E.nz[i][j]) {
         H[tri(i, j)] = MS.ld(LDS_HEQ + tri(i, j));
-        if constexpr (SPL::early_heq && PAT_M.nz[i][j]) H[tri(i, j)] += MS.ld(LDS_M + tri(i, j));
+        if constexpr (SPL::enabled && PAT_M.nz[i][j]) H[tri(i, j)] += MS.ld(LDS_M + tri(i, j));
       } else if constexpr (PAT_H.nz[i][j]) H[tri(i, j)] = 0.0; }); });
   static_for<10>([&](auto I) { constexpr int j = I; H[tri(j, j)] += act_[j] ? Dl[j] : 0.0; });
 }
 
-// A sub-step is remote (solve_remote) when no lane of the wave has a violated limit row on a joint other than the gear joints 6 and 8.
+// A sub-step is remote (cols) when no lane of the wave has a violated limit row on a joint other than the gear joints 6 and 8.
 // The RNE wave's side of that decision, from the q slots (the waves of a workgroup cover the same lanes and read the same q): the same
 // compares as the limit rows of robot_substep, from which the main wave decides.
 template <class SPL, class LS>
@@ -793,7 +779,7 @@ MCG_DEV void gear_rows_solve(real* x, const real* z6, const real* z8, real Dl6, 
 }
 
 // The L^T D L factor of M + hB for the Euler step, from M in LDS (after S2); damp returns the twelve damping coefficients.  One function for
-// the helper wave (helper_substep) and the main wave (helper_cols).
+// the helper wave (helper_substep) and the main wave (cols).
 template <class LS>
 MCG_DEV void factor_m_hb(ModelPtr Pm, const LS MS, real h, real* Mh, real* dinv, real* damp) {
   static_for<NB>([&](auto I) { constexpr int i = I;
@@ -802,8 +788,8 @@ MCG_DEV void factor_m_hb(ModelPtr Pm, const LS MS, real h, real* Mh, real* dinv,
   ldl_factor<PAT_M>(Mh, dinv);
 }
 
-// COMMIT = false: the new q / qd / qacc_warmstart go to *next and S stays as it was (speculative sub-step of the two-wave
-// PickAndPlace kernel: discarded when the helper wave's collision pass finds a pad contact).
+// COMMIT = false: the new q / qd / qacc_warmstart go to *next and S stays as it was (speculative sub-step of the four-wave
+// PickAndPlace kernel's robot wave: redone with the coupled acceleration in a lane the cube wave's collision pass flags).
 // mj_checkPos / mj_checkVel / mj_checkAcc [RECALL]: a coordinate that is not finite or beyond 1e10 makes mj_step call mj_resetData
 MCG_DEV bool bad_value(real x) { return !(fabs(x) <= 1e10); }
 
@@ -815,18 +801,18 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   if constexpr (SPL::enabled) __syncthreads();                     // S1
   const real h = launder(Pm)->timestep;
   real cs[NB], sn[NB];
-  if constexpr (SPL::trig_once) trig_exchange<0>(MS, [&](auto I) { return S.q[I]; }, sn, cs);
+  if constexpr (SPL::reach) trig_exchange<0>(MS, [&](auto I) { return S.q[I]; }, sn, cs);
   else {
     const TrigC T = load_trig();
     static_for<NB>([&](auto I) { constexpr int i = I; sincos_cw(T, AXS[i] * S.q[i], sn[i], cs[i]); });
   }
-  if constexpr (!(SPL::warm_lds && !CPL::enabled)) static_for<6>([&](auto I) { constexpr int i = I; qlag6[i] = S.q[i]; });      // (else: to LDS at the end of the sub-step)
+  if constexpr (!SPL::reach) static_for<6>([&](auto I) { constexpr int i = I; qlag6[i] = S.q[i]; });      // (else: to LDS at the end of the sub-step)
   static_for<NB>([&](auto I) { constexpr int i = I; pin(sn[i]); pin(cs[i]); });
   MCG_FENCE();
 
   MCG_TICK(ST_TRIG);
   real fs[NB];        // becomes qfrc_smooth = passive - bias + actuation
-  if constexpr (SPL::rne_remote) { static_for<NB>([&](auto I) { constexpr int i = I; fs[i] = 0; }); }   // a third wave computes it meanwhile
+  if constexpr (SPL::enabled) { static_for<NB>([&](auto I) { constexpr int i = I; fs[i] = 0; }); }   // the RNE wave computes it meanwhile
   else rne_bias(Pm, cs, sn, S.qd, fs);
   MCG_TICK(ST_RNE);
   // ---- P7 actuation                                                             (mj_fwdActuation)
@@ -846,11 +832,11 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     fs[6] += c0 * f; fs[8] += c1 * f;
   }
   static_for<NB>([&](auto I) { constexpr int i = I; pin(fs[i]); });
-  if constexpr (SPL::solve_remote) static_for<8>([&](auto K) { constexpr int k = K; MS.st(LDS_RACT + k, fs[RACT_DOF[k]]); });      // read back after S2, by this wave or the RNE wave
+  if constexpr (SPL::cols) static_for<8>([&](auto K) { constexpr int k = K; MS.st(LDS_RACT + k, fs[RACT_DOF[k]]); });      // read back after S2, by this wave or the RNE wave
   MCG_FENCE();
 
   MCG_TICK(ST_ACT);
-  if constexpr (!SPL::enabled) crb_to_lds(Pm, cs, sn, MS);        // two-wave variant: the helper wave does it meanwhile
+  if constexpr (!SPL::enabled) crb_to_lds(Pm, cs, sn, MS);        // split kernels: the helper wave does it meanwhile
   MCG_TICK(ST_CRB);
   // ---- P5 constraint rows                                                   (mj_makeConstraint)
   // arm joint axes expressed in the link6 frame (for the tiny arm columns of the connect rows)
@@ -1040,33 +1026,25 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   if constexpr (WLD::enabled)
     static_for<6>([&](auto Rr) { constexpr int r = Rr; const real da = Dw[r / 3] * arefw[r];
       static_for<6>([&](auto I) { constexpr int j = I; g0[j] = fma(Jw[r][j], da, g0[j]); }); });
-  if constexpr (SPL::solve_remote) static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RG0 + i, g0[i]); });      // the constraint part, parked (see LDS_RG0)
-  if constexpr (SPL::early_heq) assemble_heq(std::false_type{});      // J^T D J only: M is not there yet
-#if MCG_DUP == 3        // critical-path probe: the robot wave's assembly twice (same numbers to the same slots)
-  if constexpr (SPL::early_heq && SPL::mesh_split) { MCG_FENCE(); static_for<2>([&](auto Sd) { constexpr int sd = Sd; pin(Dc[sd]); }); assemble_heq(std::false_type{}); }
-#endif
+  if constexpr (SPL::cols) static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RG0 + i, g0[i]); });      // the constraint part, parked (see LDS_RG0)
+  if constexpr (SPL::enabled) assemble_heq(std::false_type{});      // J^T D J only: M is not there yet
   // Four-wave PickAndPlace kernel: M and passive - bias are in LDS at S1b already; S1c and S2 only fence the other three waves' mesh
   // phase and solver numbers.  When the workgroup HAS a mesh phase (some lane's candidate mask is set: the same masks every wave reads)
   // this wave runs its whole solve now, under it, and passes S1c / S2 when it is done; when it has none the solve stays behind S2, where
   // it runs beside the cube wave's own solve as before.
-  // solve_remote: the RNE wave has the two parts of g0 apart (RG0, RACT: parked above) and forms g0c + (actuation + (passive - bias)),
-  // the association of the sums below; a remote sub-step adds the gear rows' numbers
+  // cols: the RNE wave has the two parts of g0 apart (RG0, RACT: parked above) and forms g0c + (actuation + (passive - bias)),
+  // the association of the sums below
   bool remote = false;                                             // wave-uniform
-  if constexpr (SPL::solve_remote) {
-    static_assert(!CPL::enabled && !SPL::mesh_split && SPL::rne_remote && SPL::factor_remote && SPL::early_heq && SPL::warm_lds,
-                  "the remote solve replaces the direct solve of the three-wave Reach kernel; a coupled solve would skip it");
+  if constexpr (SPL::cols) {
     bool other = false;
     static_for<10>([&](auto I) { constexpr int j = I; if constexpr (j != 6 && j != 8) other = other || (sgl[j] != 0); });
     remote = !__any(other);
-    if (remote) {
 #ifdef MCG_STAGE_CLOCKS      // counted here for the RNE wave's solve, in the slots of the direct solve
+    if (remote) {
       MCG_COUNT(CN_NEWTON_IT);
       if (__any(sgl[6] != 0 || sgl[8] != 0)) MCG_COUNT(CN_LINESEARCH);
-#endif
-      if constexpr (!SPL::helper_cols)                              // (helper_cols: this wave finishes the gear rows itself, after S3)
-      static_for<2>([&](auto Sd) { constexpr int j = 6 + 2 * Sd;
-        MS.st(LDS_RLIM + 3 * Sd, Dl[j]); MS.st(LDS_RLIM + 3 * Sd + 1, arefl[j]); MS.st(LDS_RLIM + 3 * Sd + 2, sgl[j]); });
     }
+#endif
   }
   bool ahead = false;
   if constexpr (SPL::enabled) {
@@ -1075,17 +1053,17 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
       ahead = __any(MS.ld(SPL::MASK0) != 0.0 || MS.ld(SPL::MASK0 + 1) != 0.0 || MS.ld(SPL::MASK0 + 2) != 0.0);
       if (!ahead) { __syncthreads(); __syncthreads(); }             // S1c, S2
     } else __syncthreads();                                         // S2: M and passive - bias are in LDS
-    if constexpr (SPL::solve_remote) {
+    if constexpr (SPL::cols) {
       if (!remote) {                                                // this wave solves: its parked parts back, summed as below
         static_for<NB>([&](auto I) { constexpr int i = I; fs[i] = 0; g0[i] = MS.ld(LDS_RG0 + i); });
         static_for<8>([&](auto K) { constexpr int k = K; fs[RACT_DOF[k]] = MS.ld(LDS_RACT + k); });
         static_for<NB>([&](auto I) { constexpr int i = I; fs[i] += MS.ld(SPL::FS + i); });
       }
-    } else if constexpr (SPL::rne_remote) static_for<NB>([&](auto I) { constexpr int i = I; fs[i] += MS.ld(SPL::FS + i); });
+    } else static_for<NB>([&](auto I) { constexpr int i = I; fs[i] += MS.ld(SPL::FS + i); });
   }
   static_for<NB>([&](auto I) { constexpr int i = I; g0[i] += fs[i]; });      // (remote: not read again)
   if constexpr (CPL::publishes) CP->publish(g0, Dl, arefl, sgl, S.qd, S.warm, !ahead);
-  if constexpr (!SPL::early_heq) assemble_heq(std::true_type{});
+  if constexpr (!SPL::enabled) assemble_heq(std::true_type{});
   auto build_H = [&](real* H, const bool* act_) { mcg::build_H<SPL>(MS, H, act_, Dl); };
 
   MCG_TICK_PIN(g0, NB);
@@ -1094,7 +1072,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   // Wave-uniform loop; a lane that has converged keeps recomputing its own (unchanged) system and commits nothing.
   real a[NB];
   bool act[10];
-  if constexpr (SPL::warm_lds && !CPL::enabled) {     // the warm start is read below, and only if the general iteration runs
+  if constexpr (SPL::reach) {     // the warm start is read below, and only if the general iteration runs
     static_for<NB>([&](auto I) { constexpr int i = I; a[i] = 0; });
     static_for<10>([&](auto I) { constexpr int j = I; act[j] = false; });
   } else {
@@ -1102,14 +1080,6 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     static_for<10>([&](auto I) { constexpr int j = I; act[j] = (sgl[j] != 0) && (sgl[j] * a[j] - arefl[j] < 0); });
   }
   bool conv = remote;                                  // remote sub-step: neither solve below runs, a arrives after S3
-  if constexpr (CPL::enabled) {
-    if (__any(CP->any_pad)) {     // wave-uniform: every lane of the wave takes the coupled path (same minimiser)
-      MCG_TICK(ST_G0);
-      CP->template solve_coupled_call<SPL::early_heq>(g0, Dl, arefl, sgl, S.qd, a);      // out of line, on copies (mcg_cube.hpp)
-      conv = true;
-      MCG_TICK(ST_COUPLED);
-    }
-  }
   // Direct solve (the usual case: at most two violated limit rows per lane -- in practice the two gear joints, which start
   // every episode ON their lower limit, qpos0 = range[0] = 0).  A limit row is J = +-e_j, so with Z = H_eq^-1 the minimiser is
   //   a = abar - sum_s z_s sg_s nu_s,   abar = Z g0,  z_s = Z e_{j_s},  nu_s = D_s r_s on active rows (r_s < 0), else 0,
@@ -1167,7 +1137,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     }
   }
   // General iteration (three or more violated limit rows in some lane of the wave: arm or finger limits, rare)
-  if constexpr (SPL::warm_lds && !CPL::enabled) {
+  if constexpr (SPL::reach) {
     if (__any(!conv)) {
       static_for<NB>([&](auto I) { constexpr int i = I; a[i] = MS.ld(SPL::WARM + i); });
       static_for<10>([&](auto I) { constexpr int j = I; act[j] = (sgl[j] != 0) && (sgl[j] * a[j] - arefl[j] < 0); });
@@ -1246,9 +1216,8 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   MCG_TICK(ST_NEWTON);
   // ---- constraint forces -> qfrc_constraint; P10 implicit-damping Euler                  (mj_Euler, mj_advance)
   real rhs[NB];
-  real q_pre[NB], qd_pre[NB];                                         // helper_cols: q(t), qd(t) back from their slots before S3
-  if constexpr (SPL::helper_cols) {
-    static_assert(SPL::solve_remote && SPL::factor_remote, "helper_cols moves pieces of the remote solve and of the remote factor");
+  real q_pre[NB], qd_pre[NB];                                         // cols: q(t), qd(t) back from their slots before S3
+  if constexpr (SPL::cols) {
     real Lf[NB * (NB + 1) / 2], dinv[NB], damp[NB];
     factor_m_hb(Pm, MS, h, Lf, dinv, damp);                         // remote: beside the other waves' solves; else after this wave's own
     // what the integration below needs besides a: read (and the lagged q parked) while this wave has slack before S3, not after it
@@ -1272,21 +1241,13 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = damp[i] * a[i]; });
     ldl_solve<PAT_M>(Lf, dinv, rhs);
     static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = fma(-h, rhs[i], a[i]); });
-  } else if constexpr (SPL::factor_remote) {
-    real damp[NB];
-    if constexpr (SPL::solve_remote) {      // a remote sub-step only waits here: the damping's batch of s_loads flies during the wait
-      if (remote) { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; damp[i] = Q->body[i].damping; }); }
-    }
-    __syncthreads();                                                // S3: the helper's factor of M + hB is in LDS (remote: and the RNE wave's a)
+  } else if constexpr (SPL::reach) {
+    __syncthreads();                                                // S3: the helper's factor of M + hB is in LDS
     MCG_TICK(ST_M_S3);
-    if constexpr (SPL::solve_remote) { if (remote) static_for<NB>([&](auto I) { constexpr int i = I; a[i] = MS.ld(LDS_RA + i); }); }
     real Lf[NB * (NB + 1) / 2], dinv[NB];
     static_for<NB>([&](auto I) { constexpr int i = I; dinv[i] = MS.ld(LDS_FDINV + i);
       static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) Lf[tri(i, j)] = MS.ld(LDS_FAC + tri(i, j)); }); });
-    if constexpr (SPL::solve_remote) {
-      if (!remote) { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; damp[i] = Q->body[i].damping; }); }
-      static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = damp[i] * a[i]; });
-    } else { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = Q->body[i].damping * a[i]; }); }      // one batch of s_loads
+    { ModelPtr Q = launder(Pm); static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = Q->body[i].damping * a[i]; }); }      // one batch of s_loads
     ldl_solve<PAT_M>(Lf, dinv, rhs);
     static_for<NB>([&](auto I) { constexpr int i = I; rhs[i] = fma(-h, rhs[i], a[i]); });
   } else {
@@ -1297,8 +1258,8 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   bool bad = false;
   static_for<NB>([&](auto I) { constexpr int i = I;
     real q_old, qd_old;
-    if constexpr (SPL::helper_cols) { q_old = q_pre[i]; qd_old = qd_pre[i]; }
-    else if constexpr (SPL::warm_lds && !CPL::enabled) { q_old = MS.ld(SPL::QB + i); qd_old = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_old); }
+    if constexpr (SPL::cols) { q_old = q_pre[i]; qd_old = qd_pre[i]; }
+    else if constexpr (SPL::reach) { q_old = MS.ld(SPL::QB + i); qd_old = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_old); }
     else { q_old = S.q[i]; qd_old = S.qd[i]; }
     qdn[i] = fma(h, rhs[i], qd_old); qn[i] = fma(h, qdn[i], q_old);
     if constexpr (COMMIT) bad = bad || bad_value(qn[i]) || bad_value(qdn[i]) || bad_value(a[i]); });
@@ -1313,42 +1274,35 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   }
   static_for<NB>([&](auto I) { constexpr int i = I;
     const real qd_new = qdn[i], q_new = qn[i];
-    if constexpr (COMMIT) { S.qd[i] = qd_new; S.q[i] = q_new; if constexpr (SPL::warm_lds && !CPL::enabled) MS.st(SPL::WARM + i, a[i]); else S.warm[i] = a[i]; }
+    if constexpr (COMMIT) { S.qd[i] = qd_new; S.q[i] = q_new; if constexpr (SPL::reach) MS.st(SPL::WARM + i, a[i]); else S.warm[i] = a[i]; }
     else { next->qd[i] = qd_new; next->q[i] = q_new; next->warm[i] = a[i]; }
     if constexpr (SPL::enabled && COMMIT) { MS.st(SPL::QB + i, q_new); MS.st(SPL::QDB + i, qd_new); } });
   MCG_TICK_PIN(S.q, NB); MCG_TICK_PIN(S.qd, NB);
   MCG_TICK(ST_EULER);
-  if constexpr (SPL::enabled && SPL::mesh_split) { if (ahead) { __syncthreads(); __syncthreads(); } }      // S1c, S2
+  if constexpr (SPL::mesh_split) { if (ahead) { __syncthreads(); __syncthreads(); } }      // S1c, S2
   return bad;
 }
 
-// A side wave's sines and cosines after S1: through the exchange (trig_once: this wave evaluates joints FIRST .. FIRST + 3), or all twelve
-// from the q slots.
+// A side wave's sines and cosines after S1, through the exchange: this wave evaluates joints FIRST .. FIRST + 3.
 template <class SPL, int FIRST, class LS>
 MCG_DEV void side_trig(const LS MS, real* sn, real* cs) {
-  if constexpr (SPL::trig_once) trig_exchange<FIRST>(MS, [&](auto I) { return MS.ld(SPL::QB + I); }, sn, cs);
-  else {
-    const TrigC T = load_trig();
-    static_for<NB>([&](auto I) { constexpr int i = I; sincos_cw(T, AXS[i] * MS.ld(SPL::QB + i), sn[i], cs[i]); });
-  }
+  trig_exchange<FIRST>(MS, [&](auto I) { return MS.ld(SPL::QB + I); }, sn, cs);
   static_for<NB>([&](auto I) { constexpr int i = I; pin(sn[i]); pin(cs[i]); });
   MCG_FENCE();
 }
 
-// The helper wave's share of one sub-step (see SplitMain).
-template <class SPL = SplitMain, class LS, class SIDE = NoSideWork>
-MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
+// The helper wave's share of one sub-step of the three-wave Reach kernel (SplitMainLocal / SplitMainCols).
+template <class SPL, class LS>
+MCG_DEV void helper_substep(ModelPtr Pm, const LS MS) {
   __syncthreads();                                                  // S1
   MCG_TICK(ST_H_S1);
   real cs[NB], sn[NB];
   side_trig<SPL, 4>(MS, sn, cs);
   crb_to_lds(Pm, cs, sn, MS);
-  static_assert(!SPL::mesh_split, "the four-wave PickAndPlace kernel drives its side waves itself: helper_pre / rne_pre");
-  (void)side;
   MCG_TICK(ST_H_CRB);
   __syncthreads();                                                  // S2
   MCG_TICK(ST_H_S2);
-  if constexpr (SPL::helper_cols) {
+  if constexpr (SPL::cols) {
     // In every sub-step, remote or not (no predicate: this wave cannot disagree with another about anything): H_eq + M with no limit row
     // active, factored, and the two unit solves -- the functions the RNE wave's solve calls, in the same order, so the very same L and dinv.
     real L[NB * (NB + 1) / 2], dinv[NB], z6[NB], z8[NB];
@@ -1362,7 +1316,7 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
     MCG_TICK(ST_H_COLS);
     __syncthreads();                                                // S3
     MCG_TICK(ST_H_S3);
-  } else if constexpr (SPL::factor_remote) {
+  } else {
     const real h = launder(Pm)->timestep;
     real Mh[NB * (NB + 1) / 2], dinv[NB], damp[NB];
     factor_m_hb(Pm, MS, h, Mh, dinv, damp);
@@ -1374,9 +1328,9 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{})
   }
 }
 
-// The RNE wave's share of one sub-step (see SplitMain).
-template <class SPL = SplitMain, class LS, class SIDE = NoSideWork>
-MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
+// The RNE wave's share of one sub-step of the three-wave Reach kernel (SplitMainLocal / SplitMainCols).
+template <class SPL, class LS>
+MCG_DEV void rne_substep(ModelPtr Pm, const LS MS) {
   __syncthreads();                                                  // S1
   MCG_TICK(ST_Q_S1);
   real cs[NB], sn[NB], qd[NB], fs[NB];
@@ -1385,18 +1339,16 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
   rne_bias(Pm, cs, sn, qd, fs);
   static_for<NB>([&](auto I) { constexpr int i = I; MS.st(SPL::FS + i, fs[i]); });
   bool remote = false;
-  if constexpr (SPL::solve_remote) {
+  if constexpr (SPL::cols) {
     remote = no_other_rows<SPL>(Pm, MS);
     static_for<NB>([&](auto I) { constexpr int i = I; pin(fs[i]); });      // the sum below takes passive - bias as the main wave reads it
     MCG_FENCE();                                                           // from LDS: rounded, no product of rne_bias contracted into the add
   }
-  static_assert(!SPL::mesh_split, "the four-wave PickAndPlace kernel drives its side waves itself: helper_pre / rne_pre");
-  (void)side;
   MCG_TICK(ST_Q_BIAS);
   __syncthreads();                                                  // S2
   MCG_TICK(ST_Q_S2);
-  if constexpr (SPL::solve_remote) {
-    if (remote) {                                                   // wave-uniform: the whole constraint solve (see SplitMain)
+  if constexpr (SPL::cols) {
+    if (remote) {                                                   // wave-uniform: the equality rows' solve (see SplitMainCols)
       // H_eq + M with no limit row active, x = g0, factor, solve: the direct solve of robot_substep, by the same functions in the same order
       real L[NB * (NB + 1) / 2], dinv[NB], x[NB];
       const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
@@ -1407,22 +1359,11 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS, const SIDE& side = SIDE{}) {
       static_for<NB>([&](auto I) { constexpr int i = I; x[i] = MS.ld(LDS_RG0 + i) + (x[i] + fs[i]); });
       ldl_factor<PAT_H>(L, dinv);
       ldl_solve<PAT_H>(L, dinv, x);
-      if constexpr (!SPL::helper_cols) {                            // (helper_cols: the solve ends at abar, the main wave finishes the gear rows)
-      const real Dl6 = MS.ld(LDS_RLIM), arefl6 = MS.ld(LDS_RLIM + 1), sgl6 = MS.ld(LDS_RLIM + 2);
-      const real Dl8 = MS.ld(LDS_RLIM + 3), arefl8 = MS.ld(LDS_RLIM + 4), sgl8 = MS.ld(LDS_RLIM + 5);
-      if (__any(sgl6 != 0 || sgl8 != 0)) {                          // wave-uniform: a gear row in some lane
-        real z6[NB], z8[NB];
-        ldl_solve_unit<PAT_H, 6>(L, dinv, z6);
-        ldl_solve_unit<PAT_H, 8>(L, dinv, z8);
-        static_for<NB>([&](auto I) { constexpr int i = I; pin(z6[i]); pin(z8[i]); });      // as values read back from LDS: nothing contracted into them
-        gear_rows_solve(x, z6, z8, Dl6, arefl6, sgl6, Dl8, arefl8, sgl8);
-      }
-      }
-      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RA + i, x[i]); });
+      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RA + i, x[i]); });      // abar: the main wave finishes the gear rows
       MCG_TICK(ST_Q_COLS);
     }
   }
-  if constexpr (SPL::factor_remote) __syncthreads();                // S3
+  __syncthreads();                                                  // S3
   MCG_TICK(ST_Q_S3);
 }
 

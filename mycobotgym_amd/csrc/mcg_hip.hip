@@ -155,24 +155,14 @@ MCG_DEV void mocap_target(const Cfg& C, ModelPtr P, const real* qlag6, const flo
   normalize4(W.quat);
 }
 
-// The controllers whose three-wave kernel lets the RNE wave solve the constraint system (SplitMain::solve_remote), as a bit mask over
-// MCG_CTRL_*; the others' main wave solves in every sub-step (SplitMainLocal).  A build flag so that one tree gives both sides of an A/B.
-#ifndef MCG_SOLVE_REMOTE_CTRLS
-#define MCG_SOLVE_REMOTE_CTRLS (1 << MCG_CTRL_JOINT)
-#endif
-// Of those, the controllers whose helper wave solves the gear rows' columns while the main wave factors M + hB (SplitMainCols::helper_cols,
-// round 8); 0 builds round 7's kernels.
-#ifndef MCG_HELPER_COLS_CTRLS
-#define MCG_HELPER_COLS_CTRLS (1 << MCG_CTRL_JOINT)
-#endif
-
-// SPLIT: three waves per 64 environments (see SplitMain in mcg_dynamics.hpp): launched when the grid has at most one workgroup
-// per CU, where the extra waves run on SIMDs that would idle.  160 KB of LDS per workgroup (LDS_SLOTS_SPLIT).
+// SPLIT: three waves per 64 environments (see SplitMainLocal in mcg_dynamics.hpp): launched when the grid has at most one workgroup
+// per CU, where the extra waves run on SIMDs that would idle.  160 KB of LDS per workgroup (LDS_SLOTS_SPLIT).  The joint controller's
+// kernel lets the RNE wave solve the equality rows' system and the helper wave the gear rows' columns (SplitMainCols); the IK and mocap
+// kernels' main wave solves in every sub-step (SplitMainLocal): measured per controller, DESIGN.md section 5.
 template <int CONTROLLER, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, View V, const mcg_model* __restrict__ Pg,
                                                                       const float* __restrict__ actions, mcg_step_out O) {
-  typedef std::conditional_t<SPLIT, std::conditional_t<(MCG_SOLVE_REMOTE_CTRLS >> CONTROLLER) & 1,
-                                                      std::conditional_t<(MCG_HELPER_COLS_CTRLS >> CONTROLLER) & 1, SplitMainCols, SplitMain>, SplitMainLocal>, NoSplit> Split;
+  typedef std::conditional_t<SPLIT, std::conditional_t<CONTROLLER == MCG_CTRL_JOINT, SplitMainCols, SplitMainLocal>, NoSplit> Split;
   __shared__ real lds[SPLIT ? LDS_SLOTS_SPLIT : LDS_SLOTS][64];
   const int lane = threadIdx.x & 63;
   const LaneScratch MS(&lds[0][lane]);
@@ -488,12 +478,11 @@ MCG_DEV void hide_object(real* obs, real* ag) {
 // resets the robot's new state).  mj_resetData resets BOTH bodies; the other body follows one sub-step late here.
 // Exchange slots: mcg_coop.hpp.
 constexpr int XCH_FS = PNP_SLOTS;                 // + 12 slots, then the mesh phase's twelve (MP_CUBE ..), then four of the parked limit rows
-constexpr int PNP_SLOTS_DUAL = PNP_SLOTS_LDS;
-static_assert(PNP_SLOTS_DUAL * PNP_LANES * 8 <= 160 * 1024, "LDS of a CU");
+static_assert(PNP_SLOTS_LDS * PNP_LANES * 8 <= 160 * 1024, "LDS of a CU");
 // robot-side split of the four-wave PickAndPlace kernel: M from the helper wave, passive - bias from the RNE wave, the constraint
 // part of H_eq assembled before barrier S2; the Euler step stays with M a (no room for the factor in LDS)
-struct SplitPnp { static constexpr bool enabled = true, rne_remote = true, factor_remote = false, early_heq = true, warm_lds = false, mesh_split = true, solve_remote = false, trig_once = false, helper_cols = false;
-                  static constexpr int QB = XCH_Q, QDB = XCH_QD, FS = XCH_FS, WARM = 0, QLAG = 0, MASK0 = MP_MASK; };
+struct SplitPnp { static constexpr bool enabled = true, reach = false, mesh_split = true, cols = false;
+                  static constexpr int QB = XCH_Q, QDB = XCH_QD, FS = XCH_FS, MASK0 = MP_MASK; };
 
 MCG_DEV bool flag_coupled(real f) { return (((int)f) & 2) != 0; }       // XCH_FLAG: bit 1 = the environment goes to the cooperative solve,
 MCG_DEV bool flag_cube_bad(real f) { return (((int)f) & 8) != 0; }      // bit 3 = the cube failed mj_checkPos / mj_checkVel / mj_checkAcc
@@ -502,7 +491,7 @@ MCG_DEV bool flag_cube_bad(real f) { return (((int)f) & 8) != 0; }      // bit 3
 // cube wave has published the flags (after S2): only the flagged lanes are parked; else (the robot wave runs ahead of the mesh phase)
 // every lane is
 struct PubHook {
-  static constexpr bool enabled = false, publishes = true;
+  static constexpr bool publishes = true;
   const PnpScratch S;
   MCG_DEV void publish(const real* g0, const real* Dl, const real* arefl, const real* sgl, const real* qd, const real* warm, bool flags_known) const {
     const bool flag = !flags_known || flag_coupled(S.ld(XCH_FLAG));
@@ -713,8 +702,7 @@ MCG_DEV void pnp_side_wave(ModelPtr P, const real* __restrict__ poly, const PnpS
 template <int CONTROLLER>
 __global__ __launch_bounds__(256) void step_pnp_kernel(Cfg C, View V, const mcg_model* __restrict__ Pg, const real* __restrict__ poly,
                                                        const float* __restrict__ actions, mcg_step_out O) {
-  constexpr bool DUAL = true;                    // (the one-wave variant of rounds 1-2 went with the lane-parallel coupled solve)
-  __shared__ __attribute__((aligned(16))) real lds[PNP_SLOTS_DUAL][PNP_LANES];
+  __shared__ __attribute__((aligned(16))) real lds[PNP_SLOTS_LDS][PNP_LANES];
   // four waves over 32 environments: robot, cube, helper (M), RNE.  The robot wave runs on 32 lanes; the other three keep lanes 32-63
   // for the cooperative phase (two environments per wave there) and mask them off everywhere else (`lower`)
   if (threadIdx.x >= PNP_LANES && threadIdx.x < 64) return;
@@ -729,16 +717,14 @@ __global__ __launch_bounds__(256) void step_pnp_kernel(Cfg C, View V, const mcg_
   const bool valid = i_raw < C.n;
   const int nvalid = min(PNP_LANES, C.n - (int)blockIdx.x * PNP_LANES);
   const unsigned lds0 = (unsigned)(uintptr_t)(LdsPtr)&lds[0][0];
-  if constexpr (DUAL) {
-    if (threadIdx.x >= 64) {
-      const int total = (CONTROLLER == MCG_CTRL_IK ? C.control_steps : 1) * C.frame_skip;
-      if (threadIdx.x < 128) {
-        CubeWaveArgs A; for (int k = 0; k < 7; k++) A.qpos0_cube[k] = C.qpos0_cube[k];
-        A.cnt = C.cnt; A.coop_pair = C.coop_pair; A.nvalid = nvalid;
-        cube_wave(A, V, P, poly, MS, lds0, i, total, lower);
-      } else pnp_side_wave(P, poly, MS, lds0, total, threadIdx.x >= 192, lower, C.coop_pair != 0, lower ? V.dr(1, i) : 1.0, nvalid);
-      return;
-    }
+  if (threadIdx.x >= 64) {
+    const int total = (CONTROLLER == MCG_CTRL_IK ? C.control_steps : 1) * C.frame_skip;
+    if (threadIdx.x < 128) {
+      CubeWaveArgs A; for (int k = 0; k < 7; k++) A.qpos0_cube[k] = C.qpos0_cube[k];
+      A.cnt = C.cnt; A.coop_pair = C.coop_pair; A.nvalid = nvalid;
+      cube_wave(A, V, P, poly, MS, lds0, i, total, lower);
+    } else pnp_side_wave(P, poly, MS, lds0, total, threadIdx.x >= 192, lower, C.coop_pair != 0, lower ? V.dr(1, i) : 1.0, nvalid);
+    return;
   }
   MCG_TICK_INIT();
 #ifdef MCG_STAGE_CLOCKS
@@ -748,10 +734,9 @@ __global__ __launch_bounds__(256) void step_pnp_kernel(Cfg C, View V, const mcg_
   load_envp(V, i, E);
   const bool bad0 = guard_robot(E.R, E.qlag6);   // the state as loaded (a caller may have set it): mj_step's first check
   bool hadbad = bad0;
-  if constexpr (DUAL) { static_for<NB>([&](auto I) { constexpr int k = I; MS.st(XCH_Q + k, E.R.q[k]); MS.st(XCH_QD + k, E.R.qd[k]); });   // q(0), qd(0) for the other waves
-                        MS.st(XCH_T1, hadbad ? 1.0 : 0.0);
-                        MS.st(XCH_ACT0, 0.0); MS.st(XCH_ACT1, 0.0);         // no active set carried into an env-step (mcg_coop.hpp: coop_guess)
-                      }
+  static_for<NB>([&](auto I) { constexpr int k = I; MS.st(XCH_Q + k, E.R.q[k]); MS.st(XCH_QD + k, E.R.qd[k]); });   // q(0), qd(0) for the other waves
+  MS.st(XCH_T1, hadbad ? 1.0 : 0.0);
+  MS.st(XCH_ACT0, 0.0); MS.st(XCH_ACT1, 0.0);         // no active set carried into an env-step (mcg_coop.hpp: coop_guess)
   MCG_TICK(ST_LOAD);
   E.touch = false;
   int nsub = 0;
@@ -794,12 +779,10 @@ __global__ __launch_bounds__(256) void step_pnp_kernel(Cfg C, View V, const mcg_
     MCG_TICK(ST_CTRL);
     for (int s = 0; s < C.frame_skip; s++) substep(NoWeld{});
   }
-  if constexpr (DUAL) {                          // take the cube back from the cube wave
-    __syncthreads();
-    cube_from_lds(MS, E.Cb);
-    for (int k = 0; k < 7; k++) E.qlag7[k] = MS.ld(XCH_QL7 + k);
-    E.touch = MS.ld(XCH_T0) != 0.0;
-  }
+  __syncthreads();                               // take the cube back from the cube wave
+  cube_from_lds(MS, E.Cb);
+  for (int k = 0; k < 7; k++) E.qlag7[k] = MS.ld(XCH_QL7 + k);
+  E.touch = MS.ld(XCH_T0) != 0.0;
   hadbad |= guard_robot(E.R, E.qlag6);
   count_event(C, 1, hadbad && valid);
   int i_tail = i; asm volatile("" : "+v"(i_tail));      // recompute the state rows' addresses for the tail (see step_reach_kernel)
@@ -897,7 +880,7 @@ __global__ __launch_bounds__(PNP_LANES) void reset_pnp_kernel(Cfg C, View V, con
 // per 32 environments: lanes 0-31 the lane-parallel part (the cube wave's and the M / RNE waves' shares), all 64 the mesh phase.
 __global__ __launch_bounds__(64) void contacts_pnp_kernel(Cfg C, View V, const mcg_model* __restrict__ Pg, const real* __restrict__ poly, int32_t* __restrict__ count,
                                                           int32_t* __restrict__ dropped, double* __restrict__ data) {
-  __shared__ real lds[PNP_SLOTS_DUAL][PNP_LANES];
+  __shared__ real lds[PNP_SLOTS_LDS][PNP_LANES];
   const int lane = threadIdx.x & (PNP_LANES - 1);
   const bool lower = threadIdx.x < PNP_LANES;
   const int i_raw = blockIdx.x * PNP_LANES + lane;
@@ -1229,7 +1212,7 @@ static int launch_step(mcg_env* e, const float* actions, const mcg_step_out& o, 
     return hipGetLastError() == hipSuccess ? MCG_OK : MCG_ERR_HIP;
   }
   dim3 grid((e->cfg.n + 63) / 64);
-  // up to one workgroup per CU three SIMDs of every CU would idle: the two-wave variant puts a helper wave on one of them
+  // up to one workgroup per CU three SIMDs of every CU would idle: the three-wave variant puts a helper and an RNE wave on two of them
   const bool split = (int)grid.x <= e->num_cu && !e->no_split;
   const dim3 block(split ? 192 : 64);
 #define MCG_LAUNCH_REACH(CTRL)                                                                                                 \

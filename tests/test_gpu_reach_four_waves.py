@@ -1,7 +1,7 @@
 """GPU parity of one Reach sub-step on fast, wide states: the pieces whose inputs change waves in the split Reach kernels.
 
 Since round 6 the three waves of a split Reach workgroup evaluate each joint's sine and cosine once and exchange them through LDS
-(SplitMain::trig_once): everything downstream -- M from the composite pass, the Coriolis / centrifugal bias, the connect rows -- is
+(SplitMainLocal::reach, trig_exchange): everything downstream -- M from the composite pass, the Coriolis / centrifugal bias, the connect rows -- is
 built from values another wave computed.  (The round also tried a fourth wave for the gripper dofs' rows of M; DESIGN.md section 5
 says why it was left out.  The file keeps the name the round's plan gave it.)  The existing per-sub-step parity tests run near the
 reset pose at servo speeds, where gravity and actuation dominate qacc.  Here the arm angles are uniform within 98 % of their ranges

@@ -1,4 +1,4 @@
-"""GPU parity of the joint controller's three-wave Reach kernel with the gear rows' columns on the helper wave (SplitMainCols::helper_cols).
+"""GPU parity of the joint controller's three-wave Reach kernel with the gear rows' columns on the helper wave (SplitMainCols::cols).
 
 Between the barriers S2 and S3 of every sub-step the helper wave factors H and solves the columns z6 = H^-1 e_6, z8 = H^-1 e_8 into 24
 slots of the factor region, the RNE wave's remote solve ends at the unconstrained acceleration, and the main wave factors M + hB

@@ -1,4 +1,4 @@
-"""GPU parity of the split Reach kernels' remote constraint solve (SplitMain::solve_remote) where it meets the other paths.
+"""GPU parity of the split Reach kernels' remote constraint solve (SplitMainCols::cols) where it meets the other paths.
 
 In a sub-step where no lane of a wave violates a limit row other than the gear joints' (dofs 6 and 8), the RNE wave builds and factors
 H, solves for the acceleration and the two columns of the closed-form limit solve, and hands the acceleration to the main wave through
