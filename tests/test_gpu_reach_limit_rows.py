@@ -9,6 +9,8 @@ full workgroups and a ragged third of 37 lanes, flagged lanes in all three.
 import numpy as np
 import pytest
 
+from tests import limit_row_states as ls
+
 pytestmark = pytest.mark.gpu
 
 N = 165
@@ -22,8 +24,13 @@ def torch_cuda(built):
     return torch
 
 
-def _state(ora, kind, rng):
-    """The oracle's state after a reset and two random steps, with the gear / arm angles of `kind` written into qpos."""
+def _state(ora, kind, rng, controller="joint"):
+    """The oracle's state after a reset and two random steps, with the gear / arm angles of `kind` written into qpos.  The families of
+    tests/limit_row_states.py (finger rows, lower arm limits, five rows in a lane) are written by that module, on `controller`'s ranges."""
+    if kind in ls.FAMILIES:
+        ls.put(ora, kind, rng, ls.jnt_range(controller))                 # asserts its own census
+        q = ora.get_state()["qpos"]
+        return int((q[:, 6] < GEAR_LO).sum()), int((q[:, 8] < GEAR_LO).sum())
     s = ora.get_state()
     q, qd = s["qpos"].copy(), s["qvel"].copy()
     i = np.arange(q.shape[0])
@@ -46,29 +53,41 @@ def _state(ora, kind, rng):
     return n6, n8
 
 
-def _run(controller, kind, frame_skip):
-    from tests.common import make_pair, sync_oracle_to, step_errors
+def _run(controller, kind, frame_skip, twin=False):
+    """Worst errors against the oracle over the step from the `kind` state and the one after it: dict(obs, q, v, w).  `twin`: also the
+    oracle's own sensitivity on the same states and actions (a second oracle started +-1e-14 away on qpos), under the keys twin_obs, twin_q,
+    twin_v, twin_w; and the engine's bad-state counter over the two steps under `bad_state_resets`."""
+    from tests.common import make_oracle, make_pair, sync_oracle_to, step_errors
     kw = dict(controller_type=controller, reward_type="dense", seed=21, max_episode_steps=10 ** 9, frame_skip=frame_skip)
     if controller == "IK" and frame_skip == 1: kw["control_steps"] = 1
     envs, ora = make_pair(N, **kw)
     envs.reset(seed=21); ora.reset(seed=21)
     rng = np.random.default_rng(5)
     worst = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
+    if twin:
+        two = make_oracle(N, **kw); two.reset(seed=21)
+        prng = np.random.default_rng(7)
+        worst.update(twin_obs=0.0, twin_q=0.0, twin_v=0.0, twin_w=0.0)
     for t in range(3):
         a = rng.uniform(-1, 1, (N, envs.action_dim)).astype(np.float32)
         if t == 1:
-            n6, n8 = _state(ora, kind, rng)
-            if kind != "none": assert n6 > 0 and (kind == "gear6" or n8 > 0)
-            else: assert n6 == 0 and n8 == 0
+            n6, n8 = _state(ora, kind, rng, controller)
+            if kind == "none": assert n6 == 0 and n8 == 0
+            elif kind not in ls.FAMILIES: assert n6 > 0 and (kind == "gear6" or n8 > 0)
+            if twin: envs.counters(clear=True)
         sync_oracle_to(envs, ora)
+        before = ora.get_state() if twin and t > 0 else None
         e, flags_equal, o = step_errors(envs, ora, a)
         assert flags_equal
         if t == 0: continue
+        if twin:
+            for k, v in ls.twin_state_errors(two, before, a, ora, o, prng).items(): worst["twin_" + k] = max(worst["twin_" + k], v)
         st, so = envs.get_state(), ora.get_state()
         worst["obs"] = max(worst["obs"], float(e.max()))
         worst["q"] = max(worst["q"], float(np.abs(st["qpos"].cpu().numpy().T - so["qpos"]).max()))
         worst["v"] = max(worst["v"], float(np.abs(st["qvel"].cpu().numpy().T - so["qvel"]).max()))
         worst["w"] = max(worst["w"], float(np.abs(st["warm"].cpu().numpy().T - so["warm"]).max()))
+    if twin: worst["bad_state_resets"] = envs.counters()["bad_state_resets"]
     envs.close()
     print(f"\n{controller} {kind} frame_skip={frame_skip}: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
     return worst
