@@ -24,6 +24,7 @@
  *                       pictures, every picture stored once and a time-limit end kept apart from a termination
  *   mcg_replay_img_sample_stacked, mcg_frame_stack_push   SB3's VecFrameStack on those pictures: stacks rebuilt from the single-frame
  *                       ring when a batch is sampled, and the stack a policy acts on, updated in one launch per step
+ *   mcg_rollout_img_carry_stacked / _gather_stacked   the same stacks for the on-policy buffer, rebuilt from its single stored frames
  *   mcg_get_state / mcg_set_state   direct access to data.qpos/qvel/ctrl/qacc_warmstart (set_joint_qpos etc.)
  *
  * Conventions: every pointer in the step/reset/state calls is DEVICE memory owned by the caller;
@@ -552,6 +553,34 @@ int mcg_rollout_img_carry(const mcg_rollout_img_buf* buf, int pos, void* stream)
    row `step`, environment env.  All byte offsets are 64-bit; no address and no loop bound depends on stored content. */
 int mcg_rollout_img_gather(const mcg_rollout_img_buf* buf, uint64_t seed, uint64_t epoch, int64_t first, int64_t count,
                            const mcg_rollout_img_batch* out, void* stream);
+
+/* ---- Stacks of k = frame_stack frames (the frame stacking section below: slot s of a stack is channels s * C .. s * C + C - 1, slot
+   k - 1 the newest) gathered from the single stored frames.  The struct and mcg_rollout_img_start / _add / _gae are unchanged and run
+   on rows 0 .. T as before.  The contract of the two entries below: with frame_stack = k the caller guarantees k - 1 valid rows
+   before `pixels` (rows -(k - 1) .. -1, N * P bytes each) and k - 1 valid rows before `episode_start` (N bytes each) -- the history:
+   the last k - 1 pictures of the previous rollout and their flags -- and passes pointers to row 0, as always.
+     flag of a row   row t of environment e is the first picture of its episode iff its flag is 1: episode_start[t, e] for t < pos
+                     (t < 0: a history row), last_start[e] for row pos.
+     stack(t)        slot k - 1 - i holds the picture of row t - i for i = 0, 1, ... up to and including the first row whose flag
+                     is 1, at most k - 1 steps back; the older slots are zeros.
+
+   The carry between two rollouts: pixel rows pos - (k - 1) .. pos go to rows -(k - 1) .. 0 and episode_start rows
+   pos - (k - 1) .. pos - 1 to rows -(k - 1) .. -1, one launch; last_start stays as it is.  Source and destination overlap where
+   pos < k (a short or an unfinished rollout): a lane owns one 16-byte position of one environment in all k rows, loads them all and
+   only then stores, and likewise one lane per environment its k - 1 flag bytes.  pos = 0: nothing to do, no launch.
+   frame_stack = 1 does what mcg_rollout_img_carry does.  Refused (MCG_ERR_ARG) beyond what mcg_rollout_img_carry refuses:
+   frame_stack outside [1, 8]. */
+int mcg_rollout_img_carry_stacked(const mcg_rollout_img_buf* buf, int pos, int frame_stack, void* stream);
+
+/* mcg_rollout_img_gather with `pix` / `pix_f32` as stacks: the same permutation, planes, record and `index`; the rows of pix and
+   pix_f32 are k * Pu long, and sample k, transition (env, step), takes stack(step) of a full rollout (pos = T).  A slot before the
+   episode's start is written as zeros and its source is not read; every byte of the outputs given is written.  frame_stack = 1 gives
+   mcg_rollout_img_gather's outputs bit for bit.  No address and no loop bound depends on stored content beyond the walk back: the
+   k - 1 <= 7 flags of rows step, step - 1, ... of the sample's environment (their addresses depend on the permutation alone) are
+   loaded together and tested up to the first 1.  All byte offsets are 64-bit.  Refused (MCG_ERR_ARG) beyond what
+   mcg_rollout_img_gather refuses: frame_stack outside [1, 8]. */
+int mcg_rollout_img_gather_stacked(const mcg_rollout_img_buf* buf, int frame_stack, uint64_t seed, uint64_t epoch, int64_t first,
+                                   int64_t count, const mcg_rollout_img_batch* out, void* stream);
 
 /* ---- Off-policy replay buffer of pictures (SB3's ReplayBuffer, which SAC, TD3 and DDPG train from, scripts/train.py:62, 102-104, on
    what MyCobotImgEnv observes: the uint8 picture [C, S, S] alone).  Stateless as mcg_her_* and mcg_rollout_img_*: the caller owns all

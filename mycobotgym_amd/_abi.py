@@ -288,7 +288,7 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_her_record_bytes", "mcg_her_start", "mcg_her_add", "mcg_her_sample",
            "mcg_rollout_record_bytes", "mcg_rollout_start", "mcg_rollout_add", "mcg_rollout_gae", "mcg_rollout_gather",
            "mcg_rollout_img_record_bytes", "mcg_rollout_img_start", "mcg_rollout_img_add", "mcg_rollout_img_gae", "mcg_rollout_img_carry",
-           "mcg_rollout_img_gather",
+           "mcg_rollout_img_gather", "mcg_rollout_img_carry_stacked", "mcg_rollout_img_gather_stacked",
            "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample",
            "mcg_replay_img_sample_stacked", "mcg_frame_stack_push")
 
@@ -362,6 +362,10 @@ def load():
         L.mcg_rollout_img_gae.argtypes = [img, C.c_void_p, C.c_void_p]
         L.mcg_rollout_img_carry.argtypes = [img, C.c_int, C.c_void_p]
         L.mcg_rollout_img_gather.argtypes = [img, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(McgRolloutImgBatch), C.c_void_p]
+    if hasattr(L, "mcg_rollout_img_gather_stacked"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_rollout_img_carry_stacked.argtypes = [C.POINTER(McgRolloutImgBuf), C.c_int, C.c_int, C.c_void_p]
+        L.mcg_rollout_img_gather_stacked.argtypes = [C.POINTER(McgRolloutImgBuf), C.c_int, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64,
+                                                     C.POINTER(McgRolloutImgBatch), C.c_void_p]
     if hasattr(L, "mcg_replay_img_sample"):  # absent only from older builds selected through MCG_LIB for A/B timing
         rimg = C.POINTER(McgReplayImgBuf)
         L.mcg_replay_img_record_bytes.argtypes = [C.c_int]; L.mcg_replay_img_record_bytes.restype = C.c_int64

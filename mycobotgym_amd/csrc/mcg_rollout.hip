@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <utility>
 
 #include "mcg.h"
 #include "mcg_buffer.hpp"        // what the replay buffer has too: launched, record_bytes, carry, copy_phase; philox4x32_10
@@ -23,6 +24,7 @@ constexpr int ROLLOUT_STREAM = 4;       // Philox stream of the permutation (0: 
 constexpr int FEISTEL_ROUNDS = 4;
 constexpr int ADD_LANES = 256;
 constexpr int GAE_LANES = 64;           // lane = environment and nothing is shared: one wave per block spreads 8192 environments over 128 CUs
+constexpr int MAX_FRAME_STACK = 8;      // frames of a stack that the picture buffer's stacked entries rebuild (mcg_frame_stack_push's limit)
 
 struct Layout {                          // word indices inside a record: obs at 0
   int D, A, w_ach, w_des, w_act, w_logp, words;
@@ -284,6 +286,32 @@ __global__ __launch_bounds__(ADD_LANES) void img_carry_kernel(Roll B, Pix X, int
   to[x] = to[(size_t)row * n16 + x];
 }
 
+// The carry of a buffer that hands out stacks of k frames: pixel rows pos - (k - 1) .. pos go to rows -(k - 1) .. 0 and episode_start
+// rows pos - (k - 1) .. pos - 1 to rows -(k - 1) .. -1 (rows before row 0: the caller's history rows).  Source and destination overlap
+// where pos < k, so this is frame_stack_push_kernel's in-place shift: a lane owns one 16-byte position of one environment in all k
+// rows, loads them all and only then stores; no other lane touches that position in any row.  After the pixels one lane per
+// environment does the same with its k - 1 flag bytes.  Row offsets are signed and 64-bit.  The rows a lane holds are a pack expansion
+// over I = 0 .. K - 1 of the compiler's own 16-byte vector type: held as HIP's uint4 (a class), more than five rows went to scratch.
+template <class V, int... I>
+MCG_DEV void shift_rows(V* at, int pos, long long stride, std::integer_sequence<int, I...>) {
+  const V v[] = {at[(long long)(pos - I) * stride]...};          // row pos - I, every load before the first store
+  ((at[-(long long)I * stride] = v[I]), ...);                    // to row -I
+}
+
+template <int K>
+__global__ __launch_bounds__(ADD_LANES) void img_carry_stacked_kernel(Roll B, Pix X, int pos) {
+  const long long x = (long long)blockIdx.x * ADD_LANES + threadIdx.x, n16 = (long long)B.n * (X.P >> 4);
+  if (x < n16) {
+    typedef unsigned int word16 __attribute__((ext_vector_type(4)));
+    shift_rows(reinterpret_cast<word16*>(X.px) + x, pos, n16, std::make_integer_sequence<int, K>{});
+    return;
+  }
+  const long long e = x - n16;
+  if (e >= B.n) return;
+  if constexpr (K > 1)                   // flag rows pos - 1 .. pos - (K - 1) to rows -1 .. -(K - 1): the same shift, one row further back
+    shift_rows(B.start + e - B.n, pos, (long long)B.n, std::make_integer_sequence<int, K - 1>{});
+}
+
 struct ImgBatch { uint8_t* pix; float *pix_f32, *act, *val, *logp, *adv, *ret; int32_t* index; };
 
 // One sample per wave, four per block: a minibatch of 4096 is 4096 waves, four on every SIMD of the chip, each with its sample's
@@ -330,6 +358,80 @@ __global__ __launch_bounds__(SAMPLE_LANES) void img_gather_kernel(Roll B, Pix X,
         [&](int q, uint32_t v) { reinterpret_cast<float4*>(row)[q] = quotient_255(v); });
     } else {
       each_unit<uint8_t>(lane, X.Pu, [&](int q) { return from[q]; }, [&](int q, uint8_t v) { row[q] = (float)v / 255.0f; });
+    }
+  }
+}
+
+// img_gather_kernel on stacks of k frames rebuilt from the single stored frames: one sample per wave, four per block, the walk, the
+// plane words and the record exactly as there.  Index phase: the flags of rows t, t - 1, .. t - (k - 2) of the sample's environment
+// are loaded together -- their addresses depend on the draw alone (a row before row 0 is one of the caller's history rows), so the
+// phase waits for memory once more, not k - 1 times -- and then tested up to the first episode start: `depth` frames of the stack
+// belong to the sample's episode.  Copy phase: the source picture is the outer loop, slot s = 0 .. k - 1 takes row t - (k - 1 - s) in
+// one full-width pass of each_unit (no unit has to find its picture); a slot before the episode's start is stored as zeros and its
+// source is not loaded.  Every byte of the output row (k * Pu long) is written.  Slot s starts at byte s * Pu of the row, so ALIGN,
+// which divides Pu and the output pointers (store_align), divides every slot's address too.
+template <int ALIGN>
+__global__ __launch_bounds__(SAMPLE_LANES) void img_gather_stacked_kernel(Roll B, Pix X, unsigned long long seed, unsigned long long epoch,
+                                                                          int first, int count, int h, int k, ImgBatch O) {
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * (SAMPLE_LANES / 64) + (threadIdx.x >> 6);   // wave-uniform; the output row of this wave
+  if (j >= count) return;
+  // ---- index phase
+  const uint32_t M = (uint32_t)B.n * (uint32_t)B.T;                     // < 2^31 (host check)
+  const uint32_t x = walk(true, (uint32_t)first + (uint32_t)j, M, h, seed, epoch);
+  const long long t = x % (uint32_t)B.T, e = x / (uint32_t)B.T, n = B.n;
+  const size_t src = (size_t)(t * n + e);            // row in the [T, N] planes; < M
+  uint8_t flag[MAX_FRAME_STACK - 1];
+#pragma unroll
+  for (int i = 0; i < MAX_FRAME_STACK - 1; i++)
+    flag[i] = i < k - 1 ? B.start[(t - i) * n + e] : (uint8_t)1;
+  if (lane == 0) {                       // the sample's plane words
+    const float v = B.val[src], a = B.adv[src], g = B.ret[src];
+    if (O.val) O.val[j] = v;
+    if (O.adv) O.adv[j] = a;
+    if (O.ret) O.ret[j] = g;
+    if (O.index) O.index[j] = (int32_t)x;
+  }
+  const uint32_t* rec = B.rec + src * X.rw;          // and its record: action[A], log_prob
+  if (O.act)
+    for (int w = lane; w < X.A; w += 64) O.act[(size_t)j * X.A + w] = __uint_as_float(rec[w]);
+  if (O.logp && lane == 0) O.logp[j] = __uint_as_float(rec[X.A]);
+  int depth = 1;
+#pragma unroll
+  for (int i = 0; i < MAX_FRAME_STACK - 1; i++)     // row t - i is no episode start: row t - i - 1 belongs to the same episode
+    if (depth == i + 1 && flag[i] == 0) depth = i + 2;
+  depth = __builtin_amdgcn_readfirstlane(depth);    // (every lane holds the same value: the copy loop's branch is a scalar one)
+  // ---- copy phase
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  for (int s = 0; s < k; s++) {
+    const int back = k - 1 - s;
+    const bool live = back < depth;
+    const uint8_t* from = X.px + ((t - back) * n + e) * X.P;
+    const size_t slot = ((size_t)j * k + s) * X.Pu;
+    if (O.pix) {
+      uint8_t* row = O.pix + slot;
+      if (live)
+        each_unit<uint4>(lane, X.P >> 4,
+          [&](int q) { return reinterpret_cast<const uint4*>(from)[q]; },
+          [&](int q, uint4 v) { store_u8<ALIGN>(row, X.Pu, q, v); });
+      else
+        for (int q = lane; q < (X.P >> 4); q += 64) store_u8<ALIGN>(row, X.Pu, q, zero);
+    }
+    if (O.pix_f32) {                     // byte / 255: the correctly rounded float32 quotient (IEEE division, nothing reciprocal)
+      float* row = O.pix_f32 + slot;
+      if constexpr (ALIGN >= 4) {
+        if (live)
+          each_unit<uint32_t>(lane, X.Pu >> 2,
+            [&](int q) { return reinterpret_cast<const uint32_t*>(from)[q]; },
+            [&](int q, uint32_t v) { reinterpret_cast<float4*>(row)[q] = quotient_255(v); });
+        else
+          for (int q = lane; q < (X.Pu >> 2); q += 64) reinterpret_cast<float4*>(row)[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      } else {
+        if (live)
+          each_unit<uint8_t>(lane, X.Pu, [&](int q) { return from[q]; }, [&](int q, uint8_t v) { row[q] = (float)v / 255.0f; });
+        else
+          for (int q = lane; q < X.Pu; q += 64) row[q] = 0.0f;
+      }
     }
   }
 }
@@ -518,6 +620,55 @@ int mcg_rollout_img_gather(const mcg_rollout_img_buf* buf, uint64_t seed, uint64
   const dim3 grid(blocks(count, SAMPLE_LANES / 64)), block(SAMPLE_LANES);
 #define MCG_IMG_GATHER(AL) hipLaunchKernelGGL(img_gather_kernel<AL>, grid, block, 0, (hipStream_t)stream, B, X, (unsigned long long)seed, \
                                               (unsigned long long)epoch, (int)first, (int)count, b / 2, O)
+  switch (align) {
+    case 16: MCG_IMG_GATHER(16); break;
+    case 4: MCG_IMG_GATHER(4); break;
+    default: MCG_IMG_GATHER(1);
+  }
+#undef MCG_IMG_GATHER
+  return launched("mcg_rollout_img");
+}
+
+int mcg_rollout_img_carry_stacked(const mcg_rollout_img_buf* buf, int pos, int frame_stack, void* stream) {
+  const char* who = "mcg_rollout_img_carry_stacked";
+  if (const int rc = check_img(buf, who)) return rc;
+  if (frame_stack < 1 || frame_stack > MAX_FRAME_STACK) return mcg_fail(MCG_ERR_ARG, "%s: frame_stack must be in [1, 8]", who);
+  if (pos < 0 || pos > buf->n_steps) return mcg_fail(MCG_ERR_ARG, "%s: pos outside [0, n_steps]", who);
+  if (pos == 0) return MCG_OK;           // every row is where it belongs already
+  const Roll B = planes(buf);
+  const Pix X = pixels(buf);
+  const dim3 grid(blocks((long long)B.n * (X.P / 16) + B.n, ADD_LANES)), block(ADD_LANES);
+#define MCG_IMG_CARRY(K) case K: hipLaunchKernelGGL(img_carry_stacked_kernel<K>, grid, block, 0, (hipStream_t)stream, B, X, pos); break
+  switch (frame_stack) {
+    MCG_IMG_CARRY(1); MCG_IMG_CARRY(2); MCG_IMG_CARRY(3); MCG_IMG_CARRY(4); MCG_IMG_CARRY(5); MCG_IMG_CARRY(6); MCG_IMG_CARRY(7);
+    MCG_IMG_CARRY(8);
+  }
+#undef MCG_IMG_CARRY
+  return launched("mcg_rollout_img");
+}
+
+int mcg_rollout_img_gather_stacked(const mcg_rollout_img_buf* buf, int frame_stack, uint64_t seed, uint64_t epoch, int64_t first,
+                                   int64_t count, const mcg_rollout_img_batch* out, void* stream) {
+  const char* who = "mcg_rollout_img_gather_stacked";
+  if (const int rc = check_img(buf, who)) return rc;
+  if (frame_stack < 1 || frame_stack > MAX_FRAME_STACK) return mcg_fail(MCG_ERR_ARG, "%s: frame_stack must be in [1, 8]", who);
+  const int64_t M = (int64_t)buf->n_steps * buf->n_envs;
+  if (first < 0) return mcg_fail(MCG_ERR_ARG, "%s: first < 0", who);
+  if (count < 1) return mcg_fail(MCG_ERR_ARG, "%s: count must be >= 1", who);
+  if (first > M || count > M - first) return mcg_fail(MCG_ERR_ARG, "%s: first + count > n_steps * n_envs", who);
+  if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_rollout_img_batch", who);
+  if (!out->pix && !out->pix_f32 && !out->action && !out->old_value && !out->old_log_prob && !out->advantage && !out->returns &&
+      !out->index)
+    return mcg_fail(MCG_ERR_ARG, "%s: all outputs are null", who);
+  int b = 2;
+  while ((1ll << b) < M) b += 2;         // as mcg_rollout_gather
+  const Roll B = planes(buf);
+  const Pix X = pixels(buf);
+  const ImgBatch O = {out->pix, out->pix_f32, out->action, out->old_value, out->old_log_prob, out->advantage, out->returns, out->index};
+  const int align = store_align(X.Pu, (uint64_t)(uintptr_t)out->pix, (uint64_t)(uintptr_t)out->pix_f32);
+  const dim3 grid(blocks(count, SAMPLE_LANES / 64)), block(SAMPLE_LANES);
+#define MCG_IMG_GATHER(AL) hipLaunchKernelGGL(img_gather_stacked_kernel<AL>, grid, block, 0, (hipStream_t)stream, B, X, \
+                                              (unsigned long long)seed, (unsigned long long)epoch, (int)first, (int)count, b / 2, frame_stack, O)
   switch (align) {
     case 16: MCG_IMG_GATHER(16); break;
     case 4: MCG_IMG_GATHER(4); break;
