@@ -398,8 +398,8 @@ constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM
 // The hand-over of the remote solve (SplitMainCols: the RNE wave solves the equality rows' system).  In EVERY sub-step the main wave
 // parks its eight actuation forces (RACT: dofs 0..5, 6, 8 -- the other four are exactly zero) as soon as it has them and the constraint
 // part of g0 (RG0, 12) likewise, and reads them back after S2 if it solves itself: neither stays in registers across the rows and the
-// assembly of H_eq.  In a remote sub-step the RNE wave leaves abar in RA (12) before S3; the main wave keeps D, aref, sign of the limit
-// rows 6 and 8 in registers and finishes the gear rows itself.  Lifetimes of the slots borrowed:
+// assembly of H_eq.  In a remote sub-step the RNE wave leaves abar in RA (12) before S3; the main wave prepares what the limit
+// rows 6 and 8 need of its own numbers before S3 (gear_rows_prepare) and finishes the gear rows itself.  Lifetimes of the slots borrowed:
 //   RA in WARM:       only the general iteration reads the warm start, a remote sub-step never runs it, and the Euler step after S3 writes
 //                     the slots again (with a: from what the RNE wave left there, or zero in a lane that was reset) before the next
 //                     sub-step could fall back and read them;
@@ -421,6 +421,13 @@ static_assert(LDS_SN >= LDS_FAC && LDS_CS + NB <= LDS_FDINV + NB && LDS_FDINV + 
 constexpr int LDS_Z6 = LDS_CS + NB, LDS_Z8 = LDS_Z6 + NB;
 static_assert(LDS_Z6 == LDS_FAC + 24 && LDS_Z6 >= LDS_SN + NB && LDS_Z6 >= LDS_CS + NB && LDS_Z8 == LDS_Z6 + NB && LDS_Z8 + NB <= LDS_QB,
               "the gear rows' columns must lie inside the factor slots, clear of the sine / cosine exchange and of the published q");
+// What the main wave reads and writes around S3 under SplitMainCols -- the columns (Z6, Z8), abar and the warm start (RA = WARM), the
+// published and the lagged state (QB, QDB, QLAG) -- lies within 128 slots, the reach of a ds_ offset field, but beyond it from slot 0:
+// the main wave addresses these through a window of the lane's column that starts at LDS_WIN (LaneScratchT::window).
+constexpr int LDS_WIN = LDS_QLAG + 6 - 128;
+static_assert(LDS_WIN >= 0 && LDS_WIN <= LDS_Z6 && LDS_WIN <= LDS_QB && LDS_QDB + NB <= LDS_WIN + 128 && LDS_RA + NB <= LDS_WIN + 128
+              && LDS_QLAG + 6 <= LDS_WIN + 128 && (128 - 1) * 64 * sizeof(double) < 65536,
+              "the slots of the main wave's window must lie within one 16-bit ds_ offset of its base");
 // The lane's LDS column.  The pointer carries the LDS address space explicitly: passed through structs as a generic
 // pointer the accesses degrade to flat_load/flat_store with 64-bit address arithmetic instead of ds_read/ds_write
 // with immediate offsets.
@@ -438,6 +445,12 @@ struct LaneScratchT {
   MCG_DEV explicit LaneScratchT(LdsPtr column) : base(column) {}
   MCG_DEV real ld(int k) const { return base[k * STRIDE]; }
   MCG_DEV void st(int k, real v) const { base[k * STRIDE] = v; }
+  // The same column seen from slot k0: slot k0 + k of this scratch is slot k of the window.  A ds_ instruction's offset field reaches
+  // 64 KB -- 128 slots of 512 B -- from its address register; for a slot beyond that the compiler re-forms the address in front of the
+  // access (one v_or_b32 with a 32-bit literal each, where registers are short) and pairs nothing.  The window's base is one more
+  // register, opaque to the compiler: the accesses through it are base + immediate, and neighbours merge into ds_read2st64_b64 /
+  // ds_write2st64_b64, whose stride is the slot stride.
+  MCG_DEV LaneScratchT window(int k0) const { LdsPtr p = base + k0 * STRIDE; asm volatile("" : "+v"(p)); return LaneScratchT(p); }
 };
 typedef LaneScratchT<64> LaneScratch;
 
@@ -688,10 +701,13 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // SplitMainLocal's does and the RNE wave goes straight to S3.  In EVERY sub-step the helper wave solves the gear rows' columns z6, z8
 // from its own factor of H (no limit row active: the RNE wave's H) into the slots LDS_Z6 / LDS_Z8, and the main wave factors M + hB
 // itself between S2 and S3 (after its own solve in a sub-step that is not remote) and keeps the factor in registers; after S3 a remote
-// sub-step reads abar, finishes the gear rows from the columns (gear_rows_solve, from D / aref / sign it kept in registers) and takes
-// the Euler step.  Nothing is handed over in the factor slots.
+// sub-step finishes the gear rows from abar and the columns (gear_rows_forces from five of the numbers and from what gear_rows_prepare
+// made of D / aref / sign of rows 6 and 8 before S3, then the columns applied as they are read) and takes the Euler step.  Between S3
+// and the next S1 this wave runs alone, so what can be done before S3 is, and what it touches there goes through the window LDS_WIN.
+// Nothing is handed over in the factor slots.
 // History: round 5 split the limit solve's columns behind a fourth barrier, S2b; round 6 added the sine / cosine
-// exchange; round 7 moved the whole solve to the RNE wave (kept for the joint controller only); round 8 added the helper columns.
+// exchange; round 7 moved the whole solve to the RNE wave (kept for the joint controller only); round 8 added the helper columns; round 10
+// shortened the main wave's stretch after S3.
 struct NoSplit { static constexpr bool enabled = false, reach = false, mesh_split = false, cols = false; };
 struct SplitMainLocal { static constexpr bool enabled = true, reach = true, mesh_split = false, cols = false;
                         static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
@@ -740,9 +756,11 @@ MCG_DEV bool no_other_rows(ModelPtr Pm, const LS MS) {
 
 // The closed-form solve's 2 x 2 complementarity problem over the limit rows in slots 0 and 1 (e0 / e1: the slot holds a row), enumerated
 // in closed form; returns the rows' forces times their signs, f = sg nu.
-MCG_DEV void limit_pair(bool e0, bool e1, real D0, real D1, real s0, real s1, real rb0, real rb1, real W00, real W01, real W11,
-                        real& f0, real& f1) {
-  const real A00 = rcp_nr(D0) + W00, A11 = rcp_nr(D1) + W11;
+// RCP: d0, d1 are 1 / D0, 1 / D1 (rcp_nr) already, where the caller has formed them ahead of the rest (gear_rows_prepare); else D0, D1.
+template <bool RCP>
+MCG_DEV void limit_pair_t(bool e0, bool e1, real d0, real d1, real s0, real s1, real rb0, real rb1, real W00, real W01, real W11,
+                          real& f0, real& f1) {
+  const real A00 = (RCP ? d0 : rcp_nr(d0)) + W00, A11 = (RCP ? d1 : rcp_nr(d1)) + W11;
   const real n0 = rb0 * rcp_nr(A00), n1 = rb1 * rcp_nr(A11);               // one active row
   const real idet = rcp_nr(A00 * A11 - W01 * W01);                          // both active
   const real b0 = (A11 * rb0 - W01 * rb1) * idet, b1 = (A00 * rb1 - W01 * rb0) * idet;
@@ -758,24 +776,42 @@ MCG_DEV void limit_pair(bool e0, bool e1, real D0, real D1, real s0, real s1, re
   nu0 = cN ? 0.0 : nu0; nu1 = cN ? 0.0 : nu1;
   f0 = s0 * nu0; f1 = s1 * nu1;
 }
+MCG_DEV void limit_pair(bool e0, bool e1, real D0, real D1, real s0, real s1, real rb0, real rb1, real W00, real W01, real W11,
+                        real& f0, real& f1) {
+  limit_pair_t<false>(e0, e1, D0, D1, s0, s1, rb0, rb1, W00, W01, W11, f0, f1);
+}
 
-// The closed-form solve when the only limit rows are the gear joints' (remote sub-step): x = abar on entry, a on return; z6 = H^-1 e_6,
-// z8 = H^-1 e_8; D, aref, sign of rows 6 and 8 (sign 0: no row).  The rows sit in slots 0 / 1 as in the direct solve of robot_substep.
-MCG_DEV void gear_rows_solve(real* x, const real* z6, const real* z8, real Dl6, real arefl6, real sgl6, real Dl8, real arefl8, real sgl8) {
-  const bool v6 = sgl6 != 0, v8 = sgl8 != 0, both = v6 && v8;
-  const real D0 = v6 ? Dl6 : (v8 ? Dl8 : 1.0), D1 = both ? Dl8 : 1.0;
-  const real ar0 = v6 ? arefl6 : arefl8, ar1 = both ? arefl8 : 0.0;
-  const real s0 = v6 ? sgl6 : sgl8, s1 = both ? sgl8 : 0.0;
-  const real xa0 = v6 ? x[6] : (v8 ? x[8] : 0.0), xa1 = both ? x[8] : 0.0;
-  real W00 = v6 ? z6[6] : (v8 ? z8[8] : 0.0), W01 = both ? z6[8] : 0.0;
-  const real W11 = both ? z8[8] : 0.0;
-  W01 *= s0 * s1;
-  const real rb0 = s0 * xa0 - ar0, rb1 = s1 * xa1 - ar1;
+// The closed-form solve when the only limit rows are the gear joints' (remote sub-step), in three pieces along what each needs.  The rows
+// sit in slots 0 / 1 as in the direct solve of robot_substep: slot 0 is row 6 where row 6 is violated, else row 8.
+//   gear_rows_prepare  from D, aref, sign of rows 6 and 8 (sign 0: no row) alone, which the main wave holds before S2: the slots'
+//                      D, aref, sign selected, 1 / D0, 1 / D1 and s0 s1.  Runs before S3, in the main wave's slack; pinned, so that
+//                      only these ten values cross the barrier and none of the selects or reciprocal chains sinks below it.
+//   gear_rows_forces   from five numbers that arrive at S3 -- abar[6], abar[8], z6[6], z6[8], z8[8] (z6 = H^-1 e_6, z8 = H^-1 e_8):
+//                      the forces on the two columns.  The other column of a lane with one row enters with a zero force.
+//   the application    x[i] = fma(-z8[i], g8, fma(-z6[i], g6, x[i])), by the caller, row by row as abar and the columns stream in
+//                      (finite z, zero force: exactly x).
+// The same operations on the same operands, in the same order, as when the three were one function.
+struct GearPrep { bool v6, v8, both; real rD0, rD1, ar0, ar1, s0, s1, s01; };
+MCG_DEV GearPrep gear_rows_prepare(real Dl6, real arefl6, real sgl6, real Dl8, real arefl8, real sgl8) {
+  GearPrep G;
+  G.v6 = sgl6 != 0; G.v8 = sgl8 != 0; G.both = G.v6 && G.v8;
+  const real D0 = G.v6 ? Dl6 : (G.v8 ? Dl8 : 1.0), D1 = G.both ? Dl8 : 1.0;
+  G.ar0 = G.v6 ? arefl6 : arefl8; G.ar1 = G.both ? arefl8 : 0.0;
+  G.s0 = G.v6 ? sgl6 : sgl8; G.s1 = G.both ? sgl8 : 0.0;
+  G.s01 = G.s0 * G.s1;
+  G.rD0 = rcp_nr(D0); G.rD1 = rcp_nr(D1);
+  pin(G.rD0); pin(G.rD1); pin(G.ar0); pin(G.ar1); pin(G.s0); pin(G.s1); pin(G.s01);
+  return G;
+}
+MCG_DEV void gear_rows_forces(const GearPrep& G, real a6, real a8, real z66, real z68, real z88, real& g6, real& g8) {
+  const real xa0 = G.v6 ? a6 : (G.v8 ? a8 : 0.0), xa1 = G.both ? a8 : 0.0;
+  real W00 = G.v6 ? z66 : (G.v8 ? z88 : 0.0), W01 = G.both ? z68 : 0.0;
+  const real W11 = G.both ? z88 : 0.0;
+  W01 *= G.s01;
+  const real rb0 = G.s0 * xa0 - G.ar0, rb1 = G.s1 * xa1 - G.ar1;
   real f0, f1;
-  limit_pair(v6 || v8, both, D0, D1, s0, s1, rb0, rb1, W00, W01, W11, f0, f1);
-  // slot 0 is row 6 where row 6 is violated, else row 8; the other column enters with a zero force (finite z: exactly x)
-  const real g6 = v6 ? f0 : 0.0, g8 = v6 ? f1 : f0;
-  static_for<NB>([&](auto I) { constexpr int i = I; x[i] = fma(-z8[i], g8, fma(-z6[i], g6, x[i])); });
+  limit_pair_t<true>(G.v6 || G.v8, G.both, G.rD0, G.rD1, G.s0, G.s1, rb0, rb1, W00, W01, W11, f0, f1);
+  g6 = G.v6 ? f0 : 0.0; g8 = G.v6 ? f1 : f0;
 }
 
 // The L^T D L factor of M + hB for the Euler step, from M in LDS (after S2); damp returns the twelve damping coefficients.  One function for
@@ -1217,24 +1253,49 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   // ---- constraint forces -> qfrc_constraint; P10 implicit-damping Euler                  (mj_Euler, mj_advance)
   real rhs[NB];
   real q_pre[NB], qd_pre[NB];                                         // cols: q(t), qd(t) back from their slots before S3
+  // cols: the slots around S3 through the window (LDS_WIN); every other policy: the column itself
+  constexpr int WIN = SPL::cols ? LDS_WIN : 0;
+  const LS MW = [&] { if constexpr (WIN != 0) return MS.window(WIN); else return MS; }();
   if constexpr (SPL::cols) {
     real Lf[NB * (NB + 1) / 2], dinv[NB], damp[NB];
     factor_m_hb(Pm, MS, h, Lf, dinv, damp);                         // remote: beside the other waves' solves; else after this wave's own
     // what the integration below needs besides a: read (and the lagged q parked) while this wave has slack before S3, not after it
-    static_for<NB>([&](auto I) { constexpr int i = I; q_pre[i] = MS.ld(SPL::QB + i); qd_pre[i] = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_pre[i]); });
+    static_for<NB>([&](auto I) { constexpr int i = I; q_pre[i] = MW.ld(SPL::QB - WIN + i); qd_pre[i] = MW.ld(SPL::QDB - WIN + i); if constexpr (i < 6) MW.st(SPL::QLAG - WIN + i, q_pre[i]); });
     static_for<NB>([&](auto I) { constexpr int i = I; pin(dinv[i]);         // the factor exists BEFORE S3: unpinned, its arithmetic sinks below
       static_for<i>([&](auto Jj) { constexpr int j = Jj; if constexpr (PAT_M.nz[i][j]) pin(Lf[tri(i, j)]); }); });      // the barrier towards its use
+    // ... and so does the part of the gear rows' solve that needs nothing from the other waves (remote sub-step with a gear row in some
+    // lane of the wave: wave-uniform): after S3 only this wave runs, before it this wave waits for the RNE wave
+    GearPrep G = {};
+    bool gear = false;
+    if (remote) {
+      gear = __any(sgl[6] != 0 || sgl[8] != 0);
+      if (gear) G = gear_rows_prepare(Dl[6], arefl[6], sgl[6], Dl[8], arefl[8], sgl[8]);
+    }
     MCG_FENCE();
     MCG_TICK(ST_M_FACTOR);
     __syncthreads();                                                // S3: remote: the RNE wave's abar and the helper's columns are in LDS
     MCG_TICK(ST_M_S3);
     if (remote) {
-      static_for<NB>([&](auto I) { constexpr int i = I; a[i] = MS.ld(LDS_RA + i); });
-      if (__any(sgl[6] != 0 || sgl[8] != 0)) {                      // wave-uniform: a gear row in some lane
-        real z6[NB], z8[NB];
-        static_for<NB>([&](auto I) { constexpr int i = I; z6[i] = MS.ld(LDS_Z6 + i); z8[i] = MS.ld(LDS_Z8 + i); });
-        gear_rows_solve(a, z6, z8, Dl[6], arefl[6], sgl[6], Dl[8], arefl[8], sgl[8]);
-      }
+      if (gear) {
+        // the five numbers of the forces first, then abar and the columns four rows at a time, each batch read while the one before
+        // it is applied: at no point are all thirty-six live next to the factor and the state (which sends them through AGPRs)
+        const real a6 = MW.ld(LDS_RA - WIN + 6), a8 = MW.ld(LDS_RA - WIN + 8);
+        const real z66 = MW.ld(LDS_Z6 - WIN + 6), z68 = MW.ld(LDS_Z6 - WIN + 8), z88 = MW.ld(LDS_Z8 - WIN + 8);
+        real xb[3][4], z6b[3][4], z8b[3][4];
+        auto rows_in = [&](auto B_) { constexpr int b = B_;
+          static_for<4>([&](auto K) { constexpr int k = K; constexpr int i = 4 * b + k;
+            xb[b][k] = (i == 6) ? a6 : (i == 8) ? a8 : MW.ld(LDS_RA - WIN + i);
+            z6b[b][k] = (i == 6) ? z66 : (i == 8) ? z68 : MW.ld(LDS_Z6 - WIN + i);
+            z8b[b][k] = (i == 8) ? z88 : MW.ld(LDS_Z8 - WIN + i); }); };
+        real g6, g8;
+        rows_in(std::integral_constant<int, 0>{});
+        gear_rows_forces(G, a6, a8, z66, z68, z88, g6, g8);
+        pin(g6); pin(g8);
+        static_for<3>([&](auto B_) { constexpr int b = B_;
+          asm volatile("" ::: "memory");                            // the next batch's reads stay behind the one before
+          if constexpr (b + 1 < 3) rows_in(std::integral_constant<int, b + 1>{});
+          static_for<4>([&](auto K) { constexpr int k = K; a[4 * b + k] = fma(-z8b[b][k], g8, fma(-z6b[b][k], g6, xb[b][k])); }); });
+      } else static_for<NB>([&](auto I) { constexpr int i = I; a[i] = MW.ld(LDS_RA - WIN + i); });
       MCG_TICK_PIN(a, NB);
       MCG_TICK(ST_M_GEAR);
     }
@@ -1274,9 +1335,9 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   }
   static_for<NB>([&](auto I) { constexpr int i = I;
     const real qd_new = qdn[i], q_new = qn[i];
-    if constexpr (COMMIT) { S.qd[i] = qd_new; S.q[i] = q_new; if constexpr (SPL::reach) MS.st(SPL::WARM + i, a[i]); else S.warm[i] = a[i]; }
+    if constexpr (COMMIT) { S.qd[i] = qd_new; S.q[i] = q_new; if constexpr (SPL::reach) MW.st(SPL::WARM - WIN + i, a[i]); else S.warm[i] = a[i]; }
     else { next->qd[i] = qd_new; next->q[i] = q_new; next->warm[i] = a[i]; }
-    if constexpr (SPL::enabled && COMMIT) { MS.st(SPL::QB + i, q_new); MS.st(SPL::QDB + i, qd_new); } });
+    if constexpr (SPL::enabled && COMMIT) { MW.st(SPL::QB - WIN + i, q_new); MW.st(SPL::QDB - WIN + i, qd_new); } });
   MCG_TICK_PIN(S.q, NB); MCG_TICK_PIN(S.qd, NB);
   MCG_TICK(ST_EULER);
   if constexpr (SPL::mesh_split) { if (ahead) { __syncthreads(); __syncthreads(); } }      // S1c, S2

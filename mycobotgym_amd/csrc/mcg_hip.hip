@@ -221,7 +221,12 @@ __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, Vie
   load_robot(V, i, E);
   const bool bad0 = guard_robot(E.R, E.qlag6);      // the state as loaded (a caller may have set it): mj_step's first check
   bool hadbad = bad0;
-  if constexpr (SPLIT) static_for<NB>([&](auto I) { constexpr int k = I; MS.st(LDS_QB + k, E.R.q[k]); MS.st(LDS_QDB + k, E.R.qd[k]); MS.st(LDS_WARM + k, E.R.warm[k]); if constexpr (k < 6) MS.st(LDS_QLAG + k, E.qlag6[k]); });   // q(0), qd(0) for the other waves; warm start and lagged q parked
+  // Through the window of these slots (LDS_WIN), here and after the sub-steps, each time from a base of its own: the addresses formed from
+  // the column's base would otherwise be carried, spilled, across the sub-step loop for the reads after it.  Not in the IK kernel, which
+  // is 1.3 % slower with it (measured): there the column's own addresses, as before.
+  constexpr int WIN = (SPLIT && CONTROLLER != MCG_CTRL_IK) ? LDS_WIN : 0;
+  auto state_slots = [&] { if constexpr (WIN != 0) return MS.window(WIN); else return MS; };
+  if constexpr (SPLIT) { const LaneScratch MW = state_slots(); static_for<NB>([&](auto I) { constexpr int k = I; MW.st(LDS_QB - WIN + k, E.R.q[k]); MW.st(LDS_QDB - WIN + k, E.R.qd[k]); MW.st(LDS_WARM - WIN + k, E.R.warm[k]); if constexpr (k < 6) MW.st(LDS_QLAG - WIN + k, E.qlag6[k]); }); }   // q(0), qd(0) for the other waves; warm start and lagged q parked
   MCG_TICK(ST_LOAD);
   float act[8];
   _Pragma("unroll") for (int k = 0; k < 8; k++) {   // act_dim is 7, 4 (fetch) or 8 (mocap): static indices keep the array in registers
@@ -274,7 +279,7 @@ __global__ __launch_bounds__(SPLIT ? 192 : 64) void step_reach_kernel(Cfg C, Vie
     for (int s = 0; s < C.frame_skip; s++) hadbad |= robot_substep<LaneScratch, NoCoupling, NoWeld, Split>(P, E.R, E.qlag6, MS);
   }
 
-  if constexpr (SPLIT) static_for<NB>([&](auto I) { constexpr int k = I; E.R.warm[k] = MS.ld(LDS_WARM + k); if constexpr (k < 6) E.qlag6[k] = MS.ld(LDS_QLAG + k); });     // warm start and lagged q back from LDS
+  if constexpr (SPLIT) { const LaneScratch MW = state_slots(); static_for<NB>([&](auto I) { constexpr int k = I; E.R.warm[k] = MW.ld(LDS_WARM - WIN + k); if constexpr (k < 6) E.qlag6[k] = MW.ld(LDS_QLAG - WIN + k); }); }     // warm start and lagged q back from LDS
   hadbad |= guard_robot(E.R, E.qlag6);
   if (__any(hadbad)) {                              // a reset in the last sub-step: the positions of "the last forward pass" are the reset ones
     bool zero = true;
