@@ -29,39 +29,8 @@
 
 namespace mcg {
 
-// ---- exchange slots of the four-wave kernel (all per-lane columns).
-// Clip-polygon area, first 32 slots (the collision pass clips there, before barrier S2; afterwards:) flags and the cube's hand-over.
-// XCH_FLAG: 0 = no contact reaches the robot | 2 = one does (a pad or a mesh on the cube, the table or the ground), or the cube alone
-// holds more contacts than its own solve has row slots for: the environment's 18 dofs go to the cooperative solve.
-constexpr int XCH_FLAG = LDS_POLY, XCH_T0 = LDS_POLY + 1, XCH_T1 = LDS_POLY + 2, XCH_NCON = LDS_POLY + 3;
-constexpr int XCH_CB = LDS_POLY + 4, XCH_QL7 = LDS_POLY + 23, XCH_DR = LDS_POLY + 30;      // cube: pos 3, quat 4, vel 6, warm 6; lagged pose 7; DR scales 2
-static_assert(XCH_DR + 2 <= LDS_POLY + 32, "exchange area exceeds the clip-polygon slots");
-// ... second 32 slots, which no pass writes: q(t), qd(t) of the robot for the other waves -- written at the end of a sub-step, read after
-// S1 by the M, RNE and cube waves and between S4 and S5 by the cooperative solves -- and the workgroup's hand-out counter of that phase
-// (an unsigned in the first word of lane 0's slot).
-constexpr int XCH_Q = LDS_POLY + 32, XCH_QD = XCH_Q + NB, COOP_CTR_SLOT = XCH_QD + NB;
-// XCH_T1 (robot wave -> cube wave, read after S1) / XCH_BADC (cube wave -> robot wave, read after S4): the other body failed mj_checkPos /
-// mj_checkVel, mj_resetData resets both
-constexpr int XCH_BADC = COOP_CTR_SLOT + 1;
-// XCH_ACT0 / XCH_ACT1: the active set the environment's last cooperative solve ended with, as raw bits -- [signature of the contact list |
-// rows 0-31], [rows 32-63 | rows 64-95] -- cleared at the start of an env-step.  The next sub-step's solve starts from it (see coop_guess).
-constexpr int XCH_ACT0 = XCH_BADC + 1, XCH_ACT1 = XCH_ACT0 + 1;
-static_assert(XCH_ACT1 + 1 <= LDS_POLY + 62, "exchange area (slots 62, 63: a stage-clock census)");
-// Row area (LDS_ROW .. LDS_ROW + 144 slot rows of PNP_LANES doubles):
-//   between S1 and S1c: the frames of the bodies that carry candidate meshes (MP_FRAME, mcg_cube.hpp);
-//   after S2: [0, 144) the cube wave's own solves (12 slots per contact, list positions 0..11: a lane whose list is longer is flagged);
-//   between barriers S4 and S5, when every lane-parallel solve is over: [0, 96) cooperative workspace, 768 doubles per wave.
-// The inputs of a lane's cooperative solve, parked by the robot wave (PubHook) -- right after S1b when the workgroup has a mesh phase to
-// overlap with (then for every lane: the flags do not exist yet), else after S2 for the flagged lanes -- live in slots that are free from
-// S1b to S5: g0 in the robot's q(t) slots (read for the last time before S1b, rewritten when the sub-step ends), the warm start in the
-// bias-force slots (the robot wave has taken them; the RNE wave rewrites them after the next S1), the limit rows in the cube-alone
-// solve's mask slots (a flagged lane has no such solve; an unflagged lane's solve initialises its masks) and four slots of their own.
-constexpr int PUB_G0 = XCH_Q, PUB_WARM = PNP_SLOTS /* = XCH_FS */, PUB_SD = LDS_ACT, PUB_AREF_A = LDS_ACT + 10, PUB_AREF_B = PNP_SLOTS_ALL;
-MCG_DEV constexpr int pub_aref(int j) { return j < 6 ? PUB_AREF_A + j : PUB_AREF_B + (j - 6); }
-constexpr int PNP_SLOTS_LDS = PUB_AREF_B + 4;
-static_assert(MAXCON >= 16, "the limit rows borrow sixteen mask slots");
-constexpr int COOP_WS_ROW = LDS_ROW, COOP_WS_DOUBLES = 768;
-static_assert(4 * COOP_WS_DOUBLES <= 96 * PNP_LANES, "cooperative workspace exceeds the first 96 rows of the row area");
+// The exchange slots of the four-wave kernel (XCH_*), the inputs the robot wave parks for a solve (PUB_*) and the workspaces in the row area
+// (COOP_WS_*): mcg_lds.hpp.
 constexpr int COOP_NV = 18, COOP_WIN = 16, COOP_WSTRIDE = 20;          // window: 16 active rows x (D, D aref, J[18])
 static_assert(COOP_WIN * COOP_WSTRIDE <= COOP_WS_DOUBLES && COOP_NV * COOP_NV + COOP_NV <= COOP_WS_DOUBLES, "window / matrix buffer");
 constexpr int COOP_ROWS = 10 + 6 * MAXCON, COOP_SETS = (COOP_ROWS + PNP_LANES - 1) / PNP_LANES;      // limits first, then the contacts
@@ -208,7 +177,7 @@ MCG_DEV void coop_build_row(const PnpScratch ME, const CSYS& CS, const real* cpo
 MCG_DEV void coop_twists(const PnpScratch ME, const real* cpos, bool grip, real (*tc)[6]) {
   _Pragma("unroll") for (int j = 0; j < NB; j++) {
     real ax[3], d[3], v[3];
-    _Pragma("unroll") for (int k = 0; k < 3; k++) { ax[k] = ME.ld(LDS_WJ + j * 6 + k); d[k] = ME.ld(LDS_WJ + j * 6 + 3 + k) - cpos[k]; }
+    _Pragma("unroll") for (int k = 0; k < 3; k++) { ax[k] = ME.ld(LDS_WJ + j * WJ_STRIDE + WJ_AXIS + k); d[k] = ME.ld(LDS_WJ + j * WJ_STRIDE + WJ_ANCHOR + k) - cpos[k]; }
     cross(d, ax, v);
     const bool ok = (j < 6) || grip;
     _Pragma("unroll") for (int k = 0; k < 3; k++) { tc[j][k] = sel(ok, v[k], 0.0); tc[j][3 + k] = sel(ok, ax[k], 0.0); }
@@ -229,9 +198,9 @@ MCG_DEV void coop_solve(ModelPtr Pm, LdsPtr lds0, int e, LdsPtr ws, int ncon, Co
 #endif
   // ---- the environment's cube and pair numbers (uniform), as the lane-parallel solve derives them
   Cube Cb; real drs[2];
-  for (int k = 0; k < 3; k++) Cb.pos[k] = ME.ld(XCH_CB + k);
-  for (int k = 0; k < 4; k++) Cb.quat[k] = ME.ld(XCH_CB + 3 + k);
-  for (int k = 0; k < 6; k++) { Cb.vel[k] = ME.ld(XCH_CB + 7 + k); Cb.warm[k] = ME.ld(XCH_CB + 13 + k); }
+  for (int k = 0; k < 3; k++) Cb.pos[k] = ME.ld(XCH_CB_POS + k);
+  for (int k = 0; k < 4; k++) Cb.quat[k] = ME.ld(XCH_CB_QUAT + k);
+  for (int k = 0; k < 6; k++) { Cb.vel[k] = ME.ld(XCH_CB_VEL + k); Cb.warm[k] = ME.ld(XCH_CB_WARM + k); }
   drs[0] = ME.ld(XCH_DR); drs[1] = ME.ld(XCH_DR + 1);
   CubeSys<PnpScratch> CS(ME, Cb, drs);          // (for its pair numbers only)
   CS.pm_bits = (unsigned long long)Pm;
@@ -299,7 +268,7 @@ MCG_DEV void coop_solve(ModelPtr Pm, LdsPtr lds0, int e, LdsPtr ws, int ncon, Co
   MCG_TICK_PIN(H0, COOP_NV);
   COOP_TICK(ST_CO_H0);
   // ---- the iterate lives one number per lane (lane i holds a_i); a uniform copy of a vector is made where one is needed, by v_readlane
-  real al = ME.ld(sel(i < NB, PUB_WARM + i, XCH_CB + 13 + (i - NB)));
+  real al = ME.ld(sel(i < NB, PUB_WARM + i, XCH_CB_WARM + (i - NB)));
   // Assembly layout: all 32 lanes work on the 16 x 18 upper block of the increment, lane (ia, hb) on row ia, columns 9 hb .. 9 hb + 8;
   // rows 16 and 17 come from the symmetry (columns 16, 17 of the hb = 1 lanes) and their 2 x 2 corner from the broadcast values every
   // hb = 1 lane holds anyway.  One active row costs a lane 7 LDS reads and 18 flops (the row layout: 21 and 40).
@@ -510,7 +479,7 @@ MCG_DEV void coop_solve(ModelPtr Pm, LdsPtr lds0, int e, LdsPtr ws, int ncon, Co
 #endif
   // ---- hand the accelerations back: robot part where the warm start was, cube part in the cube's warm-start slots
   if (L < NB) ME.st(PUB_WARM + L, al);
-  else if (L < COOP_NV) ME.st(XCH_CB + 13 + (L - NB), al);
+  else if (L < COOP_NV) ME.st(XCH_CB_WARM + (L - NB), al);
   if (L == 0) { ME.st(XCH_ACT0, coop_pack((conv && NSETS <= 3) ? sig : 0u, fin[0])); ME.st(XCH_ACT1, coop_pack(fin[1], fin[2])); }      // (four sets do not fit the two slots: no set is carried)
   COOP_TICK(ST_CO_OUT);
 }
@@ -566,9 +535,9 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
 #endif
   // ---- the environment's cube and pair numbers
   Cube Cb; real drs[2];
-  for (int k = 0; k < 3; k++) Cb.pos[k] = ME.ld(XCH_CB + k);
-  for (int k = 0; k < 4; k++) Cb.quat[k] = ME.ld(XCH_CB + 3 + k);
-  for (int k = 0; k < 6; k++) { Cb.vel[k] = ME.ld(XCH_CB + 7 + k); Cb.warm[k] = ME.ld(XCH_CB + 13 + k); }
+  for (int k = 0; k < 3; k++) Cb.pos[k] = ME.ld(XCH_CB_POS + k);
+  for (int k = 0; k < 4; k++) Cb.quat[k] = ME.ld(XCH_CB_QUAT + k);
+  for (int k = 0; k < 6; k++) { Cb.vel[k] = ME.ld(XCH_CB_VEL + k); Cb.warm[k] = ME.ld(XCH_CB_WARM + k); }
   drs[0] = ME.ld(XCH_DR); drs[1] = ME.ld(XCH_DR + 1);
   CubeSys<PnpScratch> CS(ME, Cb, drs);
   CS.pm_bits = (unsigned long long)Pm;
@@ -647,8 +616,8 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
   MCG_TICK_PIN(H0, N);
   COOP_TICK(ST_CO_H0);
   // ---- the iterate: a_i in lane i of the DPP rows (i < 16), a_16 and a_17 in every lane
-  real am = ME.ld(sel(i < NB, PUB_WARM + i, XCH_CB + 13 + (i - NB)));
-  real a6 = ME.ld(XCH_CB + 13 + 4), a7 = ME.ld(XCH_CB + 13 + 5);
+  real am = ME.ld(sel(i < NB, PUB_WARM + i, XCH_CB_WARM + (i - NB)));
+  real a6 = ME.ld(XCH_CB_WARM + 4), a7 = ME.ld(XCH_CB_WARM + 5);
   bool done = !have;
   const LdsPtr wsB = wsw + CP_WS;
   // The increments J~^T [J~ aref~] stay in the matrix cores' accumulators ACROSS the iterations: an iteration passes only the rows whose
@@ -906,7 +875,7 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
 #endif
 #ifdef MCG_STAGE_CLOCKS
   {   // census: would the set of TWO sub-steps ago have been right (period-2 chatter)?
-    const real q0 = ME.ld(LDS_POLY + 62), q1 = ME.ld(LDS_POLY + 63);
+    const real q0 = ME.ld(XCH_CENSUS), q1 = ME.ld(XCH_CENSUS + 1);
     const bool sig2 = (unsigned)__double2hiint(q0) == sig;
     const unsigned g20 = (unsigned)__double2loint(q0), g21 = (unsigned)__double2hiint(q1);
     const bool eq2 = have && conv && sig2 && g20 == fin[0] && g21 == fin[1 % NSETS];
@@ -914,7 +883,7 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
     const unsigned long long b2 = __ballot(eq2 && hl == 0), b1 = __ballot(eq1 && hl == 0), b12 = __ballot(eq2 && !eq1 && hl == 0);
     if (T == 0) { atomicAdd(&g_stage_clocks[ST_COUNT + CN_G_EQ1], (unsigned long long)__popcll(b1)); atomicAdd(&g_stage_clocks[ST_COUNT + CN_G_EQ2], (unsigned long long)__popcll(b2));
                   atomicAdd(&g_stage_clocks[ST_COUNT + CN_G_EQ2N1], (unsigned long long)__popcll(b12)); }
-    if (have && hl == 0) { ME.st(LDS_POLY + 62, ME.ld(XCH_ACT0)); ME.st(LDS_POLY + 63, ME.ld(XCH_ACT1)); }      // (before the hand-back overwrites them)
+    if (have && hl == 0) { ME.st(XCH_CENSUS, ME.ld(XCH_ACT0)); ME.st(XCH_CENSUS + 1, ME.ld(XCH_ACT1)); }      // (before the hand-back overwrites them)
   }
   {   // where a carried active set was wrong: rows by class, missing from / surplus in the guess
     _Pragma("unroll") for (int s = 0; s < NSETS; s++) {
@@ -938,8 +907,8 @@ MCG_DEV void coop_solve_pair(ModelPtr Pm, LdsPtr lds0, LdsPtr wsw, int eA, int e
   // ---- hand the accelerations back
   if (have && (drow & 1) == 0) {
     if (l16 < NB) ME.st(PUB_WARM + l16, am);
-    else ME.st(XCH_CB + 13 + (l16 - NB), am);
-    if (l16 == 0) { ME.st(XCH_CB + 13 + 4, a6); ME.st(XCH_CB + 13 + 5, a7);
+    else ME.st(XCH_CB_WARM + (l16 - NB), am);
+    if (l16 == 0) { ME.st(XCH_CB_WARM + 4, a6); ME.st(XCH_CB_WARM + 5, a7);
                     ME.st(XCH_ACT0, coop_pack(conv ? sig : 0u, fin[0])); ME.st(XCH_ACT1, coop_pack(fin[1 % NSETS], 0u)); }
   }
   COOP_TICK(ST_CO_OUT);
@@ -981,6 +950,9 @@ static __device__ __noinline__ void coop_solve_single(unsigned long long model_b
 // run must reproduce bit for bit -- so the robot wave's share is fixed by rank: of the flagged environments, in lane order, every
 // seventh is the robot wave's (a 32-lane solve takes about as long as a pair's), the others are handed out in pairs.  (Who is paired
 // with whom does race; a half's arithmetic never sees the other half's numbers.)
+// the hand-out counter: an unsigned in the first word of lane 0's slot COOP_CTR_SLOT (lds0 = slot 0 of lane 0 of the workgroup's array)
+typedef __attribute__((address_space(3))) unsigned* LdsCtr;
+MCG_DEV LdsCtr coop_counter(LdsPtr lds0) { return (LdsCtr)(lds0 + COOP_CTR_SLOT * PNP_LANES); }
 constexpr int COOP_ROBOT_EVERY = 13;     // (round 4: 7 -> 13.  With twice the flagged environments the robot wave had a share in every fifth sub-step, and each of its out-of-line calls is scratch traffic; it now joins only when the other three waves would need a third round)
 template <bool PAIRS = true>      // PAIRS = false: the robot wave's instance (modes 0 and 2 only) -- without the inlined pair solve its out-of-line
                                   // frame saves a handful of registers per call instead of ~50 dwords a lane
@@ -991,8 +963,7 @@ MCG_DEV void coop_phase_body(ModelPtr P, LdsPtr lds0, unsigned m, int w, int mod
   for (int k = 0; k < ST_CO_IDLE - ST_CO_SETUP; k++) CK.t[k] = 0;
   for (int k = 0; k < 8; k++) CK.n[k] = 0;
 #endif
-  typedef __attribute__((address_space(3))) unsigned* LdsCtr;
-  const LdsCtr ctr = (LdsCtr)(lds0 + COOP_CTR_SLOT * PNP_LANES);
+  const LdsCtr ctr = coop_counter(lds0);
   const int total = __popc(m);
   auto grab = [&]() {
     unsigned k = 0;

@@ -8,28 +8,14 @@
 // the cube's part of mj_fwdConstraint (P9); mj_Euler for a free joint (P10).  An environment in which a contact reaches the robot is
 // solved by mcg_coop.hpp (one environment per 32 lanes).
 //
-// Contacts of one env live in LDS (runtime-indexed lists cannot live in registers): 10 slots per contact.
+// Contacts of one env live in LDS (runtime-indexed lists cannot live in registers): 10 slots per contact.  The column's map: mcg_lds.hpp.
 #pragma once
 
 #include "mcg_dynamics.hpp"
 
 namespace mcg {
 
-constexpr int MAXCON = 16;           // list ENTRIES kept per env (a mesh's twin geoms: one entry of double weight); the oracle cuts its list at the
-                                     // same entry (mco_model.maxentry).  MuJoCo has no cap; mcg_counters.contacts_dropped counts what this one cuts
-constexpr int CON_STRIDE = 10;       // pos[3] n[3] dist D kterm type   (the tangents are re-derived from n: make_frame)
-constexpr int CON_DIST = 6, CON_D = 7, CON_KTERM = 8, CON_TYPE = 9;
-constexpr int PNP_LANES = 32;        // envs per wave in the PickAndPlace kernels: twice the LDS per env; a wave costs the
-                                     // same with 32 or 64 active lanes (measured), and 8192 envs then cover all 256 CUs
-constexpr int ROW_SLOTS = 144;       // the row area: line-search rows of the cube-alone solve, cooperative workspaces, parked inputs (mcg_coop.hpp)
-constexpr int NJW = 12;              // joints whose world axis + anchor are kept for the contact rows: all twelve
-constexpr int LDS_CON = LDS_SLOTS;
-constexpr int LDS_POLY = LDS_CON + MAXCON * CON_STRIDE;     // two clip polygons of 8 x 2 in the first 32 slots (a quadrilateral clipped by
-                                                            // four half-planes has at most 8 vertices); the other 32: exchange slots of the four-wave kernel
-constexpr int LDS_ROW = LDS_POLY + 64;                      // per pyramid row: r0, dr (line search)
-constexpr int LDS_ACT = LDS_ROW + ROW_SLOTS;                // per contact: active-row bit mask (as a double)
-constexpr int LDS_WJ = LDS_ACT + MAXCON;                    // world axis + anchor of the twelve joints
-constexpr int PNP_SLOTS = LDS_WJ + 6 * NJW;
+constexpr int CON_DIST = 6, CON_D = 7, CON_KTERM = 8, CON_TYPE = 9;      // (of CON_STRIDE: pos[3] n[3] dist D kterm type)
 typedef LaneScratchT<PNP_LANES> PnpScratch;
 
 // Pair types (slot CON_TYPE of a list entry; rows of mcg_model.pair_tran).  The ground plane carries the table's parameters (both are
@@ -59,18 +45,6 @@ MCG_DEV int pair_robot_body(int type) {
 MCG_DEV bool joint_in_chain(int j, int rb) {
   return rb >= 0 && (j < 6 ? j <= (rb < 5 ? rb : 5) : (j == 6 ? (rb == 6 || rb == 7) : (j == 8 ? (rb == 8 || rb == 9) : j == rb)));
 }
-
-// What the mesh phase (mcg_mesh.hpp) reads, columns of every lane.  MP_FRAME: the row area, free between barriers S1 and S2 (its solves run
-// after S2): the world frame (rotation 9, origin 3) of each of the twelve robot bodies that carries a candidate mesh, parked by the wave
-// whose broad phase found it -- ONE producer per body (M wave: bodies 0-3, RNE wave: 4, 5, cube wave: 6-11), so that a frame is one
-// wave's arithmetic.  MP_*: twelve slots of their own behind the robot-side exchange slots.
-constexpr int MP_FRAME = LDS_ROW;
-static_assert(12 * NB <= ROW_SLOTS, "frames of the twelve bodies");
-constexpr int MP_CUBE = PNP_SLOTS + NB;                          // the cube's position (published when a sub-step ENDS: the M / RNE waves' broad phase reads it
-                                                                 // before S1b) and its normalised quaternion (written after S1, read in the mesh phase)
-constexpr int MP_MASK = MP_CUBE + 7;                             // candidate pairs of the broad phases: M wave, RNE wave, cube wave (bit 3 m + o; o: ground, table, cube)
-constexpr int MP_NCON = MP_MASK + 3, MP_DROP = MP_NCON + 1;     // the list's length (the mesh phase appends); contacts the cap cut there
-constexpr int PNP_SLOTS_ALL = MP_DROP + 1;
 
 struct Cube {
   real pos[3], quat[4], vel[6], warm[6];     // vel = world linear velocity, body-frame angular velocity (MuJoCo free joint)
@@ -209,13 +183,13 @@ MCG_DEV void box_box(ContactList<LS>& CL, bool live, const real* pa, const real*
   const real m11 = dot3(Rrc1, Ria1), m12 = dot3(Rrc1, Ria2), m21 = dot3(Rrc2, Ria1), m22 = dot3(Rrc2, Ria2);
   const real k1 = m11*hia1, k2 = m21*hia1, k3 = m12*hia2, k4 = m22*hia2;
   const real rect[2] = {pickv(hr, c1), pickv(hr, c2)};
-  // polygons in LDS: P at LDS_POLY + 2 v + {0,1}, T at LDS_POLY + 16 + 2 v + {0,1}
-  S.st(LDS_POLY + 0, cx - k1 - k3); S.st(LDS_POLY + 1, cy - k2 - k4);
-  S.st(LDS_POLY + 2, cx - k1 + k3); S.st(LDS_POLY + 3, cy - k2 + k4);
-  S.st(LDS_POLY + 4, cx + k1 + k3); S.st(LDS_POLY + 5, cy + k2 + k4);
-  S.st(LDS_POLY + 6, cx + k1 - k3); S.st(LDS_POLY + 7, cy + k2 - k4);
+  // polygons in LDS: P at LDS_POLY_P + 2 v + {0,1}, T at LDS_POLY_T + 2 v + {0,1}
+  S.st(LDS_POLY_P + 0, cx - k1 - k3); S.st(LDS_POLY_P + 1, cy - k2 - k4);
+  S.st(LDS_POLY_P + 2, cx - k1 + k3); S.st(LDS_POLY_P + 3, cy - k2 + k4);
+  S.st(LDS_POLY_P + 4, cx + k1 + k3); S.st(LDS_POLY_P + 5, cy + k2 + k4);
+  S.st(LDS_POLY_P + 6, cx + k1 - k3); S.st(LDS_POLY_P + 7, cy + k2 - k4);
   int np = sel(face, 4, 0);
-  int src = LDS_POLY, dst = LDS_POLY + 16;
+  int src = LDS_POLY_P, dst = LDS_POLY_T;
   // Sutherland-Hodgman keeps a polygon that lies strictly inside all four limits as it is (same vertices, same order):
   // the usual case of the cube on the table needs no clipping pass at all.
   const bool inside = fabs(cx) + fabs(k1) + fabs(k3) < rect[0] && fabs(cy) + fabs(k2) + fabs(k4) < rect[1];
@@ -329,8 +303,8 @@ MCG_DEV int mesh_broad(ModelPtr Pm, int m, const real* R, const real* p, const r
 MCG_DEV void park_frame(const PnpScratch& S, int body, const real* R, const real* p, bool doit) {
   if (__any(doit)) {                                               // wave-uniform
     if (doit) {                                                    // plain LDS stores of live registers
-      _Pragma("unroll") for (int k = 0; k < 9; k++) S.st(MP_FRAME + body * 12 + k, R[k]);
-      _Pragma("unroll") for (int k = 0; k < 3; k++) S.st(MP_FRAME + body * 12 + 9 + k, p[k]);
+      _Pragma("unroll") for (int k = 0; k < 9; k++) S.st(MP_FRAME + body * MP_FRAME_STRIDE + MP_FRAME_ROT + k, R[k]);
+      _Pragma("unroll") for (int k = 0; k < 3; k++) S.st(MP_FRAME + body * MP_FRAME_STRIDE + MP_FRAME_POS + k, p[k]);
     }
   }
 }
@@ -339,7 +313,7 @@ MCG_DEV void arm_broad_stage(ModelPtr Pm, const LS S, const real* sn, const real
   ModelPtr Q = launder(Pm);
   real tp[3], th[3], hc[3]; ldc<3>(Q->table_pos, tp); ldc<3>(Q->table_half, th); ldc<3>(Q->cube_half, hc);
   const real crad = sqrt(dot3(hc, hc));
-  const real cpos[3] = {S.ld(MP_CUBE), S.ld(MP_CUBE + 1), S.ld(MP_CUBE + 2)};      // (published when the last sub-step ended)
+  const real cpos[3] = {S.ld(MP_CUBE_POS), S.ld(MP_CUBE_POS + 1), S.ld(MP_CUBE_POS + 2)};      // (published when the last sub-step ended)
   real R[9], p[3];
   _Pragma("unroll") for (int k = 0; k < 9; k++) R[k] = Q->base_mat[k];
   _Pragma("unroll") for (int k = 0; k < 3; k++) p[k] = Q->base_pos[k];
@@ -539,7 +513,7 @@ struct CubeSys {
       _Pragma("unroll") for (int k = 0; k < 3; k++) p[k] = Q->base_pos[k];
       auto joint = [&](int slot, int K, int sg, const real* r, real ang, real* Rio, real* pio) {
         _Pragma("unroll") for (int k = 0; k < 3; k++) pio[k] += Rio[3*k]*r[0] + Rio[3*k+1]*r[1] + Rio[3*k+2]*r[2];
-        _Pragma("unroll") for (int k = 0; k < 3; k++) { S.st(LDS_WJ + slot*6 + k, sg * Rio[3*k + K]); S.st(LDS_WJ + slot*6 + 3 + k, pio[k]); }
+        _Pragma("unroll") for (int k = 0; k < 3; k++) { S.st(LDS_WJ + slot*WJ_STRIDE + WJ_AXIS + k, sg * Rio[3*k + K]); S.st(LDS_WJ + slot*WJ_STRIDE + WJ_ANCHOR + k, pio[k]); }
         real sn_, cs_; sincos_cw(T, sg * ang, sn_, cs_);
         const int A = (K + 1) % 3, B = (K + 2) % 3;
         _Pragma("unroll") for (int k = 0; k < 3; k++) {
@@ -640,10 +614,10 @@ struct CubeSys {
     MCG_TICK2(ST_A_MAP);
     ncon = CL.n; ndropped = CL.ndrop;
     if constexpr (MESHES) {
-      if constexpr (ARM) { _Pragma("unroll") for (int k = 0; k < 3; k++) S.st(MP_CUBE + k, Cb.pos[k]); }      // (else: published when the last sub-step ended)
-      _Pragma("unroll") for (int k = 0; k < 4; k++) S.st(MP_CUBE + 3 + k, Cb.quat[k]);
-      S.st(MP_MASK + 2, (real)mbits); S.st(MP_NCON, (real)ncon); S.st(MP_DROP, 0.0);
-      if constexpr (ARM) { S.st(MP_MASK, 0.0); S.st(MP_MASK + 1, 0.0); }
+      if constexpr (ARM) { _Pragma("unroll") for (int k = 0; k < 3; k++) S.st(MP_CUBE_POS + k, Cb.pos[k]); }      // (else: published when the last sub-step ended)
+      _Pragma("unroll") for (int k = 0; k < 4; k++) S.st(MP_CUBE_QUAT + k, Cb.quat[k]);
+      S.st(MP_MASK_CUBE, (real)mbits); S.st(MP_NCON, (real)ncon); S.st(MP_DROP, 0.0);
+      if constexpr (ARM) { S.st(MP_MASK_M, 0.0); S.st(MP_MASK_RNE, 0.0); }
     }
     MCG_TICK2(ST_A_STORE);
   }
@@ -683,7 +657,7 @@ struct CubeSys {
   MCG_DEV void clean_rows(bool skip = false) const {
     for (int c = 0; __any(c < ncon); c++) {
       if (c >= ncon && !skip) {
-        _Pragma("unroll") for (int k = 0; k < 12; k++) S.st(LDS_ROW + c * 12 + k, 0.0);
+        _Pragma("unroll") for (int k = 0; k < ALONE_CON_SLOTS; k++) S.st(LDS_ROW + c * ALONE_CON_SLOTS + k, 0.0);
         S.st(LDS_ACT + c, 0.0);
       }
     }

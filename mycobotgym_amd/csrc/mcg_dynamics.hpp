@@ -386,48 +386,11 @@ struct Robot {
   real q[NB], qd[NB], ctrl[7], warm[NB];
 };
 
-// Per-lane scratch in LDS: slot k of this lane lives at base[k * 64] (lane-contiguous rows: conflict-free
-// ds_read_b64 / ds_write_b64 with immediate offsets).  The joint-space inertia M is kept here between the stages
-// that consume it, so that only one 12x12 system occupies registers at a time.
-constexpr int LDS_M = 0;                              // packed lower triangle of M                     (78 slots)
-constexpr int LDS_HEQ = NB * (NB + 1) / 2;            // H_eq = M + J^T D J over the equality (and weld) rows  (78 slots)
-constexpr int LDS_SLOTS = 2 * (NB * (NB + 1) / 2);
-// three-wave Reach kernel (SplitMainLocal / helper_substep): factor of M + hB, its reciprocal pivots, and q, qd published for the side waves
-constexpr int LDS_FAC = LDS_SLOTS, LDS_FDINV = LDS_FAC + NB * (NB + 1) / 2, LDS_QB = LDS_FDINV + NB, LDS_QDB = LDS_QB + NB;
-constexpr int LDS_FS = LDS_QDB + NB, LDS_WARM = LDS_FS + NB, LDS_QLAG = LDS_WARM + NB, LDS_IKT = LDS_QLAG + 6;      // LDS_WARM: qacc_warmstart parked between sub-steps; LDS_QLAG: q of the last forward pass; LDS_IKT: the IK controller's six ctrl increments of a control step, handed from the RNE wave to the main wave (two slots spare)
-// The hand-over of the remote solve (SplitMainCols: the RNE wave solves the equality rows' system).  In EVERY sub-step the main wave
-// parks its eight actuation forces (RACT: dofs 0..5, 6, 8 -- the other four are exactly zero) as soon as it has them and the constraint
-// part of g0 (RG0, 12) likewise, and reads them back after S2 if it solves itself: neither stays in registers across the rows and the
-// assembly of H_eq.  In a remote sub-step the RNE wave leaves abar in RA (12) before S3; the main wave prepares what the limit
-// rows 6 and 8 need of its own numbers before S3 (gear_rows_prepare) and finishes the gear rows itself.  Lifetimes of the slots borrowed:
-//   RA in WARM:       only the general iteration reads the warm start, a remote sub-step never runs it, and the Euler step after S3 writes
-//                     the slots again (with a: from what the RNE wave left there, or zero in a lane that was reset) before the next
-//                     sub-step could fall back and read them;
-//   RACT = IKT:       the IK increments are live between the control-step barriers C1 and C2 only, the sub-steps run after C2;
-//   RG0:              slots of its own.
-constexpr int LDS_RA = LDS_WARM, LDS_RACT = LDS_IKT, LDS_RG0 = LDS_IKT + 8, LDS_SLOTS_SPLIT = LDS_RG0 + NB;
-constexpr int RACT_DOF[8] = {0, 1, 2, 3, 4, 5, 6, 8};                       // the dofs an actuator drives
-static_assert(LDS_RA + NB == LDS_QLAG && LDS_RACT >= LDS_QLAG + 6 && LDS_RACT + 8 <= LDS_RG0,
-              "the remote solve's hand-over must stay inside the warm-start and IK-increment slots (the lagged q between them is live)");
-static_assert(LDS_SLOTS_SPLIT * 64 * sizeof(real) <= 160 * 1024, "the split Reach kernel's LDS exceeds the 160 KB of a gfx950 workgroup");
-// The sines and cosines of a sub-step, each evaluated by one of the three waves (trig_exchange), are exchanged between S1 and S1t in the
-// FACTOR slots: the main wave's last read of the factor (after S3) comes before it reaches the next S1, and the helper's next write comes
-// after the next S2, by which every wave has read its sines and cosines -- the two uses never overlap.
-constexpr int LDS_SN = LDS_FAC, LDS_CS = LDS_SN + NB;
-static_assert(LDS_SN >= LDS_FAC && LDS_CS + NB <= LDS_FDINV + NB && LDS_FDINV + NB == LDS_QB, "the sine / cosine exchange must lie inside the factor slots");
-// The gear rows' columns z6 = H^-1 e_6, z8 = H^-1 e_8 (SplitMainCols::cols: the helper wave solves them between S2 and S3, the main
-// wave reads them after S3).  Under that policy the main wave factors M + hB itself and nobody writes the factor slots, so the columns
-// take 24 of them, behind the sine / cosine exchange: written after S2 and read before the next S1, they never meet it either.
-constexpr int LDS_Z6 = LDS_CS + NB, LDS_Z8 = LDS_Z6 + NB;
-static_assert(LDS_Z6 == LDS_FAC + 24 && LDS_Z6 >= LDS_SN + NB && LDS_Z6 >= LDS_CS + NB && LDS_Z8 == LDS_Z6 + NB && LDS_Z8 + NB <= LDS_QB,
-              "the gear rows' columns must lie inside the factor slots, clear of the sine / cosine exchange and of the published q");
-// What the main wave reads and writes around S3 under SplitMainCols -- the columns (Z6, Z8), abar and the warm start (RA = WARM), the
-// published and the lagged state (QB, QDB, QLAG) -- lies within 128 slots, the reach of a ds_ offset field, but beyond it from slot 0:
-// the main wave addresses these through a window of the lane's column that starts at LDS_WIN (LaneScratchT::window).
-constexpr int LDS_WIN = LDS_QLAG + 6 - 128;
-static_assert(LDS_WIN >= 0 && LDS_WIN <= LDS_Z6 && LDS_WIN <= LDS_QB && LDS_QDB + NB <= LDS_WIN + 128 && LDS_RA + NB <= LDS_WIN + 128
-              && LDS_QLAG + 6 <= LDS_WIN + 128 && (128 - 1) * 64 * sizeof(double) < 65536,
-              "the slots of the main wave's window must lie within one 16-bit ds_ offset of its base");
+}  // namespace mcg
+#include "mcg_lds.hpp"      // the LDS slot map of the step kernels (LDS_*, XCH_*, MP_*, PUB_*); it needs real, NB and MCG_DEV from above
+namespace mcg {
+
+constexpr int RACT_DOF[8] = {0, 1, 2, 3, 4, 5, 6, 8};                       // the dofs an actuator drives (the eight forces parked at LDS_RACT)
 // The lane's LDS column.  The pointer carries the LDS address space explicitly: passed through structs as a generic
 // pointer the accesses degrade to flat_load/flat_store with 64-bit address arithmetic instead of ds_read/ds_write
 // with immediate offsets.

@@ -481,9 +481,7 @@ MCG_DEV void hide_object(real* obs, real* ag) {
 // wave leaves its verdict on the state it has just produced in XCH_T1 (the cube wave reads it with q(t) after S1 and resets the cube),
 // the cube wave adds its verdict on the cube as bit 3 of the flag it publishes before S2 (the robot wave reads the flag after S4 and
 // resets the robot's new state).  mj_resetData resets BOTH bodies; the other body follows one sub-step late here.
-// Exchange slots: mcg_coop.hpp.
-constexpr int XCH_FS = PNP_SLOTS;                 // + 12 slots, then the mesh phase's twelve (MP_CUBE ..), then four of the parked limit rows
-static_assert(PNP_SLOTS_LDS * PNP_LANES * 8 <= 160 * 1024, "LDS of a CU");
+// Exchange slots: mcg_lds.hpp.
 // robot-side split of the four-wave PickAndPlace kernel: M from the helper wave, passive - bias from the RNE wave, the constraint
 // part of H_eq assembled before barrier S2; the Euler step stays with M a (no room for the factor in LDS)
 struct SplitPnp { static constexpr bool enabled = true, reach = false, mesh_split = true, cols = false;
@@ -492,7 +490,7 @@ struct SplitPnp { static constexpr bool enabled = true, reach = false, mesh_spli
 MCG_DEV bool flag_coupled(real f) { return (((int)f) & 2) != 0; }       // XCH_FLAG: bit 1 = the environment goes to the cooperative solve,
 MCG_DEV bool flag_cube_bad(real f) { return (((int)f) & 8) != 0; }      // bit 3 = the cube failed mj_checkPos / mj_checkVel / mj_checkAcc
 
-// the robot wave's hook into robot_substep: park a lane's Newton inputs for the cooperative solve (slots: mcg_coop.hpp).  flags_known: the
+// the robot wave's hook into robot_substep: park a lane's Newton inputs for the cooperative solve (slots: mcg_lds.hpp).  flags_known: the
 // cube wave has published the flags (after S2): only the flagged lanes are parked; else (the robot wave runs ahead of the mesh phase)
 // every lane is
 struct PubHook {
@@ -509,15 +507,16 @@ struct PubHook {
   }
 };
 
+// the cube's hand-over record (XCH_CB_*: mcg_lds.hpp); the cooperative solves unpack it by hand (as a call their instruction streams change)
 MCG_DEV void cube_to_lds(const PnpScratch MS, const Cube& Cb) {
-  for (int k = 0; k < 3; k++) MS.st(XCH_CB + k, Cb.pos[k]);
-  for (int k = 0; k < 4; k++) MS.st(XCH_CB + 3 + k, Cb.quat[k]);
-  for (int k = 0; k < 6; k++) { MS.st(XCH_CB + 7 + k, Cb.vel[k]); MS.st(XCH_CB + 13 + k, Cb.warm[k]); }
+  for (int k = 0; k < 3; k++) MS.st(XCH_CB_POS + k, Cb.pos[k]);
+  for (int k = 0; k < 4; k++) MS.st(XCH_CB_QUAT + k, Cb.quat[k]);
+  for (int k = 0; k < 6; k++) { MS.st(XCH_CB_VEL + k, Cb.vel[k]); MS.st(XCH_CB_WARM + k, Cb.warm[k]); }
 }
 MCG_DEV void cube_from_lds(const PnpScratch MS, Cube& Cb) {
-  for (int k = 0; k < 3; k++) Cb.pos[k] = MS.ld(XCH_CB + k);
-  for (int k = 0; k < 4; k++) Cb.quat[k] = MS.ld(XCH_CB + 3 + k);
-  for (int k = 0; k < 6; k++) { Cb.vel[k] = MS.ld(XCH_CB + 7 + k); Cb.warm[k] = MS.ld(XCH_CB + 13 + k); }
+  for (int k = 0; k < 3; k++) Cb.pos[k] = MS.ld(XCH_CB_POS + k);
+  for (int k = 0; k < 4; k++) Cb.quat[k] = MS.ld(XCH_CB_QUAT + k);
+  for (int k = 0; k < 6; k++) { Cb.vel[k] = MS.ld(XCH_CB_VEL + k); Cb.warm[k] = MS.ld(XCH_CB_WARM + k); }
 }
 // the flagged lanes, the same in all four waves; nvalid: the workgroup's real environments (a ragged last workgroup's surplus lanes
 // shadow the last environment: same arithmetic, but they are never handed out, counted or stored)
@@ -539,7 +538,7 @@ MCG_DEV void cube_wave(const CubeWaveArgs& C, const View& V, ModelPtr P, const r
     for (int k = 0; k < 6; k++) { Cb.vel[k] = V.qvel(12 + k, i); Cb.warm[k] = V.warm(12 + k, i); }
     for (int k = 0; k < 7; k++) qlag7[k] = V.qlag(12 + k, i);
     dr[0] = V.dr(0, i); dr[1] = V.dr(1, i);
-    for (int k = 0; k < 3; k++) MS.st(MP_CUBE + k, Cb.pos[k]);        // for the M / RNE waves' broad phase (read after S1)
+    for (int k = 0; k < 3; k++) MS.st(MP_CUBE_POS + k, Cb.pos[k]);        // for the M / RNE waves' broad phase (read after S1)
   }
   MCG_TICK2_INIT();
   for (int s = 0; s < total; s++) {
@@ -563,7 +562,7 @@ MCG_DEV void cube_wave(const CubeWaveArgs& C, const View& V, ModelPtr P, const r
           for (int k = 0; k < 4; k++) Cb.quat[k] = sel(reset, C.qpos0_cube[3 + k], Cb.quat[k]);
           for (int k = 0; k < 6; k++) { Cb.vel[k] = sel(reset, 0.0, Cb.vel[k]); Cb.warm[k] = sel(reset, 0.0, Cb.warm[k]); }
           CS.Cb = Cb;
-          if (reset) { for (int k = 0; k < 3; k++) MS.st(MP_CUBE + k, Cb.pos[k]); }      // (the M / RNE waves' broad phase of THIS sub-step may still see the old position)
+          if (reset) { for (int k = 0; k < 3; k++) MS.st(MP_CUBE_POS + k, Cb.pos[k]); }      // (the M / RNE waves' broad phase of THIS sub-step may still see the old position)
           if (__any(cbad)) { if (cbad && valid && C.cnt) atomicAdd(C.cnt + 1, 1ull); }
         }
       }
@@ -582,7 +581,7 @@ MCG_DEV void cube_wave(const CubeWaveArgs& C, const View& V, ModelPtr P, const r
       touch = CS.touch[0] && CS.touch[1];
       // 0: nothing reaches the robot | 2: a contact does (a pad or a mesh on the cube, the table or the ground), or the cube's own list is
       // longer than its solve's row slots: the environment's 18 dofs go to the cooperative solve
-      kind = (CS.any_pad || CS.ncon > ROW_SLOTS / 12) ? 2 : 0;
+      kind = (CS.any_pad || CS.ncon > ALONE_MAXCON) ? 2 : 0;
       MS.st(XCH_FLAG, (real)(kind + (cbad ? 8 : 0)));
       const unsigned nflag = (unsigned)__popc((unsigned)__ballot(kind != 0 && valid));      // (the ballot OUTSIDE the one-lane branch: rounds 2-3 took it inside
       if (nflag != 0u || __any(kind != 0)) {                                                 // and counted lane 0's flag only, 1/32 of the coupled env-sub-steps)
@@ -594,7 +593,7 @@ MCG_DEV void cube_wave(const CubeWaveArgs& C, const View& V, ModelPtr P, const r
       __syncthreads();                                              // S2 (the robot side's "M and bias ready")
       MCG_TICK2(ST_X_S2);
       CS.solve_alone(kind == 2);                                    // flagged lanes walk an empty list, store nothing
-      if (!__any(kind == 2)) { CS.finish(qlag7); Cb = CS.Cb; for (int k = 0; k < 3; k++) MS.st(MP_CUBE + k, Cb.pos[k]); }
+      if (!__any(kind == 2)) { CS.finish(qlag7); Cb = CS.Cb; for (int k = 0; k < 3; k++) MS.st(MP_CUBE_POS + k, Cb.pos[k]); }
       MCG_TICK2(ST_W2_CUBE);
     }
     __syncthreads();                                                // S4: end of the lane-parallel part
@@ -606,9 +605,9 @@ MCG_DEV void cube_wave(const CubeWaveArgs& C, const View& V, ModelPtr P, const r
       __syncthreads();                                              // S5
       MCG_TICK2(ST_CO_IDLE);
       if (lower) {
-        _Pragma("unroll") for (int k = 0; k < 6; k++) CS.a_c[k] = sel(kind == 2, MS.ld(XCH_CB + 13 + k), CS.a_c[k]);
+        _Pragma("unroll") for (int k = 0; k < 6; k++) CS.a_c[k] = sel(kind == 2, MS.ld(XCH_CB_WARM + k), CS.a_c[k]);
         CS.finish(qlag7); Cb = CS.Cb;
-        for (int k = 0; k < 3; k++) MS.st(MP_CUBE + k, Cb.pos[k]);
+        for (int k = 0; k < 3; k++) MS.st(MP_CUBE_POS + k, Cb.pos[k]);
       }
     }
   }
@@ -627,7 +626,7 @@ MCG_DEV bool pnp_substep_robot(const Cfg& C, ModelPtr P, EnvP& E, const PnpScrat
   PubHook hook{MS};
   robot_substep<PnpScratch, PubHook, WLD, SplitPnp, false>(P, E.R, E.qlag6, MS, &hook, &W, &nx);     // S1, S1b, S1c, S2 inside
   MCG_TICK(ST_POST);
-  if ((threadIdx.x & 63) == 0) *(__attribute__((address_space(3))) unsigned*)(uintptr_t)(lds0 + COOP_CTR_SLOT * PNP_LANES * 8) = 0u;      // the cooperative phase's hand-out counter
+  if ((threadIdx.x & 63) == 0) *coop_counter((LdsPtr)(uintptr_t)lds0) = 0u;      // the cooperative phase's hand-out counter
   __syncthreads();                                                  // S4
   MCG_TICK(ST_W1_WAIT);
   const real fl = MS.ld(XCH_FLAG);
@@ -679,8 +678,8 @@ MCG_DEV void pnp_side_wave(ModelPtr P, const real* __restrict__ poly, const PnpS
   MCG_TICK_INIT();
   for (int s = 0; s < total; s++) {
     if (lower) {                                                    // S1 inside; its own share, then the arm meshes' broad phase
-      if (rne) rne_pre<SplitPnp>(P, MS, PnpSideWork<4, 8>{P, MS, MP_MASK + 1});
-      else helper_pre<SplitPnp>(P, MS, PnpSideWork<0, 4>{P, MS, MP_MASK});
+      if (rne) rne_pre<SplitPnp>(P, MS, PnpSideWork<4, 8>{P, MS, MP_MASK_RNE});
+      else helper_pre<SplitPnp>(P, MS, PnpSideWork<0, 4>{P, MS, MP_MASK_M});
     }
     __syncthreads();                                                // S1b
     MCG_TICK(ST_S_S1B);

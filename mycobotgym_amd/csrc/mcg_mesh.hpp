@@ -262,14 +262,14 @@ MCG_DEV bool mesh_box(const MeshTab& T, int L, const real* Rm, const real* pm, c
 MCG_DEV void mesh_env(ModelPtr Pm, const real* __restrict__ poly, LdsPtr lds0, int e) {
   const int L = threadIdx.x & 63;
   const PnpScratch ME(lds0 + e);                   // env e's column: a uniform slot index is a broadcast read
-  unsigned long long bits = (unsigned long long)(long long)ME.ld(MP_MASK) | (unsigned long long)(long long)ME.ld(MP_MASK + 1) | (unsigned long long)(long long)ME.ld(MP_MASK + 2);
+  unsigned long long bits = (unsigned long long)(long long)ME.ld(MP_MASK_M) | (unsigned long long)(long long)ME.ld(MP_MASK_RNE) | (unsigned long long)(long long)ME.ld(MP_MASK_CUBE);
   bits = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(bits >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((unsigned)bits);
   int ncon = __builtin_amdgcn_readfirstlane((int)ME.ld(MP_NCON)), ndrop = 0;
   // ---- the static box and the cube
   real tp[3], th[3], hc[3], Rc[9], cp[3];
   { ModelPtr Qb = launder(Pm); ldc<3>(Qb->table_pos, tp); ldc<3>(Qb->table_half, th); ldc<3>(Qb->cube_half, hc); }
-  { real cq[4]; _Pragma("unroll") for (int k = 0; k < 3; k++) cp[k] = ME.ld(MP_CUBE + k);
-    _Pragma("unroll") for (int k = 0; k < 4; k++) cq[k] = ME.ld(MP_CUBE + 3 + k);
+  { real cq[4]; _Pragma("unroll") for (int k = 0; k < 3; k++) cp[k] = ME.ld(MP_CUBE_POS + k);
+    _Pragma("unroll") for (int k = 0; k < 4; k++) cq[k] = ME.ld(MP_CUBE_QUAT + k);
     quat_to_mat(cq, Rc); }
   const real Rt[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   const real mult = launder(Pm)->mesh_mult;
@@ -278,8 +278,8 @@ MCG_DEV void mesh_env(ModelPtr Pm, const real* __restrict__ poly, LdsPtr lds0, i
     const int bit = (int)__builtin_ctzll(bits); bits &= bits - 1ull;
     const int m = bit / 3, o = bit - 3 * m, body = mesh_body(m);
     real Rm[9], pm[3];
-    _Pragma("unroll") for (int k = 0; k < 9; k++) Rm[k] = ME.ld(MP_FRAME + body * 12 + k);
-    _Pragma("unroll") for (int k = 0; k < 3; k++) pm[k] = ME.ld(MP_FRAME + body * 12 + 9 + k);
+    _Pragma("unroll") for (int k = 0; k < 9; k++) Rm[k] = ME.ld(MP_FRAME + body * MP_FRAME_STRIDE + MP_FRAME_ROT + k);
+    _Pragma("unroll") for (int k = 0; k < 3; k++) pm[k] = ME.ld(MP_FRAME + body * MP_FRAME_STRIDE + MP_FRAME_POS + k);
     const MeshTab T = mesh_tab(poly, m);
     real pos[3], nrm[3], dist = 1.0; bool hit;
     MCG_COUNTW(CN_MP_PAIRS, 1); MCG_COUNTW(CN_MP_CUBE, o == 2);
@@ -320,7 +320,7 @@ MCG_DEV void mesh_phase(ModelPtr Pm, const real* __restrict__ poly, LdsPtr lds0,
   int cnt = 0;
   if (T < PNP_LANES) {
     const PnpScratch MS(lds0 + T);
-    const unsigned long long b = (unsigned long long)(long long)MS.ld(MP_MASK) | (unsigned long long)(long long)MS.ld(MP_MASK + 1) | (unsigned long long)(long long)MS.ld(MP_MASK + 2);
+    const unsigned long long b = (unsigned long long)(long long)MS.ld(MP_MASK_M) | (unsigned long long)(long long)MS.ld(MP_MASK_RNE) | (unsigned long long)(long long)MS.ld(MP_MASK_CUBE);
     cnt = __popcll(b);
   }
   unsigned em = __builtin_amdgcn_readfirstlane((unsigned)__ballot(cnt != 0));

@@ -63,7 +63,7 @@ typedef struct mco_model {
   int geom_poly[48];
   const double* poly;
   int maxentry;                  /* the contact list is cut after this many ENTRIES (a primitive contact, or the identical contacts of a
-                                    mesh's twin geoms: one entry); the HIP kernels hold 16 (MAXCON in csrc/mcg_cube.hpp).  MuJoCo has no cap. */
+                                    mesh's twin geoms: one entry); the HIP kernels hold 16 (MAXCON in csrc/mcg_lds.hpp).  MuJoCo has no cap. */
   /* Study switches (oracle/rule_study.py): alternatives to [RECALL] rules the reference's keyframes can discriminate.
    * All zero = the adopted rule set, which is what the HIP kernels implement and every parity test runs.
    *   rule[0] weld diagApprox   0 one common (translational) weight for the six rows | 1 translational rows 0-2, rotational rows 3-5
