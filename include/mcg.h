@@ -701,6 +701,57 @@ int mcg_frame_stack_push(uint8_t* stack, uint8_t* final_stack, int n_envs, int c
                          int64_t final_chan_stride, const uint8_t* done /* [N] device */, const uint8_t* mask /* [N] device or NULL */,
                          void* stream);
 
+/* ---- The actor-critic policy forward (SB3's MultiInputPolicy as PPO / A2C use it, scripts/train.py:99-101: for a Dict space of Boxes
+   two MLPs without shared layers and a DiagGaussianDistribution).  Stateless: the caller owns the weights (one float32 device blob, laid
+   out as mcg_policy.hip's head states and mycobotgym_amd/policy.py packs it) and the call number.  One launch on `stream`, no
+   synchronisation.
+     features   [achieved_goal(3), desired_goal(3), observation(D)] (SB3's CombinedExtractor: the keys in sorted order), each float64
+                rounded to float32 (round to nearest even), read where the engine wrote them.
+     trunks     n_pi / n_vf layers of pi_width / vf_width units, x -> act(W x + b), act = tanh or max(., 0); float32 throughout
+                (v_mfma_f32_16x16x4_f32; the order of a sum over k is the kernel's).
+     heads      mean = action_net(policy trunk) [N, A];  value = value_net(value trunk) [N].
+     noise      eps [N, A]: Philox4x32-10, key `seed`, counter ((uint32)gid, (uint32)call, pair ^ ((uint32)(call >> 32) << 8),
+                6 ^ ((uint32)(gid >> 32) << 8)), gid = env_id_offset + env, pair = 0 .. ceil(A / 2) - 1 (domain 6; 0-5: the reset, scene,
+                HER, rollout and picture-replay draws).  The block's two 53-bit uniforms u0, u1 (as every draw here maps them) give
+                eps[2 pair] = sqrt(-2 ln(1 - u0)) cos(2 pi u1) and eps[2 pair + 1] = sqrt(-2 ln(1 - u0)) sin(2 pi u1), evaluated in
+                double and rounded to float32 once.  deterministic != 0: eps = 0, nothing is drawn.
+     action     mean + exp(log_std) eps, evaluated in double from the float32 mean, log_std and eps and rounded once; not clipped
+                (SB3 stores the unclipped action; mcg_step clips what it reads).  deterministic: the mean's bits.
+     log_prob   sum over k of (-eps_k^2 / 2 - log_std_k - ln(2 pi) / 2) in float32.
+   With action, log_prob, mean and noise all NULL the policy trunk is not evaluated (the value of a final observation).  A row of the
+   outputs depends on its own environment alone; rows past n_envs of the last tile of 16 are not stored.
+   Checked on the host before any HIP call (MCG_ERR_ARG, each with a message that names the field): a null struct; a null blob; n_envs,
+   obs_dim or act_dim < 1; obs_dim > 4096; act_dim > 16; n_pi or n_vf outside [1, 3]; a width that is no multiple of 16 in [16, 256];
+   an activation other than the two below; blob_floats != mcg_policy_blob_floats of the shape; a blob that is not 16-byte aligned; a
+   null mcg_step_out or obs / achieved_goal / desired_goal in it; a null mcg_policy_out or all five outputs null. */
+#define MCG_POLICY_TANH 0
+#define MCG_POLICY_RELU 1
+
+typedef struct mcg_policy {
+  const float* blob;                /* device, 16-byte aligned, blob_floats floats */
+  int32_t n_envs, obs_dim, act_dim;
+  int32_t n_pi, n_vf;               /* hidden layers of the policy and the value trunk: 1..3 */
+  int32_t pi_width[3], vf_width[3]; /* their widths: multiples of 16, at most 256 (entries from n_pi / n_vf on are not read) */
+  int32_t activation;               /* MCG_POLICY_TANH or MCG_POLICY_RELU */
+  int64_t blob_floats;              /* must equal mcg_policy_blob_floats of this shape */
+} mcg_policy;
+
+typedef struct mcg_policy_out {     /* device pointers, any may be NULL to skip (not all) */
+  float* action;         /* [N, A] */
+  float* value;          /* [N] */
+  float* log_prob;       /* [N] */
+  float* mean;           /* [N, A] */
+  float* noise;          /* [N, A]  eps */
+} mcg_policy_out;
+
+/* Size of the blob in floats; 0 for a refused shape. */
+int64_t mcg_policy_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_vf, const int32_t* vf_width);
+
+/* `obs`: what mcg_reset / mcg_step wrote (obs, achieved_goal, desired_goal are read; a final observation goes into the same three
+   fields).  `call`: the number of the sampling call, the caller's to count. */
+int mcg_policy_forward(const mcg_policy* pol, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset,
+                       int deterministic, const mcg_policy_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ The numeric path is the HIP library ``libmycobot_hip.so`` (C ABI in ``include/mc
 package does not need a GPU, constructing an environment does.
 """
 from .frame_stack import FrameStack  # noqa: F401
+from .policy import ActorCritic  # noqa: F401
 from .registry import REGISTRY, spec  # noqa: F401
 from .replay import HerBuffer, HerSamples  # noqa: F401
 from .replay_img import ImageReplayBuffer, ReplaySamples  # noqa: F401

@@ -279,6 +279,20 @@ def replay_img_record_dtype(act_dim: int) -> np.dtype:
     return np.dtype(fields + [("pad", "u1", ((used + 15) // 16 * 16 - used,))])
 
 
+POLICY_TANH, POLICY_RELU = 0, 1
+
+
+class McgPolicy(C.Structure):
+    """The policy's weights and shape (include/mcg.h: mcg_policy); the caller owns the blob."""
+    _fields_ = [("blob", C.c_void_p), ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_pi", C.c_int32),
+                ("n_vf", C.c_int32), ("pi_width", C.c_int32 * 3), ("vf_width", C.c_int32 * 3), ("activation", C.c_int32),
+                ("blob_floats", C.c_int64)]
+
+
+class McgPolicyOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("action", "value", "log_prob", "mean", "noise")]
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -290,7 +304,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_rollout_img_record_bytes", "mcg_rollout_img_start", "mcg_rollout_img_add", "mcg_rollout_img_gae", "mcg_rollout_img_carry",
            "mcg_rollout_img_gather", "mcg_rollout_img_carry_stacked", "mcg_rollout_img_gather_stacked",
            "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample",
-           "mcg_replay_img_sample_stacked", "mcg_frame_stack_push")
+           "mcg_replay_img_sample_stacked", "mcg_frame_stack_push",
+           "mcg_policy_blob_floats", "mcg_policy_forward")
 
 _lib = None
 
@@ -378,6 +393,11 @@ def load():
                                                     C.POINTER(McgReplayImgBatch), C.c_void_p]
         L.mcg_frame_stack_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mcg_policy_forward"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_policy_blob_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
+        L.mcg_policy_blob_floats.restype = C.c_int64
+        L.mcg_policy_forward.argtypes = [C.POINTER(McgPolicy), C.POINTER(McgStepOut), C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
+                                         C.POINTER(McgPolicyOut), C.c_void_p]
     _lib = L
     return L
 

@@ -1,0 +1,294 @@
+// mcg_policy.hip -- the actor-critic policy forward of on-policy collection (include/mcg.h: mcg_policy_*): SB3's MultiInputPolicy for a
+// Dict space of Boxes -- two MLP trunks without shared layers, a diagonal Gaussian -- as one launch that reads the engine's float64
+// observation in place and writes action, value and log-prob in the forms mcg_rollout_add takes.
+//
+// A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives.  Kernel and C entries are both here.  The
+// C side is stateless; of mcg_engine.hpp it uses the error reporting alone.
+//
+// ---- Work split.  One wave per tile of 16 environments and net, one wave per workgroup: the value net and the policy net of a tile
+// share nothing but the input, so they are two workgroups (grid.y), and 8192 environments are 1024 waves, about one per SIMD; the
+// value-only call launches the value net's half.  Every layer is the transposed product on v_mfma_f32_16x16x4_f32, float32 in and out:
+//     D[unit][env] += W[unit][k] * X[k][env]        A operand: 16 units x 4 k of the weights, B operand: 4 k x 16 environments
+// Lane l = 16 g + i holds A[i][g] and B[g][i], and after the instruction D[4 g + r][i] in register r = 0..3 (checked against a host
+// product: tools/microbench/mfma_f32.hip).  So lane l holds, of output tile t, the units 16 t + 4 g + r of environment i: and since a
+// sum over k has no order, the next layer takes register r of tile t as the B operand of its k-block 4 t + r as it stands, provided
+// its weights were packed with that k-block being the units {16 t + 4 g + r : g = 0..3}.  No activation ever leaves the registers; the
+// kernel uses no LDS and no barrier.
+//
+// ---- Operand staging.  The weights are read as A operands straight from global memory: one coalesced 256-byte load per instruction,
+// at an address that depends on nothing computed, so the loads run ahead of the matrix instructions.  The blob of a [64, 64] policy is
+// about 50 KB and of a [256, 256] one about 620 KB: both stay in L2 (4 MiB per XCD), the first in L1 as well.  One code path serves
+// all widths; the kernel is instantiated for trunks of at most 64 units (4 tiles of registers per layer) and of at most 256 (16).
+//
+// ---- The blob (float32; mycobotgym_amd/policy.py: pack / unpack restate it).  In this order: the policy net's layers, its head
+// (action_net, A rows padded with zeros to 16), the value net's layers, its head (value_net, 1 row padded to 16), log_std padded to
+// 16.  A layer of `out` units (a multiple of 16; a head: 16) over `nkb` k-blocks is out / 16 * nkb tiles of 64 floats, then its bias,
+// `out` floats:
+//     tile (T, kb), float l = 16 g + i:   W[16 T + i][k(kb, g)]
+//     first layer   nkb = ceil((D + 6) / 4),  k(kb, g) = 4 kb + g: column of [achieved_goal(3), desired_goal(3), observation(D)], the
+//                   sorted key order of SB3's CombinedExtractor; columns from D + 6 on are zeros
+//     later layers  nkb = in / 4,             k(4 t + r, g) = 16 t + 4 g + r
+// Every piece is a multiple of 16 floats, so with a 16-byte aligned blob every bias row of 4 is one aligned 16-byte load.
+//
+// ---- The noise: counter layout policy_pair.  Philox4x32-10 (mcg_philox.hpp), key = seed, counter
+//     ((uint32)gid, (uint32)call, pair ^ ((uint32)(call >> 32) << 8), 6 ^ ((uint32)(gid >> 32) << 8))
+// gid = env_id_offset + i the global environment id, `call` the caller's count of sampling calls, pair = 0 .. ceil(A / 2) - 1.  The low
+// byte of the last word is the domain: 0-2 are the reset and scene draws (rng_pair, scene_pair), 3 her_pair, 4 the rollout
+// permutation, 5 the picture replay's draws, 6 this.  One block is two uniforms u0, u1 of 53 bits (philox_pair) and serves two action
+// components by Box-Muller, evaluated in double and rounded to float32 once:
+//     eps[2 pair] = sqrt(-2 ln(1 - u0)) cos(2 pi u1),   eps[2 pair + 1] = sqrt(-2 ln(1 - u0)) sin(2 pi u1)
+// An environment's draws depend on (seed, gid, call) alone: not on the tile it falls into, nor on how many ranks share the job.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+
+#include "mcg.h"
+#include "mcg_buffer.hpp"        // blocks, launched; mcg_fail; philox_pair
+
+using namespace mcg;
+
+namespace {
+
+constexpr uint32_t POLICY_STREAM = 6;
+constexpr int MAX_LAYERS = 3, MAX_WIDTH = 256, MAX_ACT = 16, MAX_OBS = 4096;
+constexpr int WAVE = 64, TILE = 16;
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+struct Net {                             // one trunk and its head: layer n is the head
+  int n, nt[MAX_LAYERS];                 // hidden layers and their widths in tiles of 16 units
+  int w[MAX_LAYERS + 1], b[MAX_LAYERS + 1];      // offsets of a layer's tiles and of its bias in the blob, in floats
+};
+struct Pol {                             // mcg_policy as the kernel sees it; net[0]: the value net, net[1]: the policy net
+  const float* blob; Net net[2]; int log_std, N, D, A, kb0, act;
+};
+struct Out { float *action, *value, *log_prob, *mean, *noise; };
+
+MCG_DEV f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+MCG_DEV float activate(int act, float x) { return act == MCG_POLICY_TANH ? tanhf(x) : fmaxf(x, 0.0f); }
+
+MCG_DEV void policy_pair(unsigned long long seed, unsigned long long gid, unsigned long long call, uint32_t pair, double& u0, double& u1) {
+  philox_pair((uint32_t)gid, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), POLICY_STREAM ^ ((uint32_t)(gid >> 32) << 8), seed, u0, u1);
+}
+
+// x[L], L = 0..3, by selects (the layer loop is a loop: its index is no constant)
+MCG_DEV int sel4(const int (&x)[MAX_LAYERS + 1], int L) { return L == 0 ? x[0] : L == 1 ? x[1] : L == 2 ? x[2] : x[3]; }
+
+// The first layer: the k-blocks are a loop (any D), the environment's columns are read where they lie and rounded to float32.
+template <int MT>
+MCG_DEV void first_layer(const Pol& P, const Net& net, const double* __restrict__ obs, const double* __restrict__ ach,
+                         const double* __restrict__ des, int env, int g, int lane, f4 (&out)[MT]) {
+  const float* __restrict__ W = P.blob + net.w[0];
+  const float* __restrict__ bias = P.blob + net.b[0];
+  const int nt = net.nt[0], D = P.D;
+#pragma unroll
+  for (int t = 0; t < MT; t++) {
+    out[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (t < nt) out[t] = *reinterpret_cast<const f4*>(bias + 16 * t + 4 * g);
+  }
+  for (int kb = 0; kb < P.kb0; kb++) {
+    const int f = 4 * kb + g;
+    float x = 0.0f;
+    if (f < 3) x = (float)ach[(size_t)env * 3 + f];
+    else if (f < 6) x = (float)des[(size_t)env * 3 + (f - 3)];
+    else if (f < D + 6) x = (float)obs[(size_t)env * D + (f - 6)];
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+      if (t < nt) out[t] = mfma(W[(t * P.kb0 + kb) * WAVE + lane], x, out[t]);
+  }
+}
+
+// A later layer or a head: `in`'s registers are the B operands (the file's head); layer `L` of `net`, nti input and nto output tiles.
+template <int MTI, int MTO>
+MCG_DEV void dense(const Pol& P, const Net& net, int L, int nti, int nto, const f4 (&in)[MTI], f4 (&out)[MTO], int g, int lane) {
+  const float* __restrict__ W = P.blob + sel4(net.w, L);
+  const float* __restrict__ bias = P.blob + sel4(net.b, L);
+  const int nkb = 4 * nti;
+#pragma unroll
+  for (int T = 0; T < MTO; T++) {
+    out[T] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (T < nto) {
+      f4 c = *reinterpret_cast<const f4*>(bias + 16 * T + 4 * g);
+#pragma unroll
+      for (int t = 0; t < MTI; t++) {
+        if (t < nti) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) c = mfma(W[(T * nkb + 4 * t + r) * WAVE + lane], in[t][r], c);
+        }
+      }
+      out[T] = c;
+    }
+  }
+}
+
+// net[k] by selects: an index that is no constant would send the kernel's arguments through scratch
+MCG_DEV Net pick(const Net& x, const Net& y, int k) {
+  Net z;
+  z.n = k ? y.n : x.n;
+#pragma unroll
+  for (int L = 0; L < MAX_LAYERS; L++) z.nt[L] = k ? y.nt[L] : x.nt[L];
+#pragma unroll
+  for (int L = 0; L <= MAX_LAYERS; L++) { z.w[L] = k ? y.w[L] : x.w[L]; z.b[L] = k ? y.b[L] : x.b[L]; }
+  return z;
+}
+
+// MT: tiles of 16 units that a trunk layer may have (the host picks 4 or 16 by the widest layer).
+template <int MT>
+__global__ __launch_bounds__(WAVE) void policy_kernel(Pol P, const double* __restrict__ obs, const double* __restrict__ ach,
+                                                      const double* __restrict__ des, unsigned long long seed, unsigned long long call,
+                                                      long long env_id_offset, int deterministic, Out O) {
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int e = blockIdx.x * TILE + i;
+  const bool live = e < P.N;
+  const int env = live ? e : P.N - 1;    // a ragged tile's extra rows read a valid row and store nothing
+  const int k = blockIdx.y;              // 0: the value net; 1: the policy net (grid.y == 1: mcg_policy_forward's value-only call)
+  if (k == 0 && !O.value) return;        // (the value is not asked for)
+  const Net net = pick(P.net[0], P.net[1], k);
+  f4 a[MT], b[MT];
+  first_layer<MT>(P, net, obs, ach, des, env, g, lane, a);
+#pragma unroll
+  for (int t = 0; t < MT; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, a[t][r]);
+  for (int L = 1; L < net.n; L++) {
+    dense<MT, MT>(P, net, L, L == 1 ? net.nt[0] : net.nt[1], L == 1 ? net.nt[1] : net.nt[2], a, b, g, lane);
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, b[t][r]);
+  }
+  f4 head[1];
+  dense<MT, 1>(P, net, net.n, net.n == 1 ? net.nt[0] : net.n == 2 ? net.nt[1] : net.nt[2], 1, a, head, g, lane);
+  const f4 h = head[0];                  // lane 16 g + i: rows 4 g + r of the head, environment i
+  if (k == 0) {
+    if (O.value && live && g == 0) O.value[e] = h[0];
+    return;
+  }
+  // ---- the diagonal Gaussian: this lane has components 4 g .. 4 g + 3, pairs 2 g and 2 g + 1
+  const f4 ls = *reinterpret_cast<const f4*>(P.blob + P.log_std + 4 * g);
+  const unsigned long long gid = (unsigned long long)(env_id_offset + env);
+  float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!deterministic) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      if (4 * g + 2 * q < P.A) {
+        double u0, u1, s, c;
+        policy_pair(seed, gid, call, (uint32_t)(2 * g + q), u0, u1);
+        const double rad = sqrt(-2.0 * log(1.0 - u0));
+        sincos(6.283185307179586476925 * u1, &s, &c);
+        eps[2 * q] = (float)(rad * c);
+        eps[2 * q + 1] = (float)(rad * s);
+      }
+    }
+  }
+  float lp = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int c = 4 * g + r;
+    if (c < P.A) {
+      // mean + exp(log_std) eps in double, rounded once (the action is not clipped: the step kernels clip what they read)
+      const float act = deterministic ? h[r] : (float)((double)h[r] + exp((double)ls[r]) * (double)eps[r]);
+      lp += (-0.5f * eps[r]) * eps[r] - ls[r] - 0.918938533204672742f;          // - eps^2 / 2 - log_std - ln(2 pi) / 2
+      if (live) {
+        const size_t at = (size_t)e * P.A + c;
+        if (O.action) O.action[at] = act;
+        if (O.mean) O.mean[at] = h[r];
+        if (O.noise) O.noise[at] = eps[r];
+      }
+    }
+  }
+  lp += __shfl_xor(lp, 16);              // the four lanes of an environment, in an order that does not depend on the tile
+  lp += __shfl_xor(lp, 32);
+  if (O.log_prob && live && g == 0) O.log_prob[e] = lp;
+}
+
+// ------------------------------------------------------------------------------------------------------- host side
+// The blob's plan for a shape -> its size in floats; 0 and `why` (a message that names the field) for a refused shape.
+int64_t plan(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_vf, const int32_t* vf_width, Pol* P, const char** why) {
+  if (obs_dim < 1 || act_dim < 1) { *why = "obs_dim and act_dim must be >= 1"; return 0; }
+  if (obs_dim > MAX_OBS) { *why = "obs_dim must be <= 4096"; return 0; }
+  if (act_dim > MAX_ACT) { *why = "act_dim must be <= 16"; return 0; }
+  if (n_pi < 1 || n_pi > MAX_LAYERS) { *why = "n_pi must be in [1, 3]"; return 0; }
+  if (n_vf < 1 || n_vf > MAX_LAYERS) { *why = "n_vf must be in [1, 3]"; return 0; }
+  if (!pi_width || !vf_width) { *why = "null pi_width or vf_width"; return 0; }
+  for (int k = 0; k < 2; k++) {
+    const int n = k ? n_pi : n_vf;
+    const int32_t* w = k ? pi_width : vf_width;
+    for (int L = 0; L < n; L++)
+      if (w[L] < 16 || w[L] > MAX_WIDTH || w[L] % 16 != 0) {
+        static thread_local char msg[80];
+        snprintf(msg, sizeof msg, "%s_width[%d] must be a multiple of 16 in [16, 256]", k ? "pi" : "vf", L);
+        *why = msg;
+        return 0;
+      }
+  }
+  const int kb0 = (obs_dim + 6 + 3) / 4;
+  int64_t at = 0;
+  for (int k = 1; k >= 0; k--) {         // the policy net first
+    const int n = k ? n_pi : n_vf;
+    const int32_t* w = k ? pi_width : vf_width;
+    Net net = {};
+    net.n = n;
+    for (int L = 0; L <= n; L++) {
+      const int out_tiles = L < n ? w[L] / 16 : 1, nkb = L == 0 ? kb0 : w[L - 1] / 4;
+      if (L < n) net.nt[L] = out_tiles;
+      net.w[L] = (int)at; at += (int64_t)out_tiles * nkb * WAVE;
+      net.b[L] = (int)at; at += (int64_t)out_tiles * 16;
+    }
+    if (P) P->net[k] = net;
+  }
+  if (P) { P->log_std = (int)at; P->kb0 = kb0; P->D = obs_dim; P->A = act_dim; }
+  return at + 16;                        // < 2^21 floats at the largest shape
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mcg_policy_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_vf, const int32_t* vf_width) {
+  const char* why;
+  return plan(obs_dim, act_dim, n_pi, pi_width, n_vf, vf_width, nullptr, &why);
+}
+
+int mcg_policy_forward(const mcg_policy* pol, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset,
+                       int deterministic, const mcg_policy_out* out, void* stream) {
+  const char* who = "mcg_policy_forward";
+  if (!pol) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_policy", who);
+  if (!pol->blob) return mcg_fail(MCG_ERR_ARG, "%s: blob is null", who);
+  if (pol->n_envs < 1) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be >= 1", who);
+  if ((long long)pol->n_envs * MAX_ACT >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be below 2^27", who);
+  Pol P = {};
+  const char* why = nullptr;
+  const int64_t floats = plan(pol->obs_dim, pol->act_dim, pol->n_pi, pol->pi_width, pol->n_vf, pol->vf_width, &P, &why);
+  if (floats == 0) return mcg_fail(MCG_ERR_ARG, "%s: %s", who, why);
+  if (pol->activation != MCG_POLICY_TANH && pol->activation != MCG_POLICY_RELU)
+    return mcg_fail(MCG_ERR_ARG, "%s: activation must be MCG_POLICY_TANH or MCG_POLICY_RELU", who);
+  if (pol->blob_floats != floats)
+    return mcg_fail(MCG_ERR_ARG, "%s: blob_floats is %lld, mcg_policy_blob_floats gives %lld for this shape", who, (long long)pol->blob_floats,
+                    (long long)floats);
+  if (((uintptr_t)pol->blob & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: blob is not 16-byte aligned", who);
+  if (!obs) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_step_out", who);
+  if (!obs->obs || !obs->achieved_goal || !obs->desired_goal)
+    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved_goal and desired_goal of the observation are required", who);
+  if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_policy_out", who);
+  if (!out->action && !out->value && !out->log_prob && !out->mean && !out->noise)
+    return mcg_fail(MCG_ERR_ARG, "%s: all outputs are null", who);
+  P.blob = pol->blob; P.N = pol->n_envs; P.act = pol->activation;
+  const int nets = (out->action || out->log_prob || out->mean || out->noise) ? 2 : 1;      // value alone: the policy net is not evaluated
+  const Out O = {out->action, out->value, out->log_prob, out->mean, out->noise};
+  int widest = 0;
+  for (int L = 0; L < pol->n_pi; L++) widest = pol->pi_width[L] > widest ? pol->pi_width[L] : widest;
+  for (int L = 0; L < pol->n_vf; L++) widest = pol->vf_width[L] > widest ? pol->vf_width[L] : widest;
+  const dim3 grid(blocks(P.N, TILE), nets), block(WAVE);
+#define MCG_POLICY(MT) hipLaunchKernelGGL(policy_kernel<MT>, grid, block, 0, (hipStream_t)stream, P, obs->obs, obs->achieved_goal, \
+                                          obs->desired_goal, (unsigned long long)seed, (unsigned long long)call, (long long)env_id_offset, \
+                                          deterministic != 0, O)
+  if (widest <= 64) MCG_POLICY(4);
+  else MCG_POLICY(16);
+#undef MCG_POLICY
+  return launched("mcg_policy");
+}
+
+}  // extern "C"
