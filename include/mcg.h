@@ -752,6 +752,57 @@ int64_t mcg_policy_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t
 int mcg_policy_forward(const mcg_policy* pol, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset,
                        int deterministic, const mcg_policy_out* out, void* stream);
 
+/* ---- The policy update (the other half of PPO / A2C as SB3 runs them on that policy): evaluate_actions, the loss and its gradient
+   with respect to every parameter, and clip-by-norm + Adam on the blob in place (mcg_policy_grad.hip).  Stateless, as everything here:
+   the caller owns the blob, the gradient, the moments and the scratch; every call enqueues on `stream` and none synchronises.  The
+   minibatch is float32, in the arrays mcg_rollout_gather writes; B = its rows, any value >= 1 (pol->n_envs is not read).
+   All of it is deterministic: no floating-point atomics, every sum in an order fixed by the shape and B alone. */
+typedef struct mcg_policy_eval_out {/* device pointers, any may be NULL to skip (not all) */
+  float* value;          /* [B] */
+  float* log_prob;       /* [B]  sum_k (-(a_k - mean_k)^2 / (2 sigma_k^2) - log_std_k - ln(2 pi) / 2) */
+  float* entropy;        /* [B]  sum_k (1/2 + ln(2 pi) / 2 + log_std_k) */
+} mcg_policy_eval_out;
+
+/* SB3's evaluate_actions, forward only: obs, achieved, desired and action of `batch` are read (the other fields are not). */
+int mcg_policy_evaluate(const mcg_policy* pol, const mcg_rollout_batch* batch, int64_t B, const mcg_policy_eval_out* out, void* stream);
+
+#define MCG_LOSS_PPO 0
+#define MCG_LOSS_A2C 1
+
+typedef struct mcg_policy_hyper {   /* SB3's names; clip_range_vf is not built */
+  int32_t loss_kind;                /* MCG_LOSS_PPO or MCG_LOSS_A2C */
+  int32_t normalize_advantage;      /* != 0 and B > 1: adv <- (adv - mean) / (std + 1e-8), std the unbiased one (torch.std) */
+  float clip_range;                 /* PPO's c, > 0 (A2C: not read) */
+  float ent_coef, vf_coef;
+} mcg_policy_hyper;
+
+/* The loss of the minibatch and its gradient.  With ratio = exp(log_prob - old_log_prob):
+     policy_loss   PPO: -mean(min(adv ratio, adv clamp(ratio, 1 - c, 1 + c)));  A2C: -mean(adv log_prob)
+     value_loss    mean((returns - value)^2);     entropy_loss  -mean(entropy)
+     loss          policy_loss + ent_coef entropy_loss + vf_coef value_loss
+   obs, achieved, desired, action, old_log_prob, advantage and returns of `batch` are read (old_log_prob: PPO only).
+   grad   [blob_floats], 16-byte aligned, in the blob's own layout: the gradient of the weight at blob position p is grad[p]; every
+          padding position (head rows from A, or from 1 for the value head, up to 15; first-layer columns from D + 6 on; the log_std
+          pad) is written as +0.0f.
+   stats  [8]: loss, policy_loss, value_loss, entropy_loss, approx_kl = mean((ratio - 1) - ln ratio), clip_fraction =
+          mean(|ratio - 1| > c), 0, 0 (A2C: approx_kl and clip_fraction are 0).
+   work   scratch of work_floats >= mcg_policy_grad_work_floats(pol, B) floats, 16-byte aligned; its content before the call does not
+          matter and nothing of it needs to be kept.
+   Four launches: the advantage's mean and deviation (skipped where they are not used), the forward and backward pass per tile of 16
+   samples, the weight gradients as partial blobs in `work`, their sum in index order. */
+int64_t mcg_policy_grad_work_floats(const mcg_policy* pol, int64_t B);      /* 0 for a refused shape or B < 1 */
+int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64_t B, const mcg_policy_hyper* hyper, float* work,
+                    int64_t work_floats, float* grad, float* stats, void* stream);
+
+/* Clip by global norm as torch's clip_grad_norm_, coef = min(1, max_grad_norm / (||grad||_2 + 1e-6)) (max_grad_norm <= 0: coef = 1;
+   the norm over all blob_floats, in a fixed order, is written to norm_out [1] either way), then torch.optim.Adam's step without amsgrad
+   or weight decay, elementwise on the blob (pol->blob is written), with g = coef grad:
+     m <- beta1 m + (1 - beta1) g;   v <- beta2 v + (1 - beta2) g^2;   p <- p - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+   The two bias corrections are computed on the host in double from `step` (>= 1).  grad is not changed.  grad, m, v: [blob_floats],
+   16-byte aligned; padding positions keep g = m = v = 0 and so stay 0: the blob remains a valid blob.  Two launches. */
+int mcg_policy_adam(const mcg_policy* pol, const float* grad, float* m, float* v, int64_t step, double lr, double beta1, double beta2,
+                    double eps, double max_grad_norm, float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,19 @@ class McgPolicyOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("action", "value", "log_prob", "mean", "noise")]
 
 
+class McgPolicyEvalOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("value", "log_prob", "entropy")]
+
+
+LOSS_PPO, LOSS_A2C = 0, 1
+
+
+class McgPolicyHyper(C.Structure):
+    """The loss's hyper-parameters under SB3's names (include/mcg.h: mcg_policy_hyper)."""
+    _fields_ = [("loss_kind", C.c_int32), ("normalize_advantage", C.c_int32), ("clip_range", C.c_float), ("ent_coef", C.c_float),
+                ("vf_coef", C.c_float)]
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -305,7 +318,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_rollout_img_gather", "mcg_rollout_img_carry_stacked", "mcg_rollout_img_gather_stacked",
            "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample",
            "mcg_replay_img_sample_stacked", "mcg_frame_stack_push",
-           "mcg_policy_blob_floats", "mcg_policy_forward")
+           "mcg_policy_blob_floats", "mcg_policy_forward",
+           "mcg_policy_evaluate", "mcg_policy_grad_work_floats", "mcg_policy_grad", "mcg_policy_adam")
 
 _lib = None
 
@@ -398,6 +412,14 @@ def load():
         L.mcg_policy_blob_floats.restype = C.c_int64
         L.mcg_policy_forward.argtypes = [C.POINTER(McgPolicy), C.POINTER(McgStepOut), C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
                                          C.POINTER(McgPolicyOut), C.c_void_p]
+    if hasattr(L, "mcg_policy_grad"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_policy_evaluate.argtypes = [C.POINTER(McgPolicy), C.POINTER(McgRolloutBatch), C.c_int64, C.POINTER(McgPolicyEvalOut), C.c_void_p]
+        L.mcg_policy_grad_work_floats.argtypes = [C.POINTER(McgPolicy), C.c_int64]
+        L.mcg_policy_grad_work_floats.restype = C.c_int64
+        L.mcg_policy_grad.argtypes = [C.POINTER(McgPolicy), C.POINTER(McgRolloutBatch), C.c_int64, C.POINTER(McgPolicyHyper), C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcg_policy_adam.argtypes = [C.POINTER(McgPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, d, d, d, d, d, C.c_void_p,
+                                      C.c_void_p]
     _lib = L
     return L
 

@@ -38,100 +38,18 @@
 // components by Box-Muller, evaluated in double and rounded to float32 once:
 //     eps[2 pair] = sqrt(-2 ln(1 - u0)) cos(2 pi u1),   eps[2 pair + 1] = sqrt(-2 ln(1 - u0)) sin(2 pi u1)
 // An environment's draws depend on (seed, gid, call) alone: not on the tile it falls into, nor on how many ranks share the job.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdio>
-
-#include "mcg.h"
-#include "mcg_buffer.hpp"        // blocks, launched; mcg_fail; philox_pair
+#include "mcg_policy.hpp"       // plan, Net, Pol, mfma, activate, first_layer, dense, pick: shared with mcg_policy_grad.hip
 
 using namespace mcg;
 
 namespace {
 
 constexpr uint32_t POLICY_STREAM = 6;
-constexpr int MAX_LAYERS = 3, MAX_WIDTH = 256, MAX_ACT = 16, MAX_OBS = 4096;
-constexpr int WAVE = 64, TILE = 16;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct Net {                             // one trunk and its head: layer n is the head
-  int n, nt[MAX_LAYERS];                 // hidden layers and their widths in tiles of 16 units
-  int w[MAX_LAYERS + 1], b[MAX_LAYERS + 1];      // offsets of a layer's tiles and of its bias in the blob, in floats
-};
-struct Pol {                             // mcg_policy as the kernel sees it; net[0]: the value net, net[1]: the policy net
-  const float* blob; Net net[2]; int log_std, N, D, A, kb0, act;
-};
 struct Out { float *action, *value, *log_prob, *mean, *noise; };
-
-MCG_DEV f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-MCG_DEV float activate(int act, float x) { return act == MCG_POLICY_TANH ? tanhf(x) : fmaxf(x, 0.0f); }
 
 MCG_DEV void policy_pair(unsigned long long seed, unsigned long long gid, unsigned long long call, uint32_t pair, double& u0, double& u1) {
   philox_pair((uint32_t)gid, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), POLICY_STREAM ^ ((uint32_t)(gid >> 32) << 8), seed, u0, u1);
-}
-
-// x[L], L = 0..3, by selects (the layer loop is a loop: its index is no constant)
-MCG_DEV int sel4(const int (&x)[MAX_LAYERS + 1], int L) { return L == 0 ? x[0] : L == 1 ? x[1] : L == 2 ? x[2] : x[3]; }
-
-// The first layer: the k-blocks are a loop (any D), the environment's columns are read where they lie and rounded to float32.
-template <int MT>
-MCG_DEV void first_layer(const Pol& P, const Net& net, const double* __restrict__ obs, const double* __restrict__ ach,
-                         const double* __restrict__ des, int env, int g, int lane, f4 (&out)[MT]) {
-  const float* __restrict__ W = P.blob + net.w[0];
-  const float* __restrict__ bias = P.blob + net.b[0];
-  const int nt = net.nt[0], D = P.D;
-#pragma unroll
-  for (int t = 0; t < MT; t++) {
-    out[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (t < nt) out[t] = *reinterpret_cast<const f4*>(bias + 16 * t + 4 * g);
-  }
-  for (int kb = 0; kb < P.kb0; kb++) {
-    const int f = 4 * kb + g;
-    float x = 0.0f;
-    if (f < 3) x = (float)ach[(size_t)env * 3 + f];
-    else if (f < 6) x = (float)des[(size_t)env * 3 + (f - 3)];
-    else if (f < D + 6) x = (float)obs[(size_t)env * D + (f - 6)];
-#pragma unroll
-    for (int t = 0; t < MT; t++)
-      if (t < nt) out[t] = mfma(W[(t * P.kb0 + kb) * WAVE + lane], x, out[t]);
-  }
-}
-
-// A later layer or a head: `in`'s registers are the B operands (the file's head); layer `L` of `net`, nti input and nto output tiles.
-template <int MTI, int MTO>
-MCG_DEV void dense(const Pol& P, const Net& net, int L, int nti, int nto, const f4 (&in)[MTI], f4 (&out)[MTO], int g, int lane) {
-  const float* __restrict__ W = P.blob + sel4(net.w, L);
-  const float* __restrict__ bias = P.blob + sel4(net.b, L);
-  const int nkb = 4 * nti;
-#pragma unroll
-  for (int T = 0; T < MTO; T++) {
-    out[T] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (T < nto) {
-      f4 c = *reinterpret_cast<const f4*>(bias + 16 * T + 4 * g);
-#pragma unroll
-      for (int t = 0; t < MTI; t++) {
-        if (t < nti) {
-#pragma unroll
-          for (int r = 0; r < 4; r++) c = mfma(W[(T * nkb + 4 * t + r) * WAVE + lane], in[t][r], c);
-        }
-      }
-      out[T] = c;
-    }
-  }
-}
-
-// net[k] by selects: an index that is no constant would send the kernel's arguments through scratch
-MCG_DEV Net pick(const Net& x, const Net& y, int k) {
-  Net z;
-  z.n = k ? y.n : x.n;
-#pragma unroll
-  for (int L = 0; L < MAX_LAYERS; L++) z.nt[L] = k ? y.nt[L] : x.nt[L];
-#pragma unroll
-  for (int L = 0; L <= MAX_LAYERS; L++) { z.w[L] = k ? y.w[L] : x.w[L]; z.b[L] = k ? y.b[L] : x.b[L]; }
-  return z;
 }
 
 // MT: tiles of 16 units that a trunk layer may have (the host picks 4 or 16 by the widest layer).
@@ -147,7 +65,7 @@ __global__ __launch_bounds__(WAVE) void policy_kernel(Pol P, const double* __res
   if (k == 0 && !O.value) return;        // (the value is not asked for)
   const Net net = pick(P.net[0], P.net[1], k);
   f4 a[MT], b[MT];
-  first_layer<MT>(P, net, obs, ach, des, env, g, lane, a);
+  first_layer<MT, double>(P, net, obs, ach, des, env, g, lane, a);
 #pragma unroll
   for (int t = 0; t < MT; t++)
 #pragma unroll
@@ -202,45 +120,6 @@ __global__ __launch_bounds__(WAVE) void policy_kernel(Pol P, const double* __res
   lp += __shfl_xor(lp, 16);              // the four lanes of an environment, in an order that does not depend on the tile
   lp += __shfl_xor(lp, 32);
   if (O.log_prob && live && g == 0) O.log_prob[e] = lp;
-}
-
-// ------------------------------------------------------------------------------------------------------- host side
-// The blob's plan for a shape -> its size in floats; 0 and `why` (a message that names the field) for a refused shape.
-int64_t plan(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_vf, const int32_t* vf_width, Pol* P, const char** why) {
-  if (obs_dim < 1 || act_dim < 1) { *why = "obs_dim and act_dim must be >= 1"; return 0; }
-  if (obs_dim > MAX_OBS) { *why = "obs_dim must be <= 4096"; return 0; }
-  if (act_dim > MAX_ACT) { *why = "act_dim must be <= 16"; return 0; }
-  if (n_pi < 1 || n_pi > MAX_LAYERS) { *why = "n_pi must be in [1, 3]"; return 0; }
-  if (n_vf < 1 || n_vf > MAX_LAYERS) { *why = "n_vf must be in [1, 3]"; return 0; }
-  if (!pi_width || !vf_width) { *why = "null pi_width or vf_width"; return 0; }
-  for (int k = 0; k < 2; k++) {
-    const int n = k ? n_pi : n_vf;
-    const int32_t* w = k ? pi_width : vf_width;
-    for (int L = 0; L < n; L++)
-      if (w[L] < 16 || w[L] > MAX_WIDTH || w[L] % 16 != 0) {
-        static thread_local char msg[80];
-        snprintf(msg, sizeof msg, "%s_width[%d] must be a multiple of 16 in [16, 256]", k ? "pi" : "vf", L);
-        *why = msg;
-        return 0;
-      }
-  }
-  const int kb0 = (obs_dim + 6 + 3) / 4;
-  int64_t at = 0;
-  for (int k = 1; k >= 0; k--) {         // the policy net first
-    const int n = k ? n_pi : n_vf;
-    const int32_t* w = k ? pi_width : vf_width;
-    Net net = {};
-    net.n = n;
-    for (int L = 0; L <= n; L++) {
-      const int out_tiles = L < n ? w[L] / 16 : 1, nkb = L == 0 ? kb0 : w[L - 1] / 4;
-      if (L < n) net.nt[L] = out_tiles;
-      net.w[L] = (int)at; at += (int64_t)out_tiles * nkb * WAVE;
-      net.b[L] = (int)at; at += (int64_t)out_tiles * 16;
-    }
-    if (P) P->net[k] = net;
-  }
-  if (P) { P->log_std = (int)at; P->kb0 = kb0; P->D = obs_dim; P->A = act_dim; }
-  return at + 16;                        // < 2^21 floats at the largest shape
 }
 
 }  // namespace

@@ -1,0 +1,503 @@
+// mcg_policy_grad.hip -- the policy update (include/mcg.h: mcg_policy_evaluate, mcg_policy_grad, mcg_policy_adam): SB3's
+// evaluate_actions, the PPO / A2C loss and its gradient with respect to every parameter of the blob, and clip-by-norm + Adam on the
+// blob in place.  A code object of its own, as mcg_policy.hip, whose blob plan, operand map and forward helpers it shares
+// (mcg_policy.hpp).  Float32 throughout on v_mfma_f32_16x16x4_f32; deterministic: no atomics, every sum in an order that the shape
+// and B alone fix.
+//
+// ---- The three products of a layer, in tiles of 16 samples.  Lane l = 16 g + i holds A[i][g] and B[g][i], and afterwards D[4 g + r][i]
+// in register r (mcg_policy.hip's head; the two arrangements below against a host product: tools/microbench/mfma_f32_grad.hip).
+//   Z = W X          the forward as it stands: register r of tile t is the B operand of k-block 4 t + r of the next layer.
+//   dX = W^T dZ      dZ is in the accumulator layout too (lane 16 g + i: units 16 t + 4 g + r of sample i), so register r of tile t is
+//                    again the B operand of a k-block, the units {16 t + 4 g + r : g}.  The A operand of that block and output tile T'
+//                    is W[16 t + 4 g + r][16 T' + i]: in the blob that is tile (t, 4 T' + (i & 3)), float 16 (i >> 2) + 4 g + r -- for
+//                    r = 0..3 four consecutive floats, one 16-byte load per lane out of L2 (the blob is at most 620 KB).  No second
+//                    packed copy of the weights exists.
+//   dW = dZ X^T      the sum runs over samples, four per instruction.  Both operands are re-laid through memory as rows of 16 samples:
+//                    row u = unit u (of dZ) or input column u (of X), float s = sample s of the tile.  Lane 16 g + i then reads the four
+//                    floats 4 g .. 4 g + 3 of row 16 T + i (A) and of row 16 C + i (B) in one 16-byte load each, and instruction
+//                    q = 0..3 sums the samples {4 g + q : g}: which four samples share an instruction does not matter to a sum.  The
+//                    result, dW[16 T + 4 g + r][16 C + i] in register r, lies in the blob at four consecutive floats again.  A bias
+//                    (and log_std) is the same product with X = 1.
+//
+// ---- Work split.  grad_tile_kernel: one wave per tile of 16 samples and net, as the forward.  It runs the forward, keeps every layer's
+// activations as rows in `work` (not in registers: at [256, 256] they would not fit, and the dW product wants them re-laid anyway),
+// forms the loss's derivative at the head, walks back through W^T, and leaves every layer's dZ rows beside the activations.  It re-reads
+// its own activation rows for tanh' = 1 - y^2 / relu' = [y > 0].  grad_dw_kernel: one wave per 16 x 16 block of a weight matrix (or
+// 16 biases) and part: it walks the part's tiles of samples in order and writes its block of the part's partial blob.  The blob has
+// few blocks (about 75 at [64, 64]), so the samples are split into at most 16 parts (4 at widths above 64): 4096 samples at [64, 64]
+// are 256 tiles, 16 parts of 16 tiles, about 1200 waves.  grad_reduce_kernel adds the partial blobs in part order, adds the entropy
+// term's exact -ent_coef to log_std, and sums the tiles' loss terms in a fixed tree into `stats`.  adv_stats_kernel (one workgroup,
+// double accumulators, a fixed tree) writes the advantage's mean and std + 1e-8 first where they are used.
+//
+// ---- `work` (floats):  [0] advantage mean, [1] std + 1e-8, [2..3] unused;  [4 + 8 tile + s] the tile's sums: s = 1 policy term, 2
+// squared value error, 4 kl term, 5 clipped count;  then per net and tile `rows` rows of 16 floats (the row map: struct Rows);  then
+// `parts` partial blobs.  Every float that is read was written by the same call.
+//
+// ---- A ragged last tile: its extra lanes read the last valid sample, as in the forward, and their dZ is set to +-0 at the head, so
+// that every product they enter adds exactly nothing.
+#include "mcg_policy.hpp"
+
+using namespace mcg;
+
+namespace {
+
+constexpr int PARTS_NARROW = 16, PARTS_WIDE = 4, MAX_BLOCK_LAYERS = 2 * (MAX_LAYERS + 1) + 1;
+constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
+constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
+
+struct Rows {                            // a net's rows of a tile in `work`, in rows of 16 floats
+  int x[MAX_LAYERS + 1];                 // x[L]: the input of layer L (x[0]: the features, fr rows; x[n]: the head's input)
+  int d[MAX_LAYERS + 1];                 // d[L]: dZ of layer L (d[n]: the head's, 16 rows)
+  int ls, rows, fr;                      // the policy net's 16 rows of the log_std terms; rows in all; feature rows (D + 6 padded to 16)
+  long long base;                        // the net's first float in `work`
+};
+struct Batch { const float *obs, *ach, *des, *action, *old_lp, *adv, *ret; };
+struct Hyper { int kind, norm; float clip, ent_coef, vf_coef, inv_b; };
+struct EvalOut { float *value, *log_prob, *entropy; };
+struct Block {                           // one layer's blocks of the dW product: nT rows of (ncb blocks of 16 columns, then the bias)
+  int blk0, nT, ncb, xrow, drow, w, b, nkb, first, rows;
+  long long base;
+};
+struct Blocks { Block l[MAX_BLOCK_LAYERS]; int n, total; };
+
+MCG_DEV Rows pick_rows(const Rows& x, const Rows& y, int k) {
+  Rows z;
+#pragma unroll
+  for (int L = 0; L <= MAX_LAYERS; L++) { z.x[L] = k ? y.x[L] : x.x[L]; z.d[L] = k ? y.d[L] : x.d[L]; }
+  z.ls = k ? y.ls : x.ls; z.rows = k ? y.rows : x.rows; z.fr = k ? y.fr : x.fr; z.base = k ? y.base : x.base;
+  return z;
+}
+
+// the sum over the 16 samples of a tile, in an order that does not depend on the data (every lane gets it)
+MCG_DEV float sum16(float x) {
+  x += __shfl_xor(x, 8); x += __shfl_xor(x, 4); x += __shfl_xor(x, 2); x += __shfl_xor(x, 1);
+  return x;
+}
+
+// rows `at + 16 t + 4 g + r` of the tile's chunk <- register r of tile t (the accumulator layout), sample i
+template <int MT>
+MCG_DEV void store_rows(float* chunk, int at, int nt, const f4 (&v)[MT], int g, int i) {
+#pragma unroll
+  for (int t = 0; t < MT; t++)
+    if (t < nt) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) chunk[(size_t)(at + 16 * t + 4 * g + r) * TILE + i] = v[t][r];
+    }
+}
+
+// GRAD = false: mcg_policy_evaluate (no `work`);  true: the forward, the loss's derivative and the backward pass of one tile and net.
+template <int MT, bool GRAD>
+__global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1, Batch X, Hyper H, float* work, EvalOut E) {
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int tile = blockIdx.x, s = tile * TILE + i;
+  const bool live = s < P.N;
+  const int row = live ? s : P.N - 1;    // a ragged tile's extra lanes read a valid row and contribute nothing
+  const int k = blockIdx.y;              // 0: the value net; 1: the policy net
+  if (!GRAD && k == 0 && !E.value) return;
+  const Net net = pick(P.net[0], P.net[1], k);
+  const Rows R = pick_rows(R0, R1, k);
+  float* chunk = GRAD ? work + R.base + (size_t)tile * R.rows * TILE : nullptr;
+  const int n = net.n;
+  // ---- forward
+  f4 a[MT], b[MT];
+  first_layer<MT, float>(P, net, X.obs, X.ach, X.des, row, g, lane, a);
+  if (GRAD) {
+    for (int f = g; f < R.fr; f += 4) {  // the features as rows: the first layer's X (columns from D + 6 on are zeros)
+      float x = 0.0f;
+      if (f < 3) x = X.ach[(size_t)row * 3 + f];
+      else if (f < 6) x = X.des[(size_t)row * 3 + (f - 3)];
+      else if (f < P.D + 6) x = X.obs[(size_t)row * P.D + (f - 6)];
+      chunk[(size_t)(R.x[0] + f) * TILE + i] = x;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < MT; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, a[t][r]);
+  if (GRAD) store_rows<MT>(chunk, R.x[1], net.nt[0], a, g, i);
+  for (int L = 1; L < n; L++) {
+    dense<MT, MT>(P, net, L, L == 1 ? net.nt[0] : net.nt[1], L == 1 ? net.nt[1] : net.nt[2], a, b, g, lane);
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, b[t][r]);
+    if (GRAD) store_rows<MT>(chunk, L == 1 ? R.x[2] : R.x[3], L == 1 ? net.nt[1] : net.nt[2], a, g, i);
+  }
+  f4 head[1];
+  dense<MT, 1>(P, net, n, n == 1 ? net.nt[0] : n == 2 ? net.nt[1] : net.nt[2], 1, a, head, g, lane);
+  const f4 h = head[0];                  // lane 16 g + i: rows 4 g + r of the head, sample i
+  // ---- the head: outputs (evaluate), or the loss's derivative dh with respect to the head's rows
+  f4 dh = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (k == 0) {
+    if (!GRAD) {
+      if (live && g == 0) E.value[s] = h[0];
+      return;
+    }
+    const float diff = h[0] - X.ret[row];                       // (lanes g == 0 hold the value: row 0 of the head)
+    const bool mine = live && g == 0;
+    if (mine) dh[0] = (2.0f * H.vf_coef * H.inv_b) * diff;
+    const float sq = sum16(mine ? diff * diff : 0.0f);
+    if (lane == 0) work[4 + 8 * (size_t)tile + 2] = sq;
+  } else {
+    const f4 ls = *reinterpret_cast<const f4*>(P.blob + P.log_std + 4 * g);
+    // The log-prob from the float32 mean in double, rounded once: log_prob - old_log_prob and (ratio - 1) - ln ratio cancel most of
+    // its digits, and a sum of A terms of magnitude 1 in float32 would leave them its rounding (a few 1e-7 on a ratio near 1).
+    double lpd = 0.0;
+    f4 dmu = {0.0f, 0.0f, 0.0f, 0.0f}, dls = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int c = 4 * g + r;
+      if (c < P.A) {
+        const double inv = exp(-(double)ls[r]), zd = ((double)X.action[(size_t)row * P.A + c] - (double)h[r]) * inv;
+        lpd += -0.5 * zd * zd - (double)ls[r] - LOG_SQRT_2PI_D;
+        const float z = (float)zd;
+        dmu[r] = z * (float)inv;         // d log_prob / d mean_c = (a - mean) / sigma^2
+        dls[r] = z * z - 1.0f;           // d log_prob / d log_std_c
+      }
+    }
+    lpd += __shfl_xor(lpd, 16);          // the four lanes of a sample, in the forward's order
+    lpd += __shfl_xor(lpd, 32);
+    const float lp = (float)lpd;
+    if (!GRAD) {
+      if (live && g == 0) {
+        if (E.log_prob) E.log_prob[s] = lp;
+        if (E.entropy) {
+          float ent = 0.0f;
+          for (int c = 0; c < P.A; c++) ent += ENTROPY_0 + P.blob[P.log_std + c];
+          E.entropy[s] = ent;
+        }
+      }
+      return;
+    }
+    float adv = X.adv[row];
+    if (H.norm) adv = (adv - work[0]) / work[1];
+    float term, dlp, kl = 0.0f, clipped = 0.0f;                // the sample's policy term (its loss is -term), d loss / d log_prob
+    if (H.kind == MCG_LOSS_PPO) {
+      const double lrd = lpd - (double)X.old_lp[row];
+      const float lr = (float)lrd, ratio = expf(lr);
+      const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, 1.0f - H.clip), 1.0f + H.clip);
+      term = fminf(s1, s2);
+      dlp = s1 <= s2 ? -(adv * ratio) * H.inv_b : 0.0f;         // the clipped branch is a constant
+      kl = (float)(expm1(lrd) - lrd);
+      clipped = fabsf(ratio - 1.0f) > H.clip ? 1.0f : 0.0f;
+    } else {
+      term = adv * lp;
+      dlp = -adv * H.inv_b;
+    }
+    if (!live) { term = 0.0f; dlp = 0.0f; kl = 0.0f; clipped = 0.0f; }
+    f4 dl;
+#pragma unroll
+    for (int r = 0; r < 4; r++) { dh[r] = dlp * dmu[r]; dl[r] = dlp * dls[r]; }
+    const float st = sum16(term), sk = sum16(kl), sc = sum16(clipped);
+    if (lane == 0) { work[4 + 8 * (size_t)tile + 1] = st; work[4 + 8 * (size_t)tile + 4] = sk; work[4 + 8 * (size_t)tile + 5] = sc; }
+#pragma unroll
+    for (int r = 0; r < 4; r++) chunk[(size_t)(R.ls + 4 * g + r) * TILE + i] = dl[r];
+  }
+  // ---- backward: d[t] is dZ of layer L in the accumulator layout; dZ of layer L - 1 = act'(y) * (W_L^T dZ_L)
+  f4 d[MT], e[MT];
+#pragma unroll
+  for (int t = 0; t < MT; t++) d[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+  d[0] = dh;
+  store_rows<MT>(chunk, sel4(R.d, n), 1, d, g, i);
+  for (int L = n; L >= 1; L--) {
+    const int nto = L == n ? 1 : (L == 1 ? net.nt[1] : net.nt[2]);              // tiles of dZ_L: the product's k
+    const int nti = L == 1 ? net.nt[0] : L == 2 ? net.nt[1] : net.nt[2];        // tiles of layer L's input: the product's rows
+    const float* __restrict__ W = P.blob + sel4(net.w, L);
+    const float* y = chunk + (size_t)sel4(R.x, L) * TILE;                       // the input's activations, as this lane stored them
+    const int nkb = 4 * nti;
+#pragma unroll
+    for (int T = 0; T < MT; T++) {
+      e[T] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (T < nti) {
+        f4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int t = 0; t < MT; t++) {
+          if (t < nto) {
+            const f4 w = *reinterpret_cast<const f4*>(W + (size_t)(t * nkb + 4 * T + (i & 3)) * WAVE + 16 * (i >> 2) + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; r++) c = mfma(w[r], d[t][r], c);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const float yy = y[(size_t)(16 * T + 4 * g + r) * TILE + i];
+          c[r] *= P.act == MCG_POLICY_TANH ? 1.0f - yy * yy : (yy > 0.0f ? 1.0f : 0.0f);
+        }
+        e[T] = c;
+      }
+    }
+    store_rows<MT>(chunk, sel4(R.d, L - 1), nti, e, g, i);
+#pragma unroll
+    for (int t = 0; t < MT; t++) d[t] = e[t];
+  }
+}
+
+// One 16 x 16 block of dW (or 16 biases) over the tiles of one part -> its place in the part's partial blob.
+__global__ __launch_bounds__(WAVE) void grad_dw_kernel(Blocks Q, const float* __restrict__ work, float* __restrict__ partials,
+                                                       long long blob_floats, int ntiles, int tpp, int kb0, int D) {
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int blk = blockIdx.x, part = blockIdx.y;
+  Block me = Q.l[0];
+#pragma unroll
+  for (int q = 1; q < MAX_BLOCK_LAYERS; q++)
+    if (q < Q.n && blk >= Q.l[q].blk0) me = Q.l[q];              // (constant indices: selects, no scratch)
+  const int local = blk - me.blk0, T = local / (me.ncb + 1), cb = local % (me.ncb + 1);
+  const bool bias = cb == me.ncb;
+  const int t0 = part * tpp, t1 = min(t0 + tpp, ntiles);
+  const size_t stride = (size_t)me.rows * TILE;
+  const float* __restrict__ A = work + me.base + (size_t)(me.drow + 16 * T + i) * TILE + 4 * g;
+  const float* __restrict__ Bm = work + me.base + (size_t)(me.xrow + (bias ? 0 : 16 * cb) + i) * TILE + 4 * g;
+  f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int t = t0; t < t1; t++) {
+    const f4 a4 = *reinterpret_cast<const f4*>(A + t * stride);
+    f4 b4 = {1.0f, 1.0f, 1.0f, 1.0f};
+    if (!bias) b4 = *reinterpret_cast<const f4*>(Bm + t * stride);
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc = mfma(a4[q], b4[q], acc);
+  }
+  float* out = partials + (size_t)part * blob_floats;          // register r: dW[16 T + 4 g + r][16 cb + i]
+  if (bias) {
+    if (i == 0) *reinterpret_cast<f4*>(out + me.b + 16 * T + 4 * g) = acc;
+  } else if (me.first) {                 // column 16 cb + i = 4 kb + g': tile (T, kb), float 16 g' + 4 g + r
+    const int kb = 4 * cb + (i >> 2);
+    if (kb < kb0) {
+      if (16 * cb + i >= D + 6) acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      *reinterpret_cast<f4*>(out + me.w + (size_t)(T * kb0 + kb) * WAVE + 16 * (i & 3) + 4 * g) = acc;
+    }
+  } else {                               // column 16 cb + i = 16 t + 4 g' + r': tile (T, 4 t + r'), float 16 g' + 4 g + r
+    *reinterpret_cast<f4*>(out + me.w + (size_t)(T * me.nkb + 4 * cb + (i & 3)) * WAVE + 16 * (i >> 2) + 4 * g) = acc;
+  }
+}
+
+// grad[p] = the partial blobs' sum in part order (log_std: and the entropy term's -ent_coef); the last block: the tiles' sums -> stats.
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restrict__ work, const float* __restrict__ partials, int parts,
+                                                          long long blob_floats, int ntiles, const float* __restrict__ blob, int log_std,
+                                                          int A, Hyper H, float* __restrict__ grad, float* __restrict__ stats) {
+  if (blockIdx.x < gridDim.x - 1) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= blob_floats) return;
+    float sum = partials[p];
+    for (int q = 1; q < parts; q++) sum += partials[(size_t)q * blob_floats + p];
+    if (p >= log_std && p < log_std + A) sum -= H.ent_coef;
+    grad[p] = sum;
+    return;
+  }
+  if (threadIdx.x >= WAVE) return;
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  constexpr int slot[4] = {1, 2, 4, 5};
+  for (int t = threadIdx.x; t < ntiles; t += WAVE)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] += work[4 + 8 * (size_t)t + slot[j]];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    for (int m = 32; m >= 1; m >>= 1) acc[j] += __shfl_xor(acc[j], m);
+  if (threadIdx.x == 0) {
+    float ent = 0.0f;
+    for (int c = 0; c < A; c++) ent += ENTROPY_0 + blob[log_std + c];
+    const float policy_loss = -acc[0] * H.inv_b, value_loss = acc[1] * H.inv_b, entropy_loss = -ent;
+    stats[0] = policy_loss + H.ent_coef * entropy_loss + H.vf_coef * value_loss;
+    stats[1] = policy_loss; stats[2] = value_loss; stats[3] = entropy_loss;
+    stats[4] = acc[2] * H.inv_b; stats[5] = acc[3] * H.inv_b; stats[6] = 0.0f; stats[7] = 0.0f;
+  }
+}
+
+// the sum over a workgroup of 1024 in a fixed tree (every thread gets it)
+MCG_DEV double block_sum(double x, double* lds) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  lds[t] = x;
+  __syncthreads();
+  for (int m = 512; m >= 1; m >>= 1) {
+    if (t < m) lds[t] += lds[t + m];
+    __syncthreads();
+  }
+  return lds[0];
+}
+
+// out[0] = mean, out[1] = std + 1e-8 (the unbiased deviation, as torch.std) of adv[0..B)
+__global__ __launch_bounds__(1024) void adv_stats_kernel(const float* __restrict__ adv, long long B, float* __restrict__ out) {
+  __shared__ double lds[1024];
+  double s = 0.0;
+  for (long long j = threadIdx.x; j < B; j += 1024) s += (double)adv[j];
+  const double mean = block_sum(s, lds) / (double)B;
+  double q = 0.0;
+  for (long long j = threadIdx.x; j < B; j += 1024) { const double c = (double)adv[j] - mean; q += c * c; }
+  const double var = block_sum(q, lds) / (double)(B - 1);
+  if (threadIdx.x == 0) { out[0] = (float)mean; out[1] = (float)sqrt(var) + 1e-8f; }
+}
+
+__global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict__ grad, long long n, float* __restrict__ norm_out) {
+  __shared__ double lds[1024];
+  double s = 0.0;
+  for (long long j = threadIdx.x; j < n; j += 1024) { const double x = (double)grad[j]; s += x * x; }
+  const double sum = block_sum(s, lds);
+  if (threadIdx.x == 0) norm_out[0] = (float)sqrt(sum);
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ grad, float* __restrict__ m,
+                                                   float* __restrict__ v, long long n, const float* __restrict__ norm, float max_norm,
+                                                   float beta1, float beta2, float step_size, float bc2_sqrt, float eps) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const float coef = max_norm > 0.0f ? fminf(1.0f, max_norm / (norm[0] + 1e-6f)) : 1.0f;
+  const float gj = grad[j] * coef;
+  const float mj = beta1 * m[j] + (1.0f - beta1) * gj;
+  const float vj = beta2 * v[j] + (1.0f - beta2) * (gj * gj);
+  m[j] = mj;
+  v[j] = vj;
+  p[j] = p[j] - step_size * (mj / (sqrtf(vj) / bc2_sqrt + eps));
+}
+
+// ------------------------------------------------------------------------------------------------------- host side
+struct Layout { Rows rows[2]; Blocks blocks; int ntiles, tpp, parts; long long partials, floats; };
+
+// The row map, the block list and the split of `work` for a planned shape and B.
+Layout layout(const Pol& P, int64_t B, int widest) {
+  Layout Y = {};
+  Y.ntiles = (int)((B + TILE - 1) / TILE);
+  const int max_parts = widest <= 64 ? PARTS_NARROW : PARTS_WIDE;
+  Y.tpp = (Y.ntiles + max_parts - 1) / max_parts;
+  Y.parts = (Y.ntiles + Y.tpp - 1) / Y.tpp;
+  const int fr = (P.D + 6 + 15) / 16 * 16;
+  long long at = 4 + 8ll * Y.ntiles;
+  for (int k = 0; k < 2; k++) {
+    const Net& net = P.net[k];
+    Rows& R = Y.rows[k];
+    int row = 0;
+    R.fr = fr; R.x[0] = 0; row += fr;
+    for (int L = 0; L < net.n; L++) { R.x[L + 1] = row; row += 16 * net.nt[L]; }
+    for (int L = 0; L <= net.n; L++) { R.d[L] = row; row += L < net.n ? 16 * net.nt[L] : 16; }
+    R.ls = row;
+    if (k == 1) row += 16;
+    R.rows = row; R.base = at;
+    at += (long long)Y.ntiles * row * TILE;
+  }
+  Y.partials = at;
+  int blk = 0, q = 0;
+  for (int k = 1; k >= 0; k--) {         // the blob's order: the policy net first
+    const Net& net = P.net[k];
+    const Rows& R = Y.rows[k];
+    for (int L = 0; L <= net.n; L++) {
+      Block& b = Y.blocks.l[q++];
+      b.blk0 = blk; b.nT = L < net.n ? net.nt[L] : 1; b.ncb = L == 0 ? fr / 16 : net.nt[L - 1];
+      b.xrow = R.x[L]; b.drow = R.d[L]; b.w = net.w[L]; b.b = net.b[L]; b.nkb = L == 0 ? P.kb0 : 4 * net.nt[L - 1]; b.first = L == 0;
+      b.rows = R.rows; b.base = R.base;
+      blk += b.nT * (b.ncb + 1);
+    }
+    if (k == 1) {                        // log_std: a bias whose dZ is the policy net's log_std rows
+      Block& b = Y.blocks.l[q++];
+      b = Block{};
+      b.blk0 = blk; b.nT = 1; b.ncb = 0; b.drow = R.ls; b.b = P.log_std; b.rows = R.rows; b.base = R.base;
+      blk += 1;
+    }
+  }
+  Y.blocks.n = q; Y.blocks.total = blk;
+  return Y;
+}
+
+int check_batch(const char* who, const mcg_rollout_batch* batch, int64_t B) {
+  if (!batch) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_rollout_batch", who);
+  if (!batch->obs || !batch->achieved || !batch->desired || !batch->action)
+    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved, desired and action of the batch are required", who);
+  if (B < 1) return mcg_fail(MCG_ERR_ARG, "%s: B must be >= 1", who);
+  if (B * MAX_ACT >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: B must be below 2^27", who);
+  return MCG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcg_policy_evaluate(const mcg_policy* pol, const mcg_rollout_batch* batch, int64_t B, const mcg_policy_eval_out* out, void* stream) {
+  const char* who = "mcg_policy_evaluate";
+  Pol P = {};
+  if (checked_plan(who, pol, &P) == 0) return MCG_ERR_ARG;
+  if (const int e = check_batch(who, batch, B)) return e;
+  if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_policy_eval_out", who);
+  if (!out->value && !out->log_prob && !out->entropy) return mcg_fail(MCG_ERR_ARG, "%s: all outputs are null", who);
+  P.N = (int)B;
+  const Batch X = {batch->obs, batch->achieved, batch->desired, batch->action, nullptr, nullptr, nullptr};
+  const EvalOut E = {out->value, out->log_prob, out->entropy};
+  const Rows none = {};
+  const dim3 grid(blocks(B, TILE), (out->log_prob || out->entropy) ? 2 : 1), block(WAVE);
+  if (widest_layer(pol) <= 64) hipLaunchKernelGGL((grad_tile_kernel<4, false>), grid, block, 0, (hipStream_t)stream, P, none, none, X, Hyper{}, nullptr, E);
+  else hipLaunchKernelGGL((grad_tile_kernel<16, false>), grid, block, 0, (hipStream_t)stream, P, none, none, X, Hyper{}, nullptr, E);
+  return launched("mcg_policy_evaluate");
+}
+
+int64_t mcg_policy_grad_work_floats(const mcg_policy* pol, int64_t B) {
+  Pol P = {};
+  const char* why = nullptr;
+  if (!pol || B < 1 || B * MAX_ACT >= (1ll << 31)) return 0;
+  const int64_t floats = plan(pol->obs_dim, pol->act_dim, pol->n_pi, pol->pi_width, pol->n_vf, pol->vf_width, &P, &why);
+  if (floats == 0) return 0;
+  const Layout Y = layout(P, B, widest_layer(pol));
+  return Y.partials + (int64_t)Y.parts * floats;
+}
+
+int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64_t B, const mcg_policy_hyper* hyper, float* work,
+                    int64_t work_floats, float* grad, float* stats, void* stream) {
+  const char* who = "mcg_policy_grad";
+  Pol P = {};
+  const int64_t floats = checked_plan(who, pol, &P);
+  if (floats == 0) return MCG_ERR_ARG;
+  if (const int e = check_batch(who, batch, B)) return e;
+  if (!hyper) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_policy_hyper", who);
+  if (hyper->loss_kind != MCG_LOSS_PPO && hyper->loss_kind != MCG_LOSS_A2C)
+    return mcg_fail(MCG_ERR_ARG, "%s: loss_kind must be MCG_LOSS_PPO or MCG_LOSS_A2C", who);
+  if (hyper->loss_kind == MCG_LOSS_PPO && !(hyper->clip_range > 0.0f)) return mcg_fail(MCG_ERR_ARG, "%s: clip_range must be > 0 for MCG_LOSS_PPO", who);
+  if (!batch->advantage || !batch->returns) return mcg_fail(MCG_ERR_ARG, "%s: advantage and returns of the batch are required", who);
+  if (hyper->loss_kind == MCG_LOSS_PPO && !batch->old_log_prob) return mcg_fail(MCG_ERR_ARG, "%s: old_log_prob of the batch is required for MCG_LOSS_PPO", who);
+  if (!work) return mcg_fail(MCG_ERR_ARG, "%s: work is null", who);
+  if (!grad) return mcg_fail(MCG_ERR_ARG, "%s: grad is null", who);
+  if (!stats) return mcg_fail(MCG_ERR_ARG, "%s: stats is null", who);
+  if (((uintptr_t)work & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: work is not 16-byte aligned", who);
+  if (((uintptr_t)grad & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: grad is not 16-byte aligned", who);
+  const int widest = widest_layer(pol);
+  const Layout Y = layout(P, B, widest);
+  const int64_t need = Y.partials + (int64_t)Y.parts * floats;
+  if (work_floats < need)
+    return mcg_fail(MCG_ERR_ARG, "%s: work_floats is %lld, mcg_policy_grad_work_floats gives %lld for this shape and B", who,
+                    (long long)work_floats, (long long)need);
+  P.N = (int)B;
+  const hipStream_t st = (hipStream_t)stream;
+  const Batch X = {batch->obs, batch->achieved, batch->desired, batch->action, batch->old_log_prob, batch->advantage, batch->returns};
+  const Hyper H = {hyper->loss_kind, hyper->normalize_advantage != 0 && B > 1, hyper->clip_range, hyper->ent_coef, hyper->vf_coef,
+                   (float)(1.0 / (double)B)};
+  if (H.norm) hipLaunchKernelGGL(adv_stats_kernel, dim3(1), dim3(1024), 0, st, batch->advantage, (long long)B, work);
+  const dim3 grid(Y.ntiles, 2), block(WAVE);
+  if (widest <= 64) hipLaunchKernelGGL((grad_tile_kernel<4, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});
+  else hipLaunchKernelGGL((grad_tile_kernel<16, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});
+  hipLaunchKernelGGL(grad_dw_kernel, dim3(Y.blocks.total, Y.parts), block, 0, st, Y.blocks, (const float*)work, work + Y.partials,
+                     (long long)floats, Y.ntiles, Y.tpp, P.kb0, P.D);
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3(blocks(floats, 256) + 1), dim3(256), 0, st, (const float*)work,
+                     (const float*)(work + Y.partials), Y.parts, (long long)floats, Y.ntiles, pol->blob, P.log_std, P.A, H, grad, stats);
+  return launched("mcg_policy_grad");
+}
+
+int mcg_policy_adam(const mcg_policy* pol, const float* grad, float* m, float* v, int64_t step, double lr, double beta1, double beta2,
+                    double eps, double max_grad_norm, float* norm_out, void* stream) {
+  const char* who = "mcg_policy_adam";
+  Pol P = {};
+  const int64_t floats = checked_plan(who, pol, &P);
+  if (floats == 0) return MCG_ERR_ARG;
+  if (!grad) return mcg_fail(MCG_ERR_ARG, "%s: grad is null", who);
+  if (!m) return mcg_fail(MCG_ERR_ARG, "%s: m is null", who);
+  if (!v) return mcg_fail(MCG_ERR_ARG, "%s: v is null", who);
+  if (!norm_out) return mcg_fail(MCG_ERR_ARG, "%s: norm_out is null", who);
+  if (((uintptr_t)grad & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: grad is not 16-byte aligned", who);
+  if (((uintptr_t)m & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: m is not 16-byte aligned", who);
+  if (((uintptr_t)v & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: v is not 16-byte aligned", who);
+  if (step < 1) return mcg_fail(MCG_ERR_ARG, "%s: step must be >= 1", who);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return mcg_fail(MCG_ERR_ARG, "%s: beta1 and beta2 must be in [0, 1)", who);
+  if (!std::isfinite(lr) || !(eps >= 0.0) || !std::isfinite(max_grad_norm)) return mcg_fail(MCG_ERR_ARG, "%s: lr, eps and max_grad_norm must be finite, eps >= 0", who);
+  const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(1), dim3(1024), 0, st, grad, (long long)floats, norm_out);
+  hipLaunchKernelGGL(adam_kernel, dim3(blocks(floats, 256)), dim3(256), 0, st, const_cast<float*>(pol->blob), grad, m, v, (long long)floats,
+                     (const float*)norm_out, (float)max_grad_norm, (float)beta1, (float)beta2, (float)(lr / bc1), (float)std::sqrt(bc2),
+                     (float)eps);
+  return launched("mcg_policy_adam");
+}
+
+}  // extern "C"

@@ -15,8 +15,9 @@ the C side (``mcg_policy_forward``, csrc/mcg_policy.hip) keeps no state and no c
         buf.add(a, v, logp, obs, r, term, trunc, info, final_values=pol.values(info["final_observation"]))
     buf.finish(last_values=pol.values(obs))
 
-No CPU or PyTorch fallback: the kernel is the only implementation of the forward.  The backward pass and the optimiser are the
-caller's (any ``nn.Module`` with SB3's parameter names); after an update ``load_state_dict`` repacks the blob, off the step path.
+No CPU or PyTorch fallback: the kernel is the only implementation of the forward.  ``evaluate_actions`` is the same forward on a
+minibatch of the rollout buffer; the loss, its gradient and Adam on the blob are ``PPOUpdate`` (policy_update.py).  A caller with an
+optimiser of its own (any ``nn.Module`` with SB3's parameter names) repacks the blob with ``load_state_dict`` after an update.
 """
 from __future__ import annotations
 
@@ -133,6 +134,31 @@ def _hidden_of(sd: dict, net: str):
         widths.append(int(sd[f"mlp_extractor.{net}.{2 * L}.weight"].shape[0]))
         L += 1
     return tuple(widths)
+
+
+def minibatch_rows(observations, actions, obs_dim: int, act_dim: int, who: str) -> int:
+    """Checks a minibatch as ``RolloutBuffer.get`` yields it (``RolloutSamples.observations``: the dict of float32 tensors, and
+    ``actions``) -> its rows B.  Needs no device."""
+    if not isinstance(observations, dict):
+        raise ValueError(f"{who}: observations must be the dict of float32 tensors that RolloutBuffer yields (observation, achieved_goal, "
+                         "desired_goal); the picture buffers' samples (-v1 ids) are not supported: the policy is the MLP of the -v0 state ids")
+    missing = [k for k in ("observation", "achieved_goal", "desired_goal") if k not in observations]
+    if missing:
+        raise ValueError(f"{who}: observations lacks {missing}")
+    if not torch.is_tensor(actions) or actions.dim() != 2 or actions.shape[1] != act_dim:
+        raise ValueError(f"{who}: actions: expected a float32 tensor [B, {act_dim}], got {tuple(getattr(actions, 'shape', ()))}")
+    B = int(actions.shape[0])
+    if B < 1:
+        raise ValueError(f"{who}: the minibatch is empty (B must be >= 1)")
+    for name, t, cols in (("observations['observation']", observations["observation"], obs_dim),
+                          ("observations['achieved_goal']", observations["achieved_goal"], 3),
+                          ("observations['desired_goal']", observations["desired_goal"], 3), ("actions", actions, act_dim)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name}: expected float32, got {getattr(t, 'dtype', type(t).__name__)} (the float64 observations of "
+                             "envs.step go through RolloutBuffer, or ActorCritic.__call__)")
+        if tuple(t.shape) != (B, cols):
+            raise ValueError(f"{who}: {name}: expected shape {(B, cols)}, got {tuple(t.shape)}")
+    return B
 
 
 class ActorCritic(DeviceBuffer):
@@ -269,3 +295,31 @@ class ActorCritic(DeviceBuffer):
         v = self._new("value")["value"] if out is None else out
         self._forward(obs, 0, True, {"value": v})
         return v
+
+    # ------------------------------------------------------------------------------------------------ on a minibatch
+    def _minibatch(self, observations, actions, who, **more):
+        """The minibatch as the C side takes it -> (``McgRolloutBatch``, B, the tensors it points into: keep them until the call).
+        ``more``: further float32 [B] fields under ``mcg_rollout_batch``'s names."""
+        B = minibatch_rows(observations, actions, self.obs_dim, self.act_dim, who)
+        t = dict(obs=observations["observation"], achieved=observations["achieved_goal"], desired=observations["desired_goal"], action=actions)
+        for k, x in more.items():
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) != (B,):
+                raise ValueError(f"{who}: {k}: expected a float32 tensor of shape {(B,)}, got {getattr(x, 'dtype', type(x).__name__)} "
+                                 f"{tuple(getattr(x, 'shape', ()))}")
+            t[k] = x
+        for k, x in t.items():
+            if x.device != self.device:
+                raise ValueError(f"{who}: {k} lives on {x.device}, the policy on {self.device}")
+        keep = [x if x.is_contiguous() else x.contiguous() for x in t.values()]
+        return _abi.McgRolloutBatch(**{k: x.data_ptr() for k, x in zip(t, keep)}), B, keep
+
+    def evaluate_actions(self, observations, actions, out: Optional[dict] = None):
+        """SB3's ``evaluate_actions`` on a minibatch: ``observations`` is ``RolloutSamples.observations`` (the dict of float32 device
+        tensors [B, .]), ``actions`` float32 [B, A] -> (value [B], log_prob [B], entropy [B]), float32; one launch.  B is any number of
+        rows >= 1.  ``out``: the tensors to write into, under the names value, log_prob, entropy (any subset)."""
+        batch, B, _keep = self._minibatch(observations, actions, "evaluate_actions")
+        if out is None:
+            out = {k: torch.empty(B, dtype=torch.float32, device=self.device) for k in ("value", "log_prob", "entropy")}
+        cout = _abi.McgPolicyEvalOut(**{k: v.data_ptr() for k, v in out.items()})
+        self._call("mcg_policy_evaluate", C.byref(batch), C.c_int64(B), C.byref(cout))
+        return out.get("value"), out.get("log_prob"), out.get("entropy")
