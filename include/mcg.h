@@ -803,6 +803,111 @@ int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64
 int mcg_policy_adam(const mcg_policy* pol, const float* grad, float* m, float* v, int64_t step, double lr, double beta1, double beta2,
                     double eps, double max_grad_norm, float* norm_out, void* stream);
 
+/* ---- SAC's actor and twin critics, the gradient-free half (SB3's SACPolicy as scripts/train.py's default --algo SAC builds it with
+   MultiInputPolicy for a Dict space of Boxes; mcg_sac.hip): the collection action, the twin-critic forward, the TD target of a replay
+   batch as one launch, and the Polyak step.  Stateless, as everything here: the caller owns three float32 device blobs (actor,
+   critic = qf0 then qf1, critic_target in the critic's layout; mcg_sac.hip's head states the layouts and mycobotgym_amd/sac_policy.py
+   packs them) and the call numbers.  Every entry enqueues on `stream` and none synchronises.  Additive: MCG_ABI_VERSION stays 8.
+   The rule, restated [RECALL: stable_baselines3/sac/policies.py, common/distributions.py, sac/sac.py; SB3 is not installed next to the
+   reference]:
+     features   [achieved_goal(3), desired_goal(3), observation(D)], as for mcg_policy_forward [RECALL: CombinedExtractor].
+     actor      latent_pi: n_pi layers x -> act(W x + b), act = max(., 0) (SB3's default for SAC) or tanh; two linear heads on it, mu
+                [A, H] and log_std [A, H] [RECALL: Actor.get_action_dist_params]; float32 throughout (v_mfma_f32_16x16x4_f32).
+     log_std    clamped to [-20, 2] by fminf(fmaxf(., -20), 2) [RECALL: LOG_STD_MIN, LOG_STD_MAX]; the `log_std` output is the clamped one.
+     noise      eps [., A]: Philox4x32-10 with mcg_policy_forward's counter layout, key `seed`, counter ((uint32)id, (uint32)call,
+                pair ^ ((uint32)(call >> 32) << 8), dom ^ ((uint32)(id >> 32) << 8)), pair = 0 .. ceil(A / 2) - 1, and Box-Muller in
+                double rounded to float32 once, as there.  mcg_sac_act: dom = 7, id = env_id_offset + env; mcg_sac_target: dom = 8,
+                id = the sample's index in the batch.
+     u          (float)((double)mu + exp((double)log_std) * (double)eps), rounded once; deterministic: u = mu, nothing is drawn and
+                the noise is zeros.
+     action     (float)tanh((double)u), rounded once [RECALL: SquashedDiagGaussianDistribution]; |action| <= 1.
+     log_prob   sum over k of (-eps_k^2 / 2 - log_std_k - ln(2 pi) / 2) - sum over k of ln(1 - action_k^2 + 1e-6): the Gaussian term on
+                the pre-squash u, as SB3's action_log_prob keeps it (at u = mu + sigma eps it is the noise's), the correction SB3's
+                expression with its epsilon on the float32 action [RECALL: log_prob -= sum(log(1 - actions**2 + self.epsilon))].  Every
+                term and the sum in double from the float32 log_std, eps and action, the four lanes of a row added in a fixed order,
+                rounded to float32 once.
+     critics    n_critics = 2 [RECALL: ContinuousCritic]: qf0 and qf1, n_qf layers of the same rule on cat(features, action), a scalar
+                head each; critic_target is a second pair.
+   Rows past the count of the last tile of 16 read the last row and store nothing; a row of the outputs depends on that row alone.
+   Checked on the host before any HIP call (MCG_ERR_ARG, each with a message that names the field): a null mcg_sac; a null blob among
+   those the entry touches (mcg_sac_act: actor; mcg_sac_q: the one `which` names; mcg_sac_target: actor and critic_target;
+   mcg_sac_polyak: critic and critic_target), or one that is not 16-byte aligned; obs_dim or act_dim < 1; obs_dim > 4096; act_dim > 16;
+   n_pi or n_qf outside [1, 3]; a width that is no multiple of 16 in [16, 256] (SB3's TD3 / DDPG default [400, 300] is this case); an
+   activation other than MCG_POLICY_TANH / MCG_POLICY_RELU; actor_floats or critic_floats other than mcg_sac_blob_floats gives; and
+   what each entry lists below. */
+#define MCG_SAC_CRITIC 0
+#define MCG_SAC_CRITIC_TARGET 1
+
+typedef struct mcg_sac {
+  const float* actor;               /* device, 16-byte aligned, actor_floats floats */
+  const float* critic;              /* device, 16-byte aligned, critic_floats floats: qf0 then qf1 */
+  float* critic_target;             /* likewise; written by mcg_sac_polyak alone */
+  int32_t n_envs, obs_dim, act_dim; /* n_envs: rows of mcg_sac_act (the other entries take their rows per call) */
+  int32_t n_pi, pi_width[3];        /* latent_pi: 1..3 layers, widths multiples of 16, at most 256 (entries from n_pi on are not read) */
+  int32_t n_qf, qf_width[3];        /* each critic likewise */
+  int32_t activation;               /* MCG_POLICY_TANH or MCG_POLICY_RELU */
+  int64_t actor_floats, critic_floats;      /* must equal what mcg_sac_blob_floats gives for this shape */
+} mcg_sac;
+
+typedef struct mcg_sac_act_out {    /* device pointers, float32; all but action may be NULL to skip */
+  float* action;         /* [N, A]  required */
+  float* log_prob;       /* [N] */
+  float* mean;           /* [N, A]  mu */
+  float* log_std;        /* [N, A]  clamped */
+  float* noise;          /* [N, A]  eps */
+} mcg_sac_act_out;
+
+typedef struct mcg_sac_rows {       /* device pointers, float32, all required: the fields of mcg_her_batch under the same names */
+  const float* obs;      /* [B, D] */
+  const float* achieved; /* [B, 3] */
+  const float* desired;  /* [B, 3] */
+  const float* action;   /* [B, A] */
+} mcg_sac_rows;
+
+typedef struct mcg_sac_target_out { /* device pointers, float32; all but target may be NULL to skip */
+  float* target;         /* [B]     required */
+  float* next_action;    /* [B, A]  a' */
+  float* next_log_prob;  /* [B]     logp' */
+  float* next_q;         /* [2, B]  the two target critics at (next_obs, a'), before the min */
+  float* noise;          /* [B, A]  eps */
+} mcg_sac_target_out;
+
+/* actor_floats + critic_floats, and the two through the pointers (either may be NULL); 0, and zeros, for a refused shape. */
+int64_t mcg_sac_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_qf, const int32_t* qf_width, int64_t* actor_floats,
+                            int64_t* critic_floats);
+
+/* The collection action: `obs` is what mcg_reset / mcg_step wrote (float64, read in place and rounded to float32); `call` the number
+   of the sampling call, the caller's to count.  One launch, one wave per tile of 16 environments.  Also refused: n_envs < 1 or
+   >= 2^27; a null mcg_step_out or obs / achieved_goal / desired_goal in it; a null mcg_sac_act_out or a null action. */
+int mcg_sac_act(const mcg_sac* sac, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset, int deterministic,
+                const mcg_sac_act_out* out, void* stream);
+
+/* Both critics of the blob `which` names on B rows: q[0 .. B) is qf0, q[B .. 2 B) is qf1.  One launch, one wave per (tile, critic).
+   Also refused: `which` other than the two above; B < 1 or >= 2^27; a null mcg_sac_rows or field of it; a null q. */
+int mcg_sac_q(const mcg_sac* sac, int which, const mcg_sac_rows* rows, int64_t B, float* q /* [2, B] */, void* stream);
+
+/* SB3's target line [RECALL: SAC.train] as one launch:
+     a', logp' = actor.action_log_prob(next_obs);  next_q = min(critic_target(next_obs, a')) - alpha logp';
+     target = reward + (1 - done) gamma next_q
+   in float32 as   next_q = fmaf(-alpha, logp', fminf(q0, q1));   target = fmaf((1 - done) * gamma, next_q, reward)   (the product
+   rounded to float32 before the fmaf).  alpha = (float)exp((double)*log_ent_coef), read on the device, where log_ent_coef is not
+   NULL (SB3's ent_coef = "auto"); otherwise the host's ent_coef.  Read of `batch`, as mcg_her_sample wrote it: next_obs,
+   next_achieved, desired (also the next observation's goal), reward and done.  A row that mcg_her_sample gave up on (index -1, all
+   zeros) is computed like any other: its target is that of the all-zero transition, and the caller who samples with no check masks
+   it by `index`.  Also refused: B < 1 or >= 2^27; a null batch or one of the five fields; gamma outside [0, 1]; with a null
+   log_ent_coef an ent_coef that is negative or not finite; a null mcg_sac_target_out or a null target. */
+int mcg_sac_target(const mcg_sac* sac, const mcg_her_batch* batch, int64_t B, uint64_t seed, uint64_t call, float gamma, float ent_coef,
+                   const float* log_ent_coef /* [1] device or NULL */, const mcg_sac_target_out* out, void* stream);
+
+/* critic_target <- (1 - tau) critic_target + tau critic, elementwise over the critic_floats of the blob, as
+     t <- (float) fma(tau, (double) c, (1.0 - tau) * (double) t)
+   with 1.0 - tau formed on the host in double, the product rounded to double, the fma rounded once, and one rounding to float32: no
+   contraction setting of a compiler changes a bit.  A padding position, +0.0 in both, stays +0.0.  tau = 1 is special-cased as the copy
+   t <- c, bit for bit whatever t held (a target with non-finite elements is repaired; a critic's -0.0 stays -0.0).  For tau < 1 the
+   expression stands as written: a non-finite c or t gives a non-finite t (tau = 0 too: 0 * inf), and a sum of zeros comes out +0.0.
+   Also refused: tau outside [0, 1]; critic == critic_target. */
+int mcg_sac_polyak(const mcg_sac* sac, double tau, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

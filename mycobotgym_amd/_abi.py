@@ -306,6 +306,28 @@ class McgPolicyHyper(C.Structure):
                 ("vf_coef", C.c_float)]
 
 
+SAC_CRITIC, SAC_CRITIC_TARGET = 0, 1
+
+
+class McgSac(C.Structure):
+    """SAC's three blobs and shape (include/mcg.h: mcg_sac); the caller owns the blobs."""
+    _fields_ = [("actor", C.c_void_p), ("critic", C.c_void_p), ("critic_target", C.c_void_p), ("n_envs", C.c_int32), ("obs_dim", C.c_int32),
+                ("act_dim", C.c_int32), ("n_pi", C.c_int32), ("pi_width", C.c_int32 * 3), ("n_qf", C.c_int32), ("qf_width", C.c_int32 * 3),
+                ("activation", C.c_int32), ("actor_floats", C.c_int64), ("critic_floats", C.c_int64)]
+
+
+class McgSacActOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("action", "log_prob", "mean", "log_std", "noise")]
+
+
+class McgSacRows(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "achieved", "desired", "action")]
+
+
+class McgSacTargetOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("target", "next_action", "next_log_prob", "next_q", "noise")]
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -319,7 +341,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_replay_img_record_bytes", "mcg_replay_img_start", "mcg_replay_img_add", "mcg_replay_img_sample",
            "mcg_replay_img_sample_stacked", "mcg_frame_stack_push",
            "mcg_policy_blob_floats", "mcg_policy_forward",
-           "mcg_policy_evaluate", "mcg_policy_grad_work_floats", "mcg_policy_grad", "mcg_policy_adam")
+           "mcg_policy_evaluate", "mcg_policy_grad_work_floats", "mcg_policy_grad", "mcg_policy_adam",
+           "mcg_sac_blob_floats", "mcg_sac_act", "mcg_sac_q", "mcg_sac_target", "mcg_sac_polyak")
 
 _lib = None
 
@@ -420,6 +443,16 @@ def load():
                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcg_policy_adam.argtypes = [C.POINTER(McgPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, d, d, d, d, d, C.c_void_p,
                                       C.c_void_p]
+    if hasattr(L, "mcg_sac_target"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_sac_blob_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64)]
+        L.mcg_sac_blob_floats.restype = C.c_int64
+        L.mcg_sac_act.argtypes = [C.POINTER(McgSac), C.POINTER(McgStepOut), C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.POINTER(McgSacActOut),
+                                  C.c_void_p]
+        L.mcg_sac_q.argtypes = [C.POINTER(McgSac), C.c_int, C.POINTER(McgSacRows), C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcg_sac_target.argtypes = [C.POINTER(McgSac), C.POINTER(McgHerBatch), C.c_int64, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
+                                     C.c_void_p, C.POINTER(McgSacTargetOut), C.c_void_p]
+        L.mcg_sac_polyak.argtypes = [C.POINTER(McgSac), d, C.c_void_p]
     _lib = L
     return L
 

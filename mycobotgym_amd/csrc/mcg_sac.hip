@@ -1,0 +1,424 @@
+// mcg_sac.hip -- the gradient-free half of SAC (include/mcg.h: mcg_sac_*): SB3's SACPolicy for a Dict space of Boxes -- a squashed
+// Gaussian actor with a state-dependent log_std and twin critics with a target copy -- as the collection action (mcg_sac_act), the
+// twin-critic forward (mcg_sac_q), the fused TD target of a replay batch (mcg_sac_target) and the Polyak step (mcg_sac_polyak).
+//
+// A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives.  Kernels and C entries are both here; the
+// matrix instruction, its operand map and the layer helpers are mcg_policy.hpp's, unchanged, and mcg_policy.hip's head states them.
+// The C side is stateless and no entry synchronises.
+//
+// ---- Work split.  mcg_sac_act: one wave per tile of 16 environments.  mcg_sac_q: one wave per (tile of 16 rows, critic), grid.y = 2.
+// mcg_sac_target: one workgroup of two waves per tile of 16 samples; wave q evaluates the actor on the next observation -- both waves
+// the same instructions on the same inputs, so the same bits -- and then target critic q with the action it holds in registers; the
+// two Q rows meet through 2 x 16 floats of LDS and one barrier, and wave 0 forms and stores everything.  mcg_sac_polyak: one lane per
+// four floats of the blob.
+//
+// ---- The action as a matrix operand.  After the actor's head lane 16 g + i holds, in register r, component 4 g + r of sample i: the
+// accumulator layout, which is the B operand of a later layer's k-block r (mcg_policy.hip's head).  So the critics' first layer keeps
+// its action columns as four k-blocks in the later-layer order and takes the action where it lies; an action that comes from memory
+// (mcg_sac_q) is loaded into the same registers, lane (g, i) reading components 4 g .. 4 g + 3 of row i, those >= A as zeros.
+//
+// ---- The blobs (float32, 16-byte aligned; mycobotgym_amd/sac_policy.py: pack / unpack restate them).  Tiles and biases as in
+// mcg_policy.hip's head: tile (T, kb), float l = 16 g + i: W[16 T + i][k(kb, g)].
+//   actor    latent_pi's layers (the first over the D + 6 feature columns, k(kb, g) = 4 kb + g; later ones k(4 t + r, g) = 16 t + 4 g + r),
+//            then the head mu and the head log_std: each one tile row of 16 (A rows, the rest zeros) over H / 4 k-blocks and 16 biases.
+//   critic   qf0 then qf1.  A first layer of `out` units is out / 16 * ceil((D + 6) / 4) tiles over the feature columns (k(kb, g) =
+//            4 kb + g), then out / 16 * 4 tiles over the action padded with zero columns to 16 (k(r, g) = 4 g + r), then `out` biases;
+//            the later layers; a head of one row padded to 16.
+//   critic_target   the critic's layout.
+//
+// ---- The noise.  Philox4x32-10, mcg_policy.hip's counter layout (policy_pair) with the domain byte 7 for mcg_sac_act, id = the global
+// environment id, and 8 for mcg_sac_target, id = the sample's index in the batch (0-6 are taken: reset and scene draws, HER, the rollout
+// permutation, the picture replay, the actor-critic policy).  One block serves two components by Box-Muller in double, as there.
+#include "mcg_policy.hpp"       // Net, Pol, mfma, activate, first_layer, dense
+
+using namespace mcg;
+
+namespace {
+
+constexpr uint32_t SAC_ACT_STREAM = 7, SAC_TARGET_STREAM = 8;
+constexpr float LOG_STD_MIN = -20.0f, LOG_STD_MAX = 2.0f;
+
+// mcg_sac as the kernels see it.  pi: the actor blob; net[1] is latent_pi with the head mu, net[0] the same trunk with the head
+// log_std.  qf[k]: critic k of the critic or the target blob -- the same plan, net[0], from its own base, so that a kernel picks a
+// critic by an address in its arguments and copies nothing; qa: the first layer's action tiles.
+struct Sac { Pol pi, qf[2]; int qa; };
+
+struct ActOut { float *action, *log_prob, *mean, *log_std, *noise; };
+struct Rows { const float *obs, *achieved, *desired, *action; };
+struct Batch { const float *next_obs, *next_achieved, *desired, *reward, *done; };
+struct TargetOut { float *target, *next_action, *next_log_prob, *next_q, *noise; };
+
+// What the actor gives a lane: components 4 g + r of its sample (zeros from A on), and the sample's log-prob (on all four lanes).
+struct Draw { f4 action, mean, log_std, noise; float log_prob; };
+
+MCG_DEV int last_tiles(const Net& net) { return net.n == 1 ? net.nt[0] : net.n == 2 ? net.nt[1] : net.nt[2]; }
+
+// a: a first layer's sums -> the last hidden layer's activations
+template <int MT>
+MCG_DEV void hidden(const Pol& P, const Net& net, f4 (&a)[MT], int g, int lane) {
+  f4 b[MT];
+#pragma unroll
+  for (int t = 0; t < MT; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, a[t][r]);
+  for (int L = 1; L < net.n; L++) {
+    dense<MT, MT>(P, net, L, L == 1 ? net.nt[0] : net.nt[1], L == 1 ? net.nt[1] : net.nt[2], a, b, g, lane);
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, b[t][r]);
+  }
+}
+
+// SB3's actor.action_log_prob on one row (include/mcg.h states every rounding).  `id`, `call`, `stream`: the noise's counter.
+template <int MT, class In>
+MCG_DEV Draw actor(const Pol& P, const In* __restrict__ obs, const In* __restrict__ ach, const In* __restrict__ des, int row, int g, int lane,
+                   unsigned long long seed, unsigned long long id, unsigned long long call, uint32_t stream, bool deterministic) {
+  f4 a[MT], mu[1], ls[1];
+  first_layer<MT, In>(P, P.net[1], obs, ach, des, row, g, lane, a);
+  hidden<MT>(P, P.net[1], a, g, lane);
+  dense<MT, 1>(P, P.net[1], P.net[1].n, last_tiles(P.net[1]), 1, a, mu, g, lane);
+  dense<MT, 1>(P, P.net[0], P.net[0].n, last_tiles(P.net[0]), 1, a, ls, g, lane);
+  Draw d;
+  d.noise = f4{0.0f, 0.0f, 0.0f, 0.0f};
+  if (!deterministic) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      if (4 * g + 2 * q < P.A) {
+        double u0, u1, s, c;
+        const uint32_t pair = (uint32_t)(2 * g + q);
+        philox_pair((uint32_t)id, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), stream ^ ((uint32_t)(id >> 32) << 8), seed, u0, u1);
+        const double rad = sqrt(-2.0 * log(1.0 - u0));
+        sincos(6.283185307179586476925 * u1, &s, &c);
+        d.noise[2 * q] = (float)(rad * c);
+        if (4 * g + 2 * q + 1 < P.A) d.noise[2 * q + 1] = (float)(rad * s);
+      }
+    }
+  }
+  double lp = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    d.action[r] = d.mean[r] = d.log_std[r] = 0.0f;
+    if (4 * g + r < P.A) {
+      const float l = fminf(fmaxf(ls[0][r], LOG_STD_MIN), LOG_STD_MAX), e = d.noise[r];
+      const float u = deterministic ? mu[0][r] : (float)((double)mu[0][r] + exp((double)l) * (double)e);
+      const float act = (float)tanh((double)u);
+      lp += (-0.5 * (double)e * (double)e - (double)l - 0.91893853320467274178) - log(1.0 - (double)act * (double)act + 1e-6);
+      d.action[r] = act; d.mean[r] = mu[0][r]; d.log_std[r] = l;
+    }
+  }
+  lp += __shfl_xor(lp, 16);              // the four lanes of a sample, in an order that does not depend on the tile
+  lp += __shfl_xor(lp, 32);
+  d.log_prob = (float)lp;
+  return d;
+}
+
+// Critic k on one row: `act` is the action in the accumulator layout.  The value is row 0 of the head: valid on the lanes g == 0.
+template <int MT, class In>
+MCG_DEV float critic(const Sac& S, int k, const In* __restrict__ obs, const In* __restrict__ ach, const In* __restrict__ des,
+                     int row, const f4& act, int g, int lane) {
+  const Pol& P = k ? S.qf[1] : S.qf[0];
+  const Net& net = P.net[0];
+  f4 a[MT], head[1];
+  first_layer<MT, In>(P, net, obs, ach, des, row, g, lane, a);
+  const float* __restrict__ Wa = P.blob + S.qa;
+#pragma unroll
+  for (int t = 0; t < MT; t++) {
+    if (t < net.nt[0]) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) a[t] = mfma(Wa[(t * 4 + r) * WAVE + lane], act[r], a[t]);
+    }
+  }
+  hidden<MT>(P, net, a, g, lane);
+  dense<MT, 1>(P, net, net.n, last_tiles(net), 1, a, head, g, lane);
+  return head[0][0];
+}
+
+template <int MT>
+__global__ __launch_bounds__(WAVE) void sac_act_kernel(Sac S, const double* __restrict__ obs, const double* __restrict__ ach,
+                                                       const double* __restrict__ des, unsigned long long seed, unsigned long long call,
+                                                       long long env_id_offset, int deterministic, ActOut O) {
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int e = blockIdx.x * TILE + i;
+  const bool live = e < S.pi.N;
+  const int env = live ? e : S.pi.N - 1;   // a ragged tile's extra rows read a valid row and store nothing
+  const Draw d = actor<MT, double>(S.pi, obs, ach, des, env, g, lane, seed, (unsigned long long)(env_id_offset + env), call, SAC_ACT_STREAM,
+                                   deterministic != 0);
+  if (!live) return;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int c = 4 * g + r;
+    if (c < S.pi.A) {
+      const size_t at = (size_t)e * S.pi.A + c;
+      O.action[at] = d.action[r];
+      if (O.mean) O.mean[at] = d.mean[r];
+      if (O.log_std) O.log_std[at] = d.log_std[r];
+      if (O.noise) O.noise[at] = d.noise[r];
+    }
+  }
+  if (O.log_prob && g == 0) O.log_prob[e] = d.log_prob;
+}
+
+template <int MT>
+__global__ __launch_bounds__(WAVE) void sac_q_kernel(Sac S, Rows R, int B, float* __restrict__ q) {
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int e = blockIdx.x * TILE + i;
+  const bool live = e < B;
+  const int row = live ? e : B - 1;
+  const int k = blockIdx.y;
+  f4 act;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int c = 4 * g + r;
+    act[r] = 0.0f;
+    if (c < S.pi.A) act[r] = R.action[(size_t)row * S.pi.A + c];
+  }
+  const float v = critic<MT, float>(S, k, R.obs, R.achieved, R.desired, row, act, g, lane);
+  if (live && g == 0) q[(size_t)k * B + e] = v;
+}
+
+template <int MT>
+__global__ __launch_bounds__(2 * WAVE) void sac_target_kernel(Sac S, Batch X, int B, unsigned long long seed, unsigned long long call, float gamma,
+                                                              float ent_coef, const float* __restrict__ log_ent_coef, TargetOut O) {
+  __shared__ float qs[2][TILE];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63, g = lane >> 4, i = lane & 15;
+  const int e = blockIdx.x * TILE + i;
+  const bool live = e < B;
+  const int row = live ? e : B - 1;
+  const Draw d = actor<MT, float>(S.pi, X.next_obs, X.next_achieved, X.desired, row, g, lane, seed, (unsigned long long)row, call,
+                                  SAC_TARGET_STREAM, false);
+  const float v = critic<MT, float>(S, wave, X.next_obs, X.next_achieved, X.desired, row, d.action, g, lane);
+  if (g == 0) qs[wave][i] = v;
+  __syncthreads();
+  if (wave != 0 || !live) return;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int c = 4 * g + r;
+    if (c < S.pi.A) {
+      const size_t at = (size_t)e * S.pi.A + c;
+      if (O.next_action) O.next_action[at] = d.action[r];
+      if (O.noise) O.noise[at] = d.noise[r];
+    }
+  }
+  if (g != 0) return;
+  const float q0 = qs[0][i], q1 = qs[1][i];
+  const float alpha = log_ent_coef ? (float)exp((double)*log_ent_coef) : ent_coef;
+  const float next_q = fmaf(-alpha, d.log_prob, fminf(q0, q1));
+  O.target[e] = fmaf(__fmul_rn(1.0f - X.done[e], gamma), next_q, X.reward[e]);
+  if (O.next_log_prob) O.next_log_prob[e] = d.log_prob;
+  if (O.next_q) { O.next_q[e] = q0; O.next_q[(size_t)B + e] = q1; }
+}
+
+// target <- (float) fma(tau, (double) critic, (1 - tau) * (double) target): the product rounded to double, the fma rounded once, then
+// the one rounding to float32.  A padding position, +0 in both, stays +0.  tau = 1 (one_minus_tau == 0, the same for every lane) is the
+// copy of the critic's bits: the expression would turn a non-finite target element into NaN (0 * inf) and a critic's -0 into +0.
+__global__ __launch_bounds__(256) void sac_polyak_kernel(const float* __restrict__ critic, float* __restrict__ target, int quads, double tau,
+                                                         double one_minus_tau) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= quads) return;
+  const f4 c = reinterpret_cast<const f4*>(critic)[p];
+  f4 t = reinterpret_cast<f4*>(target)[p];
+#pragma unroll
+  for (int r = 0; r < 4; r++) t[r] = one_minus_tau == 0.0 ? c[r] : (float)fma(tau, (double)c[r], __dmul_rn(one_minus_tau, (double)t[r]));
+  reinterpret_cast<f4*>(target)[p] = t;
+}
+
+// ------------------------------------------------------------------------------------------------------- host side
+// The blobs' plan for a shape -> actor_floats + critic_floats; 0 and `why` for a refused shape.  S (where given): filled but for the
+// blob pointers, N and act.
+int64_t sac_plan(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_qf, const int32_t* qf_width, Sac* S, int64_t* actor_floats,
+                 int64_t* critic_floats, const char** why) {
+  if (obs_dim < 1 || act_dim < 1) { *why = "obs_dim and act_dim must be >= 1"; return 0; }
+  if (obs_dim > MAX_OBS) { *why = "obs_dim must be <= 4096"; return 0; }
+  if (act_dim > MAX_ACT) { *why = "act_dim must be <= 16"; return 0; }
+  if (n_pi < 1 || n_pi > MAX_LAYERS) { *why = "n_pi must be in [1, 3]"; return 0; }
+  if (n_qf < 1 || n_qf > MAX_LAYERS) { *why = "n_qf must be in [1, 3]"; return 0; }
+  if (!pi_width || !qf_width) { *why = "null pi_width or qf_width"; return 0; }
+  for (int k = 0; k < 2; k++) {
+    const int n = k ? n_qf : n_pi;
+    const int32_t* w = k ? qf_width : pi_width;
+    for (int L = 0; L < n; L++)
+      if (w[L] < 16 || w[L] > MAX_WIDTH || w[L] % 16 != 0) {
+        static thread_local char msg[80];
+        snprintf(msg, sizeof msg, "%s_width[%d] must be a multiple of 16 in [16, 256]", k ? "qf" : "pi", L);
+        *why = msg;
+        return 0;
+      }
+  }
+  const int kb0 = (obs_dim + 6 + 3) / 4;
+  // the actor: the trunk, then the two heads
+  int64_t at = 0;
+  Net pi = {};
+  pi.n = n_pi;
+  for (int L = 0; L < n_pi; L++) {
+    const int out_tiles = pi_width[L] / 16, nkb = L == 0 ? kb0 : pi_width[L - 1] / 4;
+    pi.nt[L] = out_tiles;
+    pi.w[L] = (int)at; at += (int64_t)out_tiles * nkb * WAVE;
+    pi.b[L] = (int)at; at += (int64_t)out_tiles * 16;
+  }
+  Net mu = pi, ls = pi;
+  const int64_t head = (int64_t)(pi_width[n_pi - 1] / 4) * WAVE;
+  mu.w[n_pi] = (int)at; at += head;
+  mu.b[n_pi] = (int)at; at += 16;
+  ls.w[n_pi] = (int)at; at += head;
+  ls.b[n_pi] = (int)at; at += 16;
+  const int64_t actor = at;
+  // the critics
+  at = 0;
+  Net qf = {};
+  int qa = 0;
+  qf.n = n_qf;
+  for (int L = 0; L <= n_qf; L++) {
+    const int out_tiles = L < n_qf ? qf_width[L] / 16 : 1, nkb = L == 0 ? kb0 : qf_width[L - 1] / 4;
+    if (L < n_qf) qf.nt[L] = out_tiles;
+    qf.w[L] = (int)at; at += (int64_t)out_tiles * nkb * WAVE;
+    if (L == 0) { qa = (int)at; at += (int64_t)out_tiles * 4 * WAVE; }
+    qf.b[L] = (int)at; at += (int64_t)out_tiles * 16;
+  }
+  at *= 2;                               // qf1: the same plan again
+  if (S) {
+    S->pi.net[1] = mu; S->pi.net[0] = ls; S->qf[0].net[0] = S->qf[1].net[0] = qf; S->qa = qa;
+    S->pi.kb0 = S->qf[0].kb0 = S->qf[1].kb0 = kb0; S->pi.D = S->qf[0].D = S->qf[1].D = obs_dim; S->pi.A = S->qf[0].A = S->qf[1].A = act_dim;
+  }
+  if (actor_floats) *actor_floats = actor;
+  if (critic_floats) *critic_floats = at;
+  return actor + at;                     // < 2^21 floats at the largest shape
+}
+
+enum { NEED_ACTOR = 1, NEED_CRITIC = 2, NEED_TARGET = 4 };
+
+// What every entry checks of an mcg_sac before it launches, `need` naming the blobs the entry touches -> true, and S filled but for the
+// blob pointers and N; false after mcg_fail.
+bool checked_sac(const char* who, const mcg_sac* sac, int need, Sac* S) {
+  if (!sac) { mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac", who); return false; }
+  if ((need & NEED_ACTOR) && !sac->actor) { mcg_fail(MCG_ERR_ARG, "%s: actor is null", who); return false; }
+  if ((need & NEED_CRITIC) && !sac->critic) { mcg_fail(MCG_ERR_ARG, "%s: critic is null", who); return false; }
+  if ((need & NEED_TARGET) && !sac->critic_target) { mcg_fail(MCG_ERR_ARG, "%s: critic_target is null", who); return false; }
+  const char* why = nullptr;
+  int64_t actor = 0, critic = 0;
+  if (sac_plan(sac->obs_dim, sac->act_dim, sac->n_pi, sac->pi_width, sac->n_qf, sac->qf_width, S, &actor, &critic, &why) == 0) {
+    mcg_fail(MCG_ERR_ARG, "%s: %s", who, why); return false; }
+  if (sac->activation != MCG_POLICY_TANH && sac->activation != MCG_POLICY_RELU) {
+    mcg_fail(MCG_ERR_ARG, "%s: activation must be MCG_POLICY_TANH or MCG_POLICY_RELU", who); return false; }
+  if (sac->actor_floats != actor || sac->critic_floats != critic) {
+    mcg_fail(MCG_ERR_ARG, "%s: actor_floats / critic_floats are %lld / %lld, mcg_sac_blob_floats gives %lld / %lld for this shape", who,
+             (long long)sac->actor_floats, (long long)sac->critic_floats, (long long)actor, (long long)critic);
+    return false;
+  }
+  if (((need & NEED_ACTOR) && ((uintptr_t)sac->actor & 15)) || ((need & NEED_CRITIC) && ((uintptr_t)sac->critic & 15)) ||
+      ((need & NEED_TARGET) && ((uintptr_t)sac->critic_target & 15))) {
+    mcg_fail(MCG_ERR_ARG, "%s: a blob is not 16-byte aligned", who); return false; }
+  S->pi.blob = sac->actor; S->pi.act = S->qf[0].act = S->qf[1].act = sac->activation;
+  return true;
+}
+
+bool checked_rows(const char* who, int64_t B) {
+  if (B < 1) { mcg_fail(MCG_ERR_ARG, "%s: B must be >= 1", who); return false; }
+  if (B * MAX_ACT >= (1ll << 31)) { mcg_fail(MCG_ERR_ARG, "%s: B must be below 2^27", who); return false; }
+  return true;
+}
+
+int widest(const mcg_sac* sac, bool pi, bool qf) {
+  int w = 0;
+  for (int L = 0; pi && L < sac->n_pi; L++) w = sac->pi_width[L] > w ? sac->pi_width[L] : w;
+  for (int L = 0; qf && L < sac->n_qf; L++) w = sac->qf_width[L] > w ? sac->qf_width[L] : w;
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mcg_sac_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_qf, const int32_t* qf_width, int64_t* actor_floats,
+                            int64_t* critic_floats) {
+  const char* why;
+  if (actor_floats) *actor_floats = 0;
+  if (critic_floats) *critic_floats = 0;
+  return sac_plan(obs_dim, act_dim, n_pi, pi_width, n_qf, qf_width, nullptr, actor_floats, critic_floats, &why);
+}
+
+int mcg_sac_act(const mcg_sac* sac, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset, int deterministic,
+                const mcg_sac_act_out* out, void* stream) {
+  const char* who = "mcg_sac_act";
+  Sac S = {};
+  if (!checked_sac(who, sac, NEED_ACTOR, &S)) return MCG_ERR_ARG;
+  if (sac->n_envs < 1) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be >= 1", who);
+  if ((long long)sac->n_envs * MAX_ACT >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be below 2^27", who);
+  if (!obs) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_step_out", who);
+  if (!obs->obs || !obs->achieved_goal || !obs->desired_goal)
+    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved_goal and desired_goal of the observation are required", who);
+  if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_act_out", who);
+  if (!out->action) return mcg_fail(MCG_ERR_ARG, "%s: action is required", who);
+  S.pi.N = sac->n_envs;
+  const ActOut O = {out->action, out->log_prob, out->mean, out->log_std, out->noise};
+  const dim3 grid(blocks(S.pi.N, TILE)), block(WAVE);
+#define MCG_SAC_ACT(MT) hipLaunchKernelGGL(sac_act_kernel<MT>, grid, block, 0, (hipStream_t)stream, S, obs->obs, obs->achieved_goal, \
+                                           obs->desired_goal, (unsigned long long)seed, (unsigned long long)call, (long long)env_id_offset, \
+                                           deterministic != 0, O)
+  if (widest(sac, true, false) <= 64) MCG_SAC_ACT(4);
+  else MCG_SAC_ACT(16);
+#undef MCG_SAC_ACT
+  return launched("mcg_sac_act");
+}
+
+int mcg_sac_q(const mcg_sac* sac, int which, const mcg_sac_rows* rows, int64_t B, float* q, void* stream) {
+  const char* who = "mcg_sac_q";
+  if (which != MCG_SAC_CRITIC && which != MCG_SAC_CRITIC_TARGET)
+    return mcg_fail(MCG_ERR_ARG, "%s: which must be MCG_SAC_CRITIC or MCG_SAC_CRITIC_TARGET", who);
+  Sac S = {};
+  if (!checked_sac(who, sac, which == MCG_SAC_CRITIC ? NEED_CRITIC : NEED_TARGET, &S)) return MCG_ERR_ARG;
+  if (!checked_rows(who, B)) return MCG_ERR_ARG;
+  if (!rows) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_rows", who);
+  if (!rows->obs || !rows->achieved || !rows->desired || !rows->action)
+    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved, desired and action of the rows are required", who);
+  if (!q) return mcg_fail(MCG_ERR_ARG, "%s: q is null", who);
+  S.qf[0].blob = which == MCG_SAC_CRITIC ? sac->critic : sac->critic_target;
+  S.qf[1].blob = S.qf[0].blob + sac->critic_floats / 2;
+  const Rows R = {rows->obs, rows->achieved, rows->desired, rows->action};
+  const dim3 grid(blocks(B, TILE), 2), block(WAVE);
+  if (widest(sac, false, true) <= 64) hipLaunchKernelGGL(sac_q_kernel<4>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
+  else hipLaunchKernelGGL(sac_q_kernel<16>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
+  return launched("mcg_sac_q");
+}
+
+int mcg_sac_target(const mcg_sac* sac, const mcg_her_batch* batch, int64_t B, uint64_t seed, uint64_t call, float gamma, float ent_coef,
+                   const float* log_ent_coef, const mcg_sac_target_out* out, void* stream) {
+  const char* who = "mcg_sac_target";
+  Sac S = {};
+  if (!checked_sac(who, sac, NEED_ACTOR | NEED_TARGET, &S)) return MCG_ERR_ARG;
+  if (!checked_rows(who, B)) return MCG_ERR_ARG;
+  if (!batch) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_her_batch", who);
+  if (!batch->next_obs || !batch->next_achieved || !batch->desired || !batch->reward || !batch->done)
+    return mcg_fail(MCG_ERR_ARG, "%s: next_obs, next_achieved, desired, reward and done of the batch are required", who);
+  if (!(gamma >= 0.0f && gamma <= 1.0f)) return mcg_fail(MCG_ERR_ARG, "%s: gamma must be in [0, 1]", who);
+  if (!log_ent_coef && !(ent_coef >= 0.0f && ent_coef <= 3.0e38f))
+    return mcg_fail(MCG_ERR_ARG, "%s: ent_coef must be finite and >= 0 where log_ent_coef is null", who);
+  if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_target_out", who);
+  if (!out->target) return mcg_fail(MCG_ERR_ARG, "%s: target is required", who);
+  S.qf[0].blob = sac->critic_target;
+  S.qf[1].blob = S.qf[0].blob + sac->critic_floats / 2;
+  const Batch X = {batch->next_obs, batch->next_achieved, batch->desired, batch->reward, batch->done};
+  const TargetOut O = {out->target, out->next_action, out->next_log_prob, out->next_q, out->noise};
+  const dim3 grid(blocks(B, TILE)), block(2 * WAVE);
+#define MCG_SAC_TARGET(MT) hipLaunchKernelGGL(sac_target_kernel<MT>, grid, block, 0, (hipStream_t)stream, S, X, (int)B, (unsigned long long)seed, \
+                                              (unsigned long long)call, gamma, ent_coef, log_ent_coef, O)
+  if (widest(sac, true, true) <= 64) MCG_SAC_TARGET(4);
+  else MCG_SAC_TARGET(16);
+#undef MCG_SAC_TARGET
+  return launched("mcg_sac_target");
+}
+
+int mcg_sac_polyak(const mcg_sac* sac, double tau, void* stream) {
+  const char* who = "mcg_sac_polyak";
+  Sac S = {};
+  if (!checked_sac(who, sac, NEED_CRITIC | NEED_TARGET, &S)) return MCG_ERR_ARG;
+  if (!(tau >= 0.0 && tau <= 1.0)) return mcg_fail(MCG_ERR_ARG, "%s: tau must be in [0, 1]", who);
+  if (sac->critic == sac->critic_target) return mcg_fail(MCG_ERR_ARG, "%s: critic and critic_target are the same blob", who);
+  const int quads = (int)(sac->critic_floats / 4);      // every piece of a blob is a multiple of 16 floats
+  hipLaunchKernelGGL(sac_polyak_kernel, dim3(blocks(quads, 256)), dim3(256), 0, (hipStream_t)stream, sac->critic, sac->critic_target, quads, tau,
+                     1.0 - tau);
+  return launched("mcg_sac_polyak");
+}
+
+}  // extern "C"
