@@ -416,6 +416,34 @@ struct LaneScratchT {
   MCG_DEV LaneScratchT window(int k0) const { LdsPtr p = base + k0 * STRIDE; asm volatile("" : "+v"(p)); return LaneScratchT(p); }
 };
 typedef LaneScratchT<64> LaneScratch;
+// A lane's column behind up to two windows, slot numbers unchanged: slot k goes through the upper window (base at slot HI) from slot
+// SPLIT on, through the lower one (base at slot LO) from slot LO on, else from slot 0.  k is a constant wherever this is used (static_for),
+// so the choice costs nothing; a window that LO = 0 / HI = 0 leaves out is not formed.  The constants and what they must reach: mcg_lds.hpp
+// (LDS_WIN_LO, LDS_WIN_HI, LDS_WIN_SPLIT).  Each object forms its bases anew: one per stretch between barriers, so that no base is
+// carried where it is not used.
+// Reads through it stay SINGLE ds_read_b64 (the volatile access keeps the compiler from merging neighbours; the offset still folds into
+// the instruction): it serves the side waves, which read H_eq + M at the same time right after S2, and there the LDS array's time counts,
+// not the wave's instruction count -- a ds_read2st64_b64 holds the array for 8 cycles, two ds_read_b64 for 4.  Measured (DESIGN.md
+// section 5, round 11): windows with paired reads -1.9 %, with single reads -2.4 % against none.  Stores pair as the compiler likes (a
+// paired store costs the array what two single ones do).  The main wave's window after S3 (LaneScratchT::window) keeps its pairs: that
+// wave runs alone there, and with single reads it lost all that round 10 had gained.
+template <int STRIDE, int LO, int HI, int SPLIT>
+struct WindowedScratchT {
+  LdsPtr base, lo, hi;
+  MCG_DEV explicit WindowedScratchT(LaneScratchT<STRIDE> C) : base(C.base), lo(C.base), hi(C.base) {
+    if constexpr (LO != 0) lo = C.window(LO).base;
+    if constexpr (HI != 0) hi = C.window(HI).base;
+  }
+  MCG_DEV LdsPtr at(int k) const {
+    if constexpr (HI != 0) { if (k >= SPLIT) return hi + (k - HI) * STRIDE; }
+    if constexpr (LO != 0) { if (k >= LO) return lo + (k - LO) * STRIDE; }
+    return base + k * STRIDE;
+  }
+  MCG_DEV real ld(int k) const { return *(volatile __attribute__((address_space(3))) real*)at(k); }
+  MCG_DEV void st(int k, real v) const { *at(k) = v; }
+};
+typedef WindowedScratchT<64, LDS_WIN_LO, LDS_WIN_HI, LDS_WIN_SPLIT> SideScratch;      // the side waves of SplitMainCols
+typedef WindowedScratchT<64, LDS_WIN_LO, 0, 0> LowScratch;                           // where nothing above the split is touched
 
 // One physics sub-step (mj_step) of the 12-dof robot.  `qlag` receives the positions the forward pass used.
 // Coupling hook: a hook with `publishes` is handed the Newton system's smooth right-hand side and the limit rows once they are
@@ -670,7 +698,7 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // Nothing is handed over in the factor slots.
 // History: round 5 split the limit solve's columns behind a fourth barrier, S2b; round 6 added the sine / cosine
 // exchange; round 7 moved the whole solve to the RNE wave (kept for the joint controller only); round 8 added the helper columns; round 10
-// shortened the main wave's stretch after S3.
+// shortened the main wave's stretch after S3; round 11 gave the side waves windows for their slots beyond 64 KB (WindowedScratchT).
 struct NoSplit { static constexpr bool enabled = false, reach = false, mesh_split = false, cols = false; };
 struct SplitMainLocal { static constexpr bool enabled = true, reach = true, mesh_split = false, cols = false;
                         static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
@@ -1332,11 +1360,12 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS) {
     real L[NB * (NB + 1) / 2], dinv[NB], z6[NB], z8[NB];
     const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
     const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    build_H<SPL>(MS, L, none, zero);
+    const LowScratch MW(MS);                                       // H_eq's upper rows and the columns: the lower window alone
+    build_H<SPL>(MW, L, none, zero);
     ldl_factor<PAT_H>(L, dinv);
     ldl_solve_unit<PAT_H, 6>(L, dinv, z6);
     ldl_solve_unit<PAT_H, 8>(L, dinv, z8);
-    static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_Z6 + i, z6[i]); MS.st(LDS_Z8 + i, z8[i]); });
+    static_for<NB>([&](auto I) { constexpr int i = I; MW.st(LDS_Z6 + i, z6[i]); MW.st(LDS_Z8 + i, z8[i]); });
     MCG_TICK(ST_H_COLS);
     __syncthreads();                                                // S3
     MCG_TICK(ST_H_S3);
@@ -1358,13 +1387,16 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS) {
   __syncthreads();                                                  // S1
   MCG_TICK(ST_Q_S1);
   real cs[NB], sn[NB], qd[NB], fs[NB];
+  // cols: what lies beyond a ds_ offset from slot 0 through the side waves' windows, formed once per stretch (see WindowedScratchT)
+  auto slots = [&] { if constexpr (SPL::cols) return SideScratch(MS); else return MS; };
   side_trig<SPL, 8>(MS, sn, cs);
-  static_for<NB>([&](auto I) { constexpr int i = I; qd[i] = MS.ld(SPL::QDB + i); });
+  const auto MB = slots();
+  static_for<NB>([&](auto I) { constexpr int i = I; qd[i] = MB.ld(SPL::QDB + i); });
   rne_bias(Pm, cs, sn, qd, fs);
-  static_for<NB>([&](auto I) { constexpr int i = I; MS.st(SPL::FS + i, fs[i]); });
+  static_for<NB>([&](auto I) { constexpr int i = I; MB.st(SPL::FS + i, fs[i]); });
   bool remote = false;
   if constexpr (SPL::cols) {
-    remote = no_other_rows<SPL>(Pm, MS);
+    remote = no_other_rows<SPL>(Pm, MB);
     static_for<NB>([&](auto I) { constexpr int i = I; pin(fs[i]); });      // the sum below takes passive - bias as the main wave reads it
     MCG_FENCE();                                                           // from LDS: rounded, no product of rne_bias contracted into the add
   }
@@ -1377,13 +1409,14 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS) {
       real L[NB * (NB + 1) / 2], dinv[NB], x[NB];
       const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
       const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      build_H<SPL>(MS, L, none, zero);
+      const auto MW = slots();
+      build_H<SPL>(MW, L, none, zero);
       static_for<NB>([&](auto I) { constexpr int i = I; x[i] = 0.0; });                       // the actuation forces: zero but for RACT_DOF
-      static_for<8>([&](auto K) { constexpr int k = K; x[RACT_DOF[k]] = MS.ld(LDS_RACT + k); });
-      static_for<NB>([&](auto I) { constexpr int i = I; x[i] = MS.ld(LDS_RG0 + i) + (x[i] + fs[i]); });
+      static_for<8>([&](auto K) { constexpr int k = K; x[RACT_DOF[k]] = MW.ld(LDS_RACT + k); });
+      static_for<NB>([&](auto I) { constexpr int i = I; x[i] = MW.ld(LDS_RG0 + i) + (x[i] + fs[i]); });
       ldl_factor<PAT_H>(L, dinv);
       ldl_solve<PAT_H>(L, dinv, x);
-      static_for<NB>([&](auto I) { constexpr int i = I; MS.st(LDS_RA + i, x[i]); });      // abar: the main wave finishes the gear rows
+      static_for<NB>([&](auto I) { constexpr int i = I; MW.st(LDS_RA + i, x[i]); });      // abar: the main wave finishes the gear rows
       MCG_TICK(ST_Q_COLS);
     }
   }

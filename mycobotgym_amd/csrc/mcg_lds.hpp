@@ -57,6 +57,24 @@ constexpr int LDS_WIN = LDS_QLAG + 6 - 128;
 static_assert(LDS_WIN >= 0 && LDS_WIN <= LDS_Z6 && LDS_WIN <= LDS_QB && LDS_QDB + NB <= LDS_WIN + 128 && LDS_RA + NB <= LDS_WIN + 128
               && LDS_QLAG + 6 <= LDS_WIN + 128 && (128 - 1) * 64 * sizeof(double) < 65536,
               "the slots of the main wave's window must lie within one 16-bit ds_ offset of its base");
+// The side waves' windows under SplitMainCols (WindowedScratchT in mcg_dynamics.hpp).  A single ds_ access reaches 128 slots from its
+// base, the st64 pair form 256; a slot is served by the window whose single reach it lies in, so that no access needs an address op:
+//   LDS_WIN_LO  the upper rows of H_eq (slots from 128 on) and the gear rows' columns; the sine / cosine exchange lies in its reach too.
+//               Used by the helper wave (build_H, its stores of Z6 / Z8) and by the RNE wave (build_H of the remote solve);
+//   LDS_WIN_HI  the published state, the bias forces and the remote solve's hand-over (QB, QDB, FS, RA, RACT, RG0).  Used by the RNE
+//               wave: qd, no_other_rows and its store of passive - bias before S2, the remote solve after it.
+// The exchange itself (trig_exchange, side_trig) is addressed from slot 0 in every wave: through these windows it was slower on either
+// side wave and no faster on the main wave.
+// Slots below LDS_WIN_LO are addressed from slot 0 as before; slots from LDS_WIN_SPLIT on go through the upper window, so that each
+// region is served by one base as a whole and its neighbours pair.
+constexpr int LDS_WIN_LO = 128, LDS_WIN_HI = LDS_SLOTS_SPLIT - 128, LDS_WIN_SPLIT = LDS_QB;
+static_assert(LDS_WIN_LO <= 128 && LDS_WIN_LO > LDS_HEQ && LDS_WIN_LO <= LDS_SN && LDS_CS + NB <= LDS_WIN_LO + 128
+              && LDS_Z8 + NB <= LDS_WIN_SPLIT && LDS_WIN_SPLIT <= LDS_WIN_LO + 128,
+              "the lower side-wave window: slots below it within a ds_ offset of slot 0; H_eq's upper rows, the exchange and the columns, "
+              "as every slot below the split, within one of its base");
+static_assert(LDS_WIN_HI >= LDS_WIN_LO && LDS_WIN_HI <= LDS_WIN_SPLIT && LDS_WIN_SPLIT <= LDS_QB && LDS_QDB + NB <= LDS_WIN_HI + 128 && LDS_FS + NB <= LDS_WIN_HI + 128
+              && LDS_RA + NB <= LDS_WIN_HI + 128 && LDS_RACT + 8 <= LDS_WIN_HI + 128 && LDS_RG0 + NB <= LDS_WIN_HI + 128,
+              "the upper side-wave window: the published state, the bias forces and the remote solve's hand-over within one ds_ offset of its base");
 
 // ==================================================================================================== the PickAndPlace column (32 lanes)
 constexpr int PNP_LANES = 32;        // envs per wave in the PickAndPlace kernels: twice the LDS per env; a wave costs the

@@ -14,8 +14,9 @@ for r in range(rounds):
             steps = {"reach-joint": 400, "reach-IK": 100, "pnp-joint": 300, "pnp-IK": 30, "pnp-joint-grasp": 30}.get(c, 100)
             p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--case", c, "--steps", str(steps), "--warmup", "60",
                                 "--no-cpu-baseline", "--no-secondary"], env=dict(os.environ, MCG_LIB=os.path.abspath(lib)),
-                               capture_output=True, text=True)
+                               capture_output=True, text=True, timeout=300)
             import json
             try: out.append(f"{c} {json.loads(p.stdout.strip().splitlines()[-1])['ms_per_step']:.4f}")
-            except Exception: out.append(f"{c} FAILED {p.stderr[-200:]}")
+            except Exception:      # a run that failed may have left the GPU in a bad way: start nothing after it
+                sys.exit(f"{lib} {c} FAILED (exit status {p.returncode}) {p.stderr[-2000:]}")
         print(lib, "  ".join(out), "ms/step", flush=True)
