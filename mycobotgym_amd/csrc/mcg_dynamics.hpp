@@ -133,6 +133,18 @@ MCG_DEV ModelPtr launder(ModelPtr p) { asm volatile("" : "+s"(p)); return p; }
 MCG_DEV void pin(real& a) { asm volatile("" : "+v"(a)); }
 MCG_DEV void pin3(real* v) { asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2])); }
 MCG_DEV void pin6(real* v) { asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5])); }
+// A batch of scalar loads, closed: the ten solver parameters of a row and its diag (and a connect side's five vectors) pass through ONE
+// empty asm as SGPR operands, so every load of the batch is issued above it and one wait retires them all.  It also hides from the
+// compiler that the values are loads: it turns a select whose arm is a load's only use back into a branch, and sinks the load into it.
+MCG_DEV void pin_par(real* p, real& d) {
+  asm volatile("" : "+s"(p[0]), "+s"(p[1]), "+s"(p[2]), "+s"(p[3]), "+s"(p[4]), "+s"(p[5]), "+s"(p[6]), "+s"(p[7]), "+s"(p[8]), "+s"(p[9]), "+s"(d));
+}
+// (an asm takes thirty operands, "+s" counting twice: the vectors, which no select reads, go through a second one as inputs)
+MCG_DEV void pin_side(real* a, real* b, real* c, real* d, real* e, real* p, real& dg) {
+  pin_par(p, dg);
+  asm volatile("" :: "s"(a[0]), "s"(a[1]), "s"(a[2]), "s"(b[0]), "s"(b[1]), "s"(b[2]), "s"(c[0]), "s"(c[1]), "s"(c[2]),
+                     "s"(d[0]), "s"(d[1]), "s"(d[2]), "s"(e[0]), "s"(e[1]), "s"(e[2]));
+}
 template <int N> MCG_DEV void ldc(CRealPtr src, real* dst) { for (int k = 0; k < N; k++) dst[k] = src[k]; }
 struct BodyC { real r[3], mass, mc[3], inertia[6], armature, damping; };
 MCG_DEV BodyC load_body(ModelPtr P, int i) {
@@ -199,6 +211,25 @@ MCG_DEV real impedance(const real* par, real dist) {
     imp = (x >= 1) ? dmax : imp;
     imp = (x == 0) ? d0 : imp;
   }
+  return fmin(fmax(imp, MINIMP), MAXIMP);
+}
+// The same function without a branch, for the main wave of SplitMainCols (robot_substep): a wave-uniform branch on a loaded constant
+// makes the compiler sink the loads of the later entries of par into the branch and wait for each piece on its own, and a wave alone
+// on its SIMD pays every such round trip in full.  Here the caller loads par (and the row's diag) in one batch and the wave-uniform
+// decisions are selects.  Every lane's value comes from the same operations in the same order as in impedance() (whose a - b * c the
+// compiler contracts into the fma written out here); what the selects discard may be anything, inf and nan included.
+MCG_DEV real impedance_flat(const real* par, real dist) {
+  const real d0 = par[2], dmax = par[3], width = par[4], mid = par[5], power = par[6];
+  const bool flat = (d0 == dmax) | (width <= MINVAL);
+  const real x = fabs(dist) * par[7];
+  const real u = 1 - x;
+  const real y2 = (x <= mid) ? par[8] * (x * x) : fma(-par[9], u * u, 1.0);
+  const real y = (power == 2) ? y2 : x;
+  real imp = fma(y, dmax - d0, d0);
+  imp = (x >= 1) ? dmax : imp;
+  imp = (x == 0) ? d0 : imp;
+  pin(imp);                                                             // (or the compiler branches around all of the above on `flat`)
+  imp = flat ? 0.5 * (d0 + dmax) : imp;
   return fmin(fmax(imp, MINIMP), MAXIMP);
 }
 
@@ -698,7 +729,8 @@ MCG_DEV void euler_accel(ModelPtr Pm, real h, const LS MS, const real* a, real* 
 // Nothing is handed over in the factor slots.
 // History: round 5 split the limit solve's columns behind a fourth barrier, S2b; round 6 added the sine / cosine
 // exchange; round 7 moved the whole solve to the RNE wave (kept for the joint controller only); round 8 added the helper columns; round 10
-// shortened the main wave's stretch after S3; round 11 gave the side waves windows for their slots beyond 64 KB (WindowedScratchT).
+// shortened the main wave's stretch after S3; round 11 gave the side waves windows for their slots beyond 64 KB (WindowedScratchT);
+// round 12 made the main wave fetch each constraint block's constants in one batch of scalar loads (pin_par, pin_side, impedance_flat).
 struct NoSplit { static constexpr bool enabled = false, reach = false, mesh_split = false, cols = false; };
 struct SplitMainLocal { static constexpr bool enabled = true, reach = true, mesh_split = false, cols = false;
                         static constexpr int QB = LDS_QB, QDB = LDS_QDB, FS = LDS_FS, WARM = LDS_WARM, QLAG = LDS_QLAG; };
@@ -890,6 +922,7 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     real rg[3], rh[3], rf[3], an1[3], an2[3], par[10];
     ldc<3>(Q->body[g].r, rg); ldc<3>(Q->body[hg].r, rh); ldc<3>(Q->body[fi].r, rf);
     ldc<3>(Q->eq_anchor1[sd], an1); ldc<3>(Q->eq_anchor2[sd], an2); ldc<10>(Q->eq_par[sd], par);
+    real diag = 0; if constexpr (SPL::cols) { diag = Q->eq_diag[sd]; pin_side(rg, rh, rf, an1, an2, par, diag); }      // cols: one batch for all the side reads
     real t[3], t2[3], o_f[3], p1[3], p2[3];
     rot_up<1>(cs[g], sn[g], rf, t);
     for (int k = 0; k < 3; k++) o_f[k] = rg[k] + t[k];
@@ -904,8 +937,9 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     Jc[sd][0][7] = AXS[fi] * (p1[2] - o_f[2]); Jc[sd][2][7] = -AXS[fi] * (p1[0] - o_f[0]);
     Jc[sd][0][8] = -AXS[hg] * (p2[2] - rh[2]); Jc[sd][2][8] = AXS[hg] * (p2[0] - rh[0]);
     Jc[sd][1][6] = Jc[sd][1][7] = Jc[sd][1][8] = 0;
-    const real imp = impedance(par, sqrt(dot3(pos, pos)));
-    Dc[sd] = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * Q->eq_diag[sd]));      // 1 / max(MINVAL, (1-imp) diag / imp)
+    real imp;      // (every other policy keeps its two statements as they were, here and below: those kernels' instruction streams do not change)
+    if constexpr (SPL::cols) { imp = impedance_flat(par, sqrt(dot3(pos, pos))); Dc[sd] = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * diag)); }
+    else { imp = impedance(par, sqrt(dot3(pos, pos))); Dc[sd] = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * Q->eq_diag[sd])); }      // 1 / max(MINVAL, (1-imp) diag / imp)
     static_for<3>([&](auto Kk) {
       constexpr int k = Kk;
       real vel = 0;
@@ -922,9 +956,11 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
   {
     ModelPtr Q = launder(Pm);
     real par[10]; ldc<10>(Q->eq_par[2], par);
+    real diag = 0; if constexpr (SPL::cols) { diag = Q->eq_diag[2]; pin_par(par, diag); }
     const real pos = S.q[6] - S.q[8];
-    const real imp = impedance(par, pos);
-    Dj = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * Q->eq_diag[2]));
+    real imp;
+    if constexpr (SPL::cols) { imp = impedance_flat(par, pos); Dj = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * diag)); }
+    else { imp = impedance(par, pos); Dj = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * Q->eq_diag[2])); }
     arefj = -par[1] * (S.qd[6] - S.qd[8]) - par[0] * imp * pos;
   }
   MCG_TICK_PIN(&Dj, 1); MCG_TICK_PIN(&arefj, 1);
@@ -948,8 +984,10 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     if (__any(sg != 0)) {
       ModelPtr Q = launder(Pm);
       real par[10]; ldc<10>(Q->limit_par[j], par);
-      const real imp = impedance(par, dist);
-      const real D = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * Q->limit_diag[j]));
+      real diag = 0; if constexpr (SPL::cols) { diag = Q->limit_diag[j]; pin_par(par, diag); }
+      real imp, D;
+      if constexpr (SPL::cols) { imp = impedance_flat(par, dist); D = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * diag)); }
+      else { imp = impedance(par, dist); D = imp * rcp_nr(fmax(MINVAL * imp, (1 - imp) * Q->limit_diag[j])); }
       const real ar = -par[1] * (sg * S.qd[j]) - par[0] * imp * dist;
       Dl[j] = (sg != 0) ? D : 0.0; arefl[j] = (sg != 0) ? ar : 0.0;
       any_limit = any_limit || (sg != 0);
