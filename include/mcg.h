@@ -908,6 +908,75 @@ int mcg_sac_target(const mcg_sac* sac, const mcg_her_batch* batch, int64_t B, ui
    Also refused: tau outside [0, 1]; critic == critic_target. */
 int mcg_sac_polyak(const mcg_sac* sac, double tau, void* stream);
 
+/* ---- SAC's update, the gradient half (mcg_sac_grad.hip): one gradient step of SB3's SAC.train [RECALL: sac/sac.py; SB3 is not
+   installed next to the reference] is, in this order, because each step reads what an earlier one wrote:
+     alpha = exp(log_ent_coef), the value before this step's alpha update (ent_coef = "auto"; else the constant)
+     y = mcg_sac_target(batch)                                           (before anything writes log_ent_coef)
+     critic_loss = 0.5 (mean((q0 - y)^2) + mean((q1 - y)^2)) on (obs, action); mcg_sac_critic_grad, mcg_sac_adam on `critic`
+                   (SB3's SAC clips no gradients)
+     a, logp = actor(obs), fresh noise; actor_loss = mean(alpha logp - min(q0(obs, a), q1(obs, a))) through the critic as just
+                   updated, a constant here: no critic weight gradient is formed; mcg_sac_actor_grad, mcg_sac_adam on `actor`
+     ent_coef_loss = -mean(log_ent_coef (logp + target_entropy)), logp the actor step's; mcg_sac_alpha_step ("auto" only)
+     mcg_sac_polyak every target_update_interval steps.
+   Stateless, as everything here: the caller owns the gradients, the moments and the scratch; every entry enqueues on `stream` and
+   none synchronises.  Float32 on v_mfma_f32_16x16x4_f32 in tiles of 16 samples; deterministic: no atomics, every sum in an order that
+   the shape and B alone fix.  Additive: MCG_ABI_VERSION stays 8.
+   The actor loss's derivative at the heads, per component, with a = tanh(u), s = 1 - a^2 and the log_std before the clamp:
+     d/du       = (alpha 2 a s / (s + 1e-6) - dQ/da s) / B      (the squash correction's term and the chosen critic's)
+     d/dmu      = d/du
+     d/dlog_std = d/du exp(log_std) eps - alpha / B, and 0 where the clamp acts (log_std < -20 or > 2)
+   The Gaussian term -eps^2 / 2 - log_std - ln(2 pi) / 2 is written in eps, which rsample holds fixed: its own derivative is zero
+   apart from -log_std, the -alpha / B above.  The terms are formed in double from the float32 values and rounded once.  The min's
+   choice per sample is c = (q1 < q0); dQ/da is critic c's alone.
+   The noise: mcg_sac_act's counter layout and Box-Muller with dom = 9, id = the sample's index in the batch, call = the caller's count
+   of actor-loss calls.
+   Checked on the host before any launch, as for the entries above (the kernels get bare pointers): the mcg_sac and the blobs an entry
+   touches; null or misaligned (16 bytes) work, grad, m, v; B < 1 or >= 2^27; work_floats below mcg_sac_grad_work_floats; step < 1; and
+   what each entry lists. */
+int64_t mcg_sac_grad_work_floats(const mcg_sac* sac, int64_t B);          /* scratch of both gradient entries; 0 for a refused shape or B */
+
+/* The critic loss and its gradient over the whole critic blob.  `rows`: obs, achieved, desired, action [B, .]; y [B]: the TD target.
+   grad   [critic_floats], 16-byte aligned, in the blob's own layout (the first layer's feature tiles and action tiles where the blob
+          keeps them); every padding position (feature columns from D + 6, action columns from A, head rows from 1) is written +0.0f.
+   stats  [8]: [0] critic_loss, [4] mean(q0), [5] mean(q1), [7] 0 are written; the others are left.
+   work   scratch, 16-byte aligned; its content before the call does not matter.
+   Reads `critic` alone of the blobs.  Three launches: a wave per (tile, critic), the dW blocks per part, the sum in part order. */
+int mcg_sac_critic_grad(const mcg_sac* sac, const mcg_sac_rows* rows, const float* y, int64_t B, float* work, int64_t work_floats,
+                        float* grad, float* stats, void* stream);
+
+typedef struct mcg_sac_actor_grad_out {     /* device pointers, float32; any may be NULL to skip (the struct's pointer too) */
+  float* action;         /* [B, A]  a = tanh(u) of the actor-loss draw */
+  float* noise;          /* [B, A]  eps */
+  float* q_pi;           /* [2, B]  both critics at (obs, a) */
+  float* dq_da;          /* [B, A]  the chosen critic's dQ/da */
+} mcg_sac_actor_grad_out;
+
+/* The actor loss and its gradient with respect to the actor blob alone.  `rows`: obs, achieved, desired (action is not read).
+   alpha = (float)exp((double)*log_ent_coef), read on the device, where log_ent_coef is not NULL; otherwise ent_coef (finite, >= 0).
+   grad      [actor_floats], 16-byte aligned, the blob's layout; padding (feature columns from D + 6, head rows from A) is +0.0f.
+   logp_out  [B], required: the draw's log-prob, which mcg_sac_alpha_step reads.
+   stats     [1] actor_loss, [3] alpha, [6] mean(logp) are written; the others are left.
+   Reads `actor` and `critic`; writes neither, nor critic_target.  Three launches: a workgroup of two waves per tile (both the actor,
+   wave q critic q and its dQ/da, wave 0 the head and the actor's backward pass), the dW blocks per part, the sum in part order. */
+int mcg_sac_actor_grad(const mcg_sac* sac, const mcg_sac_rows* rows, int64_t B, uint64_t seed, uint64_t call, float ent_coef,
+                       const float* log_ent_coef /* [1] device or NULL */, float* work, int64_t work_floats, float* grad,
+                       float* logp_out, float* stats, const mcg_sac_actor_grad_out* out, void* stream);
+
+/* ent_coef_loss = -mean(log_ent_coef (logp + target_entropy)) and its gradient g = -mean(logp + target_entropy): the mean in double
+   in a fixed tree, rounded to float32 once; then torch.optim.Adam's rule (as mcg_policy_adam's, no clip) on the one float with g.
+   lr = 0 makes it the gradient alone: log_ent_coef, m and v are not written (m and v may be NULL then).  grad_out [1] and stats [8]
+   (only [2], ent_coef_loss, is written) may be NULL.  One launch.  Also refused: a null log_ent_coef or logp; lr < 0 or not finite;
+   betas outside [0, 1); eps < 0; a target_entropy that is not finite. */
+int mcg_sac_alpha_step(float* log_ent_coef, const float* logp, int64_t B, float target_entropy, float* m, float* v, int64_t step,
+                       double lr, double beta1, double beta2, double eps, float* grad_out, float* stats, void* stream);
+
+/* torch.optim.Adam's step without amsgrad or weight decay on a bare blob of `floats` floats, elementwise, as mcg_policy_adam's rule
+   with no clip and with 1 - beta1, 1 - beta2 formed on the host in double and rounded to float32 once, as torch passes them; padding
+   positions keep g = m = v = 0 and stay +0.0.  blob, grad, m, v: 16-byte aligned.  One launch.  Also refused:
+   floats < 1 or >= 2^31; lr < 0 or not finite; betas outside [0, 1); eps < 0. */
+int mcg_sac_adam(float* blob, const float* grad, float* m, float* v, int64_t floats, int64_t step, double lr, double beta1, double beta2,
+                 double eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

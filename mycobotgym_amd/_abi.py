@@ -328,6 +328,11 @@ class McgSacTargetOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("target", "next_action", "next_log_prob", "next_q", "noise")]
 
 
+class McgSacActorGradOut(C.Structure):
+    """The optional intermediates of the actor loss (include/mcg.h: mcg_sac_actor_grad_out)."""
+    _fields_ = [(n, C.c_void_p) for n in ("action", "noise", "q_pi", "dq_da")]
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -342,7 +347,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_replay_img_sample_stacked", "mcg_frame_stack_push",
            "mcg_policy_blob_floats", "mcg_policy_forward",
            "mcg_policy_evaluate", "mcg_policy_grad_work_floats", "mcg_policy_grad", "mcg_policy_adam",
-           "mcg_sac_blob_floats", "mcg_sac_act", "mcg_sac_q", "mcg_sac_target", "mcg_sac_polyak")
+           "mcg_sac_blob_floats", "mcg_sac_act", "mcg_sac_q", "mcg_sac_target", "mcg_sac_polyak",
+           "mcg_sac_grad_work_floats", "mcg_sac_critic_grad", "mcg_sac_actor_grad", "mcg_sac_alpha_step", "mcg_sac_adam")
 
 _lib = None
 
@@ -453,6 +459,16 @@ def load():
         L.mcg_sac_target.argtypes = [C.POINTER(McgSac), C.POINTER(McgHerBatch), C.c_int64, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                      C.c_void_p, C.POINTER(McgSacTargetOut), C.c_void_p]
         L.mcg_sac_polyak.argtypes = [C.POINTER(McgSac), d, C.c_void_p]
+    if hasattr(L, "mcg_sac_actor_grad"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_sac_grad_work_floats.argtypes = [C.POINTER(McgSac), C.c_int64]
+        L.mcg_sac_grad_work_floats.restype = C.c_int64
+        L.mcg_sac_critic_grad.argtypes = [C.POINTER(McgSac), C.POINTER(McgSacRows), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        L.mcg_sac_actor_grad.argtypes = [C.POINTER(McgSac), C.POINTER(McgSacRows), C.c_int64, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(McgSacActorGradOut), C.c_void_p]
+        L.mcg_sac_alpha_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, d, d, d, d,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcg_sac_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, d, d, d, d, C.c_void_p]
     _lib = L
     return L
 

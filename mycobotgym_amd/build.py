@@ -17,6 +17,7 @@ SRC_FRAME_STACK = os.path.join(_HERE, "csrc", "mcg_frame_stack.hip")    # act-ti
 SRC_POLICY = os.path.join(_HERE, "csrc", "mcg_policy.hip")      # the actor-critic policy forward: likewise
 SRC_POLICY_GRAD = os.path.join(_HERE, "csrc", "mcg_policy_grad.hip")    # the policy update (gradient, Adam): likewise
 SRC_SAC = os.path.join(_HERE, "csrc", "mcg_sac.hip")            # SAC's actor, twin critics and TD target: likewise
+SRC_SAC_GRAD = os.path.join(_HERE, "csrc", "mcg_sac_grad.hip")  # SAC's update (critic, actor and alpha gradients, Adam): likewise
 DEPS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*"))) + [os.path.join(ROOT, "include", "mcg.h")]      # every source and header
 OUT = os.path.join(_HERE, "libmycobot_hip.so")
 
@@ -43,7 +44,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
         return OUT
     cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-shared",
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(_HERE, "csrc"), SRC, SRC_RENDER, SRC_REPLAY, SRC_ROLLOUT, SRC_REPLAY_IMG,
-           SRC_FRAME_STACK, SRC_POLICY, SRC_POLICY_GRAD, SRC_SAC,
+           SRC_FRAME_STACK, SRC_POLICY, SRC_POLICY_GRAD, SRC_SAC, SRC_SAC_GRAD,
            "-o", OUT]
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")

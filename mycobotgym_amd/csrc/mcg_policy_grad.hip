@@ -35,13 +35,13 @@
 //
 // ---- A ragged last tile: its extra lanes read the last valid sample, as in the forward, and their dZ is set to +-0 at the head, so
 // that every product they enter adds exactly nothing.
-#include "mcg_policy.hpp"
+#include "mcg_grad.hpp"       // sum16, store_rows, Block, dw_block, sum_parts, block_sum, adam_one (shared with mcg_sac_grad.hip)
 
 using namespace mcg;
 
 namespace {
 
-constexpr int PARTS_NARROW = 16, PARTS_WIDE = 4, MAX_BLOCK_LAYERS = 2 * (MAX_LAYERS + 1) + 1;
+constexpr int MAX_BLOCK_LAYERS = 2 * (MAX_LAYERS + 1) + 1;
 constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
 constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
 
@@ -54,10 +54,6 @@ struct Rows {                            // a net's rows of a tile in `work`, in
 struct Batch { const float *obs, *ach, *des, *action, *old_lp, *adv, *ret; };
 struct Hyper { int kind, norm; float clip, ent_coef, vf_coef, inv_b; };
 struct EvalOut { float *value, *log_prob, *entropy; };
-struct Block {                           // one layer's blocks of the dW product: nT rows of (ncb blocks of 16 columns, then the bias)
-  int blk0, nT, ncb, xrow, drow, w, b, nkb, first, rows;
-  long long base;
-};
 struct Blocks { Block l[MAX_BLOCK_LAYERS]; int n, total; };
 
 MCG_DEV Rows pick_rows(const Rows& x, const Rows& y, int k) {
@@ -66,23 +62,6 @@ MCG_DEV Rows pick_rows(const Rows& x, const Rows& y, int k) {
   for (int L = 0; L <= MAX_LAYERS; L++) { z.x[L] = k ? y.x[L] : x.x[L]; z.d[L] = k ? y.d[L] : x.d[L]; }
   z.ls = k ? y.ls : x.ls; z.rows = k ? y.rows : x.rows; z.fr = k ? y.fr : x.fr; z.base = k ? y.base : x.base;
   return z;
-}
-
-// the sum over the 16 samples of a tile, in an order that does not depend on the data (every lane gets it)
-MCG_DEV float sum16(float x) {
-  x += __shfl_xor(x, 8); x += __shfl_xor(x, 4); x += __shfl_xor(x, 2); x += __shfl_xor(x, 1);
-  return x;
-}
-
-// rows `at + 16 t + 4 g + r` of the tile's chunk <- register r of tile t (the accumulator layout), sample i
-template <int MT>
-MCG_DEV void store_rows(float* chunk, int at, int nt, const f4 (&v)[MT], int g, int i) {
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-    if (t < nt) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) chunk[(size_t)(at + 16 * t + 4 * g + r) * TILE + i] = v[t][r];
-    }
 }
 
 // GRAD = false: mcg_policy_evaluate (no `work`);  true: the forward, the loss's derivative and the backward pass of one tile and net.
@@ -234,39 +213,13 @@ __global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1
 
 // One 16 x 16 block of dW (or 16 biases) over the tiles of one part -> its place in the part's partial blob.
 __global__ __launch_bounds__(WAVE) void grad_dw_kernel(Blocks Q, const float* __restrict__ work, float* __restrict__ partials,
-                                                       long long blob_floats, int ntiles, int tpp, int kb0, int D) {
-  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+                                                       long long blob_floats, int ntiles, int tpp) {
   const int blk = blockIdx.x, part = blockIdx.y;
   Block me = Q.l[0];
 #pragma unroll
   for (int q = 1; q < MAX_BLOCK_LAYERS; q++)
     if (q < Q.n && blk >= Q.l[q].blk0) me = Q.l[q];              // (constant indices: selects, no scratch)
-  const int local = blk - me.blk0, T = local / (me.ncb + 1), cb = local % (me.ncb + 1);
-  const bool bias = cb == me.ncb;
-  const int t0 = part * tpp, t1 = min(t0 + tpp, ntiles);
-  const size_t stride = (size_t)me.rows * TILE;
-  const float* __restrict__ A = work + me.base + (size_t)(me.drow + 16 * T + i) * TILE + 4 * g;
-  const float* __restrict__ Bm = work + me.base + (size_t)(me.xrow + (bias ? 0 : 16 * cb) + i) * TILE + 4 * g;
-  f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int t = t0; t < t1; t++) {
-    const f4 a4 = *reinterpret_cast<const f4*>(A + t * stride);
-    f4 b4 = {1.0f, 1.0f, 1.0f, 1.0f};
-    if (!bias) b4 = *reinterpret_cast<const f4*>(Bm + t * stride);
-#pragma unroll
-    for (int q = 0; q < 4; q++) acc = mfma(a4[q], b4[q], acc);
-  }
-  float* out = partials + (size_t)part * blob_floats;          // register r: dW[16 T + 4 g + r][16 cb + i]
-  if (bias) {
-    if (i == 0) *reinterpret_cast<f4*>(out + me.b + 16 * T + 4 * g) = acc;
-  } else if (me.first) {                 // column 16 cb + i = 4 kb + g': tile (T, kb), float 16 g' + 4 g + r
-    const int kb = 4 * cb + (i >> 2);
-    if (kb < kb0) {
-      if (16 * cb + i >= D + 6) acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
-      *reinterpret_cast<f4*>(out + me.w + (size_t)(T * kb0 + kb) * WAVE + 16 * (i & 3) + 4 * g) = acc;
-    }
-  } else {                               // column 16 cb + i = 16 t + 4 g' + r': tile (T, 4 t + r'), float 16 g' + 4 g + r
-    *reinterpret_cast<f4*>(out + me.w + (size_t)(T * me.nkb + 4 * cb + (i & 3)) * WAVE + 16 * (i >> 2) + 4 * g) = acc;
-  }
+  dw_block(me, blk, part, work, partials, blob_floats, ntiles, tpp);
 }
 
 // grad[p] = the partial blobs' sum in part order (log_std: and the entropy term's -ent_coef); the last block: the tiles' sums -> stats.
@@ -276,8 +229,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
   if (blockIdx.x < gridDim.x - 1) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= blob_floats) return;
-    float sum = partials[p];
-    for (int q = 1; q < parts; q++) sum += partials[(size_t)q * blob_floats + p];
+    float sum = sum_parts(partials, parts, blob_floats, p);
     if (p >= log_std && p < log_std + A) sum -= H.ent_coef;
     grad[p] = sum;
     return;
@@ -299,19 +251,6 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
     stats[1] = policy_loss; stats[2] = value_loss; stats[3] = entropy_loss;
     stats[4] = acc[2] * H.inv_b; stats[5] = acc[3] * H.inv_b; stats[6] = 0.0f; stats[7] = 0.0f;
   }
-}
-
-// the sum over a workgroup of 1024 in a fixed tree (every thread gets it)
-MCG_DEV double block_sum(double x, double* lds) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  lds[t] = x;
-  __syncthreads();
-  for (int m = 512; m >= 1; m >>= 1) {
-    if (t < m) lds[t] += lds[t + m];
-    __syncthreads();
-  }
-  return lds[0];
 }
 
 // out[0] = mean, out[1] = std + 1e-8 (the unbiased deviation, as torch.std) of adv[0..B)
@@ -340,12 +279,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   const float coef = max_norm > 0.0f ? fminf(1.0f, max_norm / (norm[0] + 1e-6f)) : 1.0f;
-  const float gj = grad[j] * coef;
-  const float mj = beta1 * m[j] + (1.0f - beta1) * gj;
-  const float vj = beta2 * v[j] + (1.0f - beta2) * (gj * gj);
-  m[j] = mj;
-  v[j] = vj;
-  p[j] = p[j] - step_size * (mj / (sqrtf(vj) / bc2_sqrt + eps));
+  adam_one(p, grad[j] * coef, m, v, j, beta1, beta2, 1.0f - beta1, 1.0f - beta2, step_size, bc2_sqrt, eps);
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
@@ -355,9 +289,7 @@ struct Layout { Rows rows[2]; Blocks blocks; int ntiles, tpp, parts; long long p
 Layout layout(const Pol& P, int64_t B, int widest) {
   Layout Y = {};
   Y.ntiles = (int)((B + TILE - 1) / TILE);
-  const int max_parts = widest <= 64 ? PARTS_NARROW : PARTS_WIDE;
-  Y.tpp = (Y.ntiles + max_parts - 1) / max_parts;
-  Y.parts = (Y.ntiles + Y.tpp - 1) / Y.tpp;
+  split_parts(Y.ntiles, widest, &Y.tpp, &Y.parts);
   const int fr = (P.D + 6 + 15) / 16 * 16;
   long long at = 4 + 8ll * Y.ntiles;
   for (int k = 0; k < 2; k++) {
@@ -381,13 +313,13 @@ Layout layout(const Pol& P, int64_t B, int widest) {
       Block& b = Y.blocks.l[q++];
       b.blk0 = blk; b.nT = L < net.n ? net.nt[L] : 1; b.ncb = L == 0 ? fr / 16 : net.nt[L - 1];
       b.xrow = R.x[L]; b.drow = R.d[L]; b.w = net.w[L]; b.b = net.b[L]; b.nkb = L == 0 ? P.kb0 : 4 * net.nt[L - 1]; b.first = L == 0;
-      b.rows = R.rows; b.base = R.base;
+      b.rows = R.rows; b.base = R.base; b.cols = L == 0 ? P.D + 6 : ALL_COLUMNS; b.nb = 1;
       blk += b.nT * (b.ncb + 1);
     }
     if (k == 1) {                        // log_std: a bias whose dZ is the policy net's log_std rows
       Block& b = Y.blocks.l[q++];
       b = Block{};
-      b.blk0 = blk; b.nT = 1; b.ncb = 0; b.drow = R.ls; b.b = P.log_std; b.rows = R.rows; b.base = R.base;
+      b.blk0 = blk; b.nT = 1; b.ncb = 0; b.nb = 1; b.drow = R.ls; b.b = P.log_std; b.rows = R.rows; b.base = R.base;
       blk += 1;
     }
   }
@@ -469,7 +401,7 @@ int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64
   if (widest <= 64) hipLaunchKernelGGL((grad_tile_kernel<4, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});
   else hipLaunchKernelGGL((grad_tile_kernel<16, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});
   hipLaunchKernelGGL(grad_dw_kernel, dim3(Y.blocks.total, Y.parts), block, 0, st, Y.blocks, (const float*)work, work + Y.partials,
-                     (long long)floats, Y.ntiles, Y.tpp, P.kb0, P.D);
+                     (long long)floats, Y.ntiles, Y.tpp);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3(blocks(floats, 256) + 1), dim3(256), 0, st, (const float*)work,
                      (const float*)(work + Y.partials), Y.parts, (long long)floats, Y.ntiles, pol->blob, P.log_std, P.A, H, grad, stats);
   return launched("mcg_policy_grad");

@@ -16,8 +16,9 @@ state and no call synchronises.
     q0, q1 = pol.q_values(batch.observations, batch.actions)
     pol.polyak(tau=0.005)
 
-No CPU or PyTorch fallback: the kernels are the only implementation.  The gradient and the optimisers are not built: a caller with
-optimisers of its own (any ``nn.Module`` with SB3's parameter names) repacks the blobs with ``load_state_dict`` after an update.
+No CPU or PyTorch fallback: the kernels are the only implementation.  The gradient step is ``SACUpdate`` (sac_update.py), which
+updates the three blobs and ``log_ent_coef`` in place; a caller with optimisers of its own (any ``nn.Module`` with SB3's parameter
+names) can still repack the blobs with ``load_state_dict`` after an update.
 """
 from __future__ import annotations
 
