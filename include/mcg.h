@@ -977,6 +977,121 @@ int mcg_sac_alpha_step(float* log_ent_coef, const float* logp, int64_t B, float 
 int mcg_sac_adam(float* blob, const float* grad, float* m, float* v, int64_t floats, int64_t step, double lr, double beta1, double beta2,
                  double eps, void* stream);
 
+/* ---- TD3 and DDPG (SB3's TD3Policy as scripts/train.py's --algo TD3 / DDPG builds it with MultiInputPolicy for a Dict space of
+   Boxes; mcg_td3.hip, mcg_td3_grad.hip): a deterministic actor with a target copy, n_critics = 2 (TD3) or 1 (DDPG) critics with a
+   target copy.  Stateless: the caller owns four float32 device blobs, the call numbers and both step counts.  Every entry enqueues on
+   `stream` and none synchronises.  Additive: MCG_ABI_VERSION stays 8.
+   The rule, restated [RECALL: stable_baselines3/td3/policies.py, td3/td3.py; SB3 is not installed next to the reference]:
+     features   as for mcg_sac_act.
+     actor      actor.mu = Sequential(Linear, act, ..., Linear(A), Tanh): n_pi layers x -> act(W x + b), one linear head z [A], and
+                mean = (float)tanh((double)z), rounded once; float32 otherwise (v_mfma_f32_16x16x4_f32).  actor_target: a second one.
+     critics    qf0 (and qf1 where n_critics = 2) on cat(features, action), as SAC's; critic_target a second set.
+     noise      eps as mcg_sac_act draws it (the same counter layout and Box-Muller, rounded to float32 once), with dom = 10 and
+                id = env_id_offset + env for mcg_td3_act, dom = 11 and id = the sample's index for mcg_td3_target; scaled in float32
+                as sigma * eps, the product rounded once.  sigma == 0: the noise is +0.0f and nothing is drawn; the caller's call
+                number advances all the same, so that switching sigma does not shift later draws.
+     one step   n_updates += 1;  n = clamp(sigma eps, -c, c);  a' = clamp(actor_target(next_obs) + n, -1, 1);
+                y = r + (1 - done) gamma min_k critic_target_k(next_obs, a')                                      mcg_td3_target
+                critic_loss = sum_k mean((q_k(obs, a) - y)^2): dq_k = 2 (q_k - y) / B; Adam on `critic`           mcg_td3_critic_grad, mcg_sac_adam
+                every policy_delay-th step: actor_loss = -mean(qf0(obs, actor(obs))) through qf0 alone, as just updated, a constant
+                here; Adam on `actor` with the count of actor updates as its step;                                mcg_td3_actor_grad, mcg_sac_adam
+                then critic_target and actor_target step towards critic and actor by tau                          mcg_td3_polyak
+   Rows past the count of the last tile of 16 read the last row and store nothing; a row of the outputs depends on that row alone.
+   Checked on the host before any HIP call (MCG_ERR_ARG, each with a message that names the field): a null mcg_td3; a null blob among
+   those the entry touches (mcg_td3_act: actor; mcg_td3_q: the one `which` names; mcg_td3_target: actor_target and critic_target;
+   mcg_td3_polyak: all four; mcg_td3_critic_grad: critic; mcg_td3_actor_grad: actor and critic), or one that is not 16-byte aligned;
+   obs_dim or act_dim < 1; obs_dim > 4096; act_dim > 16; n_pi or n_qf outside [1, 3]; a width that is no multiple of 16 in [16, 256]
+   (SB3's TD3 / DDPG default [400, 300] is this case); n_critics other than 1 or 2; an activation other than MCG_POLICY_TANH /
+   MCG_POLICY_RELU; actor_floats or critic_floats other than mcg_td3_blob_floats gives; and what each entry lists below. */
+#define MCG_TD3_CRITIC 0
+#define MCG_TD3_CRITIC_TARGET 1
+
+typedef struct mcg_td3 {
+  const float* actor;               /* device, 16-byte aligned, actor_floats floats: the trunk's layers, then the head (A rows padded to 16) */
+  float* actor_target;              /* likewise; written by mcg_td3_polyak alone */
+  const float* critic;              /* device, 16-byte aligned, critic_floats floats: qf0, then qf1 where n_critics = 2 (mcg_sac's layout) */
+  float* critic_target;             /* likewise; written by mcg_td3_polyak alone */
+  int32_t n_envs, obs_dim, act_dim; /* n_envs: rows of mcg_td3_act (the other entries take their rows per call) */
+  int32_t n_pi, pi_width[3];        /* the actor's trunk: 1..3 layers, widths multiples of 16, at most 256 */
+  int32_t n_qf, qf_width[3];        /* each critic likewise */
+  int32_t activation;               /* MCG_POLICY_TANH or MCG_POLICY_RELU */
+  int32_t n_critics;                /* 2: TD3; 1: DDPG */
+  int64_t actor_floats, critic_floats;      /* must equal what mcg_td3_blob_floats gives for this shape */
+} mcg_td3;
+
+typedef struct mcg_td3_act_out {    /* device pointers, float32; all but action may be NULL to skip */
+  float* action;         /* [N, A]  required */
+  float* mean;           /* [N, A]  the actor's output, tanh of the head */
+  float* noise;          /* [N, A]  noise_std * eps */
+} mcg_td3_act_out;
+
+typedef struct mcg_td3_target_out { /* device pointers, float32; all but target may be NULL to skip */
+  float* target;         /* [B]     required */
+  float* next_action;    /* [B, A]  a' */
+  float* next_q;         /* [n_critics, B]  the target critics at (next_obs, a'), before the min */
+  float* noise;          /* [B, A]  n, after the clip */
+} mcg_td3_target_out;
+
+typedef struct mcg_td3_actor_grad_out {     /* device pointers, float32; any may be NULL to skip (the struct's pointer too) */
+  float* action;         /* [B, A]  a = actor(obs) */
+  float* q_pi;           /* [B]     qf0(obs, a) */
+  float* dq_da;          /* [B, A]  qf0's dQ/da */
+} mcg_td3_actor_grad_out;
+
+/* actor_floats + critic_floats, and the two through the pointers (either may be NULL); 0, and zeros, for a refused shape. */
+int64_t mcg_td3_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_qf, const int32_t* qf_width, int n_critics,
+                            int64_t* actor_floats, int64_t* critic_floats);
+
+/* The collection action  action = fminf(fmaxf(mean + noise, -1), 1), the sum rounded to float32 once [RECALL: NormalActionNoise with
+   mean 0, then the clip of OffPolicyAlgorithm._sample_action]; noise_std = 0 is what scripts/train.py does (it passes no action
+   noise).  `obs` is what mcg_reset / mcg_step wrote (float64, read in place and rounded to float32).  One launch, one wave per tile
+   of 16 environments.  Also refused: n_envs < 1 or >= 2^27; a null mcg_step_out or obs / achieved_goal / desired_goal in it; a
+   noise_std that is negative or not finite; a null mcg_td3_act_out or a null action. */
+int mcg_td3_act(const mcg_td3* td3, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset, float noise_std,
+                const mcg_td3_act_out* out, void* stream);
+
+/* The critics of the blob `which` names on B rows: q[0 .. B) is qf0, and with two critics q[B .. 2 B) is qf1.  One launch, one wave
+   per (tile, critic).  Also refused: `which` other than the two above; B < 1 or >= 2^27; a null mcg_sac_rows or field of it; a null q. */
+int mcg_td3_q(const mcg_td3* td3, int which, const mcg_sac_rows* rows, int64_t B, float* q /* [n_critics, B] */, void* stream);
+
+/* The smoothed TD target as one launch, in float32:
+     n = fminf(fmaxf(sigma * eps, -clip), clip);   a' = fminf(fmaxf(mean' + n, -1), 1), mean' = actor_target(next_obs);
+     target = fmaf((1 - done) * gamma, min_k q_k, reward), q_k = critic_target_k(next_obs, a')      (the product rounded to float32
+   before the fmaf, as mcg_sac_target's; with one critic the min is q_0).  A workgroup of n_critics waves per tile of 16 samples.
+   Read of `batch` as mcg_sac_target reads it.  Also refused: B < 1 or >= 2^27; a null batch or one of the five fields; gamma outside
+   [0, 1]; a sigma or clip that is negative or not finite; a null mcg_td3_target_out or a null target. */
+int mcg_td3_target(const mcg_td3* td3, const mcg_her_batch* batch, int64_t B, uint64_t seed, uint64_t call, float gamma, float sigma,
+                   float clip, const mcg_td3_target_out* out, void* stream);
+
+/* critic_target <- (1 - tau) critic_target + tau critic and actor_target <- (1 - tau) actor_target + tau actor, each by
+   mcg_sac_polyak's rule, rounding by rounding, the tau = 1 copy included.  Two launches.  Also refused: tau outside [0, 1];
+   critic == critic_target; actor == actor_target. */
+int mcg_td3_polyak(const mcg_td3* td3, double tau, void* stream);
+
+int64_t mcg_td3_grad_work_floats(const mcg_td3* td3, int64_t B);          /* scratch of both gradient entries; 0 for a refused shape or B */
+
+/* The critic loss sum_k mean((q_k - y)^2) and its gradient over the whole critic blob; dq_k = (2 (q_k - y)) * (float)(1 / B), the
+   doubling exact.  `rows`: obs, achieved, desired, action [B, .]; y [B]: the TD target.
+   grad   [critic_floats], 16-byte aligned, in the blob's own layout; every padding position is written +0.0f.
+   stats  [8]: [0] critic_loss, [2] mean(q0), [3] mean(q1) (0 with one critic), [5], [6], [7] 0 are written; [1] and [4] are left.
+   work   scratch, 16-byte aligned; its content before the call does not matter.
+   Reads `critic` alone of the blobs.  Three launches: a wave per (tile, critic), the dW blocks per part, the sum in part order.
+   Also refused: B < 1 or >= 2^27; a null mcg_sac_rows or field of it; a null y or stats; a null or misaligned grad or work;
+   work_floats below what this entry needs. */
+int mcg_td3_critic_grad(const mcg_td3* td3, const mcg_sac_rows* rows, const float* y, int64_t B, float* work, int64_t work_floats,
+                        float* grad, float* stats, void* stream);
+
+/* The actor loss -mean(qf0(obs, actor(obs))) and its gradient with respect to the actor blob alone: per component, with a = tanh(z),
+     d/dz = (float)(-(double)dQ/da (1 - a^2) / B)      (in double from the float32 values, rounded once).
+   `rows`: obs, achieved, desired (action is not read).  qf1 is not read.
+   grad   [actor_floats], 16-byte aligned, the blob's layout; padding (feature columns from D + 6, head rows from A) is +0.0f.
+   stats  [1] actor_loss, [4] mean(q_pi) are written; the others are left.
+   Reads `actor` and `critic`; writes neither, nor a target.  Three launches: a wave per tile (the actor forward, the qf0 forward,
+   the walk back to the action columns, the head, the walk back through the actor), the dW blocks per part, the sum in part order.
+   Also refused: as mcg_td3_critic_grad, without y and rows->action. */
+int mcg_td3_actor_grad(const mcg_td3* td3, const mcg_sac_rows* rows, int64_t B, float* work, int64_t work_floats, float* grad, float* stats,
+                       const mcg_td3_actor_grad_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

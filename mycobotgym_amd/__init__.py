@@ -13,6 +13,8 @@ from .policy import ActorCritic  # noqa: F401
 from .policy_update import PPOUpdate  # noqa: F401
 from .sac_policy import SACPolicy  # noqa: F401
 from .sac_update import SACUpdate  # noqa: F401
+from .td3_policy import DDPGPolicy, TD3Policy  # noqa: F401
+from .td3_update import DDPGUpdate, TD3Update  # noqa: F401
 from .registry import REGISTRY, spec  # noqa: F401
 from .replay import HerBuffer, HerSamples  # noqa: F401
 from .replay_img import ImageReplayBuffer, ReplaySamples  # noqa: F401

@@ -333,6 +333,30 @@ class McgSacActorGradOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("action", "noise", "q_pi", "dq_da")]
 
 
+TD3_CRITIC, TD3_CRITIC_TARGET = 0, 1
+
+
+class McgTd3(C.Structure):
+    """TD3's / DDPG's four blobs and shape (include/mcg.h: mcg_td3); the caller owns the blobs."""
+    _fields_ = [("actor", C.c_void_p), ("actor_target", C.c_void_p), ("critic", C.c_void_p), ("critic_target", C.c_void_p),
+                ("n_envs", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_pi", C.c_int32), ("pi_width", C.c_int32 * 3),
+                ("n_qf", C.c_int32), ("qf_width", C.c_int32 * 3), ("activation", C.c_int32), ("n_critics", C.c_int32),
+                ("actor_floats", C.c_int64), ("critic_floats", C.c_int64)]
+
+
+class McgTd3ActOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("action", "mean", "noise")]
+
+
+class McgTd3TargetOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("target", "next_action", "next_q", "noise")]
+
+
+class McgTd3ActorGradOut(C.Structure):
+    """The optional intermediates of the actor loss (include/mcg.h: mcg_td3_actor_grad_out)."""
+    _fields_ = [(n, C.c_void_p) for n in ("action", "q_pi", "dq_da")]
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -348,7 +372,9 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_policy_blob_floats", "mcg_policy_forward",
            "mcg_policy_evaluate", "mcg_policy_grad_work_floats", "mcg_policy_grad", "mcg_policy_adam",
            "mcg_sac_blob_floats", "mcg_sac_act", "mcg_sac_q", "mcg_sac_target", "mcg_sac_polyak",
-           "mcg_sac_grad_work_floats", "mcg_sac_critic_grad", "mcg_sac_actor_grad", "mcg_sac_alpha_step", "mcg_sac_adam")
+           "mcg_sac_grad_work_floats", "mcg_sac_critic_grad", "mcg_sac_actor_grad", "mcg_sac_alpha_step", "mcg_sac_adam",
+           "mcg_td3_blob_floats", "mcg_td3_act", "mcg_td3_q", "mcg_td3_target", "mcg_td3_polyak",
+           "mcg_td3_grad_work_floats", "mcg_td3_critic_grad", "mcg_td3_actor_grad")
 
 _lib = None
 
@@ -469,6 +495,22 @@ def load():
         L.mcg_sac_alpha_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, d, d, d, d,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcg_sac_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, d, d, d, d, C.c_void_p]
+    if hasattr(L, "mcg_td3_actor_grad"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        td3 = C.POINTER(McgTd3)
+        L.mcg_td3_blob_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mcg_td3_blob_floats.restype = C.c_int64
+        L.mcg_td3_act.argtypes = [td3, C.POINTER(McgStepOut), C.c_uint64, C.c_uint64, C.c_int64, C.c_float, C.POINTER(McgTd3ActOut), C.c_void_p]
+        L.mcg_td3_q.argtypes = [td3, C.c_int, C.POINTER(McgSacRows), C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcg_td3_target.argtypes = [td3, C.POINTER(McgHerBatch), C.c_int64, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_float,
+                                     C.POINTER(McgTd3TargetOut), C.c_void_p]
+        L.mcg_td3_polyak.argtypes = [td3, d, C.c_void_p]
+        L.mcg_td3_grad_work_floats.argtypes = [td3, C.c_int64]
+        L.mcg_td3_grad_work_floats.restype = C.c_int64
+        L.mcg_td3_critic_grad.argtypes = [td3, C.POINTER(McgSacRows), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        L.mcg_td3_actor_grad.argtypes = [td3, C.POINTER(McgSacRows), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.POINTER(McgTd3ActorGradOut), C.c_void_p]
     _lib = L
     return L
 

@@ -20,7 +20,7 @@ The three blobs and ``log_ent_coef`` are updated in place, so the next ``pol(obs
 the gradients, Adam's moments (float32 device tensors in the blobs' layouts), the scratch, the step count and the call number of the
 actor-loss noise (Philox domain 9); the C side (``mcg_sac_critic_grad``, ``mcg_sac_actor_grad``, ``mcg_sac_alpha_step``,
 ``mcg_sac_adam``; csrc/mcg_sac_grad.hip) keeps no state.  Deterministic: equal inputs give equal bits.  No CPU or PyTorch fallback.
-Not built: gSDE, ``n_critics != 2``, CNN critics for the -v1 picture ids, learning-rate schedules, TD3 / DDPG.
+Not built: gSDE, ``n_critics != 2``, CNN critics for the -v1 picture ids, learning-rate schedules.  TD3 and DDPG are ``TD3Update`` / ``DDPGUpdate`` (td3_update.py).
 """
 from __future__ import annotations
 
