@@ -29,9 +29,18 @@
 // term's exact -ent_coef to log_std, and sums the tiles' loss terms in a fixed tree into `stats`.  adv_stats_kernel (one workgroup,
 // double accumulators, a fixed tree) writes the advantage's mean and std + 1e-8 first where they are used.
 //
-// ---- `work` (floats):  [0] advantage mean, [1] std + 1e-8, [2..3] unused;  [4 + 8 tile + s] the tile's sums: s = 1 policy term, 2
-// squared value error, 4 kl term, 5 clipped count;  then per net and tile `rows` rows of 16 floats (the row map: struct Rows);  then
-// `parts` partial blobs.  Every float that is read was written by the same call.
+// ---- `work` (floats):  [0] advantage mean, [1] std + 1e-8, [2..3] unused, [4..5] and [6..7] the same two as doubles;
+// [8 + 8 tile + s] the tile's sums: s = 2 squared value error, 4 kl term, 5 clipped count, 6..7 the policy term as one double;  then
+// per net and tile `rows` rows of 16 floats (the row map: struct Rows);  then `parts` partial blobs.  Every float that is read was
+// written by the same call.
+//
+// ---- A2C's policy term in double.  Its summands adv * log_prob have the log-prob's magnitude (about -1.4 A: 13 on average at
+// A = 13) and, the advantages being centred, a mean of a few tenths; `loss` then subtracts again.  The float32 mean of the advantages
+// is off by up to 2^-25 of itself, which the normalisation turns into that much times mean(log_prob) / std in the term's mean, and
+// the rounding of each normalised advantage enters times its log-prob.  So the statistic's term takes the advantage's mean and std,
+// the normalised advantage, the log-prob (at hand in double already) and the sums over the tile and the tiles in double, and is
+// rounded once.  PPO's term min(adv ratio, adv clip(ratio)) stays the float32 expression and goes through the same sums.  The
+// gradient goes through neither: d loss / d log_prob keeps the float32 normalised advantage.
 //
 // ---- A ragged last tile: its extra lanes read the last valid sample, as in the forward, and their dZ is set to +-0 at the head, so
 // that every product they enter adds exactly nothing.
@@ -42,6 +51,7 @@ using namespace mcg;
 namespace {
 
 constexpr int MAX_BLOCK_LAYERS = 2 * (MAX_LAYERS + 1) + 1;
+constexpr int SUMS = 8;                                                 // the tiles' sums start here in `work`
 constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
 constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
 
@@ -52,9 +62,15 @@ struct Rows {                            // a net's rows of a tile in `work`, in
   long long base;                        // the net's first float in `work`
 };
 struct Batch { const float *obs, *ach, *des, *action, *old_lp, *adv, *ret; };
-struct Hyper { int kind, norm; float clip, ent_coef, vf_coef, inv_b; };
+struct Hyper { int kind, norm; float clip, ent_coef, vf_coef, inv_b; double inv_bd; };      // inv_bd: 1 / B for the sums held in double
 struct EvalOut { float *value, *log_prob, *entropy; };
 struct Blocks { Block l[MAX_BLOCK_LAYERS]; int n, total; };
+
+// sum16 (mcg_grad.hpp) in double
+MCG_DEV double sum16d(double x) {
+  x += __shfl_xor(x, 8); x += __shfl_xor(x, 4); x += __shfl_xor(x, 2); x += __shfl_xor(x, 1);
+  return x;
+}
 
 MCG_DEV Rows pick_rows(const Rows& x, const Rows& y, int k) {
   Rows z;
@@ -116,7 +132,7 @@ __global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1
     const bool mine = live && g == 0;
     if (mine) dh[0] = (2.0f * H.vf_coef * H.inv_b) * diff;
     const float sq = sum16(mine ? diff * diff : 0.0f);
-    if (lane == 0) work[4 + 8 * (size_t)tile + 2] = sq;
+    if (lane == 0) work[SUMS + 8 * (size_t)tile + 2] = sq;
   } else {
     const f4 ls = *reinterpret_cast<const f4*>(P.blob + P.log_std + 4 * g);
     // The log-prob from the float32 mean in double, rounded once: log_prob - old_log_prob and (ratio - 1) - ln ratio cancel most of
@@ -149,26 +165,36 @@ __global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1
       return;
     }
     float adv = X.adv[row];
-    if (H.norm) adv = (adv - work[0]) / work[1];
-    float term, dlp, kl = 0.0f, clipped = 0.0f;                // the sample's policy term (its loss is -term), d loss / d log_prob
+    double advd = (double)adv;                                  // (the statistic's: see the head)
+    if (H.norm) {
+      const double* __restrict__ nd = reinterpret_cast<const double*>(work + 4);
+      advd = (advd - nd[0]) / nd[1];
+      adv = (adv - work[0]) / work[1];
+    }
+    float dlp, kl = 0.0f, clipped = 0.0f;                      // d loss / d log_prob
+    double term;                                                // the sample's policy term (its loss is -term)
     if (H.kind == MCG_LOSS_PPO) {
       const double lrd = lpd - (double)X.old_lp[row];
       const float lr = (float)lrd, ratio = expf(lr);
       const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, 1.0f - H.clip), 1.0f + H.clip);
-      term = fminf(s1, s2);
+      term = (double)fminf(s1, s2);
       dlp = s1 <= s2 ? -(adv * ratio) * H.inv_b : 0.0f;         // the clipped branch is a constant
       kl = (float)(expm1(lrd) - lrd);
       clipped = fabsf(ratio - 1.0f) > H.clip ? 1.0f : 0.0f;
     } else {
-      term = adv * lp;
+      term = advd * lpd;
       dlp = -adv * H.inv_b;
     }
-    if (!live) { term = 0.0f; dlp = 0.0f; kl = 0.0f; clipped = 0.0f; }
+    if (!live) { term = 0.0; dlp = 0.0f; kl = 0.0f; clipped = 0.0f; }
     f4 dl;
 #pragma unroll
     for (int r = 0; r < 4; r++) { dh[r] = dlp * dmu[r]; dl[r] = dlp * dls[r]; }
-    const float st = sum16(term), sk = sum16(kl), sc = sum16(clipped);
-    if (lane == 0) { work[4 + 8 * (size_t)tile + 1] = st; work[4 + 8 * (size_t)tile + 4] = sk; work[4 + 8 * (size_t)tile + 5] = sc; }
+    const double st = sum16d(term);
+    const float sk = sum16(kl), sc = sum16(clipped);
+    if (lane == 0) {
+      *reinterpret_cast<double*>(work + SUMS + 8 * (size_t)tile + 6) = st;       // (8-byte aligned: `work` is 16-byte aligned)
+      work[SUMS + 8 * (size_t)tile + 4] = sk; work[SUMS + 8 * (size_t)tile + 5] = sc;
+    }
 #pragma unroll
     for (int r = 0; r < 4; r++) chunk[(size_t)(R.ls + 4 * g + r) * TILE + i] = dl[r];
   }
@@ -235,25 +261,30 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
     return;
   }
   if (threadIdx.x >= WAVE) return;
-  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  constexpr int slot[4] = {1, 2, 4, 5};
-  for (int t = threadIdx.x; t < ntiles; t += WAVE)
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  double term = 0.0;
+  constexpr int slot[3] = {2, 4, 5};
+  for (int t = threadIdx.x; t < ntiles; t += WAVE) {
 #pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] += work[4 + 8 * (size_t)t + slot[j]];
+    for (int j = 0; j < 3; j++) acc[j] += work[SUMS + 8 * (size_t)t + slot[j]];
+    term += *reinterpret_cast<const double*>(work + SUMS + 8 * (size_t)t + 6);
+  }
 #pragma unroll
-  for (int j = 0; j < 4; j++)
+  for (int j = 0; j < 3; j++)
     for (int m = 32; m >= 1; m >>= 1) acc[j] += __shfl_xor(acc[j], m);
+  for (int m = 32; m >= 1; m >>= 1) term += __shfl_xor(term, m);
   if (threadIdx.x == 0) {
     float ent = 0.0f;
     for (int c = 0; c < A; c++) ent += ENTROPY_0 + blob[log_std + c];
-    const float policy_loss = -acc[0] * H.inv_b, value_loss = acc[1] * H.inv_b, entropy_loss = -ent;
-    stats[0] = policy_loss + H.ent_coef * entropy_loss + H.vf_coef * value_loss;
-    stats[1] = policy_loss; stats[2] = value_loss; stats[3] = entropy_loss;
-    stats[4] = acc[2] * H.inv_b; stats[5] = acc[3] * H.inv_b; stats[6] = 0.0f; stats[7] = 0.0f;
+    const double policy_loss = -term * H.inv_bd;
+    const float value_loss = acc[0] * H.inv_b, entropy_loss = -ent;
+    stats[0] = (float)(policy_loss + (double)H.ent_coef * (double)entropy_loss + (double)H.vf_coef * (double)value_loss);
+    stats[1] = (float)policy_loss; stats[2] = value_loss; stats[3] = entropy_loss;
+    stats[4] = acc[1] * H.inv_b; stats[5] = acc[2] * H.inv_b; stats[6] = 0.0f; stats[7] = 0.0f;
   }
 }
 
-// out[0] = mean, out[1] = std + 1e-8 (the unbiased deviation, as torch.std) of adv[0..B)
+// out[0] = mean, out[1] = std + 1e-8 (the unbiased deviation, as torch.std) of adv[0..B); out[4..5] and out[6..7]: the two as doubles
 __global__ __launch_bounds__(1024) void adv_stats_kernel(const float* __restrict__ adv, long long B, float* __restrict__ out) {
   __shared__ double lds[1024];
   double s = 0.0;
@@ -262,7 +293,11 @@ __global__ __launch_bounds__(1024) void adv_stats_kernel(const float* __restrict
   double q = 0.0;
   for (long long j = threadIdx.x; j < B; j += 1024) { const double c = (double)adv[j] - mean; q += c * c; }
   const double var = block_sum(q, lds) / (double)(B - 1);
-  if (threadIdx.x == 0) { out[0] = (float)mean; out[1] = (float)sqrt(var) + 1e-8f; }
+  if (threadIdx.x == 0) {
+    out[0] = (float)mean; out[1] = (float)sqrt(var) + 1e-8f;
+    double* outd = reinterpret_cast<double*>(out + 4);
+    outd[0] = mean; outd[1] = sqrt(var) + 1e-8;
+  }
 }
 
 __global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict__ grad, long long n, float* __restrict__ norm_out) {
@@ -291,7 +326,7 @@ Layout layout(const Pol& P, int64_t B, int widest) {
   Y.ntiles = (int)((B + TILE - 1) / TILE);
   split_parts(Y.ntiles, widest, &Y.tpp, &Y.parts);
   const int fr = (P.D + 6 + 15) / 16 * 16;
-  long long at = 4 + 8ll * Y.ntiles;
+  long long at = SUMS + 8ll * Y.ntiles;
   for (int k = 0; k < 2; k++) {
     const Net& net = P.net[k];
     Rows& R = Y.rows[k];
@@ -395,7 +430,7 @@ int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64
   const hipStream_t st = (hipStream_t)stream;
   const Batch X = {batch->obs, batch->achieved, batch->desired, batch->action, batch->old_log_prob, batch->advantage, batch->returns};
   const Hyper H = {hyper->loss_kind, hyper->normalize_advantage != 0 && B > 1, hyper->clip_range, hyper->ent_coef, hyper->vf_coef,
-                   (float)(1.0 / (double)B)};
+                   (float)(1.0 / (double)B), 1.0 / (double)B};
   if (H.norm) hipLaunchKernelGGL(adv_stats_kernel, dim3(1), dim3(1024), 0, st, batch->advantage, (long long)B, work);
   const dim3 grid(Y.ntiles, 2), block(WAVE);
   if (widest <= 64) hipLaunchKernelGGL((grad_tile_kernel<4, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});

@@ -194,5 +194,8 @@ def random_obs(n: int, obs_dim: int, seed: int) -> dict:
 
 # The trunks the tests use: (pi widths, vf widths, activation)
 TRUNKS = {"64x64-tanh": ((64, 64), (64, 64), "tanh"), "48x32-relu-vf16": ((48, 32), (16,), "relu"), "16-tanh": ((16,), (16,), "tanh"),
-          "256x256-relu": ((256, 256), (256, 256), "relu")}
+          "256x256-relu": ((256, 256), (256, 256), "relu"),
+          # the shape edges of tests/policy_shape_cases.py
+          "32x48x16-tanh-16x48x32": ((32, 48, 16), (16, 48, 32), "tanh"), "80x16x112-relu-96x240x16": ((80, 16, 112), (96, 240, 16), "relu"),
+          "32-relu-80": ((32,), (80,), "relu"), "144x16-tanh-48": ((144, 16), (48,), "tanh"), "64x64x64-relu": ((64, 64, 64), (64, 64, 64), "relu")}
 DIMS = ((10, 7), (25, 4), (25, 8))

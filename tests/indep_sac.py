@@ -314,6 +314,9 @@ def replay_batch(sd: dict, activation: str, B: int, obs_dim: int, act_dim: int, 
 
 # The trunks the tests use: (actor widths, critic widths, activation)
 TRUNKS = {"16-relu": ((16,), (16,), "relu"), "48x32-relu-qf16": ((48, 32), (16,), "relu"), "64x64-tanh": ((64, 64), (64, 64), "tanh"),
-          "256x256-relu": ((256, 256), (256, 256), "relu")}
+          "256x256-relu": ((256, 256), (256, 256), "relu"),
+          # the shape edges of tests/policy_shape_cases.py
+          "32x48x16-tanh-16x48x32": ((32, 48, 16), (16, 48, 32), "tanh"), "80x16x112-relu-96x240x16": ((80, 16, 112), (96, 240, 16), "relu"),
+          "32-relu-80": ((32,), (80,), "relu"), "144x16-tanh-48": ((144, 16), (48,), "tanh"), "64x64x64-relu": ((64, 64, 64), (64, 64, 64), "relu")}
 DIMS = ((10, 7), (25, 4), (25, 8))
 CASES = [(D, A, name) for (D, A) in DIMS for name in ("16-relu", "48x32-relu-qf16", "64x64-tanh")] + [(25, 4, "256x256-relu")]

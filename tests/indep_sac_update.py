@@ -226,7 +226,10 @@ def make_batch(twin64, D: int, A: int, B: int, seed: int, noise_seed: int, calls
 
 # The trunks and sizes the GPU tests use: (D, A, trunk name of TRUNKS, B)
 TRUNKS = {"64x64-relu": ((64, 64), (64, 64), "relu"), "48x32-tanh-qf16": ((48, 32), (16,), "tanh"), "16-tanh": ((16,), (16,), "tanh"),
-          "256x256-relu": ((256, 256), (256, 256), "relu")}
+          "256x256-relu": ((256, 256), (256, 256), "relu"),
+          # the shape edges of tests/policy_shape_cases.py
+          "32x48x16-tanh-16x48x32": ((32, 48, 16), (16, 48, 32), "tanh"), "80x16x112-relu-96x240x16": ((80, 16, 112), (96, 240, 16), "relu"),
+          "32-relu-80": ((32,), (80,), "relu"), "144x16-tanh-48": ((144, 16), (48,), "tanh"), "64x64x64-relu": ((64, 64, 64), (64, 64, 64), "relu")}
 SHAPES = [(D, A, name) for (D, A) in isac.DIMS for name in ("64x64-relu", "48x32-tanh-qf16", "16-tanh")] + [(25, 4, "256x256-relu")]
 GRAD_CASES = [(D, A, t, 75) for D, A, t in SHAPES] + [(D, A, t, B) for (D, A, t) in ((10, 7, "64x64-relu"), (25, 8, "48x32-tanh-qf16"),
                                                                                       (25, 4, "256x256-relu")) for B in (600, 1)]

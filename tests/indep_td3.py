@@ -312,7 +312,10 @@ def make_batch(twin64, D: int, A: int, B: int, seed: int, noise_seed: int, call:
 
 # The trunks and sizes the tests use: (D, A, trunk name of TRUNKS, B, n_critics)
 TRUNKS = {"64x64-relu": ((64, 64), (64, 64), "relu"), "48x32-tanh-qf16": ((48, 32), (16,), "tanh"), "16-tanh": ((16,), (16,), "tanh"),
-          "256x256-relu": ((256, 256), (256, 256), "relu")}
+          "256x256-relu": ((256, 256), (256, 256), "relu"),
+          # the shape edges of tests/policy_shape_cases.py
+          "32x48x16-tanh-16x48x32": ((32, 48, 16), (16, 48, 32), "tanh"), "80x16x112-relu-96x240x16": ((80, 16, 112), (96, 240, 16), "relu"),
+          "32-relu-80": ((32,), (80,), "relu"), "144x16-tanh-48": ((144, 16), (48,), "tanh"), "64x64x64-relu": ((64, 64, 64), (64, 64, 64), "relu")}
 SHAPES = [(D, A, name) for (D, A) in DIMS for name in ("64x64-relu", "48x32-tanh-qf16", "16-tanh")] + [(25, 4, "256x256-relu")]
 CASES = ([(D, A, t, 75, 2) for D, A, t in SHAPES]
          + [(10, 7, "64x64-relu", 75, 1), (25, 8, "48x32-tanh-qf16", 75, 1), (25, 4, "16-tanh", 75, 1), (25, 4, "256x256-relu", 75, 1)]

@@ -98,10 +98,13 @@ def host(sd: dict) -> dict:
 # ------------------------------------------------------------------------------------------------- 1. evaluate_actions
 @pytest.mark.parametrize("D,A,trunk", SHAPES)
 def test_evaluate_actions_parity(built, D, A, trunk):
+    check_evaluate_actions_parity(D, A, trunk)
+
+
+def check_evaluate_actions_parity(D, A, trunk, B=75):
     """B = 75 under the yardstick (the twin's error is the maximum over the batch's rows, as test_gpu_policy.py takes it: one row's
     error alone can be anything down to 0).  B = 1 and B = 17 are the first rows of the same batch and give the same bits: a row
     depends on itself alone."""
-    B = 75
     pol, twin32 = policy_for(D, A, trunk)
     _, twin64 = twins(D, A, trunk)
     batch = batch_for(D, A, trunk, B)
@@ -118,7 +121,7 @@ def test_evaluate_actions_parity(built, D, A, trunk):
     only = {"entropy": torch.empty(B, device="cuda")}
     pol.evaluate_actions(mb.observations, mb.actions, out=only)
     assert np.array_equal(bits(only["entropy"].cpu().numpy()), bits(entropy))
-    for rows in (1, 17):
+    for rows in (r for r in (1, 17) if r <= B):
         part = pol.evaluate_actions({k: v[:rows] for k, v in mb.observations.items()}, mb.actions[:rows])
         for x, whole in zip(part, (value, log_prob, entropy)):
             assert tuple(x.shape) == (rows,) and np.array_equal(bits(x.cpu().numpy()), bits(whole[:rows]))
@@ -147,6 +150,10 @@ def test_evaluate_agrees_with_the_forwards_log_prob(built, D, A, trunk):
 # ------------------------------------------------------------------------------------------------------- 2. gradient
 @pytest.mark.parametrize("D,A,trunk,B,variant", GRAD_CASES)
 def test_gradient_parity(built, D, A, trunk, B, variant):
+    check_gradient_parity(D, A, trunk, B, variant)
+
+
+def check_gradient_parity(D, A, trunk, B, variant):
     g64, s64, g32, s32 = reference(D, A, trunk, B, variant)
     pol, opt = updater(D, A, trunk, variant)
     got = host(opt.grad(samples(batch_for(D, A, trunk, B))))
@@ -157,6 +164,7 @@ def test_gradient_parity(built, D, A, trunk, B, variant):
     assert_yardstick({k: stats[j] for j, k in enumerate(pp.STATS)}, s32, s64, "stats " + what)
     assert round(float(stats[5]) * B) == round(s64["clip_fraction"] * B)          # the same samples are clipped
     assert stats[6] == 0.0 and stats[7] == 0.0
+    return pol, opt
 
 
 # ------------------------------------------------------------------------------------------------ 3. clipped samples
@@ -213,6 +221,10 @@ def test_layout_and_padding(built, D, A, trunk):
 # ----------------------------------------------------------------------------------------------------- 5. determinism
 @pytest.mark.parametrize("D,A,trunk,B", [(10, 7, "64x64-tanh", 75), (25, 4, "256x256-relu", 75), (25, 8, "48x32-relu-vf16", 600)])
 def test_determinism_and_ragged_filler(built, D, A, trunk, B):
+    check_determinism_and_ragged_filler(D, A, trunk, B)
+
+
+def check_determinism_and_ragged_filler(D, A, trunk, B):
     batch = batch_for(D, A, trunk, B)
     runs = []
     for fill in (0.0, 0.0, float("nan")):
@@ -257,12 +269,16 @@ def test_adam_step_on_the_kernels_gradient(built, D, A, trunk, max_norm):
 
 @pytest.mark.parametrize("D,A,trunk", [(10, 7, "64x64-tanh"), (25, 4, "256x256-relu")])
 def test_five_steps_against_the_twin(built, D, A, trunk):
+    check_five_steps_against_the_twin(D, A, trunk)
+
+
+def check_five_steps_against_the_twin(D, A, trunk, B=75):
     twin32, twin64 = twins(D, A, trunk)
     pol, opt = updater(D, A, trunk, "ppo-norm-ent")
     opt32 = torch.optim.Adam(twin32.parameters(), lr=3e-4, betas=(0.9, 0.999), eps=1e-5)
     state64 = {}
     for s in range(5):
-        batch = batch_for(D, A, trunk, 75, seed=5 + s)
+        batch = batch_for(D, A, trunk, B, seed=5 + s)
         opt.step(samples(batch))
         pp.twin_update(twin64, state64, batch, s + 1, **VARIANTS["ppo-norm-ent"])
         opt32.zero_grad()
@@ -270,7 +286,8 @@ def test_five_steps_against_the_twin(built, D, A, trunk):
         torch.nn.utils.clip_grad_norm_(twin32.parameters(), 0.5)
         opt32.step()
     assert opt.steps == 5
-    assert_yardstick(host(pol.state_dict()), twin32.numpy_state(), {k: v for k, v in twin64.numpy_state().items()}, f"five steps {trunk}")
+    assert_yardstick(host(pol.state_dict()), twin32.numpy_state(), {k: v for k, v in twin64.numpy_state().items()},
+                     f"five steps {trunk}" + ("" if (D, A, B) in ((10, 7, 75), (25, 4, 75)) else f" D={D} A={A} B={B}"))
     # the forward sees the new weights at once: equal to a fresh policy loaded with them
     from mycobotgym_amd import ActorCritic
     pi, vf, act = ip.TRUNKS[trunk]
@@ -279,6 +296,7 @@ def test_five_steps_against_the_twin(built, D, A, trunk):
     obs = dev(ip.random_obs(40, D, seed=5))
     for x, y in zip(pol(obs, deterministic=True), fresh(obs, deterministic=True)):
         assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+    return pol, opt
 
 
 # --------------------------------------------------------------------------------------------------- 7. stray writes

@@ -165,14 +165,20 @@ def scales(ref: dict, names) -> dict:
 # ---------------------------------------------------------------------------------------------------------- 1. parity
 @pytest.mark.parametrize("D,A,trunk", isac.CASES)
 def test_parity_with_the_float64_rule(built, D, A, trunk):
-    """Every output of the collection call, of q_values on both blobs and of td_target with all its intermediates."""
-    pol, ref = policy_for(D, A, trunk), reference(D, A, trunk)
-    what = f"D={D} A={A} {trunk}"
+    check_parity_with_the_float64_rule(D, A, trunk)
+
+
+def check_parity_with_the_float64_rule(D, A, trunk, B=B, both_bounds=True):
+    """Every output of the collection call, of q_values on both blobs and of td_target with all its intermediates.  ``both_bounds``:
+    whether the case's float64 reference has rows at both clamp bounds of log_std (every case of this file has)."""
+    pol, ref = policy_for(D, A, trunk), reference(D, A, trunk, rows=B)
+    what = f"D={D} A={A} {trunk}" + ("" if B == 75 else f" B={B}")
     got = run_act(pol, ref["obs"])
     assert all(np.isfinite(v).all() for v in got.values())
     assert_parity(act_errors(got, ref), ref["twin_err"]["act"], scales(ref, ("mean", "log_std", "action", "log_prob")), what + " act")
     # both clamp bounds act, and where they do the kernel's log_std is the bound itself
-    assert (got["log_std"] == 2.0).any() and (got["log_std"] == -20.0).any()
+    if both_bounds:
+        assert (got["log_std"] == 2.0).any() and (got["log_std"] == -20.0).any()
     assert np.array_equal(got["log_std"] == 2.0, ref["log_std"] == 2.0) and np.array_equal(got["log_std"] == -20.0, ref["log_std"] == -20.0)
     b = ref["batch"]
     for target, name in ((False, "q_critic"), (True, "q_critic_target")):
@@ -188,14 +194,18 @@ def test_parity_with_the_float64_rule(built, D, A, trunk):
 # ----------------------------------------------------------------------------------------------------------- 2. noise
 @pytest.mark.parametrize("D,A,trunk", [(10, 7, "64x64-tanh"), (25, 8, "48x32-relu-qf16"), (25, 4, "256x256-relu")])
 def test_noise_squashing_and_deterministic(built, D, A, trunk):
-    pol, ref = policy_for(D, A, trunk), reference(D, A, trunk)
+    check_noise_squashing_and_deterministic(D, A, trunk)
+
+
+def check_noise_squashing_and_deterministic(D, A, trunk, B=B):
+    pol, ref = policy_for(D, A, trunk), reference(D, A, trunk, rows=B)
     got = run_act(pol, ref["obs"])
     assert pol.calls == 1 and pol.target_calls == 0
     assert np.array_equal(bits(got["noise"]), bits(ref["eps"]))                  # domain 7, bit for bit
     tgt = run_target(pol, ref["batch"])
     assert pol.calls == 1 and pol.target_calls == 1
     assert np.array_equal(bits(tgt["noise"]), bits(ref["eps8"]))                 # domain 8, bit for bit
-    assert not np.array_equal(bits(tgt["noise"][:N]), bits(got["noise"]))
+    assert not np.array_equal(bits(tgt["noise"][:N]), bits(got["noise"][:B]))
     # the action is tanh of the pre-squash value formed from the kernel's own mean, log_std and noise, within 1 ulp; |action| <= 1
     want = np.tanh(own_u(got["mean"], got["log_std"], got["noise"]))
     assert (np.abs(got["action"].astype(np.float64) - want) <= ulps32(want)).all()
@@ -218,7 +228,11 @@ def test_noise_squashing_and_deterministic(built, D, A, trunk):
 # ------------------------------------------------------------------------------------------------- 3. consistency
 @pytest.mark.parametrize("D,A,trunk", [(25, 8, "64x64-tanh"), (10, 7, "48x32-relu-qf16"), (25, 4, "256x256-relu")])
 def test_td_target_is_consistent_with_its_parts(built, D, A, trunk):
-    pol, ref = policy_for(D, A, trunk), reference(D, A, trunk)
+    check_td_target_is_consistent_with_its_parts(D, A, trunk)
+
+
+def check_td_target_is_consistent_with_its_parts(D, A, trunk, B=B):
+    pol, ref = policy_for(D, A, trunk), reference(D, A, trunk, rows=B)
     b = ref["batch"]
     got = run_target(pol, b)
     # next_q is q_values on the target blob at the action td_target drew, bit for bit (registers there, memory here)

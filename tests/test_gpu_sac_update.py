@@ -82,6 +82,10 @@ def padding_is_plus_zero(opt):
 @pytest.mark.parametrize("D,A,trunk,B,auto", [c + (True,) for c in su.GRAD_CASES] + [(10, 7, "64x64-relu", 75, False),
                                                                                        (25, 8, "48x32-tanh-qf16", 75, False)])
 def test_gradients_stats_and_intermediates(built, D, A, trunk, B, auto):
+    check_gradients_stats_and_intermediates(D, A, trunk, B, auto)
+
+
+def check_gradients_stats_and_intermediates(D, A, trunk, B, auto=True):
     """The three gradients per parameter tensor, the stats and q_pi, dq_da, logp, action under the yardstick, with alpha from the
     device (auto) and from the host.  The batches have rows where each clamp acts (the maker's census).  Bit for bit: the noise, q_pi
     against q_values on the action written, +0.0 at every padding position of both gradients."""
@@ -111,6 +115,10 @@ def test_gradients_stats_and_intermediates(built, D, A, trunk, B, auto):
 # ---------------------------------------------------------------------------------------------------- 2. determinism
 @pytest.mark.parametrize("D,A,trunk,B", [(10, 7, "64x64-relu", 75), (25, 4, "256x256-relu", 75), (25, 8, "48x32-tanh-qf16", 600)])
 def test_equal_inputs_give_equal_bits(built, D, A, trunk, B):
+    check_equal_inputs_give_equal_bits(D, A, trunk, B)
+
+
+def check_equal_inputs_give_equal_bits(D, A, trunk, B):
     """Across two calls, and with NaN garbage in `work` and in the rows behind the batch (the tensors are views of the first B rows
     of storage of 16 more rows, which a ragged tile's extra lanes must not read into the result)."""
     _, t64, batch, *_ = reference(D, A, trunk, B)
@@ -217,6 +225,10 @@ def run_twin(twin, batch, A, steps, **kw):
 @pytest.mark.parametrize("D,A,trunk,B", [(10, 7, "64x64-relu", 75), (25, 8, "48x32-tanh-qf16", 75), (25, 4, "256x256-relu", 75),
                                          (25, 4, "16-tanh", 600)])
 def test_five_steps_against_the_twin_in_sb3s_order(built, D, A, trunk, B):
+    check_five_steps_against_the_twin_in_sb3s_order(D, A, trunk, B)
+
+
+def check_five_steps_against_the_twin_in_sb3s_order(D, A, trunk, B):
     """Each parameter's change over five opt.step calls (the three blobs and log_ent_coef) against the float64 twin stepped in SB3's
     order, under the yardstick with the float32 twin's own five-step error.  A wrong sequence (the actor loss on the old critic, the
     target after the alpha step, alpha's loss on a stale logp) changes the later steps' gradients by parts in a thousand."""
@@ -323,8 +335,11 @@ def test_no_stray_writes(built, B):
 
 # --------------------------------------------------------------------------------------------------------- 8. checkpoint
 def test_checkpoint_continues_bit_for_bit(built):
+    check_checkpoint_continues_bit_for_bit(25, 8, "48x32-tanh-qf16", 75)
+
+
+def check_checkpoint_continues_bit_for_bit(D, A, trunk, B):
     from mycobotgym_amd import SACUpdate
-    D, A, trunk, B = 25, 8, "48x32-tanh-qf16", 75
     _, t64, batch, *_ = reference(D, A, trunk, B)
     db = dev_batch(batch)
     pol, opt = updater(t64, D, A, trunk, target_update_interval=2)

@@ -49,6 +49,18 @@ def padding_is_plus_zero(opt):
     assert torch.equal(again.view(torch.int32), g["actor"].view(torch.int32))
 
 
+def valid_blobs(pol):
+    """pack(unpack(blob)) is the blob, bit for bit, for all four: the padding is +0.0 and nothing else moved."""
+    from mycobotgym_amd import td3_policy as tp
+    D, A, nc = pol.obs_dim, pol.act_dim, pol.n_critics
+    for name in ("critic", "critic_target"):
+        again = tp.pack_critic(tp.unpack_critic(pol._t[name], D, A, pol.qf, name, nc), D, A, pol.qf, name, nc, device="cuda")
+        assert torch.equal(again.view(torch.int32), pol._t[name].view(torch.int32)), name
+    for name in ("actor", "actor_target"):
+        again = tp.pack_actor(tp.unpack_actor(pol._t[name], D, A, pol.pi, name), D, A, pol.pi, name, device="cuda")
+        assert torch.equal(again.view(torch.int32), pol._t[name].view(torch.int32)), name
+
+
 def stats_of(opt) -> dict:
     s = opt.stats.cpu().numpy().astype(np.float64)
     assert not s[5:].any()
@@ -58,6 +70,10 @@ def stats_of(opt) -> dict:
 # ---------------------------------------------------------------------------------------------------------- 1. parity
 @pytest.mark.parametrize("D,A,trunk,B,nc", it.CASES)
 def test_gradients_stats_and_intermediates(built, D, A, trunk, B, nc):
+    check_gradients_stats_and_intermediates(D, A, trunk, B, nc)
+
+
+def check_gradients_stats_and_intermediates(D, A, trunk, B, nc):
     """Both gradients per parameter tensor, the stats and q_pi, dq_da, action, y under the yardstick.  Bit for bit: q_pi against
     q_values' row 0 on the action written, +0.0 at every padding position of both gradients, and, with two critics, the actor
     gradient with qf1's weights perturbed: the actor loss goes through qf0 alone."""
@@ -92,6 +108,10 @@ def test_gradients_stats_and_intermediates(built, D, A, trunk, B, nc):
 # ---------------------------------------------------------------------------------------------------- 2. determinism
 @pytest.mark.parametrize("D,A,trunk,B,nc", [(10, 7, "64x64-relu", 75, 2), (25, 4, "256x256-relu", 75, 1), (25, 8, "48x32-tanh-qf16", 600, 1)])
 def test_equal_inputs_give_equal_bits(built, D, A, trunk, B, nc):
+    check_equal_inputs_give_equal_bits(D, A, trunk, B, nc)
+
+
+def check_equal_inputs_give_equal_bits(D, A, trunk, B, nc):
     """Across two calls, and with NaN garbage in `work`, in the gradient blobs and in the rows behind the batch (the tensors are views
     of the first B rows of storage of 16 more rows, which a ragged tile's extra lanes must not read into the result)."""
     _, t64, batch, *_ = reference(D, A, trunk, B, nc)
@@ -134,6 +154,10 @@ def run_twin(twin, batch, A, steps, sigma, clip, **kw):
                                                   (25, 4, "256x256-relu", 75, 2, 2), (25, 4, "16-tanh", 600, 2, 3),
                                                   (10, 7, "64x64-relu", 75, 1, "ddpg"), (25, 8, "48x32-tanh-qf16", 600, 1, "ddpg")])
 def test_six_steps_against_the_twin_in_sb3s_order(built, D, A, trunk, B, nc, delay):
+    check_six_steps_against_the_twin_in_sb3s_order(D, A, trunk, B, nc, delay)
+
+
+def check_six_steps_against_the_twin_in_sb3s_order(D, A, trunk, B, nc, delay):
     """After every one of six opt.step calls, each parameter's change since the start (all four blobs) against the float64 twin stepped
     in SB3's order, under the yardstick with the float32 twin's own error.  On the steps without an actor update, actor, actor_target
     and critic_target keep their bits.  policy_delay 2 and 3, and DDPG's preset (one critic, no delay, no smoothing).
@@ -180,6 +204,7 @@ def test_six_steps_against_the_twin_in_sb3s_order(built, D, A, trunk, B, nc, del
         if (s + 1) >= delay:
             assert_yardstick(stats_of(opt), s32[s], s64[s], "stats " + what)
     assert state["actor_steps"] == opt.actor_steps == 6 // delay
+    valid_blobs(pol)
     pol.polyak(1.0)
     assert torch.equal(pol._t["actor"].view(torch.int32), pol._t["actor_target"].view(torch.int32))
     assert torch.equal(pol._t["critic"].view(torch.int32), pol._t["critic_target"].view(torch.int32))
@@ -202,8 +227,11 @@ def test_the_actors_adam_counts_actor_updates(built):
 
 # --------------------------------------------------------------------------------------------------------- 4. checkpoint
 def test_checkpoint_continues_bit_for_bit(built):
+    check_checkpoint_continues_bit_for_bit(25, 8, "48x32-tanh-qf16", 75, 2)
+
+
+def check_checkpoint_continues_bit_for_bit(D, A, trunk, B, nc):
     from mycobotgym_amd import TD3Update
-    D, A, trunk, B, nc = 25, 8, "48x32-tanh-qf16", 75, 2
     _, t64, batch, *_ = reference(D, A, trunk, B, nc)
     db = dev_batch(batch)
     pol, opt = updater(t64, D, A, trunk, nc, policy_delay=2)
