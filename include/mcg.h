@@ -1092,6 +1092,17 @@ int mcg_td3_critic_grad(const mcg_td3* td3, const mcg_sac_rows* rows, const floa
 int mcg_td3_actor_grad(const mcg_td3* td3, const mcg_sac_rows* rows, int64_t B, float* work, int64_t work_floats, float* grad, float* stats,
                        const mcg_td3_actor_grad_out* out, void* stream);
 
+/* Device self-test of the step kernels' bad-value check (mj_checkPos / mj_checkVel / mj_checkAcc at the end of a sub-step): no engine
+   handle, nothing a rollout calls.  `in` is [n][MCG_SELFTEST_BAD_VALUE_IN] doubles on the device, one case per row: a[12], r[12],
+   qd_old[12], q_old[12], h.  A lane forms rhs = fma(-h, r, a), qdn = fma(h, rhs, qd_old), qn = fma(h, qdn, q_old) as the Euler step
+   of a sub-step does, writes qdn[12], qn[12] to state [n][24], and evaluates the check twice on those registers: each[c] = the 36
+   single compares !(|x| <= 1e10) ORed, any[c] = the one maximum and one sum the three-wave Reach kernel of the joint controller uses.
+   The two must be equal for every input (tests/test_gpu_reach_bad_value_tail.py holds them to that on values no state of the engine
+   reaches: +-inf, NaN, 1e10 and its neighbours).  MCG_ERR_ARG for a null pointer or n outside [1, 2^20]. */
+#define MCG_SELFTEST_BAD_VALUE_IN 49
+int mcg_selftest_bad_value(const double* in, int n, double* state /* [n][24] device */, uint8_t* each /* [n] device */,
+                           uint8_t* any /* [n] device */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -374,7 +374,7 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_sac_blob_floats", "mcg_sac_act", "mcg_sac_q", "mcg_sac_target", "mcg_sac_polyak",
            "mcg_sac_grad_work_floats", "mcg_sac_critic_grad", "mcg_sac_actor_grad", "mcg_sac_alpha_step", "mcg_sac_adam",
            "mcg_td3_blob_floats", "mcg_td3_act", "mcg_td3_q", "mcg_td3_target", "mcg_td3_polyak",
-           "mcg_td3_grad_work_floats", "mcg_td3_critic_grad", "mcg_td3_actor_grad")
+           "mcg_td3_grad_work_floats", "mcg_td3_critic_grad", "mcg_td3_actor_grad", "mcg_selftest_bad_value")
 
 _lib = None
 
@@ -495,6 +495,8 @@ def load():
         L.mcg_sac_alpha_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, d, d, d, d,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcg_sac_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, d, d, d, d, C.c_void_p]
+    if hasattr(L, "mcg_selftest_bad_value"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_selftest_bad_value.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "mcg_td3_actor_grad"):  # absent only from older builds selected through MCG_LIB for A/B timing
         td3 = C.POINTER(McgTd3)
         L.mcg_td3_blob_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,

@@ -852,6 +852,37 @@ MCG_DEV void factor_m_hb(ModelPtr Pm, const LS MS, real h, real* Mh, real* dinv,
 // mj_checkPos / mj_checkVel / mj_checkAcc [RECALL]: a coordinate that is not finite or beyond 1e10 makes mj_step call mj_resetData
 MCG_DEV bool bad_value(real x) { return !(fabs(x) <= 1e10); }
 
+// bad_value(a[i]) || bad_value(qdn[i]) || bad_value(qn[i]) over i < NB -- the same boolean for every input -- in 35 maxima, 11 sums, two
+// compares and one OR instead of 36 compares and their 35 ORs, for the main wave of SplitMainCols (its lone stretch after S3, round 13):
+//       m = the maximum of |x| over the 36 values,   s = qn[0] + ... + qn[11],   new = !(m <= 1e10) || s != s.
+// The caller guarantees what robot_substep's Euler step does: rhs[i] = fma(-h, r, a[i]), qdn[i] = fma(h, rhs[i], .), qn[i] = fma(h, qdn[i], .),
+// so that a NaN in a[i] or in qdn[i] is a NaN in qn[i] (an fma with a NaN operand is NaN, whatever the other two are).
+//   No NaN among the 36 values.  A maximum of two numbers is the larger one, so m is the largest |x| exactly.
+//     every |x| <= 1e10:  old false.  m <= 1e10; twelve terms of at most 1e10 give no infinite partial sum, s is finite, s == s: new false.
+//     some x finite beyond 1e10, or +-inf (in a, qdn or qn alike):  old true.  m >= |x| > 1e10 (m = inf for +-inf): new true.
+//       (s may be NaN here, where two opposite infinities meet in it, or not: the first compare has decided.)
+//   Some x NaN.  old true.  x = qn[i] is a term of s; x = qdn[i] or a[i] makes qn[i] NaN by the guarantee; a sum with a NaN term is NaN:
+//     new true, whatever m is -- a maximum with a NaN operand may return the other operand, or NaN, and may forget what it held.
+// So the NaN case never rests on m and the other cases never on s.  The values themselves are only read.
+// abs_max: the chain over a[] is the instruction itself.  fmax() on a value that comes from LDS (abar, in a wave without a gear row) makes
+// the compiler quiet a possible signalling NaN first, one more v_max_f64 per value, twelve in all; by the lines above no quieting is needed.
+// (It still quiets abs_max's own result, once, in front of the last fmax: an asm result is a value it knows nothing about.)
+// mcg_selftest_bad_value (mcg_selftest.hip) runs this function beside the 36 compares on +-inf, NaN and 1e10 itself.
+MCG_DEV real abs_max(const real* a) {
+  real m = fabs(a[0]);
+#pragma unroll
+  for (int i = 1; i < NB; i++) asm("v_max_f64 %0, %1, |%2|" : "=v"(m) : "v"(m), "v"(a[i]));
+  return m;
+}
+MCG_DEV bool bad_value_any(const real* a, const real* qdn, const real* qn) {
+  real mv = fabs(qdn[0]), mq = fabs(qn[0]), s0 = qn[0], s1 = qn[1];          // chains of their own: no instruction waits for the one before it
+  static_for<NB - 1>([&](auto I) { constexpr int i = I + 1;
+    mv = fmax(mv, fabs(qdn[i])); mq = fmax(mq, fabs(qn[i]));
+    if constexpr (i >= 2) { if constexpr (i % 2 == 0) s0 += qn[i]; else s1 += qn[i]; } });
+  const real m = fmax(fmax(abs_max(a), mv), mq), s = s0 + s1;
+  return !(m <= 1e10) || s != s;
+}
+
 // Returns true in the lanes whose new state failed MuJoCo's checks and was reset (COMMIT only; the speculative caller checks *next).
 template <class LS, class CPL = NoCoupling, class WLD = NoWeld, class SPL = NoSplit, bool COMMIT = true>
 MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL* CP = nullptr, const WLD* WD = nullptr,
@@ -1352,7 +1383,8 @@ MCG_DEV bool robot_substep(ModelPtr Pm, Robot& S, real* qlag6, const LS MS, CPL*
     else if constexpr (SPL::reach) { q_old = MS.ld(SPL::QB + i); qd_old = MS.ld(SPL::QDB + i); if constexpr (i < 6) MS.st(SPL::QLAG + i, q_old); }
     else { q_old = S.q[i]; qd_old = S.qd[i]; }
     qdn[i] = fma(h, rhs[i], qd_old); qn[i] = fma(h, qdn[i], q_old);
-    if constexpr (COMMIT) bad = bad || bad_value(qn[i]) || bad_value(qdn[i]) || bad_value(a[i]); });
+    if constexpr (COMMIT && !SPL::cols) bad = bad || bad_value(qn[i]) || bad_value(qdn[i]) || bad_value(a[i]); });
+  if constexpr (COMMIT && SPL::cols) bad = bad_value_any(a, qdn, qn);       // the same predicate in fewer instructions (see there)
   // mj_step checks qpos / qvel when it starts and qacc after mj_forward, and calls mj_resetData (qpos0, zero velocity, controls and
   // warm start) on a bad value [RECALL]: the new state is checked here, at the end of the sub-step that produced it -- the same
   // state the next mj_step would check first.  (Round 2 checked once per env-step.)
