@@ -93,25 +93,34 @@ MCG_DEV Net pick(const Net& x, const Net& y, int k) {
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
-// The blob's plan for a shape -> its size in floats; 0 and `why` (a message that names the field) for a refused shape.
-inline int64_t plan(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_vf, const int32_t* vf_width, Pol* P, const char** why) {
-  if (obs_dim < 1 || act_dim < 1) { *why = "obs_dim and act_dim must be >= 1"; return 0; }
-  if (obs_dim > MAX_OBS) { *why = "obs_dim must be <= 4096"; return 0; }
-  if (act_dim > MAX_ACT) { *why = "act_dim must be <= 16"; return 0; }
-  if (n_pi < 1 || n_pi > MAX_LAYERS) { *why = "n_pi must be in [1, 3]"; return 0; }
-  if (n_vf < 1 || n_vf > MAX_LAYERS) { *why = "n_vf must be in [1, 3]"; return 0; }
-  if (!pi_width || !vf_width) { *why = "null pi_width or vf_width"; return 0; }
+// The dimensions and widths every plan accepts (this one, and mcg_sac.hpp's for the off-policy learners) -> true; false and `why`, a
+// message that names the field.  `x`: the second net's prefix ("vf", "qf"); x_first: its widths are looked at before pi's.
+inline bool checked_shape(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_x, const int32_t* x_width, const char* x,
+                          bool x_first, const char** why) {
+  static thread_local char msg[80];
+  *why = msg;
+  if (obs_dim < 1 || act_dim < 1) { *why = "obs_dim and act_dim must be >= 1"; return false; }
+  if (obs_dim > MAX_OBS) { *why = "obs_dim must be <= 4096"; return false; }
+  if (act_dim > MAX_ACT) { *why = "act_dim must be <= 16"; return false; }
+  if (n_pi < 1 || n_pi > MAX_LAYERS) { *why = "n_pi must be in [1, 3]"; return false; }
+  if (n_x < 1 || n_x > MAX_LAYERS) { snprintf(msg, sizeof msg, "n_%s must be in [1, 3]", x); return false; }
+  if (!pi_width || !x_width) { snprintf(msg, sizeof msg, "null pi_width or %s_width", x); return false; }
   for (int k = 0; k < 2; k++) {
-    const int n = k ? n_pi : n_vf;
-    const int32_t* w = k ? pi_width : vf_width;
+    const bool second = (k == 0) == x_first;
+    const int n = second ? n_x : n_pi;
+    const int32_t* w = second ? x_width : pi_width;
     for (int L = 0; L < n; L++)
       if (w[L] < 16 || w[L] > MAX_WIDTH || w[L] % 16 != 0) {
-        static thread_local char msg[80];
-        snprintf(msg, sizeof msg, "%s_width[%d] must be a multiple of 16 in [16, 256]", k ? "pi" : "vf", L);
-        *why = msg;
-        return 0;
+        snprintf(msg, sizeof msg, "%s_width[%d] must be a multiple of 16 in [16, 256]", second ? x : "pi", L);
+        return false;
       }
   }
+  return true;
+}
+
+// The blob's plan for a shape -> its size in floats; 0 and `why` (a message that names the field) for a refused shape.
+inline int64_t plan(int obs_dim, int act_dim, int n_pi, const int32_t* pi_width, int n_vf, const int32_t* vf_width, Pol* P, const char** why) {
+  if (!checked_shape(obs_dim, act_dim, n_pi, pi_width, n_vf, vf_width, "vf", true, why)) return 0;
   const int kb0 = (obs_dim + 6 + 3) / 4;
   int64_t at = 0;
   for (int k = 1; k >= 0; k--) {         // the policy net first

@@ -2,9 +2,10 @@
 // Gaussian actor with a state-dependent log_std and twin critics with a target copy -- as the collection action (mcg_sac_act), the
 // twin-critic forward (mcg_sac_q), the fused TD target of a replay batch (mcg_sac_target) and the Polyak step (mcg_sac_polyak).
 //
-// A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives.  Kernels and C entries are both here; the
-// matrix instruction, its operand map and the layer helpers are mcg_policy.hpp's, unchanged, and mcg_policy.hip's head states them.
-// The C side is stateless and no entry synchronises.
+// A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives.  The C entries and SAC's own kernels (the
+// action, the TD target) are here; the critic's forward, the critics' kernel (q_kernel) and the Polyak kernel are mcg_sac.hpp's, which
+// TD3 / DDPG (mcg_td3.hip) instantiates too; the matrix instruction, its operand map and the layer helpers are mcg_policy.hpp's,
+// unchanged, and mcg_policy.hip's head states them.  The C side is stateless and no entry synchronises.
 //
 // ---- Work split.  mcg_sac_act: one wave per tile of 16 environments.  mcg_sac_q: one wave per (tile of 16 rows, critic), grid.y = 2.
 // mcg_sac_target: one workgroup of two waves per tile of 16 samples; wave q evaluates the actor on the next observation -- both waves
@@ -15,9 +16,9 @@
 // ---- The action as a matrix operand.  After the actor's head lane 16 g + i holds, in register r, component 4 g + r of sample i: the
 // accumulator layout, which is the B operand of a later layer's k-block r (mcg_policy.hip's head).  So the critics' first layer keeps
 // its action columns as four k-blocks in the later-layer order and takes the action where it lies; an action that comes from memory
-// (mcg_sac_q) is loaded into the same registers, lane (g, i) reading components 4 g .. 4 g + 3 of row i, those >= A as zeros.
+// (mcg_sac_q) is loaded into the same registers (load_action), lane (g, i) reading components 4 g .. 4 g + 3 of row i, those >= A as zeros.
 //
-// ---- The blobs (float32, 16-byte aligned; mycobotgym_amd/sac_policy.py: pack / unpack restate them).  Tiles and biases as in
+// ---- The blobs (float32, 16-byte aligned; mycobotgym_amd/_offpolicy.py: pack_net / unpack_net restate them).  Tiles and biases as in
 // mcg_policy.hip's head: tile (T, kb), float l = 16 g + i: W[16 T + i][k(kb, g)].
 //   actor    latent_pi's layers (the first over the D + 6 feature columns, k(kb, g) = 4 kb + g; later ones k(4 t + r, g) = 16 t + 4 g + r),
 //            then the head mu and the head log_std: each one tile row of 16 (A rows, the rest zeros) over H / 4 k-blocks and 16 biases.
@@ -28,16 +29,16 @@
 //
 // ---- The noise.  Philox4x32-10, mcg_policy.hip's counter layout (policy_pair) with the domain byte 7 for mcg_sac_act, id = the global
 // environment id, and 8 for mcg_sac_target, id = the sample's index in the batch (0-6 are taken: reset and scene draws, HER, the rollout
-// permutation, the picture replay, the actor-critic policy).  One block serves two components by Box-Muller in double, as there.
-#include "mcg_sac.hpp"          // Sac, Draw, hidden, squash, sac_plan, checked_sac (shared with mcg_sac_grad.hip); mcg_policy.hpp
+// permutation, the picture replay, the actor-critic policy).  One block serves two components by Box-Muller in double, as there: gauss4
+// (mcg_sac.hpp) is the one place that forms the counter words, for SAC's three streams and for TD3's two (10, 11).
+#include "mcg_sac.hpp"          // Sac, Rows, Batch, Draw, hidden, squash, critic, q_kernel, polyak_kernel, blob_plan, the host checks (shared
+                                // with mcg_sac_grad.hip and, through mcg_td3.hpp, with TD3 / DDPG); mcg_policy.hpp
 
 using namespace mcg;
 
 namespace {
 
 struct ActOut { float *action, *log_prob, *mean, *log_std, *noise; };
-struct Rows { const float *obs, *achieved, *desired, *action; };
-struct Batch { const float *next_obs, *next_achieved, *desired, *reward, *done; };
 struct TargetOut { float *target, *next_action, *next_log_prob, *next_q, *noise; };
 
 // SB3's actor.action_log_prob on one row (include/mcg.h states every rounding).  `id`, `call`, `stream`: the noise's counter.
@@ -50,27 +51,6 @@ MCG_DEV Draw actor(const Pol& P, const In* __restrict__ obs, const In* __restric
   dense<MT, 1>(P, P.net[1], P.net[1].n, last_tiles(P.net[1]), 1, a, mu, g, lane);
   dense<MT, 1>(P, P.net[0], P.net[0].n, last_tiles(P.net[0]), 1, a, ls, g, lane);
   return squash(P.A, mu[0], ls[0], g, seed, id, call, stream, deterministic);
-}
-
-// Critic k on one row: `act` is the action in the accumulator layout.  The value is row 0 of the head: valid on the lanes g == 0.
-template <int MT, class In>
-MCG_DEV float critic(const Sac& S, int k, const In* __restrict__ obs, const In* __restrict__ ach, const In* __restrict__ des,
-                     int row, const f4& act, int g, int lane) {
-  const Pol& P = k ? S.qf[1] : S.qf[0];
-  const Net& net = P.net[0];
-  f4 a[MT], head[1];
-  first_layer<MT, In>(P, net, obs, ach, des, row, g, lane, a);
-  const float* __restrict__ Wa = P.blob + S.qa;
-#pragma unroll
-  for (int t = 0; t < MT; t++) {
-    if (t < net.nt[0]) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) a[t] = mfma(Wa[(t * 4 + r) * WAVE + lane], act[r], a[t]);
-    }
-  }
-  hidden<MT>(P, net, a, g, lane);
-  dense<MT, 1>(P, net, net.n, last_tiles(net), 1, a, head, g, lane);
-  return head[0][0];
 }
 
 template <int MT>
@@ -96,24 +76,6 @@ __global__ __launch_bounds__(WAVE) void sac_act_kernel(Sac S, const double* __re
     }
   }
   if (O.log_prob && g == 0) O.log_prob[e] = d.log_prob;
-}
-
-template <int MT>
-__global__ __launch_bounds__(WAVE) void sac_q_kernel(Sac S, Rows R, int B, float* __restrict__ q) {
-  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
-  const int e = blockIdx.x * TILE + i;
-  const bool live = e < B;
-  const int row = live ? e : B - 1;
-  const int k = blockIdx.y;
-  f4 act;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int c = 4 * g + r;
-    act[r] = 0.0f;
-    if (c < S.pi.A) act[r] = R.action[(size_t)row * S.pi.A + c];
-  }
-  const float v = critic<MT, float>(S, k, R.obs, R.achieved, R.desired, row, act, g, lane);
-  if (live && g == 0) q[(size_t)k * B + e] = v;
 }
 
 template <int MT>
@@ -149,20 +111,6 @@ __global__ __launch_bounds__(2 * WAVE) void sac_target_kernel(Sac S, Batch X, in
   if (O.next_q) { O.next_q[e] = q0; O.next_q[(size_t)B + e] = q1; }
 }
 
-// target <- (float) fma(tau, (double) critic, (1 - tau) * (double) target): the product rounded to double, the fma rounded once, then
-// the one rounding to float32.  A padding position, +0 in both, stays +0.  tau = 1 (one_minus_tau == 0, the same for every lane) is the
-// copy of the critic's bits: the expression would turn a non-finite target element into NaN (0 * inf) and a critic's -0 into +0.
-__global__ __launch_bounds__(256) void sac_polyak_kernel(const float* __restrict__ critic, float* __restrict__ target, int quads, double tau,
-                                                         double one_minus_tau) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= quads) return;
-  const f4 c = reinterpret_cast<const f4*>(critic)[p];
-  f4 t = reinterpret_cast<f4*>(target)[p];
-#pragma unroll
-  for (int r = 0; r < 4; r++) t[r] = one_minus_tau == 0.0 ? c[r] : (float)fma(tau, (double)c[r], __dmul_rn(one_minus_tau, (double)t[r]));
-  reinterpret_cast<f4*>(target)[p] = t;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------- host side (the plan and the checks: mcg_sac.hpp)
@@ -174,7 +122,7 @@ int64_t mcg_sac_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* p
   const char* why;
   if (actor_floats) *actor_floats = 0;
   if (critic_floats) *critic_floats = 0;
-  return sac_plan(obs_dim, act_dim, n_pi, pi_width, n_qf, qf_width, nullptr, actor_floats, critic_floats, &why);
+  return blob_plan(obs_dim, act_dim, n_pi, pi_width, n_qf, qf_width, 2, true, nullptr, actor_floats, critic_floats, &why);
 }
 
 int mcg_sac_act(const mcg_sac* sac, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset, int deterministic,
@@ -182,11 +130,7 @@ int mcg_sac_act(const mcg_sac* sac, const mcg_step_out* obs, uint64_t seed, uint
   const char* who = "mcg_sac_act";
   Sac S = {};
   if (!checked_sac(who, sac, NEED_ACTOR, &S)) return MCG_ERR_ARG;
-  if (sac->n_envs < 1) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be >= 1", who);
-  if ((long long)sac->n_envs * MAX_ACT >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be below 2^27", who);
-  if (!obs) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_step_out", who);
-  if (!obs->obs || !obs->achieved_goal || !obs->desired_goal)
-    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved_goal and desired_goal of the observation are required", who);
+  if (!checked_envs(who, sac->n_envs) || !checked_obs(who, obs)) return MCG_ERR_ARG;
   if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_act_out", who);
   if (!out->action) return mcg_fail(MCG_ERR_ARG, "%s: action is required", who);
   S.pi.N = sac->n_envs;
@@ -207,17 +151,14 @@ int mcg_sac_q(const mcg_sac* sac, int which, const mcg_sac_rows* rows, int64_t B
     return mcg_fail(MCG_ERR_ARG, "%s: which must be MCG_SAC_CRITIC or MCG_SAC_CRITIC_TARGET", who);
   Sac S = {};
   if (!checked_sac(who, sac, which == MCG_SAC_CRITIC ? NEED_CRITIC : NEED_TARGET, &S)) return MCG_ERR_ARG;
-  if (!checked_rows(who, B)) return MCG_ERR_ARG;
-  if (!rows) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_rows", who);
-  if (!rows->obs || !rows->achieved || !rows->desired || !rows->action)
-    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved, desired and action of the rows are required", who);
+  if (!checked_rows(who, B) || !checked_rows_arg(who, rows, true)) return MCG_ERR_ARG;
   if (!q) return mcg_fail(MCG_ERR_ARG, "%s: q is null", who);
   S.qf[0].blob = which == MCG_SAC_CRITIC ? sac->critic : sac->critic_target;
   S.qf[1].blob = S.qf[0].blob + sac->critic_floats / 2;
   const Rows R = {rows->obs, rows->achieved, rows->desired, rows->action};
   const dim3 grid(blocks(B, TILE), 2), block(WAVE);
-  if (widest(sac, false, true) <= 64) hipLaunchKernelGGL(sac_q_kernel<4>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
-  else hipLaunchKernelGGL(sac_q_kernel<16>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
+  if (widest(sac, false, true) <= 64) hipLaunchKernelGGL(q_kernel<4>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
+  else hipLaunchKernelGGL(q_kernel<16>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
   return launched("mcg_sac_q");
 }
 
@@ -226,10 +167,7 @@ int mcg_sac_target(const mcg_sac* sac, const mcg_her_batch* batch, int64_t B, ui
   const char* who = "mcg_sac_target";
   Sac S = {};
   if (!checked_sac(who, sac, NEED_ACTOR | NEED_TARGET, &S)) return MCG_ERR_ARG;
-  if (!checked_rows(who, B)) return MCG_ERR_ARG;
-  if (!batch) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_her_batch", who);
-  if (!batch->next_obs || !batch->next_achieved || !batch->desired || !batch->reward || !batch->done)
-    return mcg_fail(MCG_ERR_ARG, "%s: next_obs, next_achieved, desired, reward and done of the batch are required", who);
+  if (!checked_rows(who, B) || !checked_batch(who, batch)) return MCG_ERR_ARG;
   if (!(gamma >= 0.0f && gamma <= 1.0f)) return mcg_fail(MCG_ERR_ARG, "%s: gamma must be in [0, 1]", who);
   if (!log_ent_coef && !(ent_coef >= 0.0f && ent_coef <= 3.0e38f))
     return mcg_fail(MCG_ERR_ARG, "%s: ent_coef must be finite and >= 0 where log_ent_coef is null", who);
@@ -255,7 +193,7 @@ int mcg_sac_polyak(const mcg_sac* sac, double tau, void* stream) {
   if (!(tau >= 0.0 && tau <= 1.0)) return mcg_fail(MCG_ERR_ARG, "%s: tau must be in [0, 1]", who);
   if (sac->critic == sac->critic_target) return mcg_fail(MCG_ERR_ARG, "%s: critic and critic_target are the same blob", who);
   const int quads = (int)(sac->critic_floats / 4);      // every piece of a blob is a multiple of 16 floats
-  hipLaunchKernelGGL(sac_polyak_kernel, dim3(blocks(quads, 256)), dim3(256), 0, (hipStream_t)stream, sac->critic, sac->critic_target, quads, tau,
+  hipLaunchKernelGGL(polyak_kernel<256>, dim3(blocks(quads, 256)), dim3(256), 0, (hipStream_t)stream, sac->critic, sac->critic_target, quads, tau,
                      1.0 - tau);
   return launched("mcg_sac_polyak");
 }

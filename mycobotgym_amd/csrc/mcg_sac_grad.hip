@@ -1,11 +1,13 @@
 // mcg_sac_grad.hip -- SAC's update (include/mcg.h: mcg_sac_critic_grad, mcg_sac_actor_grad, mcg_sac_alpha_step, mcg_sac_adam): the
 // critic loss's gradient over the critic blob, the actor loss's gradient over the actor blob through the twin critics as constants,
 // the entropy coefficient's step, and Adam on a bare blob.  A code object of its own, as mcg_sac.hip, whose plan, actor draw and host
-// checks it shares (mcg_sac.hpp); the three products of a layer, the work split (a tile kernel, a dW kernel per block and part, a
-// reduce in part order) and their helpers are mcg_policy_grad.hip's (its head states them; mcg_grad.hpp holds what both use).
+// checks it shares (mcg_sac.hpp); the critic tile kernel, the dW kernel, the forward with rows kept, the walk back and both entries'
+// layouts of `work` are mcg_sac_grad.hpp's, shared with TD3 / DDPG (mcg_td3_grad.hip); the three products of a layer, the work split (a
+// tile kernel, a dW kernel per block and part, a reduce in part order) and their helpers are mcg_policy_grad.hip's (its head states
+// them; mcg_grad.hpp holds what both use).  Here: SAC's actor tile kernel, its reduce, the alpha step and Adam.
 // Float32 throughout on v_mfma_f32_16x16x4_f32; deterministic: no atomics, every sum in an order that the shape and B alone fix.
 //
-// ---- The critic tile kernel: one wave per (tile of 16 samples, critic).  The forward on (features, action) with mcg_sac.hip's
+// ---- The critic tile kernel (critic_tile_kernel<MT, false>, mcg_sac_grad.hpp): one wave per (tile of 16 samples, critic).  The forward on (features, action) with mcg_sac.hip's
 // action-as-operand layout, every layer's input kept as rows in `work` (the features, the action padded to 16 rows, the activations);
 // dq = (q - y) / B at the head; the backward pass to every layer's dZ rows.  The first layer's dW has two column groups, the feature
 // tiles (first-layer order) and the action tile (later-layer order, 4 k-blocks): two entries of the block list, the second without a
@@ -23,44 +25,14 @@
 // their q sums; actor entry: s = 0 the loss terms, 1 the log-probs); then the row chunks (struct GRows) per net and tile; then `parts`
 // partial blobs.  Every float that is read was written by the same call.  A ragged last tile's extra lanes read the last valid sample
 // and get dZ = +-0 at the head, so that every product they enter adds exactly nothing.
-#include "mcg_sac_grad.hpp"     // GRows, SBlocks, critic_forward, walk_back, wt_acc (shared with mcg_td3_grad.hip); mcg_grad.hpp, mcg_sac.hpp
+#include "mcg_sac_grad.hpp"     // GRows, SBlocks, critic_tile_kernel, dw_kernel, hidden_rows, critic_forward, walk_back, wt_acc, Layout,
+                                // critic_layout, actor_layout, checked_work (shared with mcg_td3_grad.hip); mcg_grad.hpp, mcg_sac.hpp
 
 using namespace mcg;
 
 namespace {
 
 struct ActorOut { float *action, *noise, *q_pi, *dq_da, *logp; };
-
-template <int MT>
-__global__ __launch_bounds__(WAVE) void sac_critic_tile_kernel(Sac S, GRows R, SRows X, const float* __restrict__ y, int B, float inv_b,
-                                                               float* work) {
-  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
-  const int tile = blockIdx.x, s = tile * TILE + i;
-  const bool live = s < B;
-  const int row = live ? s : B - 1;
-  const int k = blockIdx.y;
-  const Pol& P = k ? S.qf[1] : S.qf[0];
-  float* chunk = work + R.base + (size_t)k * R.stride + (size_t)tile * R.rows * TILE;
-  f4 act;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int c = 4 * g + r;
-    act[r] = 0.0f;
-    if (c < P.A) act[r] = X.action[(size_t)row * P.A + c];
-  }
-  const f4 h = critic_forward<MT, true>(P, S.qa, R, chunk, X, row, act, g, i, lane);
-  const bool mine = live && g == 0;      // (lanes g == 0 hold the value: row 0 of the head)
-  const float diff = h[0] - y[row];
-  const float sq = sum16(mine ? diff * diff : 0.0f), qs = sum16(mine ? h[0] : 0.0f);
-  if (lane == 0) { work[4 + 8 * (size_t)tile + k] = sq; work[4 + 8 * (size_t)tile + 2 + k] = qs; }
-  f4 d[MT];
-#pragma unroll
-  for (int t = 0; t < MT; t++) d[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-  if (mine) d[0][0] = diff * inv_b;
-  const Net& net = P.net[0];
-  store_rows<MT>(chunk, sel4(R.d, net.n), 1, d, g, i);
-  walk_back<MT, true>(P, net, R, chunk, net.n, 0, d, g, i);
-}
 
 template <int MT>
 __global__ __launch_bounds__(2 * WAVE) void sac_actor_tile_kernel(Sac S, GRows RA, GRows RQ, SRows X, int B, unsigned long long seed,
@@ -77,25 +49,13 @@ __global__ __launch_bounds__(2 * WAVE) void sac_actor_tile_kernel(Sac S, GRows R
   const Net& net = PA.net[1];
   const int n = net.n;
   float* chunk = work + RA.base + (size_t)tile * RA.rows * TILE;
-  // ---- the actor, as mcg_sac.hip's actor(): both waves; wave 0 keeps the rows
+  // ---- the actor, as mcg_sac.hip's actor() with hidden_rows for hidden(): both waves; wave 0 keeps the rows
   f4 mu[1], ls[1];
   {
-    f4 a[MT], b[MT];
+    f4 a[MT];
     first_layer<MT, float>(PA, net, X.obs, X.ach, X.des, row, g, lane, a);
     if (wave == 0) store_features(chunk, RA.x[0], RA.fr, PA.D, X, row, g, i);
-#pragma unroll
-    for (int t = 0; t < MT; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) a[t][r] = activate(PA.act, a[t][r]);
-    if (wave == 0) store_rows<MT>(chunk, RA.x[1], net.nt[0], a, g, i);
-    for (int L = 1; L < n; L++) {
-      dense<MT, MT>(PA, net, L, L == 1 ? net.nt[0] : net.nt[1], L == 1 ? net.nt[1] : net.nt[2], a, b, g, lane);
-#pragma unroll
-      for (int t = 0; t < MT; t++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) a[t][r] = activate(PA.act, b[t][r]);
-      if (wave == 0) store_rows<MT>(chunk, L == 1 ? RA.x[2] : RA.x[3], L == 1 ? net.nt[1] : net.nt[2], a, g, i);
-    }
+    hidden_rows<MT>(PA, net, RA, chunk, wave == 0, a, g, i, lane);
     dense<MT, 1>(PA, PA.net[1], n, last_tiles(net), 1, a, mu, g, lane);
     dense<MT, 1>(PA, PA.net[0], n, last_tiles(net), 1, a, ls, g, lane);
   }
@@ -181,17 +141,6 @@ __global__ __launch_bounds__(2 * WAVE) void sac_actor_tile_kernel(Sac S, GRows R
   walk_back<MT, true>(PA, net, RA, chunk, n - 1, 0, d, g, i);
 }
 
-// One 16 x 16 block of dW (or 16 biases) over the tiles of one part -> its place in the part's partial blob.
-__global__ __launch_bounds__(WAVE) void sac_dw_kernel(SBlocks Q, const float* __restrict__ work, float* __restrict__ partials,
-                                                      long long blob_floats, int ntiles, int tpp) {
-  const int blk = blockIdx.x, part = blockIdx.y;
-  Block me = Q.l[0];
-#pragma unroll
-  for (int q = 1; q < SAC_BLOCK_LAYERS; q++)
-    if (q < Q.n && blk >= Q.l[q].blk0) me = Q.l[q];              // (constant indices: selects, no scratch)
-  dw_block(me, blk, part, work, partials, blob_floats, ntiles, tpp);
-}
-
 // grad[p] = the partial blobs' sum in part order; the last block: the tiles' sums -> stats (actor: 0 the critic entry, 1 the actor's).
 __global__ __launch_bounds__(256) void sac_reduce_kernel(const float* __restrict__ work, const float* __restrict__ partials, int parts,
                                                          long long blob_floats, int ntiles, int actor, float inv_b, float ent_coef,
@@ -245,97 +194,12 @@ __global__ __launch_bounds__(256) void sac_adam_kernel(float* __restrict__ p, co
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
-struct Layout { GRows a, q; SBlocks blocks; int ntiles, tpp, parts; long long partials, need; };
-
-// The critic entry's row map, block list and split of `work`.
-Layout critic_layout(const Sac& S, int64_t B, int widest_qf, int64_t critic_floats) {
-  Layout Y = {};
-  Y.ntiles = (int)((B + TILE - 1) / TILE);
-  split_parts(Y.ntiles, widest_qf, &Y.tpp, &Y.parts);
-  const Net& net = S.qf[0].net[0];
-  const int fr = (S.pi.D + 6 + 15) / 16 * 16;
-  GRows& R = Y.q;
-  int row = 0;
-  R.fr = fr; R.x[0] = 0; row += fr;
-  R.xa = row; row += 16;
-  for (int L = 0; L < net.n; L++) { R.x[L + 1] = row; row += 16 * net.nt[L]; }
-  for (int L = 0; L <= net.n; L++) { R.d[L] = row; row += L < net.n ? 16 * net.nt[L] : 16; }
-  R.rows = row; R.base = 4 + 8ll * Y.ntiles; R.stride = (long long)Y.ntiles * row * TILE;
-  Y.partials = R.base + 2 * R.stride;
-  Y.need = Y.partials + (long long)Y.parts * critic_floats;
-  int blk = 0;
-  const int half = (int)(critic_floats / 2);
-  for (int k = 0; k < 2; k++)
-    for (int L = 0; L <= net.n; L++) {
-      Block b = {};
-      b.nT = L < net.n ? net.nt[L] : 1; b.ncb = L == 0 ? fr / 16 : net.nt[L - 1]; b.nb = 1;
-      b.xrow = R.x[L]; b.drow = R.d[L]; b.w = net.w[L] + k * half; b.b = net.b[L] + k * half;
-      b.nkb = L == 0 ? S.pi.kb0 : 4 * net.nt[L - 1]; b.first = L == 0; b.cols = L == 0 ? S.pi.D + 6 : ALL_COLUMNS;
-      b.rows = R.rows; b.base = R.base + k * R.stride;
-      add_block(Y.blocks, blk, b);
-      if (L == 0) {                      // the action tiles: 16 columns in the later-layer order, no bias of their own
-        Block a = b;
-        a.ncb = 1; a.nb = 0; a.xrow = R.xa; a.w = S.qa + k * half; a.nkb = 4; a.first = 0; a.cols = S.pi.A;
-        add_block(Y.blocks, blk, a);
-      }
-    }
-  Y.blocks.total = blk;
-  return Y;
-}
-
-// The actor entry's: the actor's rows and blocks; per critic only the activation rows (no dZ is kept: no critic dW is formed).
-Layout actor_layout(const Sac& S, int64_t B, int widest_pi, int64_t actor_floats) {
-  Layout Y = {};
-  Y.ntiles = (int)((B + TILE - 1) / TILE);
-  split_parts(Y.ntiles, widest_pi, &Y.tpp, &Y.parts);
-  const Net& net = S.pi.net[1];
-  const Net& ls = S.pi.net[0];
-  const int fr = (S.pi.D + 6 + 15) / 16 * 16, n = net.n;
-  GRows& R = Y.a;
-  int row = 0;
-  R.fr = fr; R.x[0] = 0; row += fr;
-  for (int L = 0; L < n; L++) { R.x[L + 1] = row; row += 16 * net.nt[L]; }
-  for (int L = 0; L <= n; L++) { R.d[L] = row; row += L < n ? 16 * net.nt[L] : 16; }
-  R.d2 = row; row += 16;
-  R.rows = row; R.base = 4 + 8ll * Y.ntiles; R.stride = 0;
-  const Net& qnet = S.qf[0].net[0];
-  GRows& Q = Y.q;
-  row = 0;
-  for (int L = 0; L < qnet.n; L++) { Q.x[L + 1] = row; row += 16 * qnet.nt[L]; }
-  Q.rows = row; Q.base = R.base + (long long)Y.ntiles * R.rows * TILE; Q.stride = (long long)Y.ntiles * row * TILE;
-  Y.partials = Q.base + 2 * Q.stride;
-  Y.need = Y.partials + (long long)Y.parts * actor_floats;
-  int blk = 0;
-  for (int L = 0; L <= n + 1; L++) {     // the trunk, the head mu, the head log_std
-    const Net& from = L <= n ? net : ls;
-    const int M = L <= n ? L : n;
-    Block b = {};
-    b.nT = M < n ? net.nt[M] : 1; b.ncb = M == 0 ? fr / 16 : net.nt[M - 1]; b.nb = 1;
-    b.xrow = R.x[M]; b.drow = L <= n ? R.d[M] : R.d2; b.w = from.w[M]; b.b = from.b[M];
-    b.nkb = M == 0 ? S.pi.kb0 : 4 * net.nt[M - 1]; b.first = M == 0; b.cols = M == 0 ? S.pi.D + 6 : ALL_COLUMNS;
-    b.rows = R.rows; b.base = R.base;
-    add_block(Y.blocks, blk, b);
-  }
-  Y.blocks.total = blk;
-  return Y;
-}
-
 bool checked_adam(const char* who, int64_t step, double lr, double beta1, double beta2, double eps) {
   if (step < 1) { mcg_fail(MCG_ERR_ARG, "%s: step must be >= 1", who); return false; }
   if (!(lr >= 0.0) || !std::isfinite(lr)) { mcg_fail(MCG_ERR_ARG, "%s: lr must be finite and >= 0", who); return false; }
   if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) {
     mcg_fail(MCG_ERR_ARG, "%s: beta1 and beta2 must be in [0, 1)", who); return false; }
   if (!(eps >= 0.0) || !std::isfinite(eps)) { mcg_fail(MCG_ERR_ARG, "%s: eps must be finite and >= 0", who); return false; }
-  return true;
-}
-
-bool checked_work(const char* who, const float* work, int64_t work_floats, long long need) {
-  if (!checked_buffer(who, work, "work")) return false;
-  if (work_floats < need) {
-    mcg_fail(MCG_ERR_ARG, "%s: work_floats is %lld, this entry needs %lld for this shape and B (mcg_sac_grad_work_floats covers both)", who,
-             (long long)work_floats, need);
-    return false;
-  }
   return true;
 }
 
@@ -348,8 +212,9 @@ int64_t mcg_sac_grad_work_floats(const mcg_sac* sac, int64_t B) {
   const char* why = nullptr;
   int64_t actor = 0, critic = 0;
   if (!sac || B < 1 || B * MAX_ACT >= (1ll << 31)) return 0;
-  if (sac_plan(sac->obs_dim, sac->act_dim, sac->n_pi, sac->pi_width, sac->n_qf, sac->qf_width, &S, &actor, &critic, &why) == 0) return 0;
-  const long long c = critic_layout(S, B, widest(sac, false, true), critic).need, a = actor_layout(S, B, widest(sac, true, false), actor).need;
+  if (blob_plan(sac->obs_dim, sac->act_dim, sac->n_pi, sac->pi_width, sac->n_qf, sac->qf_width, 2, true, &S, &actor, &critic, &why) == 0) return 0;
+  const long long c = critic_layout(S, B, widest(sac, false, true), critic, 2).need;
+  const long long a = actor_layout(S, B, widest(sac, true, false), actor, true, 2).need;
   return c > a ? c : a;
 }
 
@@ -358,25 +223,22 @@ int mcg_sac_critic_grad(const mcg_sac* sac, const mcg_sac_rows* rows, const floa
   const char* who = "mcg_sac_critic_grad";
   Sac S = {};
   if (!checked_sac(who, sac, NEED_CRITIC, &S)) return MCG_ERR_ARG;
-  if (!checked_rows(who, B)) return MCG_ERR_ARG;
-  if (!rows) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_rows", who);
-  if (!rows->obs || !rows->achieved || !rows->desired || !rows->action)
-    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved, desired and action of the rows are required", who);
+  if (!checked_rows(who, B) || !checked_rows_arg(who, rows, true)) return MCG_ERR_ARG;
   if (!y) return mcg_fail(MCG_ERR_ARG, "%s: y is null", who);
   if (!stats) return mcg_fail(MCG_ERR_ARG, "%s: stats is null", who);
   if (!checked_buffer(who, grad, "grad")) return MCG_ERR_ARG;
   const int wq = widest(sac, false, true);
-  const Layout Y = critic_layout(S, B, wq, sac->critic_floats);
-  if (!checked_work(who, work, work_floats, Y.need)) return MCG_ERR_ARG;
+  const Layout Y = critic_layout(S, B, wq, sac->critic_floats, 2);
+  if (!checked_work(who, work, work_floats, Y.need, "mcg_sac_grad_work_floats")) return MCG_ERR_ARG;
   S.qf[0].blob = sac->critic;
   S.qf[1].blob = sac->critic + sac->critic_floats / 2;
   const hipStream_t st = (hipStream_t)stream;
   const SRows X = {rows->obs, rows->achieved, rows->desired, rows->action};
   const float inv_b = (float)(1.0 / (double)B);
   const dim3 grid(Y.ntiles, 2), block(WAVE);
-  if (wq <= 64) hipLaunchKernelGGL(sac_critic_tile_kernel<4>, grid, block, 0, st, S, Y.q, X, y, (int)B, inv_b, work);
-  else hipLaunchKernelGGL(sac_critic_tile_kernel<16>, grid, block, 0, st, S, Y.q, X, y, (int)B, inv_b, work);
-  hipLaunchKernelGGL(sac_dw_kernel, dim3(Y.blocks.total, Y.parts), block, 0, st, Y.blocks, (const float*)work, work + Y.partials,
+  if (wq <= 64) hipLaunchKernelGGL((critic_tile_kernel<4, false>), grid, block, 0, st, S, Y.q, X, y, (int)B, inv_b, work);
+  else hipLaunchKernelGGL((critic_tile_kernel<16, false>), grid, block, 0, st, S, Y.q, X, y, (int)B, inv_b, work);
+  hipLaunchKernelGGL(dw_kernel, dim3(Y.blocks.total, Y.parts), block, 0, st, Y.blocks, (const float*)work, work + Y.partials,
                      (long long)sac->critic_floats, Y.ntiles, Y.tpp);
   hipLaunchKernelGGL(sac_reduce_kernel, dim3(blocks(sac->critic_floats, 256) + 1), dim3(256), 0, st, (const float*)work,
                      (const float*)(work + Y.partials), Y.parts, (long long)sac->critic_floats, Y.ntiles, 0, inv_b, 0.0f,
@@ -390,16 +252,14 @@ int mcg_sac_actor_grad(const mcg_sac* sac, const mcg_sac_rows* rows, int64_t B, 
   const char* who = "mcg_sac_actor_grad";
   Sac S = {};
   if (!checked_sac(who, sac, NEED_ACTOR | NEED_CRITIC, &S)) return MCG_ERR_ARG;
-  if (!checked_rows(who, B)) return MCG_ERR_ARG;
-  if (!rows) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_rows", who);
-  if (!rows->obs || !rows->achieved || !rows->desired) return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved and desired of the rows are required", who);
+  if (!checked_rows(who, B) || !checked_rows_arg(who, rows, false)) return MCG_ERR_ARG;
   if (!log_ent_coef && !(ent_coef >= 0.0f && ent_coef <= 3.0e38f))
     return mcg_fail(MCG_ERR_ARG, "%s: ent_coef must be finite and >= 0 where log_ent_coef is null", who);
   if (!logp_out) return mcg_fail(MCG_ERR_ARG, "%s: logp_out is null", who);
   if (!stats) return mcg_fail(MCG_ERR_ARG, "%s: stats is null", who);
   if (!checked_buffer(who, grad, "grad")) return MCG_ERR_ARG;
-  const Layout Y = actor_layout(S, B, widest(sac, true, false), sac->actor_floats);
-  if (!checked_work(who, work, work_floats, Y.need)) return MCG_ERR_ARG;
+  const Layout Y = actor_layout(S, B, widest(sac, true, false), sac->actor_floats, true, 2);
+  if (!checked_work(who, work, work_floats, Y.need, "mcg_sac_grad_work_floats")) return MCG_ERR_ARG;
   S.qf[0].blob = sac->critic;
   S.qf[1].blob = sac->critic + sac->critic_floats / 2;
   const hipStream_t st = (hipStream_t)stream;
@@ -413,7 +273,7 @@ int mcg_sac_actor_grad(const mcg_sac* sac, const mcg_sac_rows* rows, int64_t B, 
   if (widest(sac, true, true) <= 64) MCG_SAC_ACTOR_TILE(4);
   else MCG_SAC_ACTOR_TILE(16);
 #undef MCG_SAC_ACTOR_TILE
-  hipLaunchKernelGGL(sac_dw_kernel, dim3(Y.blocks.total, Y.parts), dim3(WAVE), 0, st, Y.blocks, (const float*)work, work + Y.partials,
+  hipLaunchKernelGGL(dw_kernel, dim3(Y.blocks.total, Y.parts), dim3(WAVE), 0, st, Y.blocks, (const float*)work, work + Y.partials,
                      (long long)sac->actor_floats, Y.ntiles, Y.tpp);
   hipLaunchKernelGGL(sac_reduce_kernel, dim3(blocks(sac->actor_floats, 256) + 1), dim3(256), 0, st, (const float*)work,
                      (const float*)(work + Y.partials), Y.parts, (long long)sac->actor_floats, Y.ntiles, 1, (float)inv_b, ent_coef,

@@ -4,8 +4,10 @@
 // (mcg_td3_polyak).  DDPG is n_critics = 1 with sigma = 0.
 //
 // A translation unit, and so a code object, of its own, for the reason mcg_render.hip gives.  The matrix instruction, its operand map
-// and the layer helpers are mcg_policy.hpp's, the action-as-operand rule and the critic's layout mcg_sac.hip's (its head states them).
-// The C side is stateless and no entry synchronises.
+// and the layer helpers are mcg_policy.hpp's; the critic's forward, the critics' kernel (q_kernel), the Polyak kernel, the Gaussian draw
+// and the blobs' plan are mcg_sac.hpp's, instantiated here a second time; the action-as-operand rule and the critic's layout are
+// stated at mcg_sac.hip's head.  Here: TD3's own kernels (the action, the smoothed target) and the C entries.  The C side is stateless
+// and no entry synchronises.
 //
 // ---- Work split.  mcg_td3_act: one wave per tile of 16 environments.  mcg_td3_q: one wave per (tile of 16 rows, critic), grid.y =
 // n_critics.  mcg_td3_target: one workgroup of n_critics waves per tile of 16 samples; each wave evaluates actor_target on the next
@@ -13,45 +15,22 @@
 // in its registers, and then runs target critic `wave` on it; the Q rows meet through LDS and one barrier, and wave 0 forms and stores
 // everything.  mcg_td3_polyak: one lane per four floats of a blob, one launch per pair.
 //
-// ---- The blobs (float32, 16-byte aligned; mycobotgym_amd/td3_policy.py: pack / unpack restate them), tiles and biases as in
+// ---- The blobs (float32, 16-byte aligned; mycobotgym_amd/_offpolicy.py: pack_net / unpack_net restate them), tiles and biases as in
 // mcg_sac.hip's head.
 //   actor, actor_target    the trunk's layers, then the one head (A rows, the rest zeros) over H / 4 k-blocks and 16 biases.
 //   critic, critic_target  qf0 alone (n_critics = 1) or qf0 then qf1, each in mcg_sac.hip's critic layout.
 //
-// ---- The noise.  Philox4x32-10 in mcg_sac_act's counter layout and Box-Muller in double, with the domain byte 10 for mcg_td3_act,
+// ---- The noise.  mcg_sac.hpp's gauss4 (Philox4x32-10, Box-Muller in double: the draw of mcg_sac_act), with the domain byte 10 for mcg_td3_act,
 // id = the global environment id, and 11 for mcg_td3_target, id = the sample's index in the batch (0-9 are taken).  Scaled in float32:
 // __fmul_rn(sigma, eps).  sigma == 0: the noise is +0 and no block is computed.
-#include "mcg_td3.hpp"          // td3_plan, checked_td3, scaled_noise, td3_actor, add_clamped; mcg_sac.hpp, mcg_policy.hpp
+#include "mcg_td3.hpp"          // checked_td3, scaled_noise, td3_actor, add_clamped; mcg_sac.hpp (q_kernel, polyak_kernel, blob_plan), mcg_policy.hpp
 
 using namespace mcg;
 
 namespace {
 
 struct ActOut { float *action, *mean, *noise; };
-struct Rows { const float *obs, *achieved, *desired, *action; };
-struct Batch { const float *next_obs, *next_achieved, *desired, *reward, *done; };
 struct TargetOut { float *target, *next_action, *next_q, *noise; };
-
-// Critic k on one row: `act` is the action in the accumulator layout.  The value is row 0 of the head: valid on the lanes g == 0.
-template <int MT, class In>
-MCG_DEV float critic(const Sac& S, int k, const In* __restrict__ obs, const In* __restrict__ ach, const In* __restrict__ des, int row,
-                     const f4& act, int g, int lane) {
-  const Pol& P = k ? S.qf[1] : S.qf[0];
-  const Net& net = P.net[0];
-  f4 a[MT], head[1];
-  first_layer<MT, In>(P, net, obs, ach, des, row, g, lane, a);
-  const float* __restrict__ Wa = P.blob + S.qa;
-#pragma unroll
-  for (int t = 0; t < MT; t++) {
-    if (t < net.nt[0]) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) a[t] = mfma(Wa[(t * 4 + r) * WAVE + lane], act[r], a[t]);
-    }
-  }
-  hidden<MT>(P, net, a, g, lane);
-  dense<MT, 1>(P, net, net.n, last_tiles(net), 1, a, head, g, lane);
-  return head[0][0];
-}
 
 template <int MT>
 __global__ __launch_bounds__(WAVE) void td3_act_kernel(Sac S, const double* __restrict__ obs, const double* __restrict__ ach,
@@ -75,24 +54,6 @@ __global__ __launch_bounds__(WAVE) void td3_act_kernel(Sac S, const double* __re
       if (O.noise) O.noise[at] = n[r];
     }
   }
-}
-
-template <int MT>
-__global__ __launch_bounds__(WAVE) void td3_q_kernel(Sac S, Rows R, int B, float* __restrict__ q) {
-  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
-  const int e = blockIdx.x * TILE + i;
-  const bool live = e < B;
-  const int row = live ? e : B - 1;
-  const int k = blockIdx.y;
-  f4 act;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int c = 4 * g + r;
-    act[r] = 0.0f;
-    if (c < S.pi.A) act[r] = R.action[(size_t)row * S.pi.A + c];
-  }
-  const float v = critic<MT, float>(S, k, R.obs, R.achieved, R.desired, row, act, g, lane);
-  if (live && g == 0) q[(size_t)k * B + e] = v;
 }
 
 // blockDim.x = 64 n_critics
@@ -134,18 +95,6 @@ __global__ __launch_bounds__(2 * WAVE) void td3_target_kernel(Sac S, Batch X, in
   }
 }
 
-// mcg_sac_polyak's rule (include/mcg.h) on one pair of blobs, the tau = 1 copy included.
-__global__ __launch_bounds__(256) void td3_polyak_kernel(const float* __restrict__ net, float* __restrict__ target, int quads, double tau,
-                                                         double one_minus_tau) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= quads) return;
-  const f4 c = reinterpret_cast<const f4*>(net)[p];
-  f4 t = reinterpret_cast<f4*>(target)[p];
-#pragma unroll
-  for (int r = 0; r < 4; r++) t[r] = one_minus_tau == 0.0 ? c[r] : (float)fma(tau, (double)c[r], __dmul_rn(one_minus_tau, (double)t[r]));
-  reinterpret_cast<f4*>(target)[p] = t;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------- host side (the plan and the checks: mcg_td3.hpp)
@@ -157,7 +106,7 @@ int64_t mcg_td3_blob_floats(int obs_dim, int act_dim, int n_pi, const int32_t* p
   const char* why;
   if (actor_floats) *actor_floats = 0;
   if (critic_floats) *critic_floats = 0;
-  return td3_plan(obs_dim, act_dim, n_pi, pi_width, n_qf, qf_width, n_critics, nullptr, actor_floats, critic_floats, &why);
+  return blob_plan(obs_dim, act_dim, n_pi, pi_width, n_qf, qf_width, n_critics, false, nullptr, actor_floats, critic_floats, &why);
 }
 
 int mcg_td3_act(const mcg_td3* td3, const mcg_step_out* obs, uint64_t seed, uint64_t call, int64_t env_id_offset, float noise_std,
@@ -165,11 +114,7 @@ int mcg_td3_act(const mcg_td3* td3, const mcg_step_out* obs, uint64_t seed, uint
   const char* who = "mcg_td3_act";
   Sac S = {};
   if (!checked_td3(who, td3, TD3_ACTOR, &S)) return MCG_ERR_ARG;
-  if (td3->n_envs < 1) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be >= 1", who);
-  if ((long long)td3->n_envs * MAX_ACT >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: n_envs must be below 2^27", who);
-  if (!obs) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_step_out", who);
-  if (!obs->obs || !obs->achieved_goal || !obs->desired_goal)
-    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved_goal and desired_goal of the observation are required", who);
+  if (!checked_envs(who, td3->n_envs) || !checked_obs(who, obs)) return MCG_ERR_ARG;
   if (!finite_nonneg(noise_std)) return mcg_fail(MCG_ERR_ARG, "%s: noise_std must be finite and >= 0", who);
   if (!out) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_td3_act_out", who);
   if (!out->action) return mcg_fail(MCG_ERR_ARG, "%s: action is required", who);
@@ -180,7 +125,7 @@ int mcg_td3_act(const mcg_td3* td3, const mcg_step_out* obs, uint64_t seed, uint
 #define MCG_TD3_ACT(MT) hipLaunchKernelGGL(td3_act_kernel<MT>, grid, block, 0, (hipStream_t)stream, S, obs->obs, obs->achieved_goal, \
                                            obs->desired_goal, (unsigned long long)seed, (unsigned long long)call, (long long)env_id_offset, \
                                            noise_std, O)
-  if (td3_widest(td3, true, false) <= 64) MCG_TD3_ACT(4);
+  if (widest(td3, true, false) <= 64) MCG_TD3_ACT(4);
   else MCG_TD3_ACT(16);
 #undef MCG_TD3_ACT
   return launched(who);
@@ -192,16 +137,13 @@ int mcg_td3_q(const mcg_td3* td3, int which, const mcg_sac_rows* rows, int64_t B
     return mcg_fail(MCG_ERR_ARG, "%s: which must be MCG_TD3_CRITIC or MCG_TD3_CRITIC_TARGET", who);
   Sac S = {};
   if (!checked_td3(who, td3, which == MCG_TD3_CRITIC ? TD3_CRITIC : TD3_CRITIC_TARGET, &S)) return MCG_ERR_ARG;
-  if (!checked_rows(who, B)) return MCG_ERR_ARG;
-  if (!rows) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_sac_rows", who);
-  if (!rows->obs || !rows->achieved || !rows->desired || !rows->action)
-    return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved, desired and action of the rows are required", who);
+  if (!checked_rows(who, B) || !checked_rows_arg(who, rows, true)) return MCG_ERR_ARG;
   if (!q) return mcg_fail(MCG_ERR_ARG, "%s: q is null", who);
   set_critics(S, td3, which == MCG_TD3_CRITIC ? td3->critic : td3->critic_target);
   const Rows R = {rows->obs, rows->achieved, rows->desired, rows->action};
   const dim3 grid(blocks(B, TILE), td3->n_critics), block(WAVE);
-  if (td3_widest(td3, false, true) <= 64) hipLaunchKernelGGL(td3_q_kernel<4>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
-  else hipLaunchKernelGGL(td3_q_kernel<16>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
+  if (widest(td3, false, true) <= 64) hipLaunchKernelGGL(q_kernel<4>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
+  else hipLaunchKernelGGL(q_kernel<16>, grid, block, 0, (hipStream_t)stream, S, R, (int)B, q);
   return launched(who);
 }
 
@@ -210,10 +152,7 @@ int mcg_td3_target(const mcg_td3* td3, const mcg_her_batch* batch, int64_t B, ui
   const char* who = "mcg_td3_target";
   Sac S = {};
   if (!checked_td3(who, td3, TD3_ACTOR_TARGET | TD3_CRITIC_TARGET, &S)) return MCG_ERR_ARG;
-  if (!checked_rows(who, B)) return MCG_ERR_ARG;
-  if (!batch) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_her_batch", who);
-  if (!batch->next_obs || !batch->next_achieved || !batch->desired || !batch->reward || !batch->done)
-    return mcg_fail(MCG_ERR_ARG, "%s: next_obs, next_achieved, desired, reward and done of the batch are required", who);
+  if (!checked_rows(who, B) || !checked_batch(who, batch)) return MCG_ERR_ARG;
   if (!(gamma >= 0.0f && gamma <= 1.0f)) return mcg_fail(MCG_ERR_ARG, "%s: gamma must be in [0, 1]", who);
   if (!finite_nonneg(sigma)) return mcg_fail(MCG_ERR_ARG, "%s: sigma must be finite and >= 0", who);
   if (!finite_nonneg(clip)) return mcg_fail(MCG_ERR_ARG, "%s: clip must be finite and >= 0", who);
@@ -226,7 +165,7 @@ int mcg_td3_target(const mcg_td3* td3, const mcg_her_batch* batch, int64_t B, ui
   const dim3 grid(blocks(B, TILE)), block(td3->n_critics * WAVE);
 #define MCG_TD3_TARGET(MT) hipLaunchKernelGGL(td3_target_kernel<MT>, grid, block, 0, (hipStream_t)stream, S, X, (int)B, (int)td3->n_critics, \
                                               (unsigned long long)seed, (unsigned long long)call, gamma, sigma, clip, O)
-  if (td3_widest(td3, true, true) <= 64) MCG_TD3_TARGET(4);
+  if (widest(td3, true, true) <= 64) MCG_TD3_TARGET(4);
   else MCG_TD3_TARGET(16);
 #undef MCG_TD3_TARGET
   return launched(who);
@@ -240,8 +179,8 @@ int mcg_td3_polyak(const mcg_td3* td3, double tau, void* stream) {
   if (td3->critic == td3->critic_target) return mcg_fail(MCG_ERR_ARG, "%s: critic and critic_target are the same blob", who);
   if (td3->actor == td3->actor_target) return mcg_fail(MCG_ERR_ARG, "%s: actor and actor_target are the same blob", who);
   const int cq = (int)(td3->critic_floats / 4), aq = (int)(td3->actor_floats / 4);      // every piece of a blob is a multiple of 16 floats
-  hipLaunchKernelGGL(td3_polyak_kernel, dim3(blocks(cq, 256)), dim3(256), 0, (hipStream_t)stream, td3->critic, td3->critic_target, cq, tau, 1.0 - tau);
-  hipLaunchKernelGGL(td3_polyak_kernel, dim3(blocks(aq, 256)), dim3(256), 0, (hipStream_t)stream, td3->actor, td3->actor_target, aq, tau, 1.0 - tau);
+  hipLaunchKernelGGL(polyak_kernel<256>, dim3(blocks(cq, 256)), dim3(256), 0, (hipStream_t)stream, td3->critic, td3->critic_target, cq, tau, 1.0 - tau);
+  hipLaunchKernelGGL(polyak_kernel<256>, dim3(blocks(aq, 256)), dim3(256), 0, (hipStream_t)stream, td3->actor, td3->actor_target, aq, tau, 1.0 - tau);
   return launched(who);
 }
 

@@ -26,52 +26,25 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
-
-import torch
 
 from . import _abi
 from ._devbuf import _ptr
-from .sac_policy import _per_row, batch_rows, check_out, pack_actor, pack_critic, unpack_actor, unpack_critic
+from ._offpolicy import OffPolicyUpdate, _finite, check_batch, check_common_hyper, critic_shapes      # noqa: F401 (check_batch: imported from here, as ever)
+from .sac_policy import _actor_shapes
 
 _HYPER = ("learning_rate", "gamma", "tau", "ent_coef", "target_entropy", "target_update_interval", "betas", "eps")
 STATS = ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef", "q0_mean", "q1_mean", "log_prob_mean")
 
 
-def _finite(x) -> bool:
-    return isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(float(x))
-
-
 def check_hyper(learning_rate, gamma, tau, ent_coef, target_entropy, target_update_interval, betas, eps, unbuilt: dict):
     """The refusals of the constructor (no device needed) -> (auto?, the constant alpha or None, the initial alpha of "auto_x" or None)."""
-    for k in unbuilt:
-        if k in ("use_sde", "sde_sample_freq", "use_sde_at_warmup"):
-            if unbuilt[k] in (False, None, -1):
-                continue
-            raise ValueError(f"gSDE ({k}) is not built: the noise is the squashed Gaussian's, drawn per call")
-        if k == "max_grad_norm":
-            raise ValueError("max_grad_norm is not built: SB3's SAC clips no gradients")
-        if k == "n_critics":
-            raise ValueError("n_critics != 2 is not built: the kernels differentiate the twin critics qf0 and qf1")
-        if k in ("optimizer_class", "optimizer_kwargs"):
-            raise ValueError(f"{k} is not built: the optimiser is torch.optim.Adam's rule without amsgrad or weight decay")
-        if k == "action_noise":
-            raise ValueError("action_noise is not built: SAC explores through its own entropy term")
-        raise TypeError(f"SACUpdate: unexpected keyword {k!r}")
-    if callable(learning_rate):
-        raise ValueError("a learning-rate schedule is not built: learning_rate takes a float only (it may be set between steps)")
-    if not _finite(learning_rate) or not float(learning_rate) > 0.0:
-        raise ValueError(f"learning_rate must be a finite float > 0, got {learning_rate!r}")
-    if not _finite(gamma) or not 0.0 <= float(gamma) <= 1.0:
-        raise ValueError(f"gamma must be in [0, 1], got {gamma!r}")
-    if not _finite(tau) or not 0.0 < float(tau) <= 1.0:
-        raise ValueError(f"tau must be in (0, 1], got {tau!r}")
+    check_common_hyper(learning_rate, gamma, tau, betas, eps, unbuilt, {
+        "max_grad_norm": "max_grad_norm is not built: SB3's SAC clips no gradients",
+        "n_critics": "n_critics != 2 is not built: the kernels differentiate the twin critics qf0 and qf1",
+        "action_noise": "action_noise is not built: SAC explores through its own entropy term"},
+        "the noise is the squashed Gaussian's, drawn per call", "SACUpdate")
     if isinstance(target_update_interval, bool) or int(target_update_interval) != target_update_interval or int(target_update_interval) < 1:
         raise ValueError(f"target_update_interval must be an integer >= 1, got {target_update_interval!r}")
-    if len(betas) != 2 or not all(_finite(b) and 0.0 <= float(b) < 1.0 for b in betas):
-        raise ValueError(f"betas must be two numbers in [0, 1), got {betas!r}")
-    if not _finite(eps) or float(eps) < 0.0:
-        raise ValueError(f"eps must be finite and >= 0, got {eps!r}")
     if not (target_entropy == "auto" or _finite(target_entropy)):
         raise ValueError(f"target_entropy must be 'auto' (-act_dim) or a finite float, got {target_entropy!r}")
     if isinstance(ent_coef, str):
@@ -91,20 +64,9 @@ def check_hyper(learning_rate, gamma, tau, ent_coef, target_entropy, target_upda
     return False, float(ent_coef), None
 
 
-def check_batch(batch, obs_dim: int, act_dim: int, device=None, who: str = "SACUpdate") -> int:
-    """A ``HerSamples`` of ``HerBuffer.sample`` -> its rows B (no device needed); refuses the picture buffers' samples."""
-    for k in ("observations", "actions", "next_observations", "dones", "rewards"):
-        if not hasattr(batch, k):
-            raise ValueError(f"{who}: the batch has no field {k!r}: pass what HerBuffer.sample yields (a HerSamples)")
-    B = batch_rows(batch.observations, batch.actions, obs_dim, act_dim, who, device)
-    if batch_rows(batch.next_observations, None, obs_dim, act_dim, who, device) != B:
-        raise ValueError(f"{who}: next_observations has another number of rows than observations ({B})")
-    _per_row(batch.rewards, B, "rewards", who, device)
-    _per_row(batch.dones, B, "dones", who, device)
-    return B
+class SACUpdate(OffPolicyUpdate):
+    _WORK_ENTRY, _N_ROWS = "mcg_sac_grad_work_floats", 2          # (y and logp per row)
 
-
-class SACUpdate:
     def __init__(self, policy, learning_rate: float = 3e-4, gamma: float = 0.99, tau: float = 0.005, ent_coef="auto", target_entropy="auto",
                  target_update_interval: int = 1, betas=(0.9, 0.999), eps: float = 1e-8, **unbuilt):
         """``policy``: the ``SACPolicy`` whose blobs and ``log_ent_coef`` are updated in place.  The defaults are SB3's SAC's.
@@ -121,32 +83,16 @@ class SACUpdate:
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.steps = 0                   # gradient steps taken so far: Adam's step count of the three optimisers
         self.actor_calls = 0             # actor-loss draws so far: the `call` word of their noise
-        f32 = dict(dtype=torch.float32, device=policy.device)
-        n = {"critic": policy.critic_floats, "actor": policy.actor_floats, "log_ent_coef": 1}
-        self.grad_blob = {k: torch.zeros(n[k], **f32) for k in n}
-        self.m, self.v = {k: torch.zeros(n[k], **f32) for k in n}, {k: torch.zeros(n[k], **f32) for k in n}
-        self.stats = torch.zeros(8, **f32)
-        self._work, self._rows = None, {}      # the scratch, sized for the largest B seen; y and logp per B
+        self._allocate({"critic": policy.critic_floats, "actor": policy.actor_floats, "log_ent_coef": 1})
         if init is not None:
             policy.log_ent_coef.fill_(math.log(init))
 
+    def _nets(self):
+        pol = self.policy
+        return {"critic": (critic_shapes(pol.obs_dim, pol.act_dim, pol.qf, "critic"), pol.act_dim),
+                "actor": (_actor_shapes(pol.obs_dim, pol.act_dim, pol.pi), 0)}
+
     # --------------------------------------------------------------------------------------------------------- calls
-    def _bare(self, name, *args):
-        pol = self.policy
-        with torch.cuda.device(pol.device):
-            _abi.check(getattr(pol._lib, name)(*args, pol._stream()), name)
-
-    def _buffers(self, B: int):
-        pol = self.policy
-        need = int(pol._lib.mcg_sac_grad_work_floats(C.byref(pol._cbuf), C.c_int64(B)))
-        if need == 0:
-            raise ValueError(f"SACUpdate: a batch of {B} rows is not supported (1 <= B < 2^27)")
-        if self._work is None or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.float32, device=pol.device)
-        if B not in self._rows:
-            self._rows = {B: (torch.empty(B, dtype=torch.float32, device=pol.device), torch.empty(B, dtype=torch.float32, device=pol.device))}
-        return (self._work,) + self._rows[B]
-
     def _critic_grad(self, rows, y, B, work):
         self.policy._call("mcg_sac_critic_grad", C.byref(rows), _ptr(y), C.c_int64(B), _ptr(work), C.c_int64(work.numel()),
                           _ptr(self.grad_blob["critic"]), _ptr(self.stats))
@@ -164,20 +110,6 @@ class SACUpdate:
         self._bare("mcg_sac_alpha_step", _ptr(self.policy.log_ent_coef), _ptr(logp), C.c_int64(B), C.c_float(self.target_entropy), _ptr(self.m[k]),
                    _ptr(self.v[k]), C.c_int64(max(self.steps, 1)), C.c_double(lr), C.c_double(self.betas[0]), C.c_double(self.betas[1]),
                    C.c_double(self.eps), _ptr(self.grad_blob[k]), _ptr(self.stats))
-
-    def _adam(self, k):
-        self._bare("mcg_sac_adam", _ptr(self.policy._t[k]), _ptr(self.grad_blob[k]), _ptr(self.m[k]), _ptr(self.v[k]),
-                   C.c_int64(self.grad_blob[k].numel()), C.c_int64(self.steps), C.c_double(self.learning_rate), C.c_double(self.betas[0]),
-                   C.c_double(self.betas[1]), C.c_double(self.eps))
-
-    def _inputs(self, batch):
-        pol = self.policy
-        if not float(self.learning_rate) > 0.0 or not math.isfinite(self.learning_rate):
-            raise ValueError(f"learning_rate must be a finite float > 0, got {self.learning_rate!r}")
-        B = check_batch(batch, pol.obs_dim, pol.act_dim, pol.device)
-        keep = [batch.observations[k].contiguous() for k in ("observation", "achieved_goal", "desired_goal")] + [batch.actions.contiguous()]
-        rows = _abi.McgSacRows(**{k: t.data_ptr() for k, t in zip(("obs", "achieved", "desired", "action"), keep)})
-        return (B, rows, keep) + self._buffers(B)
 
     def step(self, batch, out=None):
         """One gradient step on one replay batch (``HerBuffer.sample``'s ``HerSamples``), in the order the module's head states.  No
@@ -210,59 +142,29 @@ class SACUpdate:
         pol.target_calls = calls
         self._critic_grad(rows, y, B, work)
         self._actor_grad(rows, logp, B, work, out)
-        D, A = pol.obs_dim, pol.act_dim
-        g = unpack_critic(self.grad_blob["critic"], D, A, pol.qf, "critic")
-        g.update(unpack_actor(self.grad_blob["actor"], D, A, pol.pi))
+        g = self._named({k: self.grad_blob[k] for k in ("critic", "actor")})
         if self.auto:
             self._alpha_step(logp, B, 0.0)
             g["log_ent_coef"] = self.grad_blob["log_ent_coef"].clone()
         return g
 
-    def _check_out(self, out, B):
-        if out is None:
-            return None
+    def _out_shapes(self, B):
         A = self.policy.act_dim
-        shapes = {"action": (B, A), "noise": (B, A), "q_pi": (2, B), "dq_da": (B, A)}
-        if not isinstance(out, dict) or not out:
-            raise ValueError(f"SACUpdate: out: a dict with any of {sorted(shapes)}")
-        return check_out(out, shapes, next(iter(out)), "SACUpdate", self.policy.device)
+        return {"action": (B, A), "noise": (B, A), "q_pi": (2, B), "dq_da": (B, A)}
 
     # --------------------------------------------------------------------------------------------------- checkpoints
     def state_dict(self) -> dict:
         """Adam's moments of the three optimisers as blobs (``m``, ``v``: critic, actor, log_ent_coef) and under SB3's names
         (``exp_avg``, ``exp_avg_sq``), ``step``, ``actor_calls`` and the hyper-parameters.  With the policy's and the buffer's state
         dicts, training continues bit for bit."""
-        pol = self.policy
-        D, A = pol.obs_dim, pol.act_dim
-
-        def named(t):
-            sd = unpack_critic(t["critic"], D, A, pol.qf, "critic")
-            sd.update(unpack_actor(t["actor"], D, A, pol.pi))
-            sd["log_ent_coef"] = t["log_ent_coef"].clone()
-            return sd
-        sd = {"m": {k: t.clone() for k, t in self.m.items()}, "v": {k: t.clone() for k, t in self.v.items()}, "exp_avg": named(self.m),
-              "exp_avg_sq": named(self.v), "step": self.steps, "actor_calls": self.actor_calls}
+        sd = {**self._moments_state(), "actor_calls": self.actor_calls}
         sd.update({k: getattr(self, k) for k in _HYPER})
         return sd
 
     def load_state_dict(self, sd: dict):
         """The moments from the blobs ``m`` / ``v`` where given, else packed from ``exp_avg`` / ``exp_avg_sq``."""
-        pol = self.policy
-        D, A, dev = pol.obs_dim, pol.act_dim, pol.device
-        for blob, mine, names in (("m", self.m, "exp_avg"), ("v", self.v, "exp_avg_sq")):
-            if blob in sd:
-                src = {k: torch.as_tensor(sd[blob][k], device=dev) for k in mine}
-            elif names in sd:
-                src = {"critic": pack_critic(sd[names], D, A, pol.qf, "critic", device=dev), "actor": pack_actor(sd[names], D, A, pol.pi, device=dev),
-                       "log_ent_coef": torch.as_tensor(sd[names]["log_ent_coef"], device=dev).reshape(1)}
-            else:
-                raise ValueError(f"the state dict has neither {blob!r} nor {names!r}")
-            for k, t in mine.items():
-                if src[k].dtype != torch.float32 or tuple(src[k].shape) != tuple(t.shape):
-                    raise ValueError(f"{blob}[{k!r}]: expected float32 {tuple(t.shape)}, got {src[k].dtype} {tuple(src[k].shape)}")
-            for k, t in mine.items():
-                t.copy_(src[k])
-        self.steps, self.actor_calls = int(sd["step"]), int(sd["actor_calls"])
+        self._load_moments(sd)
+        self.actor_calls = int(sd["actor_calls"])
         hyper = {k: sd.get(k, getattr(self, k)) for k in _HYPER}
         self.auto, self._alpha, _ = check_hyper(unbuilt={}, **hyper)
         for k, x in hyper.items():

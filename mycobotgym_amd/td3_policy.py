@@ -30,18 +30,16 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi
-from ._devbuf import DeviceBuffer
-from .policy import _ACTIVATIONS, _pack_layer, _unpack_layer
-from .sac_policy import _arr, _hidden_of, _param, _per_row, batch_rows, check_out
+from ._offpolicy import OffPolicyNets, _arr, _hidden_of, check_out, critic_shapes, pack_critic, pack_net, unpack_critic, unpack_net      # noqa: F401
+from .policy import _ACTIVATIONS                # (pack_critic and unpack_critic: imported from here by users and tests, as ever)
 
 _WIDTHS = ("1 to 3 hidden layers, each width a multiple of 16 in [16, 256]; SB3's default net_arch [400, 300] for TD3 / DDPG is refused: "
            "300 is no multiple of 16 and 400 is above 256 -- pass net_arch=[256, 256] to SB3 and hidden=(256, 256) here")
-_HOST = ("seed", "calls", "target_calls")
 
 
 # ----------------------------------------------------------------------------------------------------------- the blobs
-# csrc/mcg_td3.hip's head states the layouts; restated.  actor and actor_target: the trunk's layers, then the head (A rows padded to
-# 16).  critic and critic_target: qf0, then qf1 with two critics, each as sac_policy.py restates it.
+# csrc/mcg_td3.hip's head states the layouts.  actor and actor_target: the trunk's layers, then the head (A rows padded to 16).
+# critic and critic_target: qf0, then qf1 with two critics, each as _offpolicy.py's pack_net restates a critic.
 def _actor_shapes(obs_dim, act_dim, pi, prefix="actor"):
     """(module, out, in, first layer?) in the actor blob's order."""
     rows, k = [], obs_dim + 6
@@ -51,71 +49,23 @@ def _actor_shapes(obs_dim, act_dim, pi, prefix="actor"):
     return rows + [(f"{prefix}.mu.{2 * len(pi)}", act_dim, k, False)]
 
 
-def _critic_shapes(obs_dim, act_dim, qf, prefix, n_critics):
-    rows = []
-    for q in range(n_critics):
-        k = obs_dim + 6 + act_dim
-        for L, w in enumerate(qf):
-            rows.append((f"{prefix}.qf{q}.{2 * L}", w, k, L == 0))
-            k = w
-        rows.append((f"{prefix}.qf{q}.{2 * len(qf)}", 1, k, False))
-    return rows
-
-
 def state_names(n_pi: int, n_qf: int, n_critics: int = 2):
     """The weights' keys of a state dict: actor, actor_target, critic, critic_target, in the blobs' order."""
     names = []
     for m, *_ in (_actor_shapes(1, 1, [16] * n_pi) + _actor_shapes(1, 1, [16] * n_pi, "actor_target")
-                  + _critic_shapes(1, 1, [16] * n_qf, "critic", n_critics) + _critic_shapes(1, 1, [16] * n_qf, "critic_target", n_critics)):
+                  + critic_shapes(1, 1, [16] * n_qf, "critic", n_critics) + critic_shapes(1, 1, [16] * n_qf, "critic_target", n_critics)):
         names += [m + ".weight", m + ".bias"]
     return names
 
 
 def pack_actor(sd: dict, obs_dim: int, act_dim: int, pi: Sequence[int], prefix: str = "actor", device=None) -> torch.Tensor:
     """The ``actor.mu.*`` (or ``actor_target.mu.*``) entries of a state dict under SB3's names -> that blob (float32)."""
-    parts = []
-    for m, out, k, first in _actor_shapes(obs_dim, act_dim, pi, prefix):
-        parts += _pack_layer(*_param(sd, m, out, k, device), first)
-    return torch.cat(parts).contiguous()
-
-
-def pack_critic(sd: dict, obs_dim: int, act_dim: int, qf: Sequence[int], prefix: str = "critic", n_critics: int = 2, device=None) -> torch.Tensor:
-    """The ``critic.*`` (or ``critic_target.*``) entries -> that blob."""
-    parts, F = [], obs_dim + 6
-    for m, out, k, first in _critic_shapes(obs_dim, act_dim, qf, prefix, n_critics):
-        W, b = _param(sd, m, out, k, device)
-        if first:
-            Wa = torch.zeros(out, 16, dtype=torch.float32, device=W.device)
-            Wa[:, :act_dim] = W[:, F:]
-            parts += [_pack_layer(W[:, :F], b, True)[0], *_pack_layer(Wa, b, False)]
-        else:
-            parts += _pack_layer(W, b, False)
-    return torch.cat(parts).contiguous()
+    return pack_net(sd, _actor_shapes(obs_dim, act_dim, pi, prefix), device=device)
 
 
 def unpack_actor(blob: torch.Tensor, obs_dim: int, act_dim: int, pi: Sequence[int], prefix: str = "actor") -> dict:
     """The inverse of ``pack_actor``, bit for bit."""
-    sd, at = {}, 0
-    for m, out, k, first in _actor_shapes(obs_dim, act_dim, pi, prefix):
-        sd[m + ".weight"], sd[m + ".bias"], used = _unpack_layer(blob[at:], out, k, first)
-        at += used
-    return sd
-
-
-def unpack_critic(blob: torch.Tensor, obs_dim: int, act_dim: int, qf: Sequence[int], prefix: str = "critic", n_critics: int = 2) -> dict:
-    """The inverse of ``pack_critic``, bit for bit."""
-    sd, at, F = {}, 0, obs_dim + 6
-    for m, out, k, first in _critic_shapes(obs_dim, act_dim, qf, prefix, n_critics):
-        if first:
-            feat = out * (-(-F // 4) * 4)                                       # the feature tiles; then the action tiles and the bias
-            Wf = _unpack_layer(torch.cat([blob[at:at + feat], blob.new_zeros(out)]), out, F, True)[0]
-            Wa, b, used = _unpack_layer(blob[at + feat:], out, 16, False)
-            sd[m + ".weight"], sd[m + ".bias"] = torch.cat([Wf, Wa[:, :act_dim]], dim=1), b
-            at += feat + used
-        else:
-            sd[m + ".weight"], sd[m + ".bias"], used = _unpack_layer(blob[at:], out, k, False)
-            at += used
-    return sd
+    return unpack_net(blob, _actor_shapes(obs_dim, act_dim, pi, prefix))
 
 
 def _refuse_foreign(keys):
@@ -136,11 +86,12 @@ def _refuse_widths(widths):
         raise ValueError("net_arch [400, 300] (SB3's default for TD3 / DDPG) is not supported: " + _WIDTHS)
 
 
-class TD3Policy(DeviceBuffer):
-    _FROM_ENVS = (("num_envs", "num_envs"), ("obs_dim", "obs_dim"), ("act_dim", "action_dim"))
+class TD3Policy(OffPolicyNets):
     _NO_IMAGES = ("the -v1 image ids (and a FrameStack around them) observe uint8 pictures, which SB3 gives a CNN extractor: TD3Policy is "
                   "the MLP policy of the -v0 state ids; CNN critics are not supported")
     _N_CRITICS = 2
+    _WIDTHS = _WIDTHS
+    _refuse_foreign = staticmethod(_refuse_foreign)
 
     def __init__(self, envs=None, hidden=(256, 256), activation: str = "relu", seed: int = 0, n_critics: Optional[int] = None, *,
                  use_sde: bool = False, num_envs: Optional[int] = None, obs_dim: Optional[int] = None, act_dim: Optional[int] = None,
@@ -155,35 +106,8 @@ class TD3Policy(DeviceBuffer):
         if isinstance(n_critics, bool) or int(n_critics) != n_critics or int(n_critics) not in (1, 2):
             raise ValueError(f"n_critics must be 1 or 2 (got {n_critics}): n_critics > 2 is not supported, the kernels evaluate qf0, or qf0 and qf1")
         self.n_critics = int(n_critics)
-        num_envs, obs_dim, act_dim = self._resolve(envs, device, dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim))
-        self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
-        if env_id_offset is None:
-            env_id_offset = int(envs._cfg.env_id_offset) if envs is not None and hasattr(envs, "_cfg") else 0
-        self.env_id_offset = int(env_id_offset)
-        if isinstance(hidden, dict):
-            if set(hidden) != {"pi", "qf"}:
-                raise ValueError("hidden: a dict must have exactly the keys 'pi' and 'qf'")
-            self.pi, self.qf = tuple(int(w) for w in hidden["pi"]), tuple(int(w) for w in hidden["qf"])
-        else:
-            self.pi = self.qf = tuple(int(w) for w in hidden)
-        _refuse_widths(self.pi); _refuse_widths(self.qf)
-        if activation not in _ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}, got {activation!r}")
-        self.activation = activation
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.calls = 0                   # calls of __call__ so far: the `call` word of the collection noise
-        self.target_calls = 0            # td_target calls so far: the `call` word of the smoothing noise
-        fa, fc = C.c_int64(0), C.c_int64(0)
-        if len(self.pi) <= 3 and len(self.qf) <= 3:
-            self._lib.mcg_td3_blob_floats(self.obs_dim, self.act_dim, len(self.pi), _arr(self.pi), len(self.qf), _arr(self.qf), self.n_critics,
-                                          C.byref(fa), C.byref(fc))
-        self.actor_floats, self.critic_floats = int(fa.value), int(fc.value)
-        if self.actor_floats == 0:
-            raise ValueError(f"unsupported shape: obs_dim {self.obs_dim}, act_dim {self.act_dim} (1..16), actor {self.pi}, critics {self.qf}: "
-                             + _WIDTHS)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self._t = {"actor": torch.zeros(self.actor_floats, **f32), "actor_target": torch.zeros(self.actor_floats, **f32),
-                   "critic": torch.zeros(self.critic_floats, **f32), "critic_target": torch.zeros(self.critic_floats, **f32)}
+        self._setup(envs, hidden, activation, seed, dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim), device, env_id_offset,
+                    ("actor", "actor_target", "critic", "critic_target"), _refuse_widths)
         self._cbuf = _abi.McgTd3(**{k: t.data_ptr() for k, t in self._t.items()}, n_envs=self.num_envs, obs_dim=self.obs_dim,
                                  act_dim=self.act_dim, n_pi=len(self.pi), pi_width=_arr(self.pi), n_qf=len(self.qf), qf_width=_arr(self.qf),
                                  activation=_ACTIVATIONS[activation], n_critics=self.n_critics, actor_floats=self.actor_floats,
@@ -191,51 +115,29 @@ class TD3Policy(DeviceBuffer):
         self._load_weights(self._initial_weights())
 
     # ------------------------------------------------------------------------------------------------------- weights
-    def _initial_weights(self) -> dict:
-        gen = torch.Generator().manual_seed(self.seed % (2 ** 63))
-        sd = {}
-        for m, out, k, _first in (_actor_shapes(self.obs_dim, self.act_dim, self.pi)
-                                  + _critic_shapes(self.obs_dim, self.act_dim, self.qf, "critic", self.n_critics)):
-            bound = 1.0 / math.sqrt(k)
-            sd[m + ".weight"] = (torch.rand(out, k, generator=gen) * 2.0 - 1.0) * bound
-            sd[m + ".bias"] = (torch.rand(out, generator=gen) * 2.0 - 1.0) * bound
-        for net in ("actor", "critic"):
-            sd.update({k.replace(net + ".", net + "_target.", 1): v for k, v in sd.items() if k.startswith(net + ".")})
-        return sd
+    def _nets(self):
+        D, A, nc = self.obs_dim, self.act_dim, self.n_critics
+        return (("actor", _actor_shapes(D, A, self.pi), 0), ("actor_target", _actor_shapes(D, A, self.pi, "actor_target"), 0),
+                ("critic", critic_shapes(D, A, self.qf, "critic", nc), A), ("critic_target", critic_shapes(D, A, self.qf, "critic_target", nc), A))
 
-    def _load_weights(self, sd: dict):
-        D, A, dev, nc = self.obs_dim, self.act_dim, self.device, self.n_critics
-        for name, blob in (("actor", pack_actor(sd, D, A, self.pi, "actor", device=dev)),
-                           ("actor_target", pack_actor(sd, D, A, self.pi, "actor_target", device=dev)),
-                           ("critic", pack_critic(sd, D, A, self.qf, "critic", nc, device=dev)),
-                           ("critic_target", pack_critic(sd, D, A, self.qf, "critic_target", nc, device=dev))):
-            assert blob.numel() == self._t[name].numel(), (name, blob.numel(), self._t[name].numel())
-            self._t[name].copy_(blob)    # in place: the struct keeps pointing at it
+    def _blob_floats(self):
+        return self._floats_of("mcg_td3_blob_floats", self.n_critics)
+
+    def _state_names(self):
+        return state_names(len(self.pi), len(self.qf), self.n_critics)
+
+    def _fit(self):
+        return f"actor {self.pi} / {self.n_critics} critic(s) {self.qf}"
 
     def state_dict(self) -> dict:
         """The weights under SB3's ``TD3Policy`` names (device tensors, unpacked from the blobs), and ``seed``, ``calls``,
         ``target_calls``."""
-        D, A, nc = self.obs_dim, self.act_dim, self.n_critics
-        sd = unpack_actor(self._t["actor"], D, A, self.pi, "actor")
-        sd.update(unpack_actor(self._t["actor_target"], D, A, self.pi, "actor_target"))
-        sd.update(unpack_critic(self._t["critic"], D, A, self.qf, "critic", nc))
-        sd.update(unpack_critic(self._t["critic_target"], D, A, self.qf, "critic_target", nc))
-        sd.update({k: getattr(self, k) for k in _HOST})
-        return sd
+        return self._state_dict()
 
     def load_state_dict(self, sd: dict):
         """Weights under SB3's names (an SB3 ``TD3Policy``'s ``state_dict()`` as it stands, or this class's); repacks the four blobs.
         ``seed``, ``calls`` and ``target_calls`` are taken where given."""
-        sd = dict(sd)
-        host = {k: sd.pop(k) for k in _HOST if k in sd}
-        _refuse_foreign(sd)
-        want = set(state_names(len(self.pi), len(self.qf), self.n_critics))
-        missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
-        if missing or extra:
-            raise ValueError(f"state dict does not fit actor {self.pi} / {self.n_critics} critic(s) {self.qf}: missing {missing}, unexpected {extra}")
-        self._load_weights(sd)
-        for k, v in host.items():
-            setattr(self, k, int(v) & (2 ** 64 - 1) if k == "seed" else int(v))
+        self._load_state_dict(sd)
 
     @classmethod
     def from_module(cls, module, envs=None, activation: Optional[str] = None, seed: int = 0, **dims):
@@ -246,17 +148,11 @@ class TD3Policy(DeviceBuffer):
             raise ValueError("gSDE (use_sde=True) is not supported: TD3's and DDPG's actor is deterministic")
         sd = {k: v for k, v in module.state_dict().items()}
         _refuse_foreign(sd)
-        fn = getattr(module, "activation_fn", None)
-        if activation is None and fn is not None:
-            name = getattr(fn, "__name__", type(fn).__name__).lower()
-            if name not in _ACTIVATIONS:
-                raise ValueError(f"activation_fn {name!r} is not supported: relu or tanh")
-            activation = name
         pi, qf = _hidden_of(sd, "actor.mu")[:-1], _hidden_of(sd, "critic.qf0")[:-1]
         if not pi or not qf:
             raise ValueError("the module's state dict has no actor.mu / critic.qf0 layers")
         n_critics = 2 if any(k.startswith("critic.qf1.") for k in sd) else 1
-        pol = cls(envs, hidden=dict(pi=pi, qf=qf), activation=activation or "relu", seed=seed, n_critics=n_critics, **dims)
+        pol = cls(envs, hidden=dict(pi=pi, qf=qf), activation=cls._activation_of(module, activation), seed=seed, n_critics=n_critics, **dims)
         pol.load_state_dict(sd)
         return pol
 
@@ -293,15 +189,7 @@ class TD3Policy(DeviceBuffer):
         """The critic(s) on a batch: ``observations`` the dict of float32 device tensors [B, .] that ``HerBuffer.sample`` yields,
         ``actions`` float32 [B, A] -> a tuple of ``n_critics`` rows [B] of one float32 [n_critics, B] tensor (``out``); one launch.
         ``target``: the target critics."""
-        B = batch_rows(observations, actions, self.obs_dim, self.act_dim, "q_values", self.device)
-        keep = [observations[k].contiguous() for k in ("observation", "achieved_goal", "desired_goal")] + [actions.contiguous()]
-        rows = _abi.McgSacRows(**{k: t.data_ptr() for k, t in zip(("obs", "achieved", "desired", "action"), keep)})
-        nc = self.n_critics
-        q = torch.empty(nc, B, dtype=torch.float32, device=self.device) if out is None else out
-        if not torch.is_tensor(q) or q.dtype != torch.float32 or tuple(q.shape) != (nc, B) or not q.is_contiguous() or q.device != self.device:
-            raise ValueError(f"q_values: out: expected a contiguous float32 tensor {(nc, B)} on {self.device}")
-        self._call("mcg_td3_q", _abi.TD3_CRITIC_TARGET if target else _abi.TD3_CRITIC, C.byref(rows), C.c_int64(B), C.c_void_p(q.data_ptr()))
-        return tuple(q[k] for k in range(nc))
+        return self._q_values("mcg_td3_q", _abi.TD3_CRITIC_TARGET if target else _abi.TD3_CRITIC, observations, actions, out)
 
     def td_target(self, batch, gamma: float = 0.99, target_policy_noise: float = 0.2, target_noise_clip: float = 0.5,
                   out: Optional[dict] = None) -> torch.Tensor:
@@ -309,25 +197,12 @@ class TD3Policy(DeviceBuffer):
         ``rewards`` and ``dones``) -> target float32 [B]; one launch, and one call number of the smoothing noise whatever the sigma.
         ``out``: the tensors to write into, under ``mcg_td3_target_out``'s names (target, and any of next_action [B, A], next_q
         [n_critics, B], noise [B, A])."""
-        who = "td_target"
-        nxt = batch.next_observations
-        B = batch_rows(nxt, None, self.obs_dim, self.act_dim, who, self.device)
-        reward, done = _per_row(batch.rewards, B, "rewards", who, self.device), _per_row(batch.dones, B, "dones", who, self.device)
-        keep = [nxt[k].contiguous() for k in ("observation", "achieved_goal", "desired_goal")]
-        cb = _abi.McgHerBatch(next_obs=keep[0].data_ptr(), next_achieved=keep[1].data_ptr(), desired=keep[2].data_ptr(),
-                              reward=reward.data_ptr(), done=done.data_ptr())
-        out = self.new_target_out(B, "target") if out is None else check_out(out, self._target_shapes(B), "target", who, self.device)
+        B, cb, _keep, out = self._her_batch(batch, out, "td_target")
         cout = _abi.McgTd3TargetOut(**{k: v.data_ptr() for k, v in out.items()})
         self._call("mcg_td3_target", C.byref(cb), C.c_int64(B), C.c_uint64(self.seed), C.c_uint64(self.target_calls), C.c_float(gamma),
                    C.c_float(target_policy_noise), C.c_float(target_noise_clip), C.byref(cout))
         self.target_calls += 1
         return out["target"]
-
-    def new_target_out(self, B: int, *names) -> dict:
-        """Fresh tensors for ``td_target``'s ``out`` under ``names``."""
-        f32 = dict(dtype=torch.float32, device=self.device)
-        shape = self._target_shapes(B)
-        return {k: torch.empty(shape[k], **f32) for k in names}
 
     def _target_shapes(self, B: int) -> dict:
         return {"target": (B,), "next_q": (self.n_critics, B), "next_action": (B, self.act_dim), "noise": (B, self.act_dim)}

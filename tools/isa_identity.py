@@ -9,6 +9,11 @@ instruction counts (first file / second file), and for a kernel .vgpr_count / .s
 A symbol's stream is what lies between its label and its .Lfunc_end, with comments, directives and label definitions dropped and
 .LBB* operands renamed by order of first appearance, so that a block renumbered by an unrelated function compares equal.  The streams
 are compared as text; the tool knows no instruction.  Exit status 1 if any symbol differs or exists in one file only.
+
+    python tools/isa_identity.py parent/mcg_sac.s new/mcg_sac.s 12sac_q_kernel=8q_kernel
+
+Further arguments old=new rename a kernel that an edit merged with another: every occurrence of `old` in the first file's text (the
+mangled name's length prefix included) reads `new` before the comparison.
 """
 import re, sys
 
@@ -36,8 +41,9 @@ def figures(text):
         if name: out[name.group(1)] = tuple((re.search(r'^ {0,4}%s:\s*(\d+)' % re.escape(f), entry, re.M) or [None, '?'])[1] for f in FIGURES)
     return out
 
-def main(a_path, b_path):
+def main(a_path, b_path, *renames):
     a, b = open(a_path).read(), open(b_path).read()
+    for old, new in (r.split('=', 1) for r in renames): a = a.replace(old, new)
     sa, sb, fa, fb = streams(a), streams(b), figures(a), figures(b)
     same = diff = 0
     for sym in sorted(set(sa) | set(sb)):
@@ -55,5 +61,5 @@ def main(a_path, b_path):
     return 1 if diff else 0
 
 if __name__ == '__main__':
-    if len(sys.argv) != 3: sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    if len(sys.argv) < 3 or not all('=' in r for r in sys.argv[3:]): sys.exit(__doc__)
+    sys.exit(main(*sys.argv[1:]))
