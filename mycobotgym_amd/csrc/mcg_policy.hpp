@@ -166,4 +166,15 @@ inline int widest_layer(const mcg_policy* pol) {
   return widest;
 }
 
+// The B every entry over rows accepts (B * MAX_ACT indexes in int); silent, for the *_work_floats entries.
+inline bool rows_in_range(int64_t B) { return B >= 1 && B * MAX_ACT < (1ll << 31); }
+
+// The same, refused in the entry's name.
+inline bool checked_rows(const char* who, int64_t B) {
+  if (rows_in_range(B)) return true;
+  if (B < 1) mcg_fail(MCG_ERR_ARG, "%s: B must be >= 1", who);
+  else mcg_fail(MCG_ERR_ARG, "%s: B must be below 2^27", who);
+  return false;
+}
+
 }  // namespace

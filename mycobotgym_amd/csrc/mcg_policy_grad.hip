@@ -22,7 +22,7 @@
 // ---- Work split.  grad_tile_kernel: one wave per tile of 16 samples and net, as the forward.  It runs the forward, keeps every layer's
 // activations as rows in `work` (not in registers: at [256, 256] they would not fit, and the dW product wants them re-laid anyway),
 // forms the loss's derivative at the head, walks back through W^T, and leaves every layer's dZ rows beside the activations.  It re-reads
-// its own activation rows for tanh' = 1 - y^2 / relu' = [y > 0].  grad_dw_kernel: one wave per 16 x 16 block of a weight matrix (or
+// its own activation rows for tanh' = 1 - y^2 / relu' = [y > 0].  dw_kernel: one wave per 16 x 16 block of a weight matrix (or
 // 16 biases) and part: it walks the part's tiles of samples in order and writes its block of the part's partial blob.  The blob has
 // few blocks (about 75 at [64, 64]), so the samples are split into at most 16 parts (4 at widths above 64): 4096 samples at [64, 64]
 // are 256 tiles, 16 parts of 16 tiles, about 1200 waves.  grad_reduce_kernel adds the partial blobs in part order, adds the entropy
@@ -31,7 +31,7 @@
 //
 // ---- `work` (floats):  [0] advantage mean, [1] std + 1e-8, [2..3] unused, [4..5] and [6..7] the same two as doubles;
 // [8 + 8 tile + s] the tile's sums: s = 2 squared value error, 4 kl term, 5 clipped count, 6..7 the policy term as one double;  then
-// per net and tile `rows` rows of 16 floats (the row map: struct Rows);  then `parts` partial blobs.  Every float that is read was
+// per net and tile `rows` rows of 16 floats (the row map: mcg_grad.hpp's struct GRows);  then `parts` partial blobs.  Every float that is read was
 // written by the same call.
 //
 // ---- A2C's policy term in double.  Its summands adv * log_prob have the log-prob's magnitude (about -1.4 A: 13 on average at
@@ -44,27 +44,24 @@
 //
 // ---- A ragged last tile: its extra lanes read the last valid sample, as in the forward, and their dZ is set to +-0 at the head, so
 // that every product they enter adds exactly nothing.
-#include "mcg_grad.hpp"       // sum16, store_rows, Block, dw_block, sum_parts, block_sum, adam_one (shared with mcg_sac_grad.hip)
+//
+// ---- Shared with SAC and TD3 / DDPG (mcg_grad.hpp): the row map, the rows' stores, the hidden layers' forward, the walk back through
+// W^T, the dW kernel and its block list, the reduce's two helpers, Adam's kernel.  Here: the pick of one of the two nets, the Gaussian
+// head and the PPO / A2C loss, the statistic in double, the advantage's and the gradient's norm kernels, the log_std block.
+#include "mcg_grad.hpp"       // GRows, Blocks, sum16, sum64, store_rows, store_features, hidden_rows, walk_back, dw_kernel, reduced_parts,
+                              // block_sum, adam_kernel, adam_step, number_rows, layer_block, add_block, split_parts, checked_buffer
 
 using namespace mcg;
 
 namespace {
 
-constexpr int MAX_BLOCK_LAYERS = 2 * (MAX_LAYERS + 1) + 1;
 constexpr int SUMS = 8;                                                 // the tiles' sums start here in `work`
 constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
 constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
 
-struct Rows {                            // a net's rows of a tile in `work`, in rows of 16 floats
-  int x[MAX_LAYERS + 1];                 // x[L]: the input of layer L (x[0]: the features, fr rows; x[n]: the head's input)
-  int d[MAX_LAYERS + 1];                 // d[L]: dZ of layer L (d[n]: the head's, 16 rows)
-  int ls, rows, fr;                      // the policy net's 16 rows of the log_std terms; rows in all; feature rows (D + 6 padded to 16)
-  long long base;                        // the net's first float in `work`
-};
 struct Batch { const float *obs, *ach, *des, *action, *old_lp, *adv, *ret; };
 struct Hyper { int kind, norm; float clip, ent_coef, vf_coef, inv_b; double inv_bd; };      // inv_bd: 1 / B for the sums held in double
 struct EvalOut { float *value, *log_prob, *entropy; };
-struct Blocks { Block l[MAX_BLOCK_LAYERS]; int n, total; };
 
 // sum16 (mcg_grad.hpp) in double
 MCG_DEV double sum16d(double x) {
@@ -72,17 +69,18 @@ MCG_DEV double sum16d(double x) {
   return x;
 }
 
-MCG_DEV Rows pick_rows(const Rows& x, const Rows& y, int k) {
-  Rows z;
+// R[k] by selects, as pick() of a Net (mcg_policy.hpp); a value net has no d2 rows
+MCG_DEV GRows pick(const GRows& x, const GRows& y, int k) {
+  GRows z = {};
 #pragma unroll
   for (int L = 0; L <= MAX_LAYERS; L++) { z.x[L] = k ? y.x[L] : x.x[L]; z.d[L] = k ? y.d[L] : x.d[L]; }
-  z.ls = k ? y.ls : x.ls; z.rows = k ? y.rows : x.rows; z.fr = k ? y.fr : x.fr; z.base = k ? y.base : x.base;
+  z.d2 = k ? y.d2 : x.d2; z.rows = k ? y.rows : x.rows; z.fr = k ? y.fr : x.fr; z.base = k ? y.base : x.base;
   return z;
 }
 
 // GRAD = false: mcg_policy_evaluate (no `work`);  true: the forward, the loss's derivative and the backward pass of one tile and net.
 template <int MT, bool GRAD>
-__global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1, Batch X, Hyper H, float* work, EvalOut E) {
+__global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, GRows R0, GRows R1, Batch X, Hyper H, float* work, EvalOut E) {
   const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
   const int tile = blockIdx.x, s = tile * TILE + i;
   const bool live = s < P.N;
@@ -90,34 +88,14 @@ __global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1
   const int k = blockIdx.y;              // 0: the value net; 1: the policy net
   if (!GRAD && k == 0 && !E.value) return;
   const Net net = pick(P.net[0], P.net[1], k);
-  const Rows R = pick_rows(R0, R1, k);
+  const GRows R = pick(R0, R1, k);
   float* chunk = GRAD ? work + R.base + (size_t)tile * R.rows * TILE : nullptr;
   const int n = net.n;
   // ---- forward
-  f4 a[MT], b[MT];
+  f4 a[MT];
   first_layer<MT, float>(P, net, X.obs, X.ach, X.des, row, g, lane, a);
-  if (GRAD) {
-    for (int f = g; f < R.fr; f += 4) {  // the features as rows: the first layer's X (columns from D + 6 on are zeros)
-      float x = 0.0f;
-      if (f < 3) x = X.ach[(size_t)row * 3 + f];
-      else if (f < 6) x = X.des[(size_t)row * 3 + (f - 3)];
-      else if (f < P.D + 6) x = X.obs[(size_t)row * P.D + (f - 6)];
-      chunk[(size_t)(R.x[0] + f) * TILE + i] = x;
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, a[t][r]);
-  if (GRAD) store_rows<MT>(chunk, R.x[1], net.nt[0], a, g, i);
-  for (int L = 1; L < n; L++) {
-    dense<MT, MT>(P, net, L, L == 1 ? net.nt[0] : net.nt[1], L == 1 ? net.nt[1] : net.nt[2], a, b, g, lane);
-#pragma unroll
-    for (int t = 0; t < MT; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, b[t][r]);
-    if (GRAD) store_rows<MT>(chunk, L == 1 ? R.x[2] : R.x[3], L == 1 ? net.nt[1] : net.nt[2], a, g, i);
-  }
+  if (GRAD) store_features(chunk, R.x[0], R.fr, P.D, X.obs, X.ach, X.des, row, g, i);
+  hidden_rows<MT>(P, net, R, chunk, GRAD, a, g, i, lane);
   f4 head[1];
   dense<MT, 1>(P, net, n, n == 1 ? net.nt[0] : n == 2 ? net.nt[1] : net.nt[2], 1, a, head, g, lane);
   const f4 h = head[0];                  // lane 16 g + i: rows 4 g + r of the head, sample i
@@ -196,71 +174,22 @@ __global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, Rows R0, Rows R1
       work[SUMS + 8 * (size_t)tile + 4] = sk; work[SUMS + 8 * (size_t)tile + 5] = sc;
     }
 #pragma unroll
-    for (int r = 0; r < 4; r++) chunk[(size_t)(R.ls + 4 * g + r) * TILE + i] = dl[r];
+    for (int r = 0; r < 4; r++) chunk[(size_t)(R.d2 + 4 * g + r) * TILE + i] = dl[r];
   }
   // ---- backward: d[t] is dZ of layer L in the accumulator layout; dZ of layer L - 1 = act'(y) * (W_L^T dZ_L)
-  f4 d[MT], e[MT];
+  f4 d[MT];
 #pragma unroll
   for (int t = 0; t < MT; t++) d[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
   d[0] = dh;
   store_rows<MT>(chunk, sel4(R.d, n), 1, d, g, i);
-  for (int L = n; L >= 1; L--) {
-    const int nto = L == n ? 1 : (L == 1 ? net.nt[1] : net.nt[2]);              // tiles of dZ_L: the product's k
-    const int nti = L == 1 ? net.nt[0] : L == 2 ? net.nt[1] : net.nt[2];        // tiles of layer L's input: the product's rows
-    const float* __restrict__ W = P.blob + sel4(net.w, L);
-    const float* y = chunk + (size_t)sel4(R.x, L) * TILE;                       // the input's activations, as this lane stored them
-    const int nkb = 4 * nti;
-#pragma unroll
-    for (int T = 0; T < MT; T++) {
-      e[T] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (T < nti) {
-        f4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-          if (t < nto) {
-            const f4 w = *reinterpret_cast<const f4*>(W + (size_t)(t * nkb + 4 * T + (i & 3)) * WAVE + 16 * (i >> 2) + 4 * g);
-#pragma unroll
-            for (int r = 0; r < 4; r++) c = mfma(w[r], d[t][r], c);
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const float yy = y[(size_t)(16 * T + 4 * g + r) * TILE + i];
-          c[r] *= P.act == MCG_POLICY_TANH ? 1.0f - yy * yy : (yy > 0.0f ? 1.0f : 0.0f);
-        }
-        e[T] = c;
-      }
-    }
-    store_rows<MT>(chunk, sel4(R.d, L - 1), nti, e, g, i);
-#pragma unroll
-    for (int t = 0; t < MT; t++) d[t] = e[t];
-  }
-}
-
-// One 16 x 16 block of dW (or 16 biases) over the tiles of one part -> its place in the part's partial blob.
-__global__ __launch_bounds__(WAVE) void grad_dw_kernel(Blocks Q, const float* __restrict__ work, float* __restrict__ partials,
-                                                       long long blob_floats, int ntiles, int tpp) {
-  const int blk = blockIdx.x, part = blockIdx.y;
-  Block me = Q.l[0];
-#pragma unroll
-  for (int q = 1; q < MAX_BLOCK_LAYERS; q++)
-    if (q < Q.n && blk >= Q.l[q].blk0) me = Q.l[q];              // (constant indices: selects, no scratch)
-  dw_block(me, blk, part, work, partials, blob_floats, ntiles, tpp);
+  walk_back<MT, true>(P, net, R, chunk, n, 0, d, g, i);
 }
 
 // grad[p] = the partial blobs' sum in part order (log_std: and the entropy term's -ent_coef); the last block: the tiles' sums -> stats.
 __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restrict__ work, const float* __restrict__ partials, int parts,
                                                           long long blob_floats, int ntiles, const float* __restrict__ blob, int log_std,
                                                           int A, Hyper H, float* __restrict__ grad, float* __restrict__ stats) {
-  if (blockIdx.x < gridDim.x - 1) {
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= blob_floats) return;
-    float sum = sum_parts(partials, parts, blob_floats, p);
-    if (p >= log_std && p < log_std + A) sum -= H.ent_coef;
-    grad[p] = sum;
-    return;
-  }
-  if (threadIdx.x >= WAVE) return;
+  if (reduced_parts(partials, parts, blob_floats, grad, log_std, A, H.ent_coef) || threadIdx.x >= WAVE) return;
   float acc[3] = {0.0f, 0.0f, 0.0f};
   double term = 0.0;
   constexpr int slot[3] = {2, 4, 5};
@@ -270,9 +199,8 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
     term += *reinterpret_cast<const double*>(work + SUMS + 8 * (size_t)t + 6);
   }
 #pragma unroll
-  for (int j = 0; j < 3; j++)
-    for (int m = 32; m >= 1; m >>= 1) acc[j] += __shfl_xor(acc[j], m);
-  for (int m = 32; m >= 1; m >>= 1) term += __shfl_xor(term, m);
+  for (int j = 0; j < 3; j++) acc[j] = sum64(acc[j]);
+  term = sum64(term);
   if (threadIdx.x == 0) {
     float ent = 0.0f;
     for (int c = 0; c < A; c++) ent += ENTROPY_0 + blob[log_std + c];
@@ -308,17 +236,8 @@ __global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict
   if (threadIdx.x == 0) norm_out[0] = (float)sqrt(sum);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ grad, float* __restrict__ m,
-                                                   float* __restrict__ v, long long n, const float* __restrict__ norm, float max_norm,
-                                                   float beta1, float beta2, float step_size, float bc2_sqrt, float eps) {
-  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const float coef = max_norm > 0.0f ? fminf(1.0f, max_norm / (norm[0] + 1e-6f)) : 1.0f;
-  adam_one(p, grad[j] * coef, m, v, j, beta1, beta2, 1.0f - beta1, 1.0f - beta2, step_size, bc2_sqrt, eps);
-}
-
 // ------------------------------------------------------------------------------------------------------- host side
-struct Layout { Rows rows[2]; Blocks blocks; int ntiles, tpp, parts; long long partials, floats; };
+struct Layout { GRows rows[2]; Blocks blocks; int ntiles, tpp, parts; long long partials, floats; };
 
 // The row map, the block list and the split of `work` for a planned shape and B.
 Layout layout(const Pol& P, int64_t B, int widest) {
@@ -328,37 +247,25 @@ Layout layout(const Pol& P, int64_t B, int widest) {
   const int fr = (P.D + 6 + 15) / 16 * 16;
   long long at = SUMS + 8ll * Y.ntiles;
   for (int k = 0; k < 2; k++) {
-    const Net& net = P.net[k];
-    Rows& R = Y.rows[k];
-    int row = 0;
-    R.fr = fr; R.x[0] = 0; row += fr;
-    for (int L = 0; L < net.n; L++) { R.x[L + 1] = row; row += 16 * net.nt[L]; }
-    for (int L = 0; L <= net.n; L++) { R.d[L] = row; row += L < net.n ? 16 * net.nt[L] : 16; }
-    R.ls = row;
-    if (k == 1) row += 16;
-    R.rows = row; R.base = at;
-    at += (long long)Y.ntiles * row * TILE;
+    GRows& R = Y.rows[k];
+    R.rows = number_rows(R, P.net[k], fr, false);
+    if (k == 1) { R.d2 = R.rows; R.rows += 16; }               // the log_std terms: a second head's dZ rows
+    R.base = at;
+    at += (long long)Y.ntiles * R.rows * TILE;
   }
   Y.partials = at;
-  int blk = 0, q = 0;
+  int blk = 0;
   for (int k = 1; k >= 0; k--) {         // the blob's order: the policy net first
     const Net& net = P.net[k];
-    const Rows& R = Y.rows[k];
-    for (int L = 0; L <= net.n; L++) {
-      Block& b = Y.blocks.l[q++];
-      b.blk0 = blk; b.nT = L < net.n ? net.nt[L] : 1; b.ncb = L == 0 ? fr / 16 : net.nt[L - 1];
-      b.xrow = R.x[L]; b.drow = R.d[L]; b.w = net.w[L]; b.b = net.b[L]; b.nkb = L == 0 ? P.kb0 : 4 * net.nt[L - 1]; b.first = L == 0;
-      b.rows = R.rows; b.base = R.base; b.cols = L == 0 ? P.D + 6 : ALL_COLUMNS; b.nb = 1;
-      blk += b.nT * (b.ncb + 1);
-    }
+    const GRows& R = Y.rows[k];
+    for (int L = 0; L <= net.n; L++) add_block(Y.blocks, blk, layer_block(P, net, R, L));
     if (k == 1) {                        // log_std: a bias whose dZ is the policy net's log_std rows
-      Block& b = Y.blocks.l[q++];
-      b = Block{};
-      b.blk0 = blk; b.nT = 1; b.ncb = 0; b.nb = 1; b.drow = R.ls; b.b = P.log_std; b.rows = R.rows; b.base = R.base;
-      blk += 1;
+      Block b = {};
+      b.nT = 1; b.ncb = 0; b.nb = 1; b.drow = R.d2; b.b = P.log_std; b.rows = R.rows; b.base = R.base;
+      add_block(Y.blocks, blk, b);
     }
   }
-  Y.blocks.n = q; Y.blocks.total = blk;
+  Y.blocks.total = blk;
   return Y;
 }
 
@@ -366,9 +273,7 @@ int check_batch(const char* who, const mcg_rollout_batch* batch, int64_t B) {
   if (!batch) return mcg_fail(MCG_ERR_ARG, "%s: null mcg_rollout_batch", who);
   if (!batch->obs || !batch->achieved || !batch->desired || !batch->action)
     return mcg_fail(MCG_ERR_ARG, "%s: obs, achieved, desired and action of the batch are required", who);
-  if (B < 1) return mcg_fail(MCG_ERR_ARG, "%s: B must be >= 1", who);
-  if (B * MAX_ACT >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: B must be below 2^27", who);
-  return MCG_OK;
+  return checked_rows(who, B) ? MCG_OK : MCG_ERR_ARG;
 }
 
 }  // namespace
@@ -385,7 +290,7 @@ int mcg_policy_evaluate(const mcg_policy* pol, const mcg_rollout_batch* batch, i
   P.N = (int)B;
   const Batch X = {batch->obs, batch->achieved, batch->desired, batch->action, nullptr, nullptr, nullptr};
   const EvalOut E = {out->value, out->log_prob, out->entropy};
-  const Rows none = {};
+  const GRows none = {};
   const dim3 grid(blocks(B, TILE), (out->log_prob || out->entropy) ? 2 : 1), block(WAVE);
   if (widest_layer(pol) <= 64) hipLaunchKernelGGL((grad_tile_kernel<4, false>), grid, block, 0, (hipStream_t)stream, P, none, none, X, Hyper{}, nullptr, E);
   else hipLaunchKernelGGL((grad_tile_kernel<16, false>), grid, block, 0, (hipStream_t)stream, P, none, none, X, Hyper{}, nullptr, E);
@@ -395,7 +300,7 @@ int mcg_policy_evaluate(const mcg_policy* pol, const mcg_rollout_batch* batch, i
 int64_t mcg_policy_grad_work_floats(const mcg_policy* pol, int64_t B) {
   Pol P = {};
   const char* why = nullptr;
-  if (!pol || B < 1 || B * MAX_ACT >= (1ll << 31)) return 0;
+  if (!pol || !rows_in_range(B)) return 0;
   const int64_t floats = plan(pol->obs_dim, pol->act_dim, pol->n_pi, pol->pi_width, pol->n_vf, pol->vf_width, &P, &why);
   if (floats == 0) return 0;
   const Layout Y = layout(P, B, widest_layer(pol));
@@ -415,11 +320,8 @@ int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64
   if (hyper->loss_kind == MCG_LOSS_PPO && !(hyper->clip_range > 0.0f)) return mcg_fail(MCG_ERR_ARG, "%s: clip_range must be > 0 for MCG_LOSS_PPO", who);
   if (!batch->advantage || !batch->returns) return mcg_fail(MCG_ERR_ARG, "%s: advantage and returns of the batch are required", who);
   if (hyper->loss_kind == MCG_LOSS_PPO && !batch->old_log_prob) return mcg_fail(MCG_ERR_ARG, "%s: old_log_prob of the batch is required for MCG_LOSS_PPO", who);
-  if (!work) return mcg_fail(MCG_ERR_ARG, "%s: work is null", who);
-  if (!grad) return mcg_fail(MCG_ERR_ARG, "%s: grad is null", who);
+  if (!checked_buffer(who, work, "work") || !checked_buffer(who, grad, "grad")) return MCG_ERR_ARG;
   if (!stats) return mcg_fail(MCG_ERR_ARG, "%s: stats is null", who);
-  if (((uintptr_t)work & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: work is not 16-byte aligned", who);
-  if (((uintptr_t)grad & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: grad is not 16-byte aligned", who);
   const int widest = widest_layer(pol);
   const Layout Y = layout(P, B, widest);
   const int64_t need = Y.partials + (int64_t)Y.parts * floats;
@@ -435,7 +337,7 @@ int mcg_policy_grad(const mcg_policy* pol, const mcg_rollout_batch* batch, int64
   const dim3 grid(Y.ntiles, 2), block(WAVE);
   if (widest <= 64) hipLaunchKernelGGL((grad_tile_kernel<4, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});
   else hipLaunchKernelGGL((grad_tile_kernel<16, true>), grid, block, 0, st, P, Y.rows[0], Y.rows[1], X, H, work, EvalOut{});
-  hipLaunchKernelGGL(grad_dw_kernel, dim3(Y.blocks.total, Y.parts), block, 0, st, Y.blocks, (const float*)work, work + Y.partials,
+  hipLaunchKernelGGL(dw_kernel, dim3(Y.blocks.total, Y.parts), block, 0, st, Y.blocks, (const float*)work, work + Y.partials,
                      (long long)floats, Y.ntiles, Y.tpp);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3(blocks(floats, 256) + 1), dim3(256), 0, st, (const float*)work,
                      (const float*)(work + Y.partials), Y.parts, (long long)floats, Y.ntiles, pol->blob, P.log_std, P.A, H, grad, stats);
@@ -448,21 +350,17 @@ int mcg_policy_adam(const mcg_policy* pol, const float* grad, float* m, float* v
   Pol P = {};
   const int64_t floats = checked_plan(who, pol, &P);
   if (floats == 0) return MCG_ERR_ARG;
-  if (!grad) return mcg_fail(MCG_ERR_ARG, "%s: grad is null", who);
-  if (!m) return mcg_fail(MCG_ERR_ARG, "%s: m is null", who);
-  if (!v) return mcg_fail(MCG_ERR_ARG, "%s: v is null", who);
+  if (!checked_buffer(who, grad, "grad") || !checked_buffer(who, m, "m") || !checked_buffer(who, v, "v")) return MCG_ERR_ARG;
   if (!norm_out) return mcg_fail(MCG_ERR_ARG, "%s: norm_out is null", who);
-  if (((uintptr_t)grad & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: grad is not 16-byte aligned", who);
-  if (((uintptr_t)m & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: m is not 16-byte aligned", who);
-  if (((uintptr_t)v & 15) != 0) return mcg_fail(MCG_ERR_ARG, "%s: v is not 16-byte aligned", who);
   if (step < 1) return mcg_fail(MCG_ERR_ARG, "%s: step must be >= 1", who);
   if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return mcg_fail(MCG_ERR_ARG, "%s: beta1 and beta2 must be in [0, 1)", who);
   if (!std::isfinite(lr) || !(eps >= 0.0) || !std::isfinite(max_grad_norm)) return mcg_fail(MCG_ERR_ARG, "%s: lr, eps and max_grad_norm must be finite, eps >= 0", who);
-  const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+  const AdamStep a = adam_step(step, lr, beta1, beta2);
+  const float max_norm = (float)max_grad_norm, b1 = (float)beta1, b2 = (float)beta2;
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(grad_norm_kernel, dim3(1), dim3(1024), 0, st, grad, (long long)floats, norm_out);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks(floats, 256)), dim3(256), 0, st, const_cast<float*>(pol->blob), grad, m, v, (long long)floats,
-                     (const float*)norm_out, (float)max_grad_norm, (float)beta1, (float)beta2, (float)(lr / bc1), (float)std::sqrt(bc2),
+  hipLaunchKernelGGL(adam_kernel<256>, dim3(blocks(floats, 256)), dim3(256), 0, st, const_cast<float*>(pol->blob), grad, m, v, (long long)floats,
+                     max_norm > 0.0f ? (const float*)norm_out : nullptr, max_norm, b1, b2, 1.0f - b1, 1.0f - b2, a.step_size, a.bc2_sqrt,
                      (float)eps);
   return launched("mcg_policy_adam");
 }

@@ -239,13 +239,7 @@ inline bool checked_sac(const char* who, const mcg_sac* sac, int need, Sac* S) {
   return true;
 }
 
-// ---- an entry's other arguments, each refused in the entry's name
-inline bool checked_rows(const char* who, int64_t B) {
-  if (B < 1) { mcg::mcg_fail(MCG_ERR_ARG, "%s: B must be >= 1", who); return false; }
-  if (B * MAX_ACT >= (1ll << 31)) { mcg::mcg_fail(MCG_ERR_ARG, "%s: B must be below 2^27", who); return false; }
-  return true;
-}
-
+// ---- an entry's other arguments, each refused in the entry's name (checked_rows: mcg_policy.hpp)
 inline bool checked_envs(const char* who, long long n_envs) {
   if (n_envs < 1) { mcg::mcg_fail(MCG_ERR_ARG, "%s: n_envs must be >= 1", who); return false; }
   if (n_envs * MAX_ACT >= (1ll << 31)) { mcg::mcg_fail(MCG_ERR_ARG, "%s: n_envs must be below 2^27", who); return false; }

@@ -1,10 +1,11 @@
 // mcg_sac_grad.hip -- SAC's update (include/mcg.h: mcg_sac_critic_grad, mcg_sac_actor_grad, mcg_sac_alpha_step, mcg_sac_adam): the
 // critic loss's gradient over the critic blob, the actor loss's gradient over the actor blob through the twin critics as constants,
 // the entropy coefficient's step, and Adam on a bare blob.  A code object of its own, as mcg_sac.hip, whose plan, actor draw and host
-// checks it shares (mcg_sac.hpp); the critic tile kernel, the dW kernel, the forward with rows kept, the walk back and both entries'
-// layouts of `work` are mcg_sac_grad.hpp's, shared with TD3 / DDPG (mcg_td3_grad.hip); the three products of a layer, the work split (a
-// tile kernel, a dW kernel per block and part, a reduce in part order) and their helpers are mcg_policy_grad.hip's (its head states
-// them; mcg_grad.hpp holds what both use).  Here: SAC's actor tile kernel, its reduce, the alpha step and Adam.
+// checks it shares (mcg_sac.hpp); the critic's forward, the critic tile kernel and both entries' layouts of `work` are
+// mcg_sac_grad.hpp's, shared with TD3 / DDPG (mcg_td3_grad.hip); the row map, the forward with rows kept, the walk back, the dW kernel,
+// the reduce's helpers and Adam's kernel are mcg_grad.hpp's, shared with PPO as well; the three products of a layer and the work split
+// (a tile kernel, a dW kernel per block and part, a reduce in part order) are stated at mcg_policy_grad.hip's head.  Here: SAC's actor
+// tile kernel, its reduce's statistics, the alpha step and Adam's entry.
 // Float32 throughout on v_mfma_f32_16x16x4_f32; deterministic: no atomics, every sum in an order that the shape and B alone fix.
 //
 // ---- The critic tile kernel (critic_tile_kernel<MT, false>, mcg_sac_grad.hpp): one wave per (tile of 16 samples, critic).  The forward on (features, action) with mcg_sac.hip's
@@ -25,8 +26,10 @@
 // their q sums; actor entry: s = 0 the loss terms, 1 the log-probs); then the row chunks (struct GRows) per net and tile; then `parts`
 // partial blobs.  Every float that is read was written by the same call.  A ragged last tile's extra lanes read the last valid sample
 // and get dZ = +-0 at the head, so that every product they enter adds exactly nothing.
-#include "mcg_sac_grad.hpp"     // GRows, SBlocks, critic_tile_kernel, dw_kernel, hidden_rows, critic_forward, walk_back, wt_acc, Layout,
-                                // critic_layout, actor_layout, checked_work (shared with mcg_td3_grad.hip); mcg_grad.hpp, mcg_sac.hpp
+#include "mcg_sac_grad.hpp"     // SRows, critic_forward, critic_tile_kernel, Layout, critic_layout, actor_layout (shared with
+                                // mcg_td3_grad.hip); mcg_sac.hpp; mcg_grad.hpp: GRows, store_features, hidden_rows, walk_back, wt_acc,
+                                // act_prime, dw_kernel, reduced_parts, sum64, block_sum, adam_one, adam_kernel, adam_step, checked_buffer,
+                                // checked_work
 
 using namespace mcg;
 
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(2 * WAVE) void sac_actor_tile_kernel(Sac S, GRows R
   {
     f4 a[MT];
     first_layer<MT, float>(PA, net, X.obs, X.ach, X.des, row, g, lane, a);
-    if (wave == 0) store_features(chunk, RA.x[0], RA.fr, PA.D, X, row, g, i);
+    if (wave == 0) store_features(chunk, RA.x[0], RA.fr, PA.D, X.obs, X.ach, X.des, row, g, i);
     hidden_rows<MT>(PA, net, RA, chunk, wave == 0, a, g, i, lane);
     dense<MT, 1>(PA, PA.net[1], n, last_tiles(net), 1, a, mu, g, lane);
     dense<MT, 1>(PA, PA.net[0], n, last_tiles(net), 1, a, ls, g, lane);
@@ -146,19 +149,13 @@ __global__ __launch_bounds__(256) void sac_reduce_kernel(const float* __restrict
                                                          long long blob_floats, int ntiles, int actor, float inv_b, float ent_coef,
                                                          const float* __restrict__ log_ent_coef, float* __restrict__ grad,
                                                          float* __restrict__ stats) {
-  if (blockIdx.x < gridDim.x - 1) {
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p < blob_floats) grad[p] = sum_parts(partials, parts, blob_floats, p);
-    return;
-  }
-  if (threadIdx.x >= WAVE) return;
+  if (reduced_parts(partials, parts, blob_floats, grad) || threadIdx.x >= WAVE) return;
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   for (int t = threadIdx.x; t < ntiles; t += WAVE)
 #pragma unroll
     for (int j = 0; j < 4; j++) acc[j] += work[4 + 8 * (size_t)t + j];
 #pragma unroll
-  for (int j = 0; j < 4; j++)
-    for (int m = 32; m >= 1; m >>= 1) acc[j] += __shfl_xor(acc[j], m);
+  for (int j = 0; j < 4; j++) acc[j] = sum64(acc[j]);
   if (threadIdx.x != 0) return;
   if (actor) {
     stats[1] = acc[0] * inv_b;
@@ -186,13 +183,6 @@ __global__ __launch_bounds__(1024) void sac_alpha_kernel(float* __restrict__ log
   if (adam) adam_one(log_ent_coef, gj, m, v, 0, beta1, beta2, omb1, omb2, step_size, bc2_sqrt, eps);
 }
 
-__global__ __launch_bounds__(256) void sac_adam_kernel(float* __restrict__ p, const float* __restrict__ grad, float* __restrict__ m,
-                                                       float* __restrict__ v, long long n, float beta1, float beta2, float omb1, float omb2,
-                                                       float step_size, float bc2_sqrt, float eps) {
-  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (j < n) adam_one(p, grad[j], m, v, j, beta1, beta2, omb1, omb2, step_size, bc2_sqrt, eps);
-}
-
 // ------------------------------------------------------------------------------------------------------- host side
 bool checked_adam(const char* who, int64_t step, double lr, double beta1, double beta2, double eps) {
   if (step < 1) { mcg_fail(MCG_ERR_ARG, "%s: step must be >= 1", who); return false; }
@@ -211,7 +201,7 @@ int64_t mcg_sac_grad_work_floats(const mcg_sac* sac, int64_t B) {
   Sac S = {};
   const char* why = nullptr;
   int64_t actor = 0, critic = 0;
-  if (!sac || B < 1 || B * MAX_ACT >= (1ll << 31)) return 0;
+  if (!sac || !rows_in_range(B)) return 0;
   if (blob_plan(sac->obs_dim, sac->act_dim, sac->n_pi, sac->pi_width, sac->n_qf, sac->qf_width, 2, true, &S, &actor, &critic, &why) == 0) return 0;
   const long long c = critic_layout(S, B, widest(sac, false, true), critic, 2).need;
   const long long a = actor_layout(S, B, widest(sac, true, false), actor, true, 2).need;
@@ -291,9 +281,9 @@ int mcg_sac_alpha_step(float* log_ent_coef, const float* logp, int64_t B, float 
   if (!checked_adam(who, step, lr, beta1, beta2, eps)) return MCG_ERR_ARG;
   const int adam = lr > 0.0;
   if (adam && (!m || !v)) return mcg_fail(MCG_ERR_ARG, "%s: m and v are required where lr > 0", who);
-  const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+  const AdamStep a = adam_step(step, lr, beta1, beta2);
   hipLaunchKernelGGL(sac_alpha_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, log_ent_coef, logp, (long long)B, target_entropy, m, v, adam,
-                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps, grad_out, stats);
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), a.step_size, a.bc2_sqrt, (float)eps, grad_out, stats);
   return launched(who);
 }
 
@@ -304,9 +294,10 @@ int mcg_sac_adam(float* blob, const float* grad, float* m, float* v, int64_t flo
     return MCG_ERR_ARG;
   if (floats < 1 || floats >= (1ll << 31)) return mcg_fail(MCG_ERR_ARG, "%s: floats must be in [1, 2^31)", who);
   if (!checked_adam(who, step, lr, beta1, beta2, eps)) return MCG_ERR_ARG;
-  const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
-  hipLaunchKernelGGL(sac_adam_kernel, dim3(blocks(floats, 256)), dim3(256), 0, (hipStream_t)stream, blob, grad, m, v, (long long)floats,
-                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps);
+  const AdamStep a = adam_step(step, lr, beta1, beta2);
+  hipLaunchKernelGGL(adam_kernel<256>, dim3(blocks(floats, 256)), dim3(256), 0, (hipStream_t)stream, blob, grad, m, v, (long long)floats,
+                     (const float*)nullptr, 0.0f, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), a.step_size,
+                     a.bc2_sqrt, (float)eps);
   return launched(who);
 }
 

@@ -1,9 +1,10 @@
 // mcg_td3_grad.hip -- TD3's and DDPG's update (include/mcg.h: mcg_td3_critic_grad, mcg_td3_actor_grad; Adam is mcg_sac_adam): the
 // critic loss's gradient over the critic blob and the deterministic actor loss's gradient over the actor blob through qf0 as a
-// constant.  A code object of its own, as mcg_td3.hip, whose host checks it shares (mcg_td3.hpp); the critic tile kernel, the dW
-// kernel, the forward with its rows kept, the walk back, the row map, the block list and both entries' layouts of `work` are
-// mcg_sac_grad.hpp's single definitions, the dW block and the sum in part order mcg_grad.hpp's (mcg_sac_grad.hip's and
-// mcg_policy_grad.hip's heads state the work split).  Here: TD3's actor tile kernel and its reduce.  Float32 throughout on
+// constant.  A code object of its own, as mcg_td3.hip, whose host checks it shares (mcg_td3.hpp); the critic's forward, the critic
+// tile kernel and both entries' layouts of `work` are mcg_sac_grad.hpp's single definitions; the row map, the block list, the forward
+// with its rows kept, the walk back, the dW kernel and the reduce's helpers are mcg_grad.hpp's, shared with PPO as well
+// (mcg_sac_grad.hip's and mcg_policy_grad.hip's heads state the work split).  Here: TD3's actor tile kernel and its reduce's
+// statistics.  Float32 throughout on
 // v_mfma_f32_16x16x4_f32; deterministic: no atomics, every sum in an order that the shape and B alone fix.
 //
 // ---- The critic tile kernel: critic_tile_kernel<MT, true> (mcg_sac_grad.hpp), one wave per (tile of 16 samples, critic), with the
@@ -16,8 +17,8 @@
 // ---- `work` (floats): [0..3] unused; [4 + 8 tile + s] the tile's sums (critic entry: s = k the squared errors of critic k, s = 2 + k
 // its q sum; actor entry: s = 0 the q sum); then the row chunks per net and tile; then `parts` partial blobs.  Every float that is read
 // was written by the same call.  A ragged last tile's extra lanes read the last valid sample and get dZ = +-0 at the head.
-#include "mcg_sac_grad.hpp"     // GRows, SRows, critic_tile_kernel, dw_kernel, hidden_rows, critic_forward, walk_back, wt_acc, critic_layout,
-                                // actor_layout, checked_work, checked_buffer; mcg_grad.hpp
+#include "mcg_sac_grad.hpp"     // SRows, critic_forward, critic_tile_kernel, Layout, critic_layout, actor_layout; mcg_grad.hpp: GRows,
+                                // store_features, hidden_rows, walk_back, wt_acc, dw_kernel, reduced_parts, sum64, checked_buffer, checked_work
 #include "mcg_td3.hpp"          // checked_td3, set_critics, tanh_head
 
 using namespace mcg;
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(WAVE) void td3_actor_tile_kernel(Sac S, GRows RA, G
   {
     f4 a[MT];
     first_layer<MT, float>(PA, net, X.obs, X.ach, X.des, row, g, lane, a);
-    store_features(chunk, RA.x[0], RA.fr, PA.D, X, row, g, i);
+    store_features(chunk, RA.x[0], RA.fr, PA.D, X.obs, X.ach, X.des, row, g, i);
     hidden_rows<MT>(PA, net, RA, chunk, true, a, g, i, lane);
     dense<MT, 1>(PA, net, n, last_tiles(net), 1, a, z, g, lane);
   }
@@ -86,12 +87,7 @@ __global__ __launch_bounds__(WAVE) void td3_actor_tile_kernel(Sac S, GRows RA, G
 __global__ __launch_bounds__(256) void td3_reduce_kernel(const float* __restrict__ work, const float* __restrict__ partials, int parts,
                                                          long long blob_floats, int ntiles, int actor, int n_critics, float inv_b,
                                                          float* __restrict__ grad, float* __restrict__ stats) {
-  if (blockIdx.x < gridDim.x - 1) {
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p < blob_floats) grad[p] = sum_parts(partials, parts, blob_floats, p);
-    return;
-  }
-  if (threadIdx.x >= WAVE) return;
+  if (reduced_parts(partials, parts, blob_floats, grad) || threadIdx.x >= WAVE) return;
   const bool two = !actor && n_critics == 2;
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   for (int t = threadIdx.x; t < ntiles; t += WAVE) {
@@ -101,8 +97,7 @@ __global__ __launch_bounds__(256) void td3_reduce_kernel(const float* __restrict
     if (two) { acc[1] += w[1]; acc[3] += w[3]; }
   }
 #pragma unroll
-  for (int j = 0; j < 4; j++)
-    for (int m = 32; m >= 1; m >>= 1) acc[j] += __shfl_xor(acc[j], m);
+  for (int j = 0; j < 4; j++) acc[j] = sum64(acc[j]);
   if (threadIdx.x != 0) return;
   if (actor) {
     const float mean = acc[0] * inv_b;
@@ -122,7 +117,7 @@ int64_t mcg_td3_grad_work_floats(const mcg_td3* td3, int64_t B) {
   Sac S = {};
   const char* why = nullptr;
   int64_t actor = 0, critic = 0;
-  if (!td3 || B < 1 || B * MAX_ACT >= (1ll << 31)) return 0;
+  if (!td3 || !rows_in_range(B)) return 0;
   if (blob_plan(td3->obs_dim, td3->act_dim, td3->n_pi, td3->pi_width, td3->n_qf, td3->qf_width, td3->n_critics, false, &S, &actor, &critic,
                 &why) == 0)
     return 0;
