@@ -18,68 +18,33 @@ the C side (``mcg_policy_forward``, csrc/mcg_policy.hip) keeps no state and no c
 No CPU or PyTorch fallback: the kernel is the only implementation of the forward.  ``evaluate_actions`` is the same forward on a
 minibatch of the rollout buffer; the loss, its gradient and Adam on the blob are ``PPOUpdate`` (policy_update.py).  A caller with an
 optimiser of its own (any ``nn.Module`` with SB3's parameter names) repacks the blob with ``load_state_dict`` after an update.
+
+What is PPO's own here: the blob's order and SB3's names for it, the orthogonal start, the refusals of SB3 configurations, the two
+entries' marshalling.  The layers' packing, the rows' check, the constructor's steps and the state dict both ways are _nets.py's,
+shared with SAC and TD3 / DDPG.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import Optional, Sequence
 
 import torch
 
 from . import _abi
-from ._devbuf import DeviceBuffer
+from ._nets import _ACTIVATIONS, Nets, _arr, _hidden_of, checked_rows, names_of, pack_net, unpack_net
 
-_ACTIVATIONS = {"tanh": _abi.POLICY_TANH, "relu": _abi.POLICY_RELU}
-_HEADS = ("action_net.weight", "action_net.bias", "value_net.weight", "value_net.bias", "log_std")
+# minibatch_rows(observations, actions, obs_dim, act_dim, who): checks a minibatch as ``RolloutBuffer.get`` yields it
+# (``RolloutSamples.observations``: the dict of float32 tensors, and ``actions``) -> its rows B.  Needs no device.
+minibatch_rows = functools.partial(checked_rows, words=("RolloutBuffer", "minibatch", "the policy is the MLP", "ActorCritic", True))
 
 
 # ------------------------------------------------------------------------------------------------------------ the blob
 # csrc/mcg_policy.hip's head states the layout; restated: the policy net's layers, its head (A rows padded to 16), the value net's
-# layers, its head (1 row padded to 16), log_std padded to 16.  A layer is its tiles -- tile (T, kb), float 16 g + i = W[16 T + i][k(kb, g)]
-# -- then its bias.  First layer: k(kb, g) = 4 kb + g over the D + 6 columns padded with zeros to a multiple of 4.  Later layers:
-# k(4 t + r, g) = 16 t + 4 g + r.
-def _layer_names(net: str, n: int):
-    return [f"mlp_extractor.{net}.{2 * L}" for L in range(n)]
-
-
-def state_names(n_pi: int, n_vf: int):
-    """The keys of a state dict, in the blob's order."""
-    names = []
-    for trunk, head in ((_layer_names("policy_net", n_pi), "action_net"), (_layer_names("value_net", n_vf), "value_net")):
-        for m in trunk + [head]:
-            names += [m + ".weight", m + ".bias"]
-    return names + ["log_std"]
-
-
-def _pack_layer(W: torch.Tensor, b: torch.Tensor, first: bool):
-    out, k = W.shape
-    out_p = -(-out // 16) * 16
-    k_p = -(-k // 4) * 4 if first else k                  # (a later layer's input is a trunk width: a multiple of 16)
-    Wp = torch.zeros(out_p, k_p, dtype=torch.float32, device=W.device)
-    Wp[:out, :k] = W
-    bp = torch.zeros(out_p, dtype=torch.float32, device=W.device)
-    bp[:out] = b
-    if first:
-        tiles = Wp.view(out_p // 16, 16, k_p // 4, 4).permute(0, 2, 3, 1)                    # [T, kb, g, i] of W[16 T + i][4 kb + g]
-    else:
-        tiles = Wp.view(out_p // 16, 16, k_p // 16, 4, 4).permute(0, 2, 4, 3, 1)             # [T, t, r, g, i] of W[16 T + i][16 t + 4 g + r]
-    return [tiles.reshape(-1), bp]
-
-
-def _unpack_layer(flat: torch.Tensor, out: int, k: int, first: bool):
-    out_p = -(-out // 16) * 16
-    k_p = -(-k // 4) * 4 if first else k
-    w, b = flat[:out_p * k_p], flat[out_p * k_p:out_p * k_p + out_p]
-    if first:
-        Wp = w.view(out_p // 16, k_p // 4, 4, 16).permute(0, 3, 1, 2)
-    else:
-        Wp = w.view(out_p // 16, k_p // 16, 4, 4, 16).permute(0, 4, 1, 3, 2)
-    return Wp.reshape(out_p, k_p)[:out, :k].clone(), b[:out].clone(), out_p * k_p + out_p
-
-
-def _shapes(obs_dim, act_dim, pi, vf):
-    """(weight key, out, in, first layer?) in the blob's order."""
+# layers, its head (1 row padded to 16), log_std padded to 16; each layer as _nets.py's pack_net packs it.
+def blob_shapes(obs_dim, act_dim, pi, vf):
+    """(weight key, out, in, first layer?) in the blob's order; the last row is the bare vector log_std."""
     rows = []
     for net, widths, head, head_out in (("policy_net", pi, "action_net", act_dim), ("value_net", vf, "value_net", 1)):
         k = obs_dim + 6
@@ -87,34 +52,22 @@ def _shapes(obs_dim, act_dim, pi, vf):
             rows.append((f"mlp_extractor.{net}.{2 * L}", w, k, L == 0))
             k = w
         rows.append((head, head_out, k, False))
-    return rows
+    return rows + [("log_std", act_dim, None, False)]
+
+
+def state_names(n_pi: int, n_vf: int):
+    """The keys of a state dict, in the blob's order."""
+    return names_of(blob_shapes(1, 1, [16] * n_pi, [16] * n_vf))
 
 
 def pack(sd: dict, obs_dim: int, act_dim: int, pi: Sequence[int], vf: Sequence[int], device=None) -> torch.Tensor:
     """A state dict under SB3's names -> the blob (float32 [blob_floats]), with plain torch ops."""
-    parts = []
-    for m, out, k, first in _shapes(obs_dim, act_dim, pi, vf):
-        W = torch.as_tensor(sd[m + ".weight"]).detach().to(device=device, dtype=torch.float32)
-        b = torch.as_tensor(sd[m + ".bias"]).detach().to(device=device, dtype=torch.float32)
-        if tuple(W.shape) != (out, k) or tuple(b.shape) != (out,):
-            raise ValueError(f"{m}: expected weight {(out, k)} and bias {(out,)}, got {tuple(W.shape)} and {tuple(b.shape)}")
-        parts += _pack_layer(W, b, first)
-    ls = torch.as_tensor(sd["log_std"]).detach().to(device=device, dtype=torch.float32)
-    if tuple(ls.shape) != (act_dim,):
-        raise ValueError(f"log_std: expected shape {(act_dim,)}, got {tuple(ls.shape)} (a state-dependent or gSDE log_std is not supported)")
-    pad = torch.zeros(16, dtype=torch.float32, device=ls.device)
-    pad[:act_dim] = ls
-    return torch.cat(parts + [pad]).contiguous()
+    return pack_net(sd, blob_shapes(obs_dim, act_dim, pi, vf), device=device)
 
 
 def unpack(blob: torch.Tensor, obs_dim: int, act_dim: int, pi: Sequence[int], vf: Sequence[int]) -> dict:
     """The inverse of ``pack``: the blob -> the state dict, bit for bit."""
-    sd, at = {}, 0
-    for m, out, k, first in _shapes(obs_dim, act_dim, pi, vf):
-        sd[m + ".weight"], sd[m + ".bias"], used = _unpack_layer(blob[at:], out, k, first)
-        at += used
-    sd["log_std"] = blob[at:at + act_dim].clone()
-    return sd
+    return unpack_net(blob, blob_shapes(obs_dim, act_dim, pi, vf))
 
 
 def _refuse_foreign(keys):
@@ -128,43 +81,13 @@ def _refuse_foreign(keys):
         raise ValueError("a features extractor with parameters is not supported: the features are the concatenated observation keys")
 
 
-def _hidden_of(sd: dict, net: str):
-    widths, L = [], 0
-    while f"mlp_extractor.{net}.{2 * L}.weight" in sd:
-        widths.append(int(sd[f"mlp_extractor.{net}.{2 * L}.weight"].shape[0]))
-        L += 1
-    return tuple(widths)
-
-
-def minibatch_rows(observations, actions, obs_dim: int, act_dim: int, who: str) -> int:
-    """Checks a minibatch as ``RolloutBuffer.get`` yields it (``RolloutSamples.observations``: the dict of float32 tensors, and
-    ``actions``) -> its rows B.  Needs no device."""
-    if not isinstance(observations, dict):
-        raise ValueError(f"{who}: observations must be the dict of float32 tensors that RolloutBuffer yields (observation, achieved_goal, "
-                         "desired_goal); the picture buffers' samples (-v1 ids) are not supported: the policy is the MLP of the -v0 state ids")
-    missing = [k for k in ("observation", "achieved_goal", "desired_goal") if k not in observations]
-    if missing:
-        raise ValueError(f"{who}: observations lacks {missing}")
-    if not torch.is_tensor(actions) or actions.dim() != 2 or actions.shape[1] != act_dim:
-        raise ValueError(f"{who}: actions: expected a float32 tensor [B, {act_dim}], got {tuple(getattr(actions, 'shape', ()))}")
-    B = int(actions.shape[0])
-    if B < 1:
-        raise ValueError(f"{who}: the minibatch is empty (B must be >= 1)")
-    for name, t, cols in (("observations['observation']", observations["observation"], obs_dim),
-                          ("observations['achieved_goal']", observations["achieved_goal"], 3),
-                          ("observations['desired_goal']", observations["desired_goal"], 3), ("actions", actions, act_dim)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise ValueError(f"{who}: {name}: expected float32, got {getattr(t, 'dtype', type(t).__name__)} (the float64 observations of "
-                             "envs.step go through RolloutBuffer, or ActorCritic.__call__)")
-        if tuple(t.shape) != (B, cols):
-            raise ValueError(f"{who}: {name}: expected shape {(B, cols)}, got {tuple(t.shape)}")
-    return B
-
-
-class ActorCritic(DeviceBuffer):
-    _FROM_ENVS = (("num_envs", "num_envs"), ("obs_dim", "obs_dim"), ("act_dim", "action_dim"))
+class ActorCritic(Nets):
     _NO_IMAGES = ("the -v1 image ids observe uint8 pictures, which SB3 gives a CNN extractor: ActorCritic is the MLP policy of the -v0 "
                   "state ids; CNN policies are not supported")
+    _CRITIC, _DICT_NOTE, _HOST = "vf", " (shared layers are not supported)", ("seed", "calls")
+    _SHAPE, _WIDTHS = "trunks {} / {}", "1 to 3 hidden layers, each width a multiple of 16, at most 256"
+    _refuse_foreign = staticmethod(_refuse_foreign)
+    _t = property(lambda self: {"blob": self._blob})      # (_blob is read at each use: it may be rebound, with _cbuf.blob)
 
     def __init__(self, envs=None, hidden=(64, 64), activation: str = "tanh", seed: int = 0, *, num_envs: Optional[int] = None,
                  obs_dim: Optional[int] = None, act_dim: Optional[int] = None, device=None, env_id_offset: Optional[int] = None):
@@ -172,39 +95,25 @@ class ActorCritic(DeviceBuffer):
         ``hidden``: the widths of both trunks, or ``dict(pi=[...], vf=[...])`` (SB3's ``net_arch``): 1 to 3 layers, multiples of 16 up
         to 256.  The weights start as SB3 initialises them (orthogonal: gain sqrt 2 in the trunks, 0.01 for the action head, 1 for the
         value head; zero biases and ``log_std``), from ``seed``."""
-        num_envs, obs_dim, act_dim = self._resolve(envs, device, dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim))
-        self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
-        if env_id_offset is None:
-            env_id_offset = int(envs._cfg.env_id_offset) if envs is not None and hasattr(envs, "_cfg") else 0
-        self.env_id_offset = int(env_id_offset)
-        if isinstance(hidden, dict):
-            if set(hidden) != {"pi", "vf"}:
-                raise ValueError("hidden: a dict must have exactly the keys 'pi' and 'vf' (shared layers are not supported)")
-            self.pi, self.vf = tuple(int(w) for w in hidden["pi"]), tuple(int(w) for w in hidden["vf"])
-        else:
-            self.pi = self.vf = tuple(int(w) for w in hidden)
-        if activation not in _ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}, got {activation!r}")
-        self.activation = activation
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.calls = 0                   # sampling calls so far: the `call` word of the noise
-        arr = lambda w: (C.c_int32 * 3)(*(list(w) + [0] * 3)[:3])
-        self.blob_floats = int(self._lib.mcg_policy_blob_floats(self.obs_dim, self.act_dim, len(self.pi), arr(self.pi), len(self.vf),
-                                                                arr(self.vf))) if len(self.pi) <= 3 and len(self.vf) <= 3 else 0
-        if self.blob_floats == 0:
-            raise ValueError(f"unsupported shape: obs_dim {self.obs_dim}, act_dim {self.act_dim} (1..16), trunks {self.pi} / {self.vf}: "
-                             "1 to 3 hidden layers, each width a multiple of 16, at most 256")
+        self._setup(envs, hidden, activation, seed, dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim), device, env_id_offset)
         self._blob = torch.zeros(self.blob_floats, dtype=torch.float32, device=self.device)
         self._cbuf = _abi.McgPolicy(blob=self._blob.data_ptr(), n_envs=self.num_envs, obs_dim=self.obs_dim, act_dim=self.act_dim,
-                                    n_pi=len(self.pi), n_vf=len(self.vf), pi_width=arr(self.pi), vf_width=arr(self.vf),
+                                    n_pi=len(self.pi), n_vf=len(self.vf), pi_width=_arr(self.pi), vf_width=_arr(self.vf),
                                     activation=_ACTIVATIONS[activation], blob_floats=self.blob_floats)
         self._load_weights(self._initial_weights())
 
     # ------------------------------------------------------------------------------------------------------- weights
+    def _nets(self):
+        return (("blob", blob_shapes(self.obs_dim, self.act_dim, self.pi, self.vf), 0),)
+
+    def _count_floats(self):
+        self.blob_floats = int(self._lib.mcg_policy_blob_floats(self.obs_dim, self.act_dim, len(self.pi), _arr(self.pi), len(self.vf), _arr(self.vf)))
+        return self.blob_floats
+
     def _initial_weights(self) -> dict:
         gen = torch.Generator().manual_seed(self.seed % (2 ** 63))
         sd = {}
-        for m, out, k, _first in _shapes(self.obs_dim, self.act_dim, self.pi, self.vf):
+        for m, out, k, _first in blob_shapes(self.obs_dim, self.act_dim, self.pi, self.vf)[:-1]:
             gain = 0.01 if m == "action_net" else 1.0 if m == "value_net" else math.sqrt(2.0)
             q, r = torch.linalg.qr(torch.randn(max(out, k), min(out, k), generator=gen, dtype=torch.float64))
             q = q * torch.sign(torch.diagonal(r))
@@ -212,33 +121,6 @@ class ActorCritic(DeviceBuffer):
             sd[m + ".bias"] = torch.zeros(out)
         sd["log_std"] = torch.zeros(self.act_dim)
         return sd
-
-    def _load_weights(self, sd: dict):
-        blob = pack(sd, self.obs_dim, self.act_dim, self.pi, self.vf, device=self.device)
-        assert blob.numel() == self.blob_floats, (blob.numel(), self.blob_floats)
-        self._blob.copy_(blob)           # in place: the struct keeps pointing at it
-
-    def state_dict(self) -> dict:
-        """The weights under SB3's ``ActorCriticPolicy`` names (device tensors, unpacked from the blob), plus ``seed`` and ``calls``."""
-        sd = unpack(self._blob, self.obs_dim, self.act_dim, self.pi, self.vf)
-        sd.update(seed=self.seed, calls=self.calls)
-        return sd
-
-    def load_state_dict(self, sd: dict):
-        """Weights under SB3's names (an SB3 policy's ``state_dict()`` as it stands, or this class's); repacks the device blob.
-        ``seed`` and ``calls`` are taken where given."""
-        sd = dict(sd)
-        host = {k: sd.pop(k) for k in ("seed", "calls") if k in sd}
-        _refuse_foreign(sd)
-        want = set(state_names(len(self.pi), len(self.vf)))
-        missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
-        if missing or extra:
-            raise ValueError(f"state dict does not fit trunks {self.pi} / {self.vf}: missing {missing}, unexpected {extra}")
-        self._load_weights(sd)
-        if "seed" in host:
-            self.seed = int(host["seed"]) & (2 ** 64 - 1)
-        if "calls" in host:
-            self.calls = int(host["calls"])
 
     @classmethod
     def from_module(cls, module, envs=None, activation: Optional[str] = None, seed: int = 0, **dims):
@@ -251,16 +133,11 @@ class ActorCritic(DeviceBuffer):
             raise ValueError("squash_output=True is not supported: the action is the unsquashed Gaussian sample")
         sd = {k: v for k, v in module.state_dict().items()}
         _refuse_foreign(sd)
-        fn = getattr(module, "activation_fn", None)
-        if activation is None and fn is not None:
-            name = getattr(fn, "__name__", type(fn).__name__).lower()
-            if name not in _ACTIVATIONS:
-                raise ValueError(f"activation_fn {name!r} is not supported: tanh or relu")
-            activation = name
-        pi, vf = _hidden_of(sd, "policy_net"), _hidden_of(sd, "value_net")
+        activation = cls._activation_of(module, activation, "tanh")
+        pi, vf = _hidden_of(sd, "mlp_extractor.policy_net"), _hidden_of(sd, "mlp_extractor.value_net")
         if not pi or not vf:
             raise ValueError("the module's state dict has no mlp_extractor.policy_net / mlp_extractor.value_net layers")
-        pol = cls(envs, hidden=dict(pi=pi, vf=vf), activation=activation or "tanh", seed=seed, **dims)
+        pol = cls(envs, hidden=dict(pi=pi, vf=vf), activation=activation, seed=seed, **dims)
         pol.load_state_dict(sd)
         return pol
 
@@ -299,14 +176,11 @@ class ActorCritic(DeviceBuffer):
     # ------------------------------------------------------------------------------------------------ on a minibatch
     def _minibatch(self, observations, actions, who, **more):
         """The minibatch as the C side takes it -> (``McgRolloutBatch``, B, the tensors it points into: keep them until the call).
-        ``more``: further float32 [B] fields under ``mcg_rollout_batch``'s names."""
+        ``more``: further fields under ``mcg_rollout_batch``'s names, float32 [B] as ``check_minibatch`` (policy_update.py) has seen
+        to."""
         B = minibatch_rows(observations, actions, self.obs_dim, self.act_dim, who)
         t = dict(obs=observations["observation"], achieved=observations["achieved_goal"], desired=observations["desired_goal"], action=actions)
-        for k, x in more.items():
-            if not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) != (B,):
-                raise ValueError(f"{who}: {k}: expected a float32 tensor of shape {(B,)}, got {getattr(x, 'dtype', type(x).__name__)} "
-                                 f"{tuple(getattr(x, 'shape', ()))}")
-            t[k] = x
+        t.update(more)
         for k, x in t.items():
             if x.device != self.device:
                 raise ValueError(f"{who}: {k} lives on {x.device}, the policy on {self.device}")

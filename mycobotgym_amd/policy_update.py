@@ -13,7 +13,8 @@ so the next ``pol(obs)`` sees the new weights with no repack.
     opt.stats                          # float32 [8] on the device: loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, 0, 0
 
 This file owns the gradient, Adam's two moments (float32 device tensors in the blob's layout), the scratch and the step count; the C
-side keeps no state.  Deterministic: equal inputs give equal bits.  ``clip_range_vf`` and ``target_kl`` are not built (the second needs
+side keeps no state.  The scratch's sizing and the moments' checkpoint are _nets.py's ``Update``, shared with SAC and TD3 / DDPG: there
+the moments are dicts by blob name, here ``m`` and ``v`` stay plain tensors and pass through it as one-entry dicts.  Deterministic: equal inputs give equal bits.  ``clip_range_vf`` and ``target_kl`` are not built (the second needs
 a host synchronisation, which a caller can do on ``opt.stats[4]``).  A sharded job all-reduces ``opt.grad_blob`` between
 ``opt.compute_grad(mb)`` and ``opt.apply()``.
 """
@@ -25,7 +26,8 @@ import torch
 
 from . import _abi
 from ._devbuf import _ptr
-from .policy import minibatch_rows, pack, unpack
+from ._nets import Update
+from .policy import blob_shapes, minibatch_rows, unpack
 
 _LOSSES = {"ppo": _abi.LOSS_PPO, "a2c": _abi.LOSS_A2C}
 _HYPER = ("learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "normalize_advantage", "betas", "adam_eps", "loss")
@@ -63,7 +65,9 @@ def check_minibatch(mb, obs_dim: int, act_dim: int, need_old: bool, who: str = "
     return B
 
 
-class PPOUpdate:
+class PPOUpdate(Update):
+    _WORK_ENTRY, _NOUN = "mcg_policy_grad_work_floats", "minibatch"
+
     def __init__(self, policy, learning_rate: float = 3e-4, clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, normalize_advantage: bool = True, betas=(0.9, 0.999), adam_eps: float = 1e-5,
                  loss: str = "ppo", **unbuilt):
@@ -83,15 +87,6 @@ class PPOUpdate:
         self._work = None                # sized for the largest B seen
 
     # --------------------------------------------------------------------------------------------------------- calls
-    def _work_for(self, B: int) -> torch.Tensor:
-        pol = self.policy
-        need = int(pol._lib.mcg_policy_grad_work_floats(C.byref(pol._cbuf), C.c_int64(B)))
-        if need == 0:
-            raise ValueError(f"PPOUpdate: a minibatch of {B} rows is not supported (1 <= B < 2^27)")
-        if self._work is None or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.float32, device=pol.device)
-        return self._work
-
     def compute_grad(self, mb) -> torch.Tensor:
         """The loss of ``mb`` (a ``RolloutSamples`` of ``RolloutBuffer``) and its gradient -> ``grad_blob`` (float32 [blob_floats], in
         the blob's layout; padding positions are 0); ``stats`` is written too.  Four launches."""
@@ -131,30 +126,24 @@ class PPOUpdate:
         return unpack(self.compute_grad(mb), pol.obs_dim, pol.act_dim, pol.pi, pol.vf)
 
     # --------------------------------------------------------------------------------------------------- checkpoints
+    def _nets(self):
+        pol = self.policy
+        return {"blob": (blob_shapes(pol.obs_dim, pol.act_dim, pol.pi, pol.vf), 0)}
+
+    def _moments(self):
+        return {"blob": self.m}, {"blob": self.v}, "{}"
+
     def state_dict(self) -> dict:
         """Adam's moments as blobs (``m``, ``v``) and under SB3's names (``exp_avg``, ``exp_avg_sq``), ``step`` and the
         hyper-parameters.  With the policy's and the buffer's state dicts, training continues bit for bit."""
-        pol = self.policy
-        shape = (pol.obs_dim, pol.act_dim, pol.pi, pol.vf)
-        sd = {"m": self.m.clone(), "v": self.v.clone(), "exp_avg": unpack(self.m, *shape), "exp_avg_sq": unpack(self.v, *shape),
-              "step": self.steps}
+        sd = self._moments_state()
+        sd.update({k: sd[k]["blob"] for k in ("m", "v")})
         sd.update({k: getattr(self, k) for k in _HYPER})
         return sd
 
     def load_state_dict(self, sd: dict):
         """The moments from the blobs ``m`` / ``v`` where given, else packed from ``exp_avg`` / ``exp_avg_sq``."""
-        pol = self.policy
-        for blob, mine, named in (("m", self.m, "exp_avg"), ("v", self.v, "exp_avg_sq")):
-            if blob in sd:
-                src = torch.as_tensor(sd[blob], device=pol.device)
-                if src.dtype != torch.float32 or tuple(src.shape) != tuple(mine.shape):
-                    raise ValueError(f"{blob}: expected float32 {tuple(mine.shape)}, got {src.dtype} {tuple(src.shape)}")
-            elif named in sd:
-                src = pack(sd[named], pol.obs_dim, pol.act_dim, pol.pi, pol.vf, device=pol.device)
-            else:
-                raise ValueError(f"the state dict has neither {blob!r} nor {named!r}")
-            mine.copy_(src)
-        self.steps = int(sd["step"])
+        self._load_moments({**sd, **{k: {"blob": sd[k]} for k in ("m", "v") if k in sd}})
         hyper = {k: sd[k] for k in _HYPER if k in sd}
         check_hyper(hyper.get("loss", self.loss), hyper.get("clip_range", self.clip_range), hyper.get("betas", self.betas), {})
         for k, x in hyper.items():

@@ -28,8 +28,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi, _offpolicy
-from ._offpolicy import OffPolicyNets, _arr, _hidden_of, _per_row, batch_rows, check_out, critic_shapes, pack_net, unpack_net      # noqa: F401
-from .policy import _ACTIVATIONS                # (_per_row and batch_rows: imported from here by users and tests, as ever)
+from ._nets import _ACTIVATIONS, _arr, _hidden_of, check_out, names_of, pack_net, unpack_net
+from ._offpolicy import OffPolicyNets, _per_row, batch_rows, critic_shapes      # noqa: F401 (_per_row and batch_rows: imported from here, as ever)
 
 _WIDTHS = ("1 to 3 hidden layers, each width a multiple of 16 in [16, 256] (SB3's TD3 / DDPG default net_arch [400, 300] is this case: "
            "300 is no multiple of 16 and 400 is above 256)")
@@ -37,7 +37,7 @@ _WIDTHS = ("1 to 3 hidden layers, each width a multiple of 16 in [16, 256] (SB3'
 
 # ----------------------------------------------------------------------------------------------------------- the blobs
 # csrc/mcg_sac.hip's head states the layouts.  actor: latent_pi's layers, the head mu, the head log_std (A rows padded to 16 each).
-# critic and critic_target: qf0 then qf1, each as _offpolicy.py's pack_net restates a critic; packing and unpacking are its functions.
+# critic and critic_target: qf0 then qf1, each as _nets.py's pack_net restates a critic; packing and unpacking are its functions.
 def _actor_shapes(obs_dim, act_dim, pi):
     """(module, out, in, first layer?) in the actor blob's order."""
     rows, k = [], obs_dim + 6
@@ -49,11 +49,7 @@ def _actor_shapes(obs_dim, act_dim, pi):
 
 def state_names(n_pi: int, n_qf: int):
     """The weights' keys of a state dict: actor, critic, critic_target, in the blobs' order."""
-    names = []
-    for m, *_ in (_actor_shapes(1, 1, [16] * n_pi) + critic_shapes(1, 1, [16] * n_qf, "critic")
-                  + critic_shapes(1, 1, [16] * n_qf, "critic_target")):
-        names += [m + ".weight", m + ".bias"]
-    return names
+    return names_of(_actor_shapes(1, 1, [16] * n_pi) + critic_shapes(1, 1, [16] * n_qf, "critic") + critic_shapes(1, 1, [16] * n_qf, "critic_target"))
 
 
 def pack_actor(sd: dict, obs_dim: int, act_dim: int, pi: Sequence[int], device=None) -> torch.Tensor:
@@ -126,9 +122,6 @@ class SACPolicy(OffPolicyNets):
     def _blob_floats(self):
         return self._floats_of("mcg_sac_blob_floats")
 
-    def _state_names(self):
-        return state_names(len(self.pi), len(self.qf))
-
     def _fit(self):
         return f"actor {self.pi} / critics {self.qf}"
 
@@ -136,16 +129,6 @@ class SACPolicy(OffPolicyNets):
     def log_ent_coef(self) -> torch.Tensor:
         """float32 [1] on the device: SB3's ``ent_coef="auto"`` parameter; ``td_target`` reads it there."""
         return self._t["log_ent_coef"]
-
-    def state_dict(self) -> dict:
-        """The weights under SB3's ``SACPolicy`` names (device tensors, unpacked from the blobs), ``log_ent_coef``, and ``seed``,
-        ``calls``, ``target_calls``."""
-        return self._state_dict()
-
-    def load_state_dict(self, sd: dict):
-        """Weights under SB3's names (an SB3 ``SACPolicy``'s ``state_dict()`` as it stands, or this class's); repacks the three blobs.
-        ``log_ent_coef``, ``seed``, ``calls`` and ``target_calls`` are taken where given."""
-        self._load_state_dict(sd)
 
     @classmethod
     def from_module(cls, module, envs=None, activation: Optional[str] = None, seed: int = 0, **dims):
@@ -162,7 +145,7 @@ class SACPolicy(OffPolicyNets):
         pi, qf = _hidden_of(sd, "actor.latent_pi"), _hidden_of(sd, "critic.qf0")[:-1]
         if not pi or not qf:
             raise ValueError("the module's state dict has no actor.latent_pi / critic.qf0 layers")
-        pol = cls(envs, hidden=dict(pi=pi, qf=qf), activation=cls._activation_of(module, activation), seed=seed, **dims)
+        pol = cls(envs, hidden=dict(pi=pi, qf=qf), activation=cls._activation_of(module, activation, "relu"), seed=seed, **dims)
         pol.load_state_dict(sd)
         return pol
 

@@ -29,7 +29,8 @@ import math
 
 from . import _abi
 from ._devbuf import _ptr
-from ._offpolicy import OffPolicyUpdate, _finite, check_batch, check_common_hyper, critic_shapes      # noqa: F401 (check_batch: imported from here, as ever)
+from ._nets import _finite
+from ._offpolicy import OffPolicyUpdate, check_batch, check_common_hyper, critic_shapes      # noqa: F401 (check_batch: imported from here, as ever)
 from .sac_policy import _actor_shapes
 
 _HYPER = ("learning_rate", "gamma", "tau", "ent_coef", "target_entropy", "target_update_interval", "betas", "eps")

@@ -30,8 +30,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi
-from ._offpolicy import OffPolicyNets, _arr, _hidden_of, check_out, critic_shapes, pack_critic, pack_net, unpack_critic, unpack_net      # noqa: F401
-from .policy import _ACTIVATIONS                # (pack_critic and unpack_critic: imported from here by users and tests, as ever)
+from ._nets import _ACTIVATIONS, _arr, _hidden_of, check_out, names_of, pack_net, unpack_net
+from ._offpolicy import OffPolicyNets, critic_shapes, pack_critic, unpack_critic      # noqa: F401 (pack_critic and unpack_critic: imported from here, as ever)
 
 _WIDTHS = ("1 to 3 hidden layers, each width a multiple of 16 in [16, 256]; SB3's default net_arch [400, 300] for TD3 / DDPG is refused: "
            "300 is no multiple of 16 and 400 is above 256 -- pass net_arch=[256, 256] to SB3 and hidden=(256, 256) here")
@@ -39,7 +39,7 @@ _WIDTHS = ("1 to 3 hidden layers, each width a multiple of 16 in [16, 256]; SB3'
 
 # ----------------------------------------------------------------------------------------------------------- the blobs
 # csrc/mcg_td3.hip's head states the layouts.  actor and actor_target: the trunk's layers, then the head (A rows padded to 16).
-# critic and critic_target: qf0, then qf1 with two critics, each as _offpolicy.py's pack_net restates a critic.
+# critic and critic_target: qf0, then qf1 with two critics, each as _nets.py's pack_net restates a critic.
 def _actor_shapes(obs_dim, act_dim, pi, prefix="actor"):
     """(module, out, in, first layer?) in the actor blob's order."""
     rows, k = [], obs_dim + 6
@@ -51,11 +51,8 @@ def _actor_shapes(obs_dim, act_dim, pi, prefix="actor"):
 
 def state_names(n_pi: int, n_qf: int, n_critics: int = 2):
     """The weights' keys of a state dict: actor, actor_target, critic, critic_target, in the blobs' order."""
-    names = []
-    for m, *_ in (_actor_shapes(1, 1, [16] * n_pi) + _actor_shapes(1, 1, [16] * n_pi, "actor_target")
-                  + critic_shapes(1, 1, [16] * n_qf, "critic", n_critics) + critic_shapes(1, 1, [16] * n_qf, "critic_target", n_critics)):
-        names += [m + ".weight", m + ".bias"]
-    return names
+    return names_of(_actor_shapes(1, 1, [16] * n_pi) + _actor_shapes(1, 1, [16] * n_pi, "actor_target")
+                    + critic_shapes(1, 1, [16] * n_qf, "critic", n_critics) + critic_shapes(1, 1, [16] * n_qf, "critic_target", n_critics))
 
 
 def pack_actor(sd: dict, obs_dim: int, act_dim: int, pi: Sequence[int], prefix: str = "actor", device=None) -> torch.Tensor:
@@ -91,7 +88,7 @@ class TD3Policy(OffPolicyNets):
                   "the MLP policy of the -v0 state ids; CNN critics are not supported")
     _N_CRITICS = 2
     _WIDTHS = _WIDTHS
-    _refuse_foreign = staticmethod(_refuse_foreign)
+    _refuse_foreign, _refuse_widths = staticmethod(_refuse_foreign), staticmethod(_refuse_widths)
 
     def __init__(self, envs=None, hidden=(256, 256), activation: str = "relu", seed: int = 0, n_critics: Optional[int] = None, *,
                  use_sde: bool = False, num_envs: Optional[int] = None, obs_dim: Optional[int] = None, act_dim: Optional[int] = None,
@@ -107,7 +104,7 @@ class TD3Policy(OffPolicyNets):
             raise ValueError(f"n_critics must be 1 or 2 (got {n_critics}): n_critics > 2 is not supported, the kernels evaluate qf0, or qf0 and qf1")
         self.n_critics = int(n_critics)
         self._setup(envs, hidden, activation, seed, dict(num_envs=num_envs, obs_dim=obs_dim, act_dim=act_dim), device, env_id_offset,
-                    ("actor", "actor_target", "critic", "critic_target"), _refuse_widths)
+                    ("actor", "actor_target", "critic", "critic_target"))
         self._cbuf = _abi.McgTd3(**{k: t.data_ptr() for k, t in self._t.items()}, n_envs=self.num_envs, obs_dim=self.obs_dim,
                                  act_dim=self.act_dim, n_pi=len(self.pi), pi_width=_arr(self.pi), n_qf=len(self.qf), qf_width=_arr(self.qf),
                                  activation=_ACTIVATIONS[activation], n_critics=self.n_critics, actor_floats=self.actor_floats,
@@ -123,21 +120,8 @@ class TD3Policy(OffPolicyNets):
     def _blob_floats(self):
         return self._floats_of("mcg_td3_blob_floats", self.n_critics)
 
-    def _state_names(self):
-        return state_names(len(self.pi), len(self.qf), self.n_critics)
-
     def _fit(self):
         return f"actor {self.pi} / {self.n_critics} critic(s) {self.qf}"
-
-    def state_dict(self) -> dict:
-        """The weights under SB3's ``TD3Policy`` names (device tensors, unpacked from the blobs), and ``seed``, ``calls``,
-        ``target_calls``."""
-        return self._state_dict()
-
-    def load_state_dict(self, sd: dict):
-        """Weights under SB3's names (an SB3 ``TD3Policy``'s ``state_dict()`` as it stands, or this class's); repacks the four blobs.
-        ``seed``, ``calls`` and ``target_calls`` are taken where given."""
-        self._load_state_dict(sd)
 
     @classmethod
     def from_module(cls, module, envs=None, activation: Optional[str] = None, seed: int = 0, **dims):
@@ -152,7 +136,7 @@ class TD3Policy(OffPolicyNets):
         if not pi or not qf:
             raise ValueError("the module's state dict has no actor.mu / critic.qf0 layers")
         n_critics = 2 if any(k.startswith("critic.qf1.") for k in sd) else 1
-        pol = cls(envs, hidden=dict(pi=pi, qf=qf), activation=cls._activation_of(module, activation), seed=seed, n_critics=n_critics, **dims)
+        pol = cls(envs, hidden=dict(pi=pi, qf=qf), activation=cls._activation_of(module, activation, "relu"), seed=seed, n_critics=n_critics, **dims)
         pol.load_state_dict(sd)
         return pol
 

@@ -30,7 +30,8 @@ import torch
 
 from . import _abi
 from ._devbuf import _ptr
-from ._offpolicy import OffPolicyUpdate, _finite, check_common_hyper, critic_shapes
+from ._nets import _finite
+from ._offpolicy import OffPolicyUpdate, check_common_hyper, critic_shapes
 from .td3_policy import _actor_shapes
 
 _HYPER = ("learning_rate", "gamma", "tau", "policy_delay", "target_policy_noise", "target_noise_clip", "betas", "eps")
