@@ -1092,6 +1092,62 @@ int mcg_td3_critic_grad(const mcg_td3* td3, const mcg_sac_rows* rows, const floa
 int mcg_td3_actor_grad(const mcg_td3* td3, const mcg_sac_rows* rows, int64_t B, float* work, int64_t work_floats, float* grad, float* stats,
                        const mcg_td3_actor_grad_out* out, void* stream);
 
+/* ---- The CNN actor-critic forward for the -v1 picture ids (SB3's CnnPolicy = ActorCriticCnnPolicy for a Box(0, 255, (C, S, S), uint8):
+   a NatureCNN features extractor shared by actor and critic, net_arch = [], a DiagGaussianDistribution; mcg_cnn.hip).  Stateless: the
+   caller owns the weights (one float32 device blob, laid out as mcg_cnn.hip's head states and mycobotgym_amd/cnn_policy.py packs it),
+   the scratch and the call number.  Two launches on `stream` (the convolutions, one workgroup per few pictures; the dense stage on
+   tiles of 32 rows), no synchronisation, no atomics.  Additive: MCG_ABI_VERSION stays 8.
+     input      x = (float)byte / 255.0f (IEEE division), or the float32 already divided (mcg_rollout_img_gather's pix_f32).
+     cnn        Conv2d(C, 32, 8, stride 4), Conv2d(32, 64, 4, stride 2), Conv2d(64, 64, 3, stride 1), each followed by max(., 0), no
+                padding: o1 = (S - 8) / 4 + 1, o2 = (o1 - 4) / 2 + 1, o3 = o2 - 2 (integer division); flattened as c o3^2 + y o3 + x.
+     linear     features = max(W x + b, 0), [rows, F];  heads: mean = action_net(features) [rows, A], value = value_net(features) [rows].
+                float32 throughout (v_mfma_f32_16x16x4_f32; the order of a sum over k is the kernel's).
+     noise      as mcg_policy_forward's, with the domain byte 12: counter ((uint32)gid, (uint32)call, pair ^ ((uint32)(call >> 32) << 8),
+                12 ^ ((uint32)(gid >> 32) << 8)); Box-Muller in double, rounded to float32 once.
+     action, log_prob (forward), log_prob, entropy (evaluate): the formulas of mcg_policy_forward and mcg_policy_evaluate.
+   A row of the outputs depends on its own picture and its global id alone.
+   Accepted: channels in [1, 16], image_size in [36, 96], features_dim a multiple of 16 in [16, 512], act_dim in [1, 16]. */
+#define MCG_CNN_UINT8 0
+#define MCG_CNN_FLOAT32 1
+
+typedef struct mcg_cnn_policy {
+  const float* blob;                /* device, 16-byte aligned, blob_floats floats */
+  float* scratch;                   /* device, 16-byte aligned: the flattened conv features, [rows, 64 o3^2]; written by every call */
+  int32_t n_envs, channels, image_size, features_dim, act_dim;
+  int64_t blob_floats;              /* must equal mcg_cnn_blob_floats of this shape */
+  int64_t scratch_floats;           /* >= mcg_cnn_scratch_floats of this shape and the call's rows */
+} mcg_cnn_policy;
+
+typedef struct mcg_cnn_obs {        /* pictures [rows, C, S, S]; only the S x S plane must be contiguous */
+  const void* pixels;               /* device */
+  int32_t dtype;                    /* MCG_CNN_UINT8, or MCG_CNN_FLOAT32: already divided by 255 */
+  int64_t env_stride, chan_stride;  /* in elements */
+} mcg_cnn_obs;
+
+typedef struct mcg_cnn_out {        /* device pointers, any may be NULL to skip (not all) */
+  float* action;         /* [N, A] */
+  float* value;          /* [N] */
+  float* log_prob;       /* [N] */
+  float* mean;           /* [N, A] */
+  float* noise;          /* [N, A]  eps */
+  float* features;       /* [N, F]  the extractor's output (tests) */
+} mcg_cnn_out;
+
+/* Sizes in floats; 0 for a refused shape (scratch: or rows outside [1, 2^27)). */
+int64_t mcg_cnn_blob_floats(int channels, int image_size, int features_dim, int act_dim);
+int64_t mcg_cnn_scratch_floats(int channels, int image_size, int features_dim, int act_dim, int64_t rows);
+
+/* rows = pol->n_envs.  With only `value` (and `features`) set no policy-head work is done; the caller then uses up no call number.
+   Refused (MCG_ERR_ARG, each by a message that names the field): a null struct, blob or scratch; a shape outside the accepted domain;
+   blob_floats or scratch_floats that do not fit; a misaligned blob or scratch; null pixels; an unknown dtype; a negative stride or a
+   channel stride below S * S while channels > 1; all outputs null. */
+int mcg_cnn_forward(const mcg_cnn_policy* pol, const mcg_cnn_obs* obs, uint64_t seed, uint64_t call, int64_t env_id_offset,
+                    int deterministic, const mcg_cnn_out* out, void* stream);
+
+/* SB3's evaluate_actions, forward only, on `rows` pictures and `actions` [rows, A] (pol->n_envs is not read). */
+int mcg_cnn_evaluate(const mcg_cnn_policy* pol, const mcg_cnn_obs* obs, const float* actions, int64_t rows,
+                     const mcg_policy_eval_out* out, void* stream);
+
 /* Device self-test of the step kernels' bad-value check (mj_checkPos / mj_checkVel / mj_checkAcc at the end of a sub-step): no engine
    handle, nothing a rollout calls.  `in` is [n][MCG_SELFTEST_BAD_VALUE_IN] doubles on the device, one case per row: a[12], r[12],
    qd_old[12], q_old[12], h.  A lane forms rhs = fma(-h, r, a), qdn = fma(h, rhs, qd_old), qn = fma(h, qdn, q_old) as the Euler step

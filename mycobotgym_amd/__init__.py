@@ -8,6 +8,7 @@
 The numeric path is the HIP library ``libmycobot_hip.so`` (C ABI in ``include/mcg.h``); importing the
 package does not need a GPU, constructing an environment does.
 """
+from .cnn_policy import CnnActorCritic  # noqa: F401
 from .frame_stack import FrameStack  # noqa: F401
 from .policy import ActorCritic  # noqa: F401
 from .policy_update import PPOUpdate  # noqa: F401

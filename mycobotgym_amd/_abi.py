@@ -357,6 +357,24 @@ class McgTd3ActorGradOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("action", "q_pi", "dq_da")]
 
 
+CNN_UINT8, CNN_FLOAT32 = 0, 1          # mcg_cnn_obs.dtype
+
+
+class McgCnnPolicy(C.Structure):
+    """The CNN policy's weights, scratch and shape (include/mcg.h: mcg_cnn_policy); the caller owns the blob and the scratch."""
+    _fields_ = [("blob", C.c_void_p), ("scratch", C.c_void_p), ("n_envs", C.c_int32), ("channels", C.c_int32), ("image_size", C.c_int32),
+                ("features_dim", C.c_int32), ("act_dim", C.c_int32), ("blob_floats", C.c_int64), ("scratch_floats", C.c_int64)]
+
+
+class McgCnnObs(C.Structure):
+    """Pictures [rows, C, S, S] where they lie (include/mcg.h: mcg_cnn_obs); the strides are in elements."""
+    _fields_ = [("pixels", C.c_void_p), ("dtype", C.c_int32), ("env_stride", C.c_int64), ("chan_stride", C.c_int64)]
+
+
+class McgCnnOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("action", "value", "log_prob", "mean", "noise", "features")]
+
+
 GEOM_SKY, GEOM_GROUND, GEOM_TABLE, GEOM_CUBE, GEOM_TARGET, GEOM_MESH0 = -1, 0, 1, 2, 3, 4      # mcg_render_out.geom
 
 EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create", "mcg_destroy", "mcg_obs_dim",
@@ -374,7 +392,8 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_sac_blob_floats", "mcg_sac_act", "mcg_sac_q", "mcg_sac_target", "mcg_sac_polyak",
            "mcg_sac_grad_work_floats", "mcg_sac_critic_grad", "mcg_sac_actor_grad", "mcg_sac_alpha_step", "mcg_sac_adam",
            "mcg_td3_blob_floats", "mcg_td3_act", "mcg_td3_q", "mcg_td3_target", "mcg_td3_polyak",
-           "mcg_td3_grad_work_floats", "mcg_td3_critic_grad", "mcg_td3_actor_grad", "mcg_selftest_bad_value")
+           "mcg_td3_grad_work_floats", "mcg_td3_critic_grad", "mcg_td3_actor_grad", "mcg_selftest_bad_value",
+           "mcg_cnn_blob_floats", "mcg_cnn_scratch_floats", "mcg_cnn_forward", "mcg_cnn_evaluate")
 
 _lib = None
 
@@ -513,6 +532,15 @@ def load():
                                           C.c_void_p]
         L.mcg_td3_actor_grad.argtypes = [td3, C.POINTER(McgSacRows), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.POINTER(McgTd3ActorGradOut), C.c_void_p]
+    if hasattr(L, "mcg_cnn_forward"):  # absent only from older builds selected through MCG_LIB for A/B timing
+        L.mcg_cnn_blob_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mcg_cnn_blob_floats.restype = C.c_int64
+        L.mcg_cnn_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
+        L.mcg_cnn_scratch_floats.restype = C.c_int64
+        L.mcg_cnn_forward.argtypes = [C.POINTER(McgCnnPolicy), C.POINTER(McgCnnObs), C.c_uint64, C.c_uint64, C.c_int64, C.c_int,
+                                      C.POINTER(McgCnnOut), C.c_void_p]
+        L.mcg_cnn_evaluate.argtypes = [C.POINTER(McgCnnPolicy), C.POINTER(McgCnnObs), C.c_void_p, C.c_int64, C.POINTER(McgPolicyEvalOut),
+                                       C.c_void_p]
     _lib = L
     return L
 

@@ -20,6 +20,7 @@ SRC_SAC = os.path.join(_HERE, "csrc", "mcg_sac.hip")            # SAC's actor, t
 SRC_SAC_GRAD = os.path.join(_HERE, "csrc", "mcg_sac_grad.hip")  # SAC's update (critic, actor and alpha gradients, Adam): likewise
 SRC_TD3 = os.path.join(_HERE, "csrc", "mcg_td3.hip")            # TD3's / DDPG's actor, critics and smoothed TD target: likewise
 SRC_TD3_GRAD = os.path.join(_HERE, "csrc", "mcg_td3_grad.hip")  # TD3's / DDPG's update (critic and actor gradients): likewise
+SRC_CNN = os.path.join(_HERE, "csrc", "mcg_cnn.hip")            # the CNN actor-critic forward of the picture ids: likewise
 SRC_SELFTEST = os.path.join(_HERE, "csrc", "mcg_selftest.hip")  # device self-tests of step-kernel functions (test-only entries): likewise
 DEPS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*"))) + [os.path.join(ROOT, "include", "mcg.h")]      # every source and header
 OUT = os.path.join(_HERE, "libmycobot_hip.so")
@@ -47,7 +48,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
         return OUT
     cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-shared",
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(_HERE, "csrc"), SRC, SRC_RENDER, SRC_REPLAY, SRC_ROLLOUT, SRC_REPLAY_IMG,
-           SRC_FRAME_STACK, SRC_POLICY, SRC_POLICY_GRAD, SRC_SAC, SRC_SAC_GRAD, SRC_TD3, SRC_TD3_GRAD, SRC_SELFTEST,
+           SRC_FRAME_STACK, SRC_POLICY, SRC_POLICY_GRAD, SRC_SAC, SRC_SAC_GRAD, SRC_TD3, SRC_TD3_GRAD, SRC_CNN, SRC_SELFTEST,
            "-o", OUT]
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
