@@ -2,16 +2,19 @@
 
 Nothing here knows "on-policy" or "off-policy".  The packing of Linear layers into a blob and back (csrc/mcg_policy.hip's and
 csrc/mcg_sac.hip's heads state the layouts; a critic's first layer and a bare vector are restated here, once), the checks of a batch's
-rows and of a caller's ``out`` tensors, ``Nets`` -- the base of ``ActorCritic`` and ``OffPolicyNets``: the constructor's shared steps,
-the weights and their state dict both ways, ``from_module``'s activation -- and ``Update`` -- the base of ``PPOUpdate`` and
-``OffPolicyUpdate``: the scratch's size and the moments' checkpoint.  A family's words (its buffer, "minibatch" or "batch", ``vf`` or
-``qf``) are arguments or class attributes.  Private: users import from the families' modules, which re-export what they always had.
+rows and of a caller's ``out`` tensors, ``Nets`` -- the base of every policy: the constructor's shared steps, the weights and their
+state dict both ways, ``from_module``'s activation --, ``GaussianActorCritic`` -- what ``ActorCritic`` and ``CnnActorCritic`` share
+beyond it: the orthogonal start, ``forward`` and ``values`` around a family's marshalling -- and ``Update`` -- the base of
+``PPOUpdate`` and ``OffPolicyUpdate``: the scratch's size and the moments' checkpoint.  A family's words (its buffer, "minibatch" or
+"batch", ``vf`` or ``qf``) are arguments or class attributes.  Private: users import from the families' modules, which re-export what
+they always had.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
 import numbers
+from typing import Optional
 
 import torch
 
@@ -106,6 +109,23 @@ def names_of(shapes):
     return [n for m, _out, k, _first in shapes for n in ([m] if k is None else [m + ".weight", m + ".bias"])]
 
 
+def orthogonal_start(shapes, seed: int, trunk: float = math.sqrt(2.0), action_net: float = 0.01, value_net: float = 1.0) -> dict:
+    """SB3's start of an actor-critic policy for the rows of ``shapes``: orthogonal weights [out, in] (the gain of the two heads by
+    their names, ``trunk`` for every other layer), zero biases, a zero bare vector.  One ``randn`` of (max, min) of a row's shape per
+    weight, in the rows' order, from a generator seeded with ``seed``: the weights of a seed are fixed by that order."""
+    gen = torch.Generator().manual_seed(seed % (2 ** 63))
+    gains, sd = {"action_net": action_net, "value_net": value_net}, {}
+    for m, out, k, _first in shapes:
+        if k is None:
+            sd[m] = torch.zeros(out)
+            continue
+        q, r = torch.linalg.qr(torch.randn(max(out, k), min(out, k), generator=gen, dtype=torch.float64))
+        q = q * torch.sign(torch.diagonal(r))
+        sd[m + ".weight"] = (gains.get(m, trunk) * (q if out >= k else q.T)).float()
+        sd[m + ".bias"] = torch.zeros(out)
+    return sd
+
+
 def _hidden_of(sd: dict, stem: str):
     """The widths of the Linear layers ``stem``.0, .2, .. (a critic's last one is its head)."""
     widths, L = [], 0
@@ -183,18 +203,26 @@ class Nets(DeviceBuffer):
     refusal of other keys adds), ``_SHAPE`` and ``_WIDTHS`` (the unsupported-shape text), ``_HOST`` (the host fields of a state dict),
     ``_refuse_foreign`` and ``_refuse_widths`` (its module's functions), and gives ``_nets()`` -- per weight blob of ``self._t``:
     (blob name, its shapes, act_dim for a critic blob else 0), in the blobs' order -- and ``_count_floats()`` (keeps the blobs' sizes,
-    0 for a refused shape); ``_fit()`` names the shape a state dict must fit."""
+    0 for a refused shape); ``_fit()`` names the shape a state dict must fit.  A family that is no MLP (the CNN) uses ``_setup_dims``
+    alone and overrides ``_as_rows`` / ``_as_sb3``; its ``_refuse_foreign`` may return the dict to go on with."""
     _FROM_ENVS = (("num_envs", "num_envs"), ("obs_dim", "obs_dim"), ("act_dim", "action_dim"))
     _DICT_NOTE = ""
     _refuse_widths = staticmethod(lambda widths: None)
 
-    def _setup(self, envs, hidden, activation, seed, dims: dict, device, env_id_offset):
-        """The constructor's shared steps: the dimensions, ``hidden``, the activation, the seed and the call number, the blobs' sizes."""
-        num_envs, obs_dim, act_dim = self._resolve(envs, device, dims)
-        self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
+    def _setup_dims(self, envs, seed, dims: dict, device, env_id_offset):
+        """The constructor's steps that know no MLP: the dimensions (attributes under ``_FROM_ENVS``'s keywords), ``env_id_offset``, the
+        seed and the call number."""
+        for (k, _attr), v in zip(self._FROM_ENVS, self._resolve(envs, device, dims)):
+            setattr(self, k, int(v))
         if env_id_offset is None:
             env_id_offset = int(envs._cfg.env_id_offset) if envs is not None and hasattr(envs, "_cfg") else 0
         self.env_id_offset = int(env_id_offset)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.calls = 0                   # sampling calls of __call__ so far: the `call` word of the collection noise
+
+    def _setup(self, envs, hidden, activation, seed, dims: dict, device, env_id_offset):
+        """``_setup_dims``, then an MLP family's steps: ``hidden``, the activation, the widths' refusals, the blobs' sizes."""
+        self._setup_dims(envs, seed, dims, device, env_id_offset)
         if isinstance(hidden, dict):
             if set(hidden) != {"pi", self._CRITIC}:
                 raise ValueError(f"hidden: a dict must have exactly the keys 'pi' and '{self._CRITIC}'" + self._DICT_NOTE)
@@ -206,8 +234,6 @@ class Nets(DeviceBuffer):
         if activation not in _ACTIVATIONS:
             raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}, got {activation!r}")
         self.activation = activation
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.calls = 0                   # sampling calls of __call__ so far: the `call` word of the collection noise
         if len(self.pi) > 3 or len(critic) > 3 or self._count_floats() == 0:
             raise ValueError(f"unsupported shape: obs_dim {self.obs_dim}, act_dim {self.act_dim} (1..16), {self._SHAPE.format(self.pi, critic)}: "
                              + self._WIDTHS)
@@ -216,7 +242,17 @@ class Nets(DeviceBuffer):
     def _fit(self):
         return self._SHAPE.format(self.pi, getattr(self, self._CRITIC))
 
+    def _as_rows(self, sd: dict) -> dict:
+        """A state dict under SB3's names and shapes -> with the [out, in] weights that ``_nets()``'s rows name (the CNN flattens its
+        convolutions)."""
+        return sd
+
+    def _as_sb3(self, sd: dict) -> dict:
+        """The inverse, on the unpacked weights: SB3's shapes, and SB3's further names for them (the CNN's aliases)."""
+        return sd
+
     def _load_weights(self, sd: dict):
+        sd = self._as_rows(sd)
         for name, shapes, a in self._nets():
             blob, mine = pack_net(sd, shapes, a, self.device), self._t[name]
             assert blob.numel() == mine.numel(), (name, blob.numel(), mine.numel())
@@ -228,6 +264,7 @@ class Nets(DeviceBuffer):
         sd, nets, t = {}, self._nets(), self._t
         for name, shapes, a in nets:
             sd.update(unpack_net(t[name], shapes, a))
+        sd = self._as_sb3(sd)
         sd.update({k: x.clone() for k, x in t.items() if k not in [n for n, *_ in nets]})      # (SAC: log_ent_coef)
         sd.update({k: getattr(self, k) for k in self._HOST})
         return sd
@@ -238,7 +275,8 @@ class Nets(DeviceBuffer):
         sd, t = dict(sd), self._t
         host = {k: sd.pop(k) for k in self._HOST if k in sd}
         other = {k: sd.pop(k, None) for k in t if k not in [n for n, *_ in self._nets()]}
-        self._refuse_foreign(sd)
+        kept = self._refuse_foreign(sd)
+        sd = sd if kept is None else kept         # (the CNN's hands the dict back without the extractor's aliases)
         want = set(names_of([row for _name, shapes, _a in self._nets() for row in shapes]))
         missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
         if missing or extra:
@@ -260,6 +298,60 @@ class Nets(DeviceBuffer):
                 raise ValueError(f"activation_fn {name!r} is not supported: {' or '.join(sorted(_ACTIVATIONS, key=lambda a: a != default))}")
             activation = name
         return activation or default
+
+
+class GaussianActorCritic(Nets):
+    """The base of ``ActorCritic`` and ``CnnActorCritic``: one blob ``_blob`` (a one-row ``_nets()`` table) whose heads are
+    ``action_net``, ``value_net`` and the bare vector ``log_std`` of a diagonal Gaussian.  A subclass gives ``_shapes()`` (output name ->
+    the shape ``forward`` writes) and ``_forward(x, call, deterministic, out, who)`` (its input's marshalling and its entry);
+    ``_caller_out`` is its check of a caller's ``out``."""
+    _HOST = ("seed", "calls")
+    _t = property(lambda self: {"blob": self._blob})      # (_blob is read at each use: it may be rebound, with _cbuf.blob)
+
+    def _initial_weights(self) -> dict:
+        return orthogonal_start(self._nets()[0][1], self.seed)
+
+    @staticmethod
+    def _refuse_module(module):
+        """What ``from_module`` refuses of an SB3 policy's own attributes, whatever its extractor."""
+        if getattr(module, "use_sde", False):
+            raise ValueError("gSDE (use_sde=True) is not supported: the noise is the diagonal Gaussian's, drawn per call")
+        if getattr(module, "squash_output", False):
+            raise ValueError("squash_output=True is not supported: the action is the unsquashed Gaussian sample")
+
+    def _caller_out(self, out, shapes: dict, who: str):
+        return out
+
+    def _new(self, *names):
+        shapes = self._shapes()
+        return {k: torch.empty(shapes[k], dtype=torch.float32, device=self.device) for k in names}
+
+    def forward(self, obs, deterministic: bool = False, out: Optional[dict] = None):
+        """``obs``: what ``envs.reset`` / ``envs.step`` returned (device tensors, read in place) -> (action [N, A], value [N],
+        log_prob [N]), float32 device tensors.  ``deterministic``: the action is the mean and no call number is used up.  ``out``: the
+        tensors to write into, under the names of the entry's out struct (``_shapes()``'s keys: any subset)."""
+        out = self._new("action", "value", "log_prob") if out is None else self._caller_out(out, self._shapes(), "forward")
+        self._forward(obs, self.calls, deterministic, out, "forward")
+        if not deterministic:
+            self.calls += 1
+        return out.get("action"), out.get("value"), out.get("log_prob")
+
+    __call__ = forward
+
+    def values(self, obs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The value alone (the bootstrap of ``info["final_observation"]``, the last value of a rollout): float32 [N]; the policy head
+        is not evaluated and no call number is used up."""
+        v = self._new("value")["value"] if out is None else out
+        self._forward(obs, 0, True, self._caller_out({"value": v}, self._shapes(), "values"), "values")
+        return v
+
+    def _eval_out(self, B: int, out, who: str):
+        """``evaluate_actions``' outputs for B rows, new or the caller's -> (the dict, ``McgPolicyEvalOut``)."""
+        if out is None:
+            out = {k: torch.empty(B, dtype=torch.float32, device=self.device) for k in ("value", "log_prob", "entropy")}
+        else:
+            out = self._caller_out(out, {k: (B,) for k in ("value", "log_prob", "entropy")}, who)
+        return out, _abi.McgPolicyEvalOut(**{k: v.data_ptr() for k, v in out.items()})
 
 
 # ---------------------------------------------------------------------------------------------------------- the update

@@ -25,14 +25,12 @@ this policy, CNN actors and critics for SAC / TD3 / DDPG, a non-empty ``net_arch
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Optional
 
 import torch
 
 from . import _abi
-from ._devbuf import DeviceBuffer
-from ._nets import check_out, names_of, pack_net, unpack_net
+from ._nets import GaussianActorCritic, check_out, names_of, pack_net, unpack_net
 
 _EXTRACTOR = "features_extractor."
 _ALIASES = ("pi_features_extractor.", "vf_features_extractor.")      # SB3 >= 1.8: the same modules under two more names
@@ -95,14 +93,18 @@ def pack(sd: dict, channels: int, image_size: int, features_dim: int, act_dim: i
     return pack_net(_flat(sd, channels), blob_shapes(channels, image_size, features_dim, act_dim), device=device)
 
 
-def unpack(blob: torch.Tensor, channels: int, image_size: int, features_dim: int, act_dim: int, aliases: bool = True) -> dict:
-    """The inverse of ``pack``: the blob -> the state dict, bit for bit; ``aliases``: with SB3 >= 1.8's two more names of the extractor."""
-    sd = unpack_net(blob, blob_shapes(channels, image_size, features_dim, act_dim))
+def _unflat(sd: dict, channels: int, aliases: bool = True) -> dict:
+    """The inverse of ``_flat``, in place; ``aliases``: and the extractor's entries again (cloned) under SB3 >= 1.8's two more names."""
     for (m, (k, _stride)), cin in zip(_CONVS.items(), (channels, 32, 64)):
         sd[m + ".weight"] = sd[m + ".weight"].reshape(-1, cin, k, k)
     if aliases:
         sd.update({a + n[len(_EXTRACTOR):]: v.clone() for a in _ALIASES for n, v in list(sd.items()) if n.startswith(_EXTRACTOR)})
     return sd
+
+
+def unpack(blob: torch.Tensor, channels: int, image_size: int, features_dim: int, act_dim: int, aliases: bool = True) -> dict:
+    """The inverse of ``pack``: the blob -> the state dict, bit for bit; ``aliases``: with SB3 >= 1.8's two more names of the extractor."""
+    return _unflat(unpack_net(blob, blob_shapes(channels, image_size, features_dim, act_dim)), channels, aliases)
 
 
 def _refuse_foreign(sd: dict) -> dict:
@@ -123,12 +125,12 @@ def _refuse_foreign(sd: dict) -> dict:
     return out
 
 
-class CnnActorCritic(DeviceBuffer):
+class CnnActorCritic(GaussianActorCritic):
     _IMAGES = True
     _FROM_ENVS = (("num_envs", "num_envs"), ("channels", "channels"), ("image_size", "image_size"), ("act_dim", "action_dim"))
     _NO_STATES = ("the -v0 ids observe float64 states with their goals, which SB3 gives an MLP policy: CnnActorCritic is the CNN policy of "
                   "the -v1 picture ids; ActorCritic is the policy for them")
-    _HOST = ("seed", "calls")
+    _refuse_foreign = staticmethod(_refuse_foreign)
 
     def __init__(self, envs=None, features_dim: int = 512, seed: int = 0, *, num_envs: Optional[int] = None, channels: Optional[int] = None,
                  image_size: Optional[int] = None, act_dim: Optional[int] = None, device=None, env_id_offset: Optional[int] = None):
@@ -136,16 +138,9 @@ class CnnActorCritic(DeviceBuffer):
         ``env_id_offset`` from; or give them by keyword.  ``features_dim``: the extractor's F, a multiple of 16 up to 512.  The weights
         start as SB3 initialises them (orthogonal: gain sqrt 2 in the extractor, 0.01 for the action head, 1 for the value head; zero
         biases and ``log_std``), from ``seed``."""
-        num_envs, channels, image_size, act_dim = self._resolve(envs, device, dict(num_envs=num_envs, channels=channels, image_size=image_size,
-                                                                                   act_dim=act_dim))
-        self.num_envs, self.channels, self.image_size, self.act_dim = int(num_envs), int(channels), int(image_size), int(act_dim)
+        self._setup_dims(envs, seed, dict(num_envs=num_envs, channels=channels, image_size=image_size, act_dim=act_dim), device, env_id_offset)
         self.features_dim = int(features_dim)
-        if env_id_offset is None:
-            env_id_offset = int(envs._cfg.env_id_offset) if envs is not None and hasattr(envs, "_cfg") else 0
-        self.env_id_offset = int(env_id_offset)
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.calls = 0                   # sampling calls of __call__ so far: the `call` word of the collection noise
-        shape = (self.channels, self.image_size, self.features_dim, self.act_dim)
+        shape = self._shape()
         if self.num_envs < 1 or not accepted(*shape):
             raise ValueError(f"unsupported shape: num_envs {self.num_envs}, channels {self.channels}, image_size {self.image_size}, "
                              f"features_dim {self.features_dim}, act_dim {self.act_dim}: " + _DOMAIN)
@@ -162,6 +157,18 @@ class CnnActorCritic(DeviceBuffer):
     def _shape(self):
         return self.channels, self.image_size, self.features_dim, self.act_dim
 
+    def _nets(self):
+        return (("blob", blob_shapes(*self._shape()), 0),)
+
+    def _fit(self):
+        return "CnnPolicy with net_arch=[]"
+
+    def _as_rows(self, sd: dict) -> dict:
+        return _flat(sd, self.channels)
+
+    def _as_sb3(self, sd: dict) -> dict:
+        return _unflat(sd, self.channels)
+
     def _scratch_for(self, rows: int) -> None:
         """The scratch between the two launches for ``rows`` pictures: it only grows, so it is sized for the most rows seen."""
         need = int(self._lib.mcg_cnn_scratch_floats(*self._shape(), C.c_int64(rows)))
@@ -172,54 +179,13 @@ class CnnActorCritic(DeviceBuffer):
             self._cbuf.scratch, self._cbuf.scratch_floats = self._scratch.data_ptr(), need
 
     def _initial_weights(self) -> dict:
-        gen = torch.Generator().manual_seed(self.seed % (2 ** 63))
-        sd = {}
-        for m, out, k, _first in blob_shapes(*self._shape())[:-1]:
-            gain = 0.01 if m == "action_net" else 1.0 if m == "value_net" else math.sqrt(2.0)
-            q, r = torch.linalg.qr(torch.randn(max(out, k), min(out, k), generator=gen, dtype=torch.float64))
-            q = q * torch.sign(torch.diagonal(r))
-            sd[m + ".weight"] = (gain * (q if out >= k else q.T)).float()
-            sd[m + ".bias"] = torch.zeros(out)
-        for (m, (k, _stride)), cin in zip(_CONVS.items(), (self.channels, 32, 64)):      # orthogonal on the flattened weight, as torch's
-            sd[m + ".weight"] = sd[m + ".weight"].reshape(-1, cin, k, k)
-        sd["log_std"] = torch.zeros(self.act_dim)
-        return sd
-
-    def _load_weights(self, sd: dict):
-        blob = pack(sd, *self._shape(), device=self.device)
-        assert blob.numel() == self._blob.numel(), (blob.numel(), self._blob.numel())
-        self._blob.copy_(blob)           # in place: the struct keeps pointing at it
-
-    def state_dict(self) -> dict:
-        """The weights under SB3's names (device tensors, unpacked from the blob; with SB3 >= 1.8's ``pi_features_extractor.*`` and
-        ``vf_features_extractor.*``, which are the shared extractor again) and the host fields ``seed`` and ``calls``."""
-        sd = unpack(self._blob, *self._shape())
-        sd.update({k: getattr(self, k) for k in self._HOST})
-        return sd
-
-    def load_state_dict(self, sd: dict):
-        """Weights under SB3's names (an SB3 ``ActorCriticCnnPolicy``'s ``state_dict()`` as it stands, or this class's); repacks the
-        blob.  The aliases of the extractor are accepted where they equal ``features_extractor.*``; ``seed`` and ``calls`` are taken
-        where given."""
-        sd = dict(sd)
-        host = {k: sd.pop(k) for k in self._HOST if k in sd}
-        sd = _refuse_foreign(sd)
-        want = set(state_names(aliases=False))
-        missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
-        if missing or extra:
-            raise ValueError(f"state dict does not fit CnnPolicy with net_arch=[]: missing {missing}, unexpected {extra}")
-        self._load_weights(sd)
-        for k, v in host.items():
-            setattr(self, k, int(v) & (2 ** 64 - 1) if k == "seed" else int(v))
+        return _unflat(super()._initial_weights(), self.channels, aliases=False)      # (orthogonal on the flattened weight, as torch's)
 
     @classmethod
     def from_module(cls, module, envs=None, seed: int = 0, **dims):
         """From any ``nn.Module`` whose ``state_dict()`` carries SB3's names (an SB3 ``ActorCriticCnnPolicy``'s does).  ``features_dim``
         comes from the linear layer's shape.  gSDE, ``squash_output``, a non-empty ``net_arch`` and separate extractors are refused."""
-        if getattr(module, "use_sde", False):
-            raise ValueError("gSDE (use_sde=True) is not supported: the noise is the diagonal Gaussian's, drawn per call")
-        if getattr(module, "squash_output", False):
-            raise ValueError("squash_output=True is not supported: the action is the unsquashed Gaussian sample")
+        cls._refuse_module(module)
         if getattr(module, "share_features_extractor", True) is False:
             raise ValueError("share_features_extractor=False is not supported: actor and critic share one NatureCNN")
         sd = _refuse_foreign({k: v for k, v in module.state_dict().items()})
@@ -252,41 +218,18 @@ class CnnActorCritic(DeviceBuffer):
         N, A, F = self.num_envs, self.act_dim, self.features_dim
         return {"action": (N, A), "mean": (N, A), "noise": (N, A), "value": (N,), "log_prob": (N,), "features": (N, F)}
 
-    def _new(self, *names):
-        shapes = self._shapes()
-        return {k: torch.empty(shapes[k], dtype=torch.float32, device=self.device) for k in names}
+    def _caller_out(self, out, shapes: dict, who: str):
+        if not isinstance(out, dict) or not out:
+            raise ValueError(f"{who}: out: a dict with at least one of {sorted(shapes)}")
+        return check_out(out, shapes, next(iter(out)), who, self.device)
 
     def _forward(self, img, call, deterministic, out: dict, who):
+        """``img``: uint8 [N, C, S, S], read in place; two launches.  ``out``: under ``mcg_cnn_out``'s names (``features`` too)."""
         cobs, _keep = self._pictures(img, who + ": img", self.num_envs, (torch.uint8,))
         cout = _abi.McgCnnOut(**{k: v.data_ptr() for k, v in out.items()})
         self._scratch_for(self.num_envs)
         self._call("mcg_cnn_forward", C.byref(cobs), C.c_uint64(self.seed), C.c_uint64(int(call) & (2 ** 64 - 1)),
                    C.c_int64(self.env_id_offset), int(bool(deterministic)), C.byref(cout))
-
-    def forward(self, img, deterministic: bool = False, out: Optional[dict] = None):
-        """``img``: what ``envs.reset`` / ``envs.step`` returned (uint8 [N, C, S, S], read in place) -> (action [N, A], value [N],
-        log_prob [N]), float32 device tensors; two launches.  ``deterministic``: the action is the mean and no call number is used up.
-        ``out``: the tensors to write into, under ``mcg_cnn_out``'s names (action, value, log_prob, mean, noise, features: any subset)."""
-        if out is None:
-            out = self._new("action", "value", "log_prob")
-        else:
-            if not isinstance(out, dict) or not out:
-                raise ValueError("forward: out: a dict with at least one of " + str(sorted(self._shapes())))
-            check_out(out, self._shapes(), next(iter(out)), "forward", self.device)
-        self._forward(img, self.calls, deterministic, out, "forward")
-        if not deterministic:
-            self.calls += 1
-        return out.get("action"), out.get("value"), out.get("log_prob")
-
-    __call__ = forward
-
-    def values(self, img, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The value alone (the bootstrap of ``info["final_observation"]``, the last value of a rollout): float32 [N]; two launches, no
-        policy-head work, no call number used up."""
-        v = self._new("value")["value"] if out is None else out
-        check_out({"value": v}, self._shapes(), "value", "values", self.device)
-        self._forward(img, 0, True, {"value": v}, "values")
-        return v
 
     # ------------------------------------------------------------------------------------------------ on a minibatch
     def evaluate_actions(self, observations, actions, out: Optional[dict] = None):
@@ -307,14 +250,7 @@ class CnnActorCritic(DeviceBuffer):
         if actions.device != self.device:
             raise ValueError(f"{who}: actions lives on {actions.device}, the policy on {self.device}")
         a = actions if actions.is_contiguous() else actions.contiguous()
-        shapes = {k: (B,) for k in ("value", "log_prob", "entropy")}
-        if out is None:
-            out = {k: torch.empty(B, dtype=torch.float32, device=self.device) for k in shapes}
-        else:
-            if not isinstance(out, dict) or not out:
-                raise ValueError(f"{who}: out: a dict with at least one of {sorted(shapes)}")
-            check_out(out, shapes, next(iter(out)), who, self.device)
+        out, cout = self._eval_out(B, out, who)
         self._scratch_for(B)
-        cout = _abi.McgPolicyEvalOut(**{k: v.data_ptr() for k, v in out.items()})
         self._call("mcg_cnn_evaluate", C.byref(cobs), C.c_void_p(a.data_ptr()), C.c_int64(B), C.byref(cout))
         return out.get("value"), out.get("log_prob"), out.get("entropy")

@@ -45,34 +45,22 @@
 // linear [F, 64 o3^2], action_net (A rows padded with zeros to 16) [16, F], value_net (1 row padded to 16) [16, F]; then log_std padded
 // to 16.  Every piece is a multiple of 16 floats.
 //
-// ---- The noise: policy_pair's counter layout (mcg_policy.hip) with a domain byte of its own, 12 (0-6: mcg_policy.hip's list; 7-11:
-// mcg_sac.hpp and mcg_td3.hpp).  Philox4x32-10, key = seed, counter
-//     ((uint32)gid, (uint32)call, pair ^ ((uint32)(call >> 32) << 8), 12 ^ ((uint32)(gid >> 32) << 8))
-// Box-Muller in double, rounded to float32 once; the action mean + exp(log_std) eps in double, rounded once.
+// ---- The noise and the Gaussian head: mcg_policy.hpp's (gauss4's counter layout, stated at mcg_policy.hip's head), with a domain byte
+// of its own, DOMAIN_CNN (enum Domain, mcg_philox.hpp).
 //
 // ---- Order.  No atomics; every sum's order is fixed by the shape alone, and a row's depends on neither its place in the batch nor
 // on the batch's size: equal pictures and equal global ids give equal bits.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
 #include <type_traits>
 
-#include "mcg.h"
-#include "mcg_buffer.hpp"        // blocks, launched; mcg_fail; philox_pair
+#include "mcg_policy.hpp"        // f4, mfma, WAVE, MAX_ACT, rows_in_range, EvalOut, the Gaussian head; mcg_buffer.hpp: blocks, launched, mcg_fail
 
 using namespace mcg;
 
 namespace {
 
-constexpr uint32_t CNN_STREAM = 12;
-constexpr int WAVE = 64, WAVES = 4, LANES = WAVE * WAVES, NP = 4, ROWS = 32, MAXM = 8, MAX_ACT = 16;
+constexpr int WAVES = 4, LANES = WAVE * WAVES, NP = 4, ROWS = 32, MAXM = 8;
 constexpr int MIN_S = 36, MAX_S = 96, MAX_C = 16, MAX_F = 512, MAX_E = 4;
 constexpr int LDS_SOFT = 64 * 1024, QUOTIENT_BYTES = 256 * (int)sizeof(float);
-constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
-constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct Cnn {                             // mcg_cnn_policy as the kernels see it; offsets into the blob in floats
   const float* blob;
@@ -80,18 +68,11 @@ struct Cnn {                             // mcg_cnn_policy as the kernels see it
   int w1, b1, w2, b2, w3, b3, wl, bl, wa, ba, wv, bv, log_std;
 };
 struct Out { float *action, *value, *log_prob, *mean, *noise, *features; };
-struct EvalOut { float *value, *log_prob, *entropy; };
-
-MCG_DEV f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // byte / 255 for all 256 bytes, by the first 256 lanes of a workgroup: the correctly rounded quotient (IEEE division, nothing
 // reciprocal), formed once per byte value instead of once per pixel and window
 MCG_DEV void quotient_of(float* table, int lane) {
   if (lane < 256) table[lane] = (float)lane / 255.0f;
-}
-
-MCG_DEV void cnn_pair(unsigned long long seed, unsigned long long gid, unsigned long long call, uint32_t pair, double& u0, double& u1) {
-  philox_pair((uint32_t)gid, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), CNN_STREAM ^ ((uint32_t)(gid >> 32) << 8), seed, u0, u1);
 }
 
 // Channel tiles T .. T + MT - 1 of a layer of `chunks` chunks of 16 k, on the column tiles pt0 .. of the Q columns (at most NP of them):
@@ -306,63 +287,28 @@ __global__ __launch_bounds__(LANES) void cnn_dense_kernel(Cnn P, const float* __
     return;
   }
   const f4 ls = *reinterpret_cast<const f4*>(P.blob + P.log_std + 4 * g);
-  if (EVAL) {
-    // the log-prob from the float32 mean in double, rounded once: mcg_policy_evaluate's rule
-    double lpd = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int c = 4 * g + r;
-      if (c < P.A) {
-        const double inv = exp(-(double)ls[r]), zd = ((double)actions[(size_t)row * P.A + c] - (double)h[r]) * inv;
-        lpd += -0.5 * zd * zd - (double)ls[r] - LOG_SQRT_2PI_D;
-      }
-    }
-    lpd += __shfl_xor(lpd, 16);          // the four lanes of a row
-    lpd += __shfl_xor(lpd, 32);
+  if (EVAL) {                            // mcg_policy_evaluate's rule (mcg_policy.hpp); the derivative is not wanted
+    f4 dmu, dls;
+    const double lpd = gauss_log_prob(P.A, h, ls, actions, (size_t)row, g, dmu, dls);
     if (live && g == 0) {
       if (V.log_prob) V.log_prob[s] = (float)lpd;
-      if (V.entropy) {
-        float ent = 0.0f;
-        for (int c = 0; c < P.A; c++) ent += ENTROPY_0 + P.blob[P.log_std + c];
-        V.entropy[s] = ent;
-      }
+      if (V.entropy) V.entropy[s] = gauss_entropy(P.A, P.blob + P.log_std);
     }
     return;
   }
-  // ---- the diagonal Gaussian: this lane has components 4 g .. 4 g + 3, pairs 2 g and 2 g + 1 (mcg_policy.hip's rule)
-  const unsigned long long gid = (unsigned long long)(env_id_offset + row);
-  float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (!deterministic) {
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      if (4 * g + 2 * q < P.A) {
-        double u0, u1, sn, cs;
-        cnn_pair(seed, gid, call, (uint32_t)(2 * g + q), u0, u1);
-        const double rad = sqrt(-2.0 * log(1.0 - u0));
-        sincos(6.283185307179586476925 * u1, &sn, &cs);
-        eps[2 * q] = (float)(rad * cs);
-        eps[2 * q + 1] = (float)(rad * sn);
-      }
-    }
-  }
-  float lp = 0.0f;
+  // ---- the diagonal Gaussian (mcg_policy.hpp): this lane has components 4 g .. 4 g + 3
+  const Sampled d = gauss_sample(P.A, h, ls, g, seed, (unsigned long long)(env_id_offset + row), call, DOMAIN_CNN, deterministic);
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     const int c = 4 * g + r;
-    if (c < P.A) {
-      const float act = deterministic ? h[r] : (float)((double)h[r] + exp((double)ls[r]) * (double)eps[r]);
-      lp += (-0.5f * eps[r]) * eps[r] - ls[r] - 0.918938533204672742f;          // - eps^2 / 2 - log_std - ln(2 pi) / 2
-      if (live) {
-        const size_t at = (size_t)s * P.A + c;
-        if (O.action) O.action[at] = act;
-        if (O.mean) O.mean[at] = h[r];
-        if (O.noise) O.noise[at] = eps[r];
-      }
+    if (c < P.A && live) {
+      const size_t at = (size_t)s * P.A + c;
+      if (O.action) O.action[at] = d.action[r];
+      if (O.mean) O.mean[at] = d.mean[r];
+      if (O.noise) O.noise[at] = d.noise[r];
     }
   }
-  lp += __shfl_xor(lp, 16);              // the four lanes of a row, in an order that does not depend on the tile
-  lp += __shfl_xor(lp, 32);
-  if (O.log_prob && live && g == 0) O.log_prob[s] = lp;
+  if (O.log_prob && live && g == 0) O.log_prob[s] = d.log_prob;
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
@@ -387,8 +333,6 @@ inline int64_t plan(int C, int S, int F, int A, Cnn* P, const char** why) {
   if (P) *P = p;
   return at;
 }
-
-inline bool rows_in_range(int64_t rows) { return rows >= 1 && rows * MAX_ACT < (1ll << 31); }
 
 // What both entries check before they launch -> MCG_OK with P filled; the code after mcg_fail.
 inline int checked(const char* who, const mcg_cnn_policy* pol, const mcg_cnn_obs* obs, int64_t rows, Cnn* P) {

@@ -48,8 +48,8 @@ MCG_DEV void rng_pair(const Cfg& C, int i, int32_t episode, uint32_t draw, uint3
 // _sample_goal (mycobot.py:238-243) with generate_random_point_inside_rectangle (utils.py:14-21); uses draws d, d+1
 MCG_DEV void sample_goal(const Cfg& C, int i, int32_t episode, uint32_t draw, real* g) {
   real ux, uy, uc, uz;
-  rng_pair(C, i, episode, draw, 0, ux, uy);
-  rng_pair(C, i, episode, draw + 1, 0, uc, uz);
+  rng_pair(C, i, episode, draw, DOMAIN_RESET, ux, uy);
+  rng_pair(C, i, episode, draw + 1, DOMAIN_RESET, uc, uz);
   // a + (b - a) * u as one explicit fma: rounds identically on the CPU oracle and here
   g[0] = fma(0.12 - -0.12, ux, -0.12);
   g[1] = fma(0.06 - -0.06, uy, -0.06);
@@ -385,7 +385,7 @@ MCG_DEV void store_envp(const View& V, int i, const EnvP& E) {
 MCG_DEV void reset_envp(const Cfg& C, int i, EnvP& E, bool doit) {
   real drs[2] = {1.0, 1.0};
   if (C.dr_enable) {
-    real um, uf; rng_pair(C, i, E.episode, 0, 1, um, uf);
+    real um, uf; rng_pair(C, i, E.episode, 0, DOMAIN_PHYSICS, um, uf);
     drs[0] = C.dr_mass[0] + (C.dr_mass[1] - C.dr_mass[0]) * um;
     drs[1] = C.dr_fric[0] + (C.dr_fric[1] - C.dr_fric[0]) * uf;
   }

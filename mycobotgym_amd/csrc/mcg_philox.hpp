@@ -9,6 +9,24 @@
 
 namespace mcg {
 
+// The domain byte: the low byte of a counter's last word, which keeps one user's draws apart from every other's under the same seed.
+// This is the one list; a new user takes the next number.
+enum Domain : uint32_t {
+  DOMAIN_RESET = 0,            // reset: the goal's and the cube's place (rng_pair, mcg_hip.hip)
+  DOMAIN_PHYSICS = 1,          // reset: the cube's mass and friction (rng_pair)
+  DOMAIN_SCENE = 2,            // reset: cameras, light and colours of the pictures (scene_pair, mcg_render.hip)
+  DOMAIN_HER = 3,              // the hindsight replay buffer's sampling (her_pair, mcg_replay.hip)
+  DOMAIN_ROLLOUT = 4,          // the rollout buffers' permutation of an epoch (mcg_rollout.hip)
+  DOMAIN_REPLAY_IMG = 5,       // the picture replay buffer's sampling (mcg_replay_img.hip)
+  DOMAIN_POLICY = 6,           // ActorCritic's collection noise (mcg_policy.hip)
+  DOMAIN_SAC_ACT = 7,          // SAC: the collection noise (mcg_sac.hip)
+  DOMAIN_SAC_TARGET = 8,       // SAC: the next action of the TD target
+  DOMAIN_SAC_ACTOR_LOSS = 9,   // SAC: the actor loss's action (mcg_sac_grad.hip)
+  DOMAIN_TD3_ACT = 10,         // TD3 / DDPG: the exploration noise (mcg_td3.hip)
+  DOMAIN_TD3_TARGET = 11,      // TD3: the target policy's smoothing noise
+  DOMAIN_CNN = 12,             // CnnActorCritic's collection noise (mcg_cnn.hip)
+};
+
 MCG_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
 #pragma unroll
   for (int r = 0; r < 10; r++) {

@@ -30,12 +30,11 @@
 //     later layers  nkb = in / 4,             k(4 t + r, g) = 16 t + 4 g + r
 // Every piece is a multiple of 16 floats, so with a 16-byte aligned blob every bias row of 4 is one aligned 16-byte load.
 //
-// ---- The noise: counter layout policy_pair.  Philox4x32-10 (mcg_philox.hpp), key = seed, counter
-//     ((uint32)gid, (uint32)call, pair ^ ((uint32)(call >> 32) << 8), 6 ^ ((uint32)(gid >> 32) << 8))
+// ---- The noise: the counter layout of gauss4 (mcg_policy.hpp).  Philox4x32-10 (mcg_philox.hpp), key = seed, counter
+//     ((uint32)gid, (uint32)call, pair ^ ((uint32)(call >> 32) << 8), DOMAIN_POLICY ^ ((uint32)(gid >> 32) << 8))
 // gid = env_id_offset + i the global environment id, `call` the caller's count of sampling calls, pair = 0 .. ceil(A / 2) - 1.  The low
-// byte of the last word is the domain: 0-2 are the reset and scene draws (rng_pair, scene_pair), 3 her_pair, 4 the rollout
-// permutation, 5 the picture replay's draws, 6 this.  One block is two uniforms u0, u1 of 53 bits (philox_pair) and serves two action
-// components by Box-Muller, evaluated in double and rounded to float32 once:
+// byte of the last word is the domain (enum Domain, mcg_philox.hpp: the one list).  One block is two uniforms u0, u1 of 53 bits
+// (philox_pair) and serves two action components by Box-Muller, evaluated in double and rounded to float32 once:
 //     eps[2 pair] = sqrt(-2 ln(1 - u0)) cos(2 pi u1),   eps[2 pair + 1] = sqrt(-2 ln(1 - u0)) sin(2 pi u1)
 // An environment's draws depend on (seed, gid, call) alone: not on the tile it falls into, nor on how many ranks share the job.
 #include "mcg_policy.hpp"       // plan, Net, Pol, mfma, activate, first_layer, dense, pick: shared with mcg_policy_grad.hip
@@ -44,13 +43,7 @@ using namespace mcg;
 
 namespace {
 
-constexpr uint32_t POLICY_STREAM = 6;
-
 struct Out { float *action, *value, *log_prob, *mean, *noise; };
-
-MCG_DEV void policy_pair(unsigned long long seed, unsigned long long gid, unsigned long long call, uint32_t pair, double& u0, double& u1) {
-  philox_pair((uint32_t)gid, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), POLICY_STREAM ^ ((uint32_t)(gid >> 32) << 8), seed, u0, u1);
-}
 
 // MT: tiles of 16 units that a trunk layer may have (the host picks 4 or 16 by the widest layer).
 template <int MT>
@@ -84,42 +77,20 @@ __global__ __launch_bounds__(WAVE) void policy_kernel(Pol P, const double* __res
     if (O.value && live && g == 0) O.value[e] = h[0];
     return;
   }
-  // ---- the diagonal Gaussian: this lane has components 4 g .. 4 g + 3, pairs 2 g and 2 g + 1
+  // ---- the diagonal Gaussian (mcg_policy.hpp): this lane has components 4 g .. 4 g + 3
   const f4 ls = *reinterpret_cast<const f4*>(P.blob + P.log_std + 4 * g);
-  const unsigned long long gid = (unsigned long long)(env_id_offset + env);
-  float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (!deterministic) {
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      if (4 * g + 2 * q < P.A) {
-        double u0, u1, s, c;
-        policy_pair(seed, gid, call, (uint32_t)(2 * g + q), u0, u1);
-        const double rad = sqrt(-2.0 * log(1.0 - u0));
-        sincos(6.283185307179586476925 * u1, &s, &c);
-        eps[2 * q] = (float)(rad * c);
-        eps[2 * q + 1] = (float)(rad * s);
-      }
-    }
-  }
-  float lp = 0.0f;
+  const Sampled d = gauss_sample(P.A, h, ls, g, seed, (unsigned long long)(env_id_offset + env), call, DOMAIN_POLICY, deterministic);
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     const int c = 4 * g + r;
-    if (c < P.A) {
-      // mean + exp(log_std) eps in double, rounded once (the action is not clipped: the step kernels clip what they read)
-      const float act = deterministic ? h[r] : (float)((double)h[r] + exp((double)ls[r]) * (double)eps[r]);
-      lp += (-0.5f * eps[r]) * eps[r] - ls[r] - 0.918938533204672742f;          // - eps^2 / 2 - log_std - ln(2 pi) / 2
-      if (live) {
-        const size_t at = (size_t)e * P.A + c;
-        if (O.action) O.action[at] = act;
-        if (O.mean) O.mean[at] = h[r];
-        if (O.noise) O.noise[at] = eps[r];
-      }
+    if (c < P.A && live) {
+      const size_t at = (size_t)e * P.A + c;
+      if (O.action) O.action[at] = d.action[r];
+      if (O.mean) O.mean[at] = d.mean[r];
+      if (O.noise) O.noise[at] = d.noise[r];
     }
   }
-  lp += __shfl_xor(lp, 16);              // the four lanes of an environment, in an order that does not depend on the tile
-  lp += __shfl_xor(lp, 32);
-  if (O.log_prob && live && g == 0) O.log_prob[e] = lp;
+  if (O.log_prob && live && g == 0) O.log_prob[e] = d.log_prob;
 }
 
 }  // namespace
@@ -157,9 +128,7 @@ int mcg_policy_forward(const mcg_policy* pol, const mcg_step_out* obs, uint64_t 
   P.blob = pol->blob; P.N = pol->n_envs; P.act = pol->activation;
   const int nets = (out->action || out->log_prob || out->mean || out->noise) ? 2 : 1;      // value alone: the policy net is not evaluated
   const Out O = {out->action, out->value, out->log_prob, out->mean, out->noise};
-  int widest = 0;
-  for (int L = 0; L < pol->n_pi; L++) widest = pol->pi_width[L] > widest ? pol->pi_width[L] : widest;
-  for (int L = 0; L < pol->n_vf; L++) widest = pol->vf_width[L] > widest ? pol->vf_width[L] : widest;
+  const int widest = widest_layer(pol);
   const dim3 grid(blocks(P.N, TILE), nets), block(WAVE);
 #define MCG_POLICY(MT) hipLaunchKernelGGL(policy_kernel<MT>, grid, block, 0, (hipStream_t)stream, P, obs->obs, obs->achieved_goal, \
                                           obs->desired_goal, (unsigned long long)seed, (unsigned long long)call, (long long)env_id_offset, \

@@ -1,6 +1,9 @@
 // mcg_policy.hpp -- what mcg_policy.hip (the forward of collection) and mcg_policy_grad.hip (evaluate_actions, the loss gradient, Adam)
 // share: the blob's plan, the kernel's view of a policy, the matrix instruction and the layer helpers of the forward pass.  The blob's
 // layout and the operand map of v_mfma_f32_16x16x4_f32 are stated in mcg_policy.hip's head; each file's own rule stays in that file.
+// And what every policy's code object shares, mcg_cnn.hip's and (through mcg_sac.hpp) the off-policy learners' too: the matrix
+// instruction, the Gaussian draw gauss4, and the diagonal Gaussian head -- sampling, the log-prob of stored actions with its
+// derivative, the entropy -- for ActorCritic and CnnActorCritic.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -90,6 +93,89 @@ MCG_DEV Net pick(const Net& x, const Net& y, int k) {
 #pragma unroll
   for (int L = 0; L <= MAX_LAYERS; L++) { z.w[L] = k ? y.w[L] : x.w[L]; z.b[L] = k ? y.b[L] : x.b[L]; }
   return z;
+}
+
+// ---------------------------------------------------------------------------------------------- the diagonal Gaussian
+// Lane 16 g + i holds rows 4 g + r of a head, r = 0..3: components 4 g .. 4 g + 3 of sample i, pairs 2 g and 2 g + 1; the four lanes of
+// a sample are summed by __shfl_xor 16, then 32: an order that does not depend on the tile.
+constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
+constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
+
+struct EvalOut { float *value, *log_prob, *entropy; };                  // mcg_policy_eval_out
+
+// n, zeros -> components 4 g .. 4 g + 3 of a row's standard Gaussian draw, those from A on left as they are: one Philox block per pair of
+// components, Box-Muller in double, the second value of a last odd pair dropped.  The counter (mcg_policy.hip's head): `id` the global
+// environment id or the row, `call` the caller's count, `stream` the domain byte (enum Domain, mcg_philox.hpp).
+MCG_DEV void gauss4(f4& n, int A, int g, unsigned long long seed, unsigned long long id, unsigned long long call, uint32_t stream) {
+#pragma unroll
+  for (int q = 0; q < 2; q++) {
+    if (4 * g + 2 * q < A) {
+      double u0, u1, s, c;
+      const uint32_t pair = (uint32_t)(2 * g + q);
+      mcg::philox_pair((uint32_t)id, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), stream ^ ((uint32_t)(id >> 32) << 8), seed, u0, u1);
+      const double rad = sqrt(-2.0 * log(1.0 - u0));
+      sincos(6.283185307179586476925 * u1, &s, &c);
+      n[2 * q] = (float)(rad * c);
+      if (4 * g + 2 * q + 1 < A) n[2 * q + 1] = (float)(rad * s);
+    }
+  }
+}
+
+// What sampling gives a lane: its components (zeros from A on; the mean is the head's rows) and the sample's log-prob (on all four lanes).
+struct Sampled { f4 action, mean, noise; float log_prob; };
+
+// The head's rows h and log_std's ls of a lane -> the sample.  The action is mean + exp(log_std) eps in double, rounded once (not clipped:
+// the step kernels clip what they read); the log-prob is float32 throughout.  deterministic: the mean, no block, the log-prob of eps = 0.
+MCG_DEV Sampled gauss_sample(int A, const f4& h, const f4& ls, int g, unsigned long long seed, unsigned long long id, unsigned long long call,
+                             uint32_t stream, bool deterministic) {
+  Sampled d;
+  d.noise = f4{0.0f, 0.0f, 0.0f, 0.0f};
+  if (!deterministic) gauss4(d.noise, A, g, seed, id, call, stream);
+  float lp = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    d.action[r] = d.mean[r] = 0.0f;
+    if (4 * g + r < A) {
+      const float eps = d.noise[r];
+      d.action[r] = deterministic ? h[r] : (float)((double)h[r] + exp((double)ls[r]) * (double)eps);
+      d.mean[r] = h[r];
+      lp += (-0.5f * eps) * eps - ls[r] - 0.918938533204672742f;               // - eps^2 / 2 - log_std - ln(2 pi) / 2
+    }
+  }
+  lp += __shfl_xor(lp, 16);
+  lp += __shfl_xor(lp, 32);
+  d.log_prob = lp;
+  return d;
+}
+
+// SB3's evaluate_actions: the log-prob of the stored `actions` of `row` -> on all four lanes, in double from the float32 mean (log_prob -
+// old_log_prob and (ratio - 1) - ln ratio cancel most of its digits, and a sum of A terms of magnitude 1 in float32 would leave them its
+// rounding: a few 1e-7 on a ratio near 1); the caller rounds it once.  dmu, dls: d log_prob / d mean_c = (a - mean) / sigma^2 and
+// d log_prob / d log_std_c of the lane's components, zeros from A on (the gradient's; an evaluation drops them).
+MCG_DEV double gauss_log_prob(int A, const f4& h, const f4& ls, const float* __restrict__ actions, size_t row, int g, f4& dmu, f4& dls) {
+  double lpd = 0.0;
+  dmu = dls = f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int c = 4 * g + r;
+    if (c < A) {
+      const double inv = exp(-(double)ls[r]), zd = ((double)actions[row * A + c] - (double)h[r]) * inv;
+      lpd += -0.5 * zd * zd - (double)ls[r] - LOG_SQRT_2PI_D;
+      const float z = (float)zd;
+      dmu[r] = z * (float)inv;
+      dls[r] = z * z - 1.0f;
+    }
+  }
+  lpd += __shfl_xor(lpd, 16);
+  lpd += __shfl_xor(lpd, 32);
+  return lpd;
+}
+
+// The entropy of the Gaussian: it depends on log_std alone.  Float32, in the components' order.
+MCG_DEV float gauss_entropy(int A, const float* log_std) {
+  float ent = 0.0f;
+  for (int c = 0; c < A; c++) ent += ENTROPY_0 + log_std[c];
+  return ent;
 }
 
 // ------------------------------------------------------------------------------------------------------- host side

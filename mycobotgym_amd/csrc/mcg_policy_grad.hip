@@ -46,8 +46,8 @@
 // that every product they enter adds exactly nothing.
 //
 // ---- Shared with SAC and TD3 / DDPG (mcg_grad.hpp): the row map, the rows' stores, the hidden layers' forward, the walk back through
-// W^T, the dW kernel and its block list, the reduce's two helpers, Adam's kernel.  Here: the pick of one of the two nets, the Gaussian
-// head and the PPO / A2C loss, the statistic in double, the advantage's and the gradient's norm kernels, the log_std block.
+// W^T, the dW kernel and its block list, the reduce's two helpers, Adam's kernel.  Shared with the forwards (mcg_policy.hpp): the
+// Gaussian head's log-prob, its derivative and the entropy.  Here: the pick of one of the two nets, the PPO / A2C loss, the statistic in double, the advantage's and the gradient's norm kernels, the log_std block.
 #include "mcg_grad.hpp"       // GRows, Blocks, sum16, sum64, store_rows, store_features, hidden_rows, walk_back, dw_kernel, reduced_parts,
                               // block_sum, adam_kernel, adam_step, number_rows, layer_block, add_block, split_parts, checked_buffer
 
@@ -56,12 +56,9 @@ using namespace mcg;
 namespace {
 
 constexpr int SUMS = 8;                                                 // the tiles' sums start here in `work`
-constexpr double LOG_SQRT_2PI_D = 0.918938533204672742;                 // ln(2 pi) / 2
-constexpr float ENTROPY_0 = 1.418938533204672742f;                      // 1/2 + ln(2 pi) / 2
 
 struct Batch { const float *obs, *ach, *des, *action, *old_lp, *adv, *ret; };
 struct Hyper { int kind, norm; float clip, ent_coef, vf_coef, inv_b; double inv_bd; };      // inv_bd: 1 / B for the sums held in double
-struct EvalOut { float *value, *log_prob, *entropy; };
 
 // sum16 (mcg_grad.hpp) in double
 MCG_DEV double sum16d(double x) {
@@ -113,32 +110,12 @@ __global__ __launch_bounds__(WAVE) void grad_tile_kernel(Pol P, GRows R0, GRows 
     if (lane == 0) work[SUMS + 8 * (size_t)tile + 2] = sq;
   } else {
     const f4 ls = *reinterpret_cast<const f4*>(P.blob + P.log_std + 4 * g);
-    // The log-prob from the float32 mean in double, rounded once: log_prob - old_log_prob and (ratio - 1) - ln ratio cancel most of
-    // its digits, and a sum of A terms of magnitude 1 in float32 would leave them its rounding (a few 1e-7 on a ratio near 1).
-    double lpd = 0.0;
-    f4 dmu = {0.0f, 0.0f, 0.0f, 0.0f}, dls = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int c = 4 * g + r;
-      if (c < P.A) {
-        const double inv = exp(-(double)ls[r]), zd = ((double)X.action[(size_t)row * P.A + c] - (double)h[r]) * inv;
-        lpd += -0.5 * zd * zd - (double)ls[r] - LOG_SQRT_2PI_D;
-        const float z = (float)zd;
-        dmu[r] = z * (float)inv;         // d log_prob / d mean_c = (a - mean) / sigma^2
-        dls[r] = z * z - 1.0f;           // d log_prob / d log_std_c
-      }
-    }
-    lpd += __shfl_xor(lpd, 16);          // the four lanes of a sample, in the forward's order
-    lpd += __shfl_xor(lpd, 32);
-    const float lp = (float)lpd;
+    f4 dmu, dls;                         // the Gaussian head (mcg_policy.hpp): the log-prob in double, rounded once, and its derivative
+    const double lpd = gauss_log_prob(P.A, h, ls, X.action, (size_t)row, g, dmu, dls);
     if (!GRAD) {
       if (live && g == 0) {
-        if (E.log_prob) E.log_prob[s] = lp;
-        if (E.entropy) {
-          float ent = 0.0f;
-          for (int c = 0; c < P.A; c++) ent += ENTROPY_0 + P.blob[P.log_std + c];
-          E.entropy[s] = ent;
-        }
+        if (E.log_prob) E.log_prob[s] = (float)lpd;
+        if (E.entropy) E.entropy[s] = gauss_entropy(P.A, P.blob + P.log_std);
       }
       return;
     }
@@ -202,8 +179,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* __restric
   for (int j = 0; j < 3; j++) acc[j] = sum64(acc[j]);
   term = sum64(term);
   if (threadIdx.x == 0) {
-    float ent = 0.0f;
-    for (int c = 0; c < A; c++) ent += ENTROPY_0 + blob[log_std + c];
+    const float ent = gauss_entropy(A, blob + log_std);
     const double policy_loss = -term * H.inv_bd;
     const float value_loss = acc[0] * H.inv_b, entropy_loss = -ent;
     stats[0] = (float)(policy_loss + (double)H.ent_coef * (double)entropy_loss + (double)H.vf_coef * (double)value_loss);

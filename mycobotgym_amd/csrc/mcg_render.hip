@@ -146,11 +146,11 @@ struct SceneRandArgs {
 namespace {
 
 // the reset draws' keying (mcg_hip.hip: rng_pair), on the pictures' stream
-constexpr uint32_t SCENE_STREAM = 2, SCENE_CAM_DRAW0 = 32, SCENE_CAM_DRAWS = 4;
+constexpr uint32_t SCENE_CAM_DRAW0 = 32, SCENE_CAM_DRAWS = 4;
 
 MCG_DEV void scene_pair(const SceneRandArgs& P, int i, int32_t episode, uint32_t draw, real& u0, real& u1) {
   const unsigned long long gid = (unsigned long long)(P.env_id_offset + i);
-  philox_pair((uint32_t)gid, (uint32_t)episode, draw, SCENE_STREAM ^ ((uint32_t)(gid >> 32) << 8), P.seed, u0, u1);
+  philox_pair((uint32_t)gid, (uint32_t)episode, draw, DOMAIN_SCENE ^ ((uint32_t)(gid >> 32) << 8), P.seed, u0, u1);
 }
 
 // a + (b - a) * u as one explicit fma, as sample_goal maps its uniforms

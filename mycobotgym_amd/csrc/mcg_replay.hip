@@ -15,7 +15,6 @@ using namespace mcg;
 namespace {
 
 constexpr int GOAL_WORDS = 18;          // achieved[3], next_achieved[3], desired[3] as doubles
-constexpr int HER_STREAM = 3;           // Philox stream of the sampling draws (0: goals, 1: mass and friction, 2: pictures)
 constexpr int HER_MAX_DRAWS = 256;      // rejection draws per sample; draw HER_MAX_DRAWS picks the future step
 constexpr int ADD_LANES = 256;
 
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(ADD_LANES) void her_add_kernel(Her B, int pos, int 
 
 // ----------------------------------------------------------------------------------------------------------- sample
 MCG_DEV void her_pair(unsigned long long seed, unsigned long long call, uint32_t k, uint32_t draw, double& u0, double& u1) {
-  philox_pair(k, (uint32_t)call, draw, (uint32_t)HER_STREAM ^ ((uint32_t)(call >> 32) << 8), seed, u0, u1);
+  philox_pair(k, (uint32_t)call, draw, DOMAIN_HER ^ ((uint32_t)(call >> 32) << 8), seed, u0, u1);
 }
 
 struct Batch { float *obs, *ach, *des, *nobs, *nach, *act, *rew, *done; int32_t* index; };

@@ -16,7 +16,6 @@ using namespace mcg;
 
 namespace {
 
-constexpr int REPLAY_IMG_STREAM = 5;    // Philox stream of the sampling draws (0-2: the reset draws, 3: HER, 4: the rollout permutation)
 constexpr int MAX_DRAWS = 256;          // rejection draws per sample
 constexpr int ADD_LANES = 256;
 constexpr uint32_t TERMINATED = 1u, TIMEOUT = 2u, NO_NEXT = 4u;      // a record's flags
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(SAMPLE_LANES) void replay_img_sample_kernel(Ring B,
   const int k = blockIdx.x * (SAMPLE_LANES / 64) + (threadIdx.x >> 6);   // wave-uniform; the output row of this wave
   if (k >= batch) return;
   // ---- index phase: the first draw whose record still has its next picture
-  const uint32_t c1 = (uint32_t)call, c3 = (uint32_t)REPLAY_IMG_STREAM ^ ((uint32_t)(call >> 32) << 8);
+  const uint32_t c1 = (uint32_t)call, c3 = DOMAIN_REPLAY_IMG ^ ((uint32_t)(call >> 32) << 8);
   int j = 0, e = 0, row = 0;
   uint32_t flags = NO_NEXT;
   for (int d = 0; d < MAX_DRAWS && (flags & NO_NEXT) != 0; d++) {
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(SAMPLE_LANES) void replay_img_sample_stacked_kernel
   const int k = blockIdx.x * (SAMPLE_LANES / 64) + (threadIdx.x >> 6);   // wave-uniform; the output row of this wave
   if (k >= batch) return;
   // ---- index phase: the first draw whose record still has its next picture
-  const uint32_t c1 = (uint32_t)call, c3 = (uint32_t)REPLAY_IMG_STREAM ^ ((uint32_t)(call >> 32) << 8);
+  const uint32_t c1 = (uint32_t)call, c3 = DOMAIN_REPLAY_IMG ^ ((uint32_t)(call >> 32) << 8);
   int j = 0, e = 0, row = 0;
   uint32_t flags = NO_NEXT;
   for (int d = 0; d < MAX_DRAWS && (flags & NO_NEXT) != 0; d++) {

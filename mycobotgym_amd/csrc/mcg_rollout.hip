@@ -20,7 +20,6 @@ using namespace mcg;
 
 namespace {
 
-constexpr int ROLLOUT_STREAM = 4;       // Philox stream of the permutation (0: goals, 1: mass and friction, 2: pictures, 3: HER)
 constexpr int FEISTEL_ROUNDS = 4;
 constexpr int ADD_LANES = 256;
 constexpr int GAE_LANES = 64;           // lane = environment and nothing is shared: one wave per block spreads 8192 environments over 128 CUs
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(GAE_LANES) void rollout_gae_kernel(Roll B, const fl
 // walks through the Feistel network until it lands below M -> the transition's flat index i = env * T + step.
 MCG_DEV uint32_t walk(bool mine, uint32_t k, uint32_t M, int h, unsigned long long seed, unsigned long long epoch) {
   const uint32_t half = (1u << h) - 1u;
-  const uint32_t c1 = (uint32_t)epoch, c3 = (uint32_t)ROLLOUT_STREAM ^ ((uint32_t)(epoch >> 32) << 8);
+  const uint32_t c1 = (uint32_t)epoch, c3 = DOMAIN_ROLLOUT ^ ((uint32_t)(epoch >> 32) << 8);
   uint32_t x = mine ? k : 0u;
   bool need = mine;
   do {                                   // wave-uniform, per-lane effects predicated on `need`; ends because a bijection's cycles close

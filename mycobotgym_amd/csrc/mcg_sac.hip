@@ -27,10 +27,10 @@
 //            the later layers; a head of one row padded to 16.
 //   critic_target   the critic's layout.
 //
-// ---- The noise.  Philox4x32-10, mcg_policy.hip's counter layout (policy_pair) with the domain byte 7 for mcg_sac_act, id = the global
-// environment id, and 8 for mcg_sac_target, id = the sample's index in the batch (0-6 are taken: reset and scene draws, HER, the rollout
-// permutation, the picture replay, the actor-critic policy).  One block serves two components by Box-Muller in double, as there: gauss4
-// (mcg_sac.hpp) is the one place that forms the counter words, for SAC's three streams and for TD3's two (10, 11).
+// ---- The noise.  Philox4x32-10, mcg_policy.hip's counter layout with the domain byte DOMAIN_SAC_ACT for mcg_sac_act, id = the global
+// environment id, and DOMAIN_SAC_TARGET for mcg_sac_target, id = the sample's index in the batch (the bytes' list: enum Domain,
+// mcg_philox.hpp).  One block serves two components by Box-Muller in double, as there: gauss4 (mcg_policy.hpp) is the one place that
+// forms the counter words, for every policy's draws.
 #include "mcg_sac.hpp"          // Sac, Rows, Batch, Draw, hidden, squash, critic, q_kernel, polyak_kernel, blob_plan, the host checks (shared
                                 // with mcg_sac_grad.hip and, through mcg_td3.hpp, with TD3 / DDPG); mcg_policy.hpp
 
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(WAVE) void sac_act_kernel(Sac S, const double* __re
   const int e = blockIdx.x * TILE + i;
   const bool live = e < S.pi.N;
   const int env = live ? e : S.pi.N - 1;   // a ragged tile's extra rows read a valid row and store nothing
-  const Draw d = actor<MT, double>(S.pi, obs, ach, des, env, g, lane, seed, (unsigned long long)(env_id_offset + env), call, SAC_ACT_STREAM,
+  const Draw d = actor<MT, double>(S.pi, obs, ach, des, env, g, lane, seed, (unsigned long long)(env_id_offset + env), call, DOMAIN_SAC_ACT,
                                    deterministic != 0);
   if (!live) return;
 #pragma unroll
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(2 * WAVE) void sac_target_kernel(Sac S, Batch X, in
   const bool live = e < B;
   const int row = live ? e : B - 1;
   const Draw d = actor<MT, float>(S.pi, X.next_obs, X.next_achieved, X.desired, row, g, lane, seed, (unsigned long long)row, call,
-                                  SAC_TARGET_STREAM, false);
+                                  DOMAIN_SAC_TARGET, false);
   const float v = critic<MT, float>(S, wave, X.next_obs, X.next_achieved, X.desired, row, d.action, g, lane);
   if (g == 0) qs[wave][i] = v;
   __syncthreads();

@@ -1,15 +1,14 @@
 // mcg_sac.hpp -- what the off-policy learners' code objects share, SAC's (mcg_sac.hip, mcg_sac_grad.hip) and TD3's / DDPG's (mcg_td3.hip,
-// mcg_td3_grad.hip, through mcg_td3.hpp): the kernels' view of the blobs, the one Gaussian draw, SAC's squash of its two heads, the
+// mcg_td3_grad.hip, through mcg_td3.hpp): the kernels' view of the blobs, SAC's squash of its two heads (its draw: mcg_policy.hpp's gauss4), the
 // critic's forward with the action as an operand, the critics' kernel and the Polyak kernel (each code object instantiates its own),
 // the blobs' plan and the host checks of an entry's arguments.  The blobs' layouts, the action-as-operand rule and the noise are stated
 // at mcg_sac.hip's head; TD3's own pieces (one head, tanh, the scaled noise) are mcg_td3.hpp's.
 #pragma once
 
-#include "mcg_policy.hpp"       // Net, Pol, mfma, activate, first_layer, dense, checked_shape
+#include "mcg_policy.hpp"       // Net, Pol, mfma, activate, first_layer, dense, gauss4, checked_shape
 
 namespace {
 
-constexpr uint32_t SAC_ACT_STREAM = 7, SAC_TARGET_STREAM = 8, SAC_ACTOR_LOSS_STREAM = 9;
 constexpr float LOG_STD_MIN = -20.0f, LOG_STD_MAX = 2.0f;
 
 // mcg_sac or mcg_td3 as the kernels see it.  pi: the actor blob (TD3: or its target); net[1] is the trunk with the head mu, net[0] the
@@ -39,24 +38,6 @@ MCG_DEV void hidden(const Pol& P, const Net& net, f4 (&a)[MT], int g, int lane) 
     for (int t = 0; t < MT; t++)
 #pragma unroll
       for (int r = 0; r < 4; r++) a[t][r] = activate(P.act, b[t][r]);
-  }
-}
-
-// n, zeros -> components 4 g .. 4 g + 3 of a row's standard Gaussian draw, those from A on left as they are: one Philox block per pair of
-// components, Box-Muller in double, the second value of a last odd pair dropped.  `id`, `call`, `stream`: the noise's counter
-// (mcg_sac.hip's head).
-MCG_DEV void gauss4(f4& n, int A, int g, unsigned long long seed, unsigned long long id, unsigned long long call, uint32_t stream) {
-#pragma unroll
-  for (int q = 0; q < 2; q++) {
-    if (4 * g + 2 * q < A) {
-      double u0, u1, s, c;
-      const uint32_t pair = (uint32_t)(2 * g + q);
-      mcg::philox_pair((uint32_t)id, (uint32_t)call, pair ^ ((uint32_t)(call >> 32) << 8), stream ^ ((uint32_t)(id >> 32) << 8), seed, u0, u1);
-      const double rad = sqrt(-2.0 * log(1.0 - u0));
-      sincos(6.283185307179586476925 * u1, &s, &c);
-      n[2 * q] = (float)(rad * c);
-      if (4 * g + 2 * q + 1 < A) n[2 * q + 1] = (float)(rad * s);
-    }
   }
 }
 

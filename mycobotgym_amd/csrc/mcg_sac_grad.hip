@@ -62,7 +62,7 @@ __global__ __launch_bounds__(2 * WAVE) void sac_actor_tile_kernel(Sac S, GRows R
     dense<MT, 1>(PA, PA.net[1], n, last_tiles(net), 1, a, mu, g, lane);
     dense<MT, 1>(PA, PA.net[0], n, last_tiles(net), 1, a, ls, g, lane);
   }
-  const Draw dr = squash(PA.A, mu[0], ls[0], g, seed, (unsigned long long)row, call, SAC_ACTOR_LOSS_STREAM, false);
+  const Draw dr = squash(PA.A, mu[0], ls[0], g, seed, (unsigned long long)row, call, DOMAIN_SAC_ACTOR_LOSS, false);
   // ---- critic `wave` on the action where it lies; the min's choice; dQ/da of the chosen critic
   const Pol& PQ = wave ? S.qf[1] : S.qf[0];
   const Net& qnet = PQ.net[0];

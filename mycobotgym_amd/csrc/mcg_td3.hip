@@ -20,8 +20,8 @@
 //   actor, actor_target    the trunk's layers, then the one head (A rows, the rest zeros) over H / 4 k-blocks and 16 biases.
 //   critic, critic_target  qf0 alone (n_critics = 1) or qf0 then qf1, each in mcg_sac.hip's critic layout.
 //
-// ---- The noise.  mcg_sac.hpp's gauss4 (Philox4x32-10, Box-Muller in double: the draw of mcg_sac_act), with the domain byte 10 for mcg_td3_act,
-// id = the global environment id, and 11 for mcg_td3_target, id = the sample's index in the batch (0-9 are taken).  Scaled in float32:
+// ---- The noise.  mcg_policy.hpp's gauss4 (Philox4x32-10, Box-Muller in double: the draw of mcg_sac_act), with the domain byte DOMAIN_TD3_ACT
+// for mcg_td3_act, id = the global environment id, and DOMAIN_TD3_TARGET for mcg_td3_target, id = the sample's index in the batch.  Scaled in float32:
 // __fmul_rn(sigma, eps).  sigma == 0: the noise is +0 and no block is computed.
 #include "mcg_td3.hpp"          // checked_td3, scaled_noise, td3_actor, add_clamped; mcg_sac.hpp (q_kernel, polyak_kernel, blob_plan), mcg_policy.hpp
 
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(WAVE) void td3_act_kernel(Sac S, const double* __re
   const bool live = e < S.pi.N;
   const int env = live ? e : S.pi.N - 1;   // a ragged tile's extra rows read a valid row and store nothing
   const f4 mean = td3_actor<MT, double>(S.pi, obs, ach, des, env, g, lane);
-  const f4 n = scaled_noise(S.pi.A, g, noise_std, seed, (unsigned long long)(env_id_offset + env), call, TD3_ACT_STREAM);
+  const f4 n = scaled_noise(S.pi.A, g, noise_std, seed, (unsigned long long)(env_id_offset + env), call, DOMAIN_TD3_ACT);
   const f4 a = add_clamped(mean, n);
   if (!live) return;
 #pragma unroll
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(2 * WAVE) void td3_target_kernel(Sac S, Batch X, in
   const bool live = e < B;
   const int row = live ? e : B - 1;
   const f4 mean = td3_actor<MT, float>(S.pi, X.next_obs, X.next_achieved, X.desired, row, g, lane);
-  f4 n = scaled_noise(S.pi.A, g, sigma, seed, (unsigned long long)row, call, TD3_TARGET_STREAM);
+  f4 n = scaled_noise(S.pi.A, g, sigma, seed, (unsigned long long)row, call, DOMAIN_TD3_TARGET);
   if (sigma != 0.0f) {
 #pragma unroll
     for (int r = 0; r < 4; r++) n[r] = fminf(fmaxf(n[r], -clip), clip);

@@ -1,17 +1,15 @@
 // mcg_td3.hpp -- what mcg_td3.hip (the gradient-free half of TD3 / DDPG) and mcg_td3_grad.hip (the update) share beyond mcg_sac.hpp: the
 // host checks of an mcg_td3, the scaled noise, and the deterministic actor's output.  The kernels' view of the blobs (`Sac` -- pi: the
-// actor or its target with the one head as net[1]; qf[k]: critic k), the Gaussian draw, the critic's forward, the critics' and the
+// actor or its target with the one head as net[1]; qf[k]: critic k), the critic's forward, the critics' and the
 // Polyak kernel and the blobs' plan are mcg_sac.hpp's single definitions: the layouts are mcg_sac.hip's but for the missing log_std
 // head and the number of critics (mcg_td3.hip's head).
 #pragma once
 
-#include "mcg_sac.hpp"          // Sac, hidden, last_tiles, gauss4, critic, blob_plan, checked_blobs, widest; mcg_policy.hpp
+#include "mcg_sac.hpp"          // Sac, hidden, last_tiles, critic, blob_plan, checked_blobs, widest; mcg_policy.hpp (gauss4)
 
 namespace {
 
-constexpr uint32_t TD3_ACT_STREAM = 10, TD3_TARGET_STREAM = 11;
-
-// sigma eps of a lane's four components (zeros from A on): eps is mcg_sac.hpp's gauss4, each product rounded to float32 once.
+// sigma eps of a lane's four components (zeros from A on): eps is mcg_policy.hpp's gauss4, each product rounded to float32 once.
 // sigma == 0: +0 and no Philox block.
 MCG_DEV f4 scaled_noise(int A, int g, float sigma, unsigned long long seed, unsigned long long id, unsigned long long call, uint32_t stream) {
   f4 n = {0.0f, 0.0f, 0.0f, 0.0f};

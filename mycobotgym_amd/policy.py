@@ -19,21 +19,21 @@ No CPU or PyTorch fallback: the kernel is the only implementation of the forward
 minibatch of the rollout buffer; the loss, its gradient and Adam on the blob are ``PPOUpdate`` (policy_update.py).  A caller with an
 optimiser of its own (any ``nn.Module`` with SB3's parameter names) repacks the blob with ``load_state_dict`` after an update.
 
-What is PPO's own here: the blob's order and SB3's names for it, the orthogonal start, the refusals of SB3 configurations, the two
-entries' marshalling.  The layers' packing, the rows' check, the constructor's steps and the state dict both ways are _nets.py's,
-shared with SAC and TD3 / DDPG.
+What is this policy's own here: the blob's order and SB3's names for it, the refusals of SB3 configurations, the two entries'
+marshalling.  The layers' packing, the rows' check, the constructor's steps and the state dict both ways are _nets.py's, shared
+with SAC and TD3 / DDPG; the orthogonal start, ``forward`` / ``values`` and the outputs of ``evaluate_actions`` are its
+``GaussianActorCritic``'s, shared with ``CnnActorCritic``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import functools
-import math
 from typing import Optional, Sequence
 
 import torch
 
 from . import _abi
-from ._nets import _ACTIVATIONS, Nets, _arr, _hidden_of, checked_rows, names_of, pack_net, unpack_net
+from ._nets import _ACTIVATIONS, GaussianActorCritic, _arr, _hidden_of, checked_rows, names_of, pack_net, unpack_net
 
 # minibatch_rows(observations, actions, obs_dim, act_dim, who): checks a minibatch as ``RolloutBuffer.get`` yields it
 # (``RolloutSamples.observations``: the dict of float32 tensors, and ``actions``) -> its rows B.  Needs no device.
@@ -81,13 +81,12 @@ def _refuse_foreign(keys):
         raise ValueError("a features extractor with parameters is not supported: the features are the concatenated observation keys")
 
 
-class ActorCritic(Nets):
+class ActorCritic(GaussianActorCritic):
     _NO_IMAGES = ("the -v1 image ids observe uint8 pictures, which SB3 gives a CNN extractor: ActorCritic is the MLP policy of the -v0 "
                   "state ids; CNN policies are not supported")
-    _CRITIC, _DICT_NOTE, _HOST = "vf", " (shared layers are not supported)", ("seed", "calls")
+    _CRITIC, _DICT_NOTE = "vf", " (shared layers are not supported)"
     _SHAPE, _WIDTHS = "trunks {} / {}", "1 to 3 hidden layers, each width a multiple of 16, at most 256"
     _refuse_foreign = staticmethod(_refuse_foreign)
-    _t = property(lambda self: {"blob": self._blob})      # (_blob is read at each use: it may be rebound, with _cbuf.blob)
 
     def __init__(self, envs=None, hidden=(64, 64), activation: str = "tanh", seed: int = 0, *, num_envs: Optional[int] = None,
                  obs_dim: Optional[int] = None, act_dim: Optional[int] = None, device=None, env_id_offset: Optional[int] = None):
@@ -110,27 +109,12 @@ class ActorCritic(Nets):
         self.blob_floats = int(self._lib.mcg_policy_blob_floats(self.obs_dim, self.act_dim, len(self.pi), _arr(self.pi), len(self.vf), _arr(self.vf)))
         return self.blob_floats
 
-    def _initial_weights(self) -> dict:
-        gen = torch.Generator().manual_seed(self.seed % (2 ** 63))
-        sd = {}
-        for m, out, k, _first in blob_shapes(self.obs_dim, self.act_dim, self.pi, self.vf)[:-1]:
-            gain = 0.01 if m == "action_net" else 1.0 if m == "value_net" else math.sqrt(2.0)
-            q, r = torch.linalg.qr(torch.randn(max(out, k), min(out, k), generator=gen, dtype=torch.float64))
-            q = q * torch.sign(torch.diagonal(r))
-            sd[m + ".weight"] = (gain * (q if out >= k else q.T)).float()
-            sd[m + ".bias"] = torch.zeros(out)
-        sd["log_std"] = torch.zeros(self.act_dim)
-        return sd
-
     @classmethod
     def from_module(cls, module, envs=None, activation: Optional[str] = None, seed: int = 0, **dims):
         """From any ``nn.Module`` whose ``state_dict()`` carries SB3's names (an SB3 ``ActorCriticPolicy`` / ``MultiInputPolicy``'s does).
         The trunks' widths come from the weights' shapes; the activation from ``module.activation_fn`` where it has one (SB3), else
         ``activation`` (default tanh).  gSDE, ``squash_output``, a CNN extractor and shared layers are refused."""
-        if getattr(module, "use_sde", False):
-            raise ValueError("gSDE (use_sde=True) is not supported: the noise is the diagonal Gaussian's, drawn per call")
-        if getattr(module, "squash_output", False):
-            raise ValueError("squash_output=True is not supported: the action is the unsquashed Gaussian sample")
+        cls._refuse_module(module)
         sd = {k: v for k, v in module.state_dict().items()}
         _refuse_foreign(sd)
         activation = cls._activation_of(module, activation, "tanh")
@@ -142,36 +126,17 @@ class ActorCritic(Nets):
         return pol
 
     # ------------------------------------------------------------------------------------------------------- forward
-    def _forward(self, obs, call, deterministic, out: dict):
+    def _forward(self, obs, call, deterministic, out: dict, who=None):
+        """``obs``: float64 device tensors, read in place; one launch.  ``out``: under ``mcg_policy_out``'s names."""
         o, ag, dg = self._goal_obs(obs, "obs")
         cobs = _abi.McgStepOut(obs=o.data_ptr(), achieved_goal=ag.data_ptr(), desired_goal=dg.data_ptr())
         cout = _abi.McgPolicyOut(**{k: v.data_ptr() for k, v in out.items()})
         self._call("mcg_policy_forward", C.byref(cobs), C.c_uint64(self.seed), C.c_uint64(int(call) & (2 ** 64 - 1)),
                    C.c_int64(self.env_id_offset), int(bool(deterministic)), C.byref(cout))
 
-    def _new(self, *names):
-        f32 = dict(dtype=torch.float32, device=self.device)
+    def _shapes(self):
         N, A = self.num_envs, self.act_dim
-        return {k: torch.empty((N, A) if k in ("action", "mean", "noise") else (N,), **f32) for k in names}
-
-    def forward(self, obs, deterministic: bool = False, out: Optional[dict] = None):
-        """``obs``: what ``envs.reset`` / ``envs.step`` returned (float64 device tensors, read in place) -> (action [N, A], value [N],
-        log_prob [N]), float32 device tensors; one launch.  ``deterministic``: the action is the mean and no call number is used up.
-        ``out``: the tensors to write into, under ``mcg_policy_out``'s names (action, value, log_prob, mean, noise: any subset)."""
-        if out is None:
-            out = self._new("action", "value", "log_prob")
-        self._forward(obs, self.calls, deterministic, out)
-        if not deterministic:
-            self.calls += 1
-        return out.get("action"), out.get("value"), out.get("log_prob")
-
-    __call__ = forward
-
-    def values(self, obs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The value net alone (the bootstrap of ``info["final_observation"]``, the last value of a rollout): float32 [N]; one launch."""
-        v = self._new("value")["value"] if out is None else out
-        self._forward(obs, 0, True, {"value": v})
-        return v
+        return {"action": (N, A), "mean": (N, A), "noise": (N, A), "value": (N,), "log_prob": (N,)}
 
     # ------------------------------------------------------------------------------------------------ on a minibatch
     def _minibatch(self, observations, actions, who, **more):
@@ -192,8 +157,6 @@ class ActorCritic(Nets):
         tensors [B, .]), ``actions`` float32 [B, A] -> (value [B], log_prob [B], entropy [B]), float32; one launch.  B is any number of
         rows >= 1.  ``out``: the tensors to write into, under the names value, log_prob, entropy (any subset)."""
         batch, B, _keep = self._minibatch(observations, actions, "evaluate_actions")
-        if out is None:
-            out = {k: torch.empty(B, dtype=torch.float32, device=self.device) for k in ("value", "log_prob", "entropy")}
-        cout = _abi.McgPolicyEvalOut(**{k: v.data_ptr() for k, v in out.items()})
+        out, cout = self._eval_out(B, out, "evaluate_actions")
         self._call("mcg_policy_evaluate", C.byref(batch), C.c_int64(B), C.byref(cout))
         return out.get("value"), out.get("log_prob"), out.get("entropy")

@@ -1,7 +1,8 @@
-"""The refusals of the Python host layer of the three policy families, word for word: each named case below must raise, and its
-(exception type, text) is compared with tests/golden/host_refusals.json, recorded before the host layer was folded onto `_nets.py`.
+"""The refusals of the Python host layer of the policy families, word for word: each named case below must raise, and its
+(exception type, text) is compared with tests/golden/host_refusals.json, recorded before the host layer was folded onto `_nets.py`
+(the `cnn-*` cases: before `CnnActorCritic` was).
 
-No GPU and no built library: the cases stop at a check that needs neither.  Tiny inputs: B = 5, D = 10, A = 7, widths 16.  Refusals
+No GPU and no built library: the cases stop at a check that needs neither.  Tiny inputs: B = 5, D = 10, A = 7, widths 16; pictures 36 x 36.  Refusals
 whose text names a device (``.. lives on ..``) are the GPU tests'.  Run as a script, this file writes the fixture:
 
     python tests/test_host_refusals_cpu.py
@@ -80,14 +81,15 @@ def bare(cls, **attrs):
     return x
 
 
-def no_device(cls):
-    """``cls`` whose constructor resolves its dimensions without loading the library: it gets as far as its own refusals."""
+def no_device(cls, **dims):
+    """``cls`` whose constructor resolves its dimensions (``dims`` where a case gives none) without loading the library: it gets as far
+    as its own refusals."""
     class NoDevice(cls):
         def _resolve(self, envs, device, given):
             self.device = CPU
             return [given[k] for k, _ in self._FROM_ENVS]
     NoDevice.__name__ = cls.__name__
-    return lambda **kw: NoDevice(**{**dict(num_envs=4, obs_dim=D, act_dim=A), **kw})
+    return lambda **kw: NoDevice(**{**(dims or dict(num_envs=4, obs_dim=D, act_dim=A)), **kw})
 
 
 def module(activation_fn=None, **seqs):
@@ -115,6 +117,26 @@ def flagged(**flags):
     return m
 
 
+def cnn_sd(channels=1, features=W, act=A, aliases=(), **over):
+    """A CnnPolicy's state dict at S = 36 (o3 = 1), zeros; ``aliases``: the extractor under these further prefixes too."""
+    sd = {"features_extractor.cnn.0.weight": torch.zeros(32, channels, 8, 8), "features_extractor.cnn.0.bias": torch.zeros(32),
+          "features_extractor.cnn.2.weight": torch.zeros(64, 32, 4, 4), "features_extractor.cnn.2.bias": torch.zeros(64),
+          "features_extractor.cnn.4.weight": torch.zeros(64, 64, 3, 3), "features_extractor.cnn.4.bias": torch.zeros(64),
+          "features_extractor.linear.0.weight": torch.zeros(features, 64), "features_extractor.linear.0.bias": torch.zeros(features),
+          "action_net.weight": torch.zeros(act, features), "action_net.bias": torch.zeros(act),
+          "value_net.weight": torch.zeros(1, features), "value_net.bias": torch.zeros(1), "log_std": torch.zeros(act)}
+    sd.update({a + k[len("features_extractor."):]: v.clone() for a in aliases for k, v in list(sd.items()) if k.startswith("features_extractor.")})
+    sd.update(over)
+    return sd
+
+
+def holding(sd, **flags):
+    """An ``nn.Module`` whose ``state_dict()`` is ``sd``, with ``flags`` as attributes."""
+    m = flagged(**flags)
+    m.state_dict = lambda: dict(sd)
+    return m
+
+
 def sac_module(activation_fn=None):
     q = [(W, D + 6 + A), (1, W)]
     return module(activation_fn, actor__latent_pi=[(W, D + 6), (W, W)], critic__qf0=q, critic__qf1=q)
@@ -126,8 +148,8 @@ def td3_module(activation_fn=None):
 
 # ----------------------------------------------------------------------------------------------------------------- cases
 def cases():
-    from mycobotgym_amd import ActorCritic, DDPGUpdate, SACPolicy, SACUpdate, TD3Policy, TD3Update
-    from mycobotgym_amd import policy, policy_update as pu, sac_policy as sp, sac_update as su, td3_policy as tp, td3_update as tu
+    from mycobotgym_amd import ActorCritic, CnnActorCritic, DDPGUpdate, SACPolicy, SACUpdate, TD3Policy, TD3Update
+    from mycobotgym_amd import cnn_policy as cp, policy, policy_update as pu, sac_policy as sp, sac_update as su, td3_policy as tp, td3_update as tu
     from mycobotgym_amd._offpolicy import check_common_hyper
     t = {}
     f64 = torch.float64
@@ -409,6 +431,75 @@ def cases():
     t["td3-load_state_dict/empty"] = lambda: td3(2).load_state_dict({"seed": 1, "optimizer": 0})
     t["ddpg-load_state_dict/second-critic"] = lambda: td3(1).load_state_dict({"critic.qf1.0.weight": 0, "critic.qf1.0.bias": 0})
     t["td3-load_state_dict/foreign"] = lambda: td3(2).load_state_dict({"actor.log_std.bias": 0})
+    # cnn_policy.py: _flat, _refuse_foreign, the constructor, load_state_dict, from_module, _pictures, evaluate_actions, forward's out
+    S, u8 = 36, torch.uint8
+    PI, VF = "pi_features_extractor.", "vf_features_extractor."
+    t["cnn-flat/conv1-channels"] = lambda: cp._flat(cnn_sd(channels=2), 1)
+    t["cnn-flat/conv3-flattened"] = lambda: cp._flat(cnn_sd(**{"features_extractor.cnn.4.weight": torch.zeros(64, 576)}), 1)
+    t["cnn-pack/linear-shape"] = lambda: cp.pack(cnn_sd(), 1, 64, W, A)
+    t["cnn-foreign/net_arch"] = lambda: cp._refuse_foreign(cnn_sd(**{"mlp_extractor.policy_net.0.weight": torch.zeros(W, W)}))
+    t["cnn-foreign/alias-alone"] = lambda: cp._refuse_foreign({PI + "cnn.0.bias": torch.zeros(32)})
+    t["cnn-foreign/alias-shape"] = lambda: cp._refuse_foreign(cnn_sd(aliases=(PI,), **{PI + "cnn.2.bias": torch.zeros(32)}))
+    t["cnn-foreign/alias-differs"] = lambda: cp._refuse_foreign(cnn_sd(aliases=(PI, VF), **{VF + "linear.0.bias": torch.ones(W)}))
+    cnn_new = no_device(CnnActorCritic, num_envs=4, channels=1, image_size=S, act_dim=A)
+    t["cnn-new/num_envs"] = lambda: cnn_new(num_envs=0)
+    t["cnn-new/channels"] = lambda: cnn_new(channels=17)
+    t["cnn-new/image_size-small"] = lambda: cnn_new(image_size=35)
+    t["cnn-new/image_size-large"] = lambda: cnn_new(image_size=97)
+    t["cnn-new/features_dim-multiple"] = lambda: cnn_new(features_dim=24)
+    t["cnn-new/features_dim-large"] = lambda: cnn_new(features_dim=528)
+    t["cnn-new/act_dim"] = lambda: cnn_new(act_dim=17, seed=3)
+    t["cnn-new/no-dimensions"] = lambda: CnnActorCritic(num_envs=4, image_size=S)
+    cnn = lambda **more: bare(CnnActorCritic, **{**dict(num_envs=4, channels=1, image_size=S, features_dim=W, act_dim=A, device=CPU, seed=0,
+                                                        calls=0, _blob=torch.zeros(1)), **more})
+    t["cnn-load_state_dict/missing"] = lambda: cnn().load_state_dict(without(cnn_sd(seed=3, calls=9), "log_std"))
+    t["cnn-load_state_dict/extra"] = lambda: cnn().load_state_dict(cnn_sd(**{"features_extractor.cnn.6.weight": 0, "optimizer": 0}))
+    t["cnn-load_state_dict/net_arch"] = lambda: cnn().load_state_dict(cnn_sd(**{"mlp_extractor.value_net.0.bias": 0}))
+    t["cnn-load_state_dict/alias-differs"] = lambda: cnn().load_state_dict(cnn_sd(aliases=(PI, VF), **{PI + "cnn.0.bias": torch.ones(32)}))
+    t["cnn-load_state_dict/alias-missing"] = lambda: cnn().load_state_dict(without(cnn_sd(aliases=(PI,)), "features_extractor.cnn.4.bias"))
+    t["cnn-load_state_dict/conv-shape"] = lambda: cnn().load_state_dict(cnn_sd(**{"features_extractor.cnn.2.weight": torch.zeros(64, 512)}))
+    t["cnn-load_state_dict/head-shape"] = lambda: cnn().load_state_dict(cnn_sd(**{"action_net.weight": torch.zeros(A, W + 16)}))
+    t["cnn-load_state_dict/log_std-shape"] = lambda: cnn().load_state_dict(cnn_sd(log_std=torch.zeros(A, A)))
+    t["cnn-module/use_sde"] = lambda: CnnActorCritic.from_module(flagged(use_sde=True))
+    t["cnn-module/squash_output"] = lambda: CnnActorCritic.from_module(flagged(squash_output=True))
+    t["cnn-module/separate-extractors"] = lambda: CnnActorCritic.from_module(flagged(share_features_extractor=False))
+    t["cnn-module/net_arch"] = lambda: CnnActorCritic.from_module(holding(cnn_sd(**{"mlp_extractor.policy_net.0.weight": torch.zeros(W, W)})))
+    t["cnn-module/alias-differs"] = lambda: CnnActorCritic.from_module(holding(cnn_sd(aliases=(PI, VF), **{VF + "cnn.4.bias": torch.ones(64)})))
+    t["cnn-module/no-linear"] = lambda: CnnActorCritic.from_module(nn.Linear(4, 4))
+    t["cnn-module/no-dimensions"] = lambda: CnnActorCritic.from_module(holding(cnn_sd(aliases=(PI, VF))), num_envs=4)
+    pics = lambda img, rows=B, dtypes=(u8,), **more: cnn(**more)._pictures(img, "forward: img", rows, dtypes)
+    t["cnn-pictures/list"] = lambda: pics([[0]])
+    t["cnn-pictures/dict"] = lambda: pics(obs(), dtypes=(u8, torch.float32))
+    t["cnn-pictures/float32"] = lambda: pics(torch.zeros(B, 1, S, S))
+    t["cnn-pictures/float64"] = lambda: pics(torch.zeros(B, 1, S, S, dtype=f64), dtypes=(u8, torch.float32))
+    t["cnn-pictures/channels"] = lambda: pics(torch.zeros(B, 2, S, S, dtype=u8))
+    t["cnn-pictures/rows"] = lambda: pics(torch.zeros(B - 1, 1, S, S, dtype=u8))
+    t["cnn-pictures/channels-last"] = lambda: pics(torch.zeros(B, S, S, 2, dtype=u8), channels=2)
+    img = lambda rows=B, dtype=torch.float32: torch.zeros(rows, 1, S, S, dtype=dtype)
+    ev = lambda o, a, **kw: cnn().evaluate_actions(o, a, **kw)
+    t["cnn-evaluate/state-dict"] = lambda: ev(obs(), torch.zeros(B, A))
+    t["cnn-evaluate/actions-none"] = lambda: ev(img(), None)
+    t["cnn-evaluate/actions-1d"] = lambda: ev(img(), torch.zeros(B))
+    t["cnn-evaluate/actions-columns"] = lambda: ev(img(), torch.zeros(B, A - 1))
+    t["cnn-evaluate/actions-float64"] = lambda: ev(img(), torch.zeros(B, A, dtype=f64))
+    t["cnn-evaluate/empty"] = lambda: ev(img(0), torch.zeros(0, A))
+    t["cnn-evaluate/observations-list"] = lambda: ev([0], torch.zeros(B, A))
+    t["cnn-evaluate/observations-int32"] = lambda: ev(img(dtype=torch.int32), torch.zeros(B, A))
+    t["cnn-evaluate/observations-rows"] = lambda: ev(img(B + 1, u8), torch.zeros(B, A))
+    t["cnn-evaluate/out-tensor"] = lambda: ev(img(), torch.zeros(B, A), out=torch.zeros(B))
+    t["cnn-evaluate/out-empty"] = lambda: ev(img(dtype=u8), torch.zeros(B, A), out={})
+    t["cnn-evaluate/out-unknown"] = lambda: ev(img(), torch.zeros(B, A), out={"value": torch.zeros(B), "action": torch.zeros(B, A)})
+    t["cnn-evaluate/out-shape"] = lambda: ev(img(), torch.zeros(B, A), out={"entropy": torch.zeros(B, 1)})
+    t["cnn-evaluate/out-float64"] = lambda: ev(img(), torch.zeros(B, A), out={"log_prob": torch.zeros(B, dtype=f64)})
+    fw = lambda out: cnn().forward(None, out=out)
+    t["cnn-forward/out-tensor"] = lambda: fw(torch.zeros(4, A))
+    t["cnn-forward/out-empty"] = lambda: fw({})
+    t["cnn-forward/out-unknown"] = lambda: fw({"action": torch.zeros(4, A), "entropy": torch.zeros(4)})
+    t["cnn-forward/out-features-shape"] = lambda: fw({"features": torch.zeros(4, W + 16)})
+    t["cnn-forward/out-strided"] = lambda: fw({"mean": torch.zeros(A, 4).T})
+    t["cnn-forward/out-list"] = lambda: fw({"value": [0.0] * 4})
+    t["cnn-values/out-shape"] = lambda: cnn().values(None, out=torch.zeros(4, 1))
+    t["cnn-values/out-float64"] = lambda: cnn().values(None, out=torch.zeros(4, dtype=f64))
     return t
 
 
