@@ -1159,6 +1159,18 @@ int mcg_cnn_evaluate(const mcg_cnn_policy* pol, const mcg_cnn_obs* obs, const fl
 int mcg_selftest_bad_value(const double* in, int n, double* state /* [n][24] device */, uint8_t* each /* [n] device */,
                            uint8_t* any /* [n] device */, void* stream);
 
+/* Device self-test of the factor of H = H_eq + M + D that the side waves of the joint controller's three-wave Reach kernel form after
+   barrier S2: no engine handle, nothing a rollout calls.  `in` is [n][MCG_SELFTEST_FACTOR_H_IN] doubles on the device, one case per
+   row: H_eq[78], M[78] (packed lower triangles, tri(i, j) = i (i + 1) / 2 + j; only the patterns' nonzeros are read), D[10] and
+   act[10] of the limit rows (act != 0: D is added to the row's diagonal), b[12].  A lane puts H_eq and M into its LDS column, where
+   the kernel keeps them, and factors and solves H x = b twice from there: by build_H + ldl_factor, the route of the main wave and of
+   every other kernel, and by build_factor_H, the side waves' row-by-row route.  out is [n][MCG_SELFTEST_FACTOR_H_OUT]: L[78] (unit
+   lower multipliers, D on the diagonal, zero off the pattern), dinv[12], x[12] of the first route, then the same of the second.  The
+   two must agree bit for bit (tests/test_gpu_reach_factor_order.py).  MCG_ERR_ARG for a null pointer or n outside [1, 2^20]. */
+#define MCG_SELFTEST_FACTOR_H_IN 188
+#define MCG_SELFTEST_FACTOR_H_OUT 204
+int mcg_selftest_factor_h(const double* in, int n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -393,6 +393,7 @@ EXPORTS = ("mcg_abi_version", "mcg_last_error", "mcg_default_model", "mcg_create
            "mcg_sac_grad_work_floats", "mcg_sac_critic_grad", "mcg_sac_actor_grad", "mcg_sac_alpha_step", "mcg_sac_adam",
            "mcg_td3_blob_floats", "mcg_td3_act", "mcg_td3_q", "mcg_td3_target", "mcg_td3_polyak",
            "mcg_td3_grad_work_floats", "mcg_td3_critic_grad", "mcg_td3_actor_grad", "mcg_selftest_bad_value",
+           "mcg_selftest_factor_h",
            "mcg_cnn_blob_floats", "mcg_cnn_scratch_floats", "mcg_cnn_forward", "mcg_cnn_evaluate")
 
 _lib = None
@@ -516,6 +517,8 @@ def load():
         L.mcg_sac_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, d, d, d, d, C.c_void_p]
     if hasattr(L, "mcg_selftest_bad_value"):  # absent only from older builds selected through MCG_LIB for A/B timing
         L.mcg_selftest_bad_value.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mcg_selftest_factor_h"):  # likewise
+        L.mcg_selftest_factor_h.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     if hasattr(L, "mcg_td3_actor_grad"):  # absent only from older builds selected through MCG_LIB for A/B timing
         td3 = C.POINTER(McgTd3)
         L.mcg_td3_blob_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,

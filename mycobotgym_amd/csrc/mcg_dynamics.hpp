@@ -761,6 +761,71 @@ MCG_DEV void build_H(const LS MS, real* H, const bool* act_, const real* Dl) {
   static_for<10>([&](auto I) { constexpr int j = I; H[tri(j, j)] += act_[j] ? Dl[j] : 0.0; });
 }
 
+// build_H and ldl_factor<PAT_H> in one, left-looking, for the side waves of SplitMainCols (the RNE wave's remote solve, the helper's
+// columns): both open the stretch after S2 with it, at the same time, while the main wave reads M.
+// What was slow: the accessor's reads are volatile (WindowedScratchT::ld) and build_H adds M to H_eq
+// entry by entry, so the compiler issued ten reads, waited for ALL of them (lgkmcnt(0)) while it added, and only then issued the next
+// ten -- thirteen exposed LDS round trips per wave, in a queue three waves fill.  The order of the rows did not matter: reading row 11
+// first, or factoring row by row behind a memory fence, measured slower than the parent, because the waits to zero stayed.
+// Here a row comes in two halves.  row_H_read issues the reads of a row and nothing else; row_H_form makes H of the raw entries -- the
+// same H = ld(HEQ); H += ld(M), zero on fill-in, D added on a limit row's diagonal -- behind a gate: an empty asm volatile per raw entry,
+// which the compiler keeps behind every read issued before it in source order (volatile accesses and asm volatile statements keep their
+// order) and, through its input, behind the pivot of the row before.  The reads run FACTOR_H_AHEAD rows ahead of the row worked on, so a
+// wait finds the next rows' reads in flight and is never a wait to zero.  Row k (k = 11 down to 0) is formed, takes the updates of rows
+// 11 .. k + 1 in that order, then gives its pivot.
+// The same bits as build_H + ldl_factor<PAT_H>: there, at pivot r, l = A[r][i] * dinv[r] and A[i][j] = fma(-l, A[r][j], A[i][j]) for
+// j <= i, with A[r][j] not yet scaled (A[r][i] becomes l only after its own updates, and the rows below i are done later); element
+// A[i][j] takes them in the order r = 11, 10, .. , i + 1.  Here U holds row r as it was when it gave its pivot (unscaled) and L the
+// multipliers, and element (k, j) takes fma(-L[r][k], U[r][j], .) in the same order of r.  L: multipliers below the diagonal, D on it.
+// (mcg_selftest_factor_h runs both routes on the same column.)
+constexpr int FACTOR_H_AHEAD = 4;                                   // measured: 1 -1.8 %, 2 -2.5 %, 3 -2.9 %, 4 -3.2 % against the parent
+template <class SPL, int k, class LS>
+MCG_DEV void row_H_read(const LS MS, real* E, real* Mr) {
+  static_for<k + 1>([&](auto Jj) { constexpr int j = Jj;
+    if constexpr (PAT_E.nz[k][j]) {
+      E[tri(k, j)] = MS.ld(LDS_HEQ + tri(k, j));
+      if constexpr (SPL::enabled && PAT_M.nz[k][j]) Mr[tri(k, j)] = MS.ld(LDS_M + tri(k, j));
+    } });
+}
+template <bool AFTER> MCG_DEV void gate(real& x, real after) {
+  if constexpr (AFTER) asm volatile("" : "+v"(x) : "v"(after)); else asm volatile("" : "+v"(x));
+}
+template <class SPL, int k, bool AFTER>
+MCG_DEV void row_H_form(real* E, real* Mr, real* H, const bool* act_, const real* Dl, real after) {
+  static_for<k + 1>([&](auto Jj) { constexpr int j = Jj;
+    if constexpr (PAT_E.nz[k][j]) {
+      gate<AFTER>(E[tri(k, j)], after);
+      H[tri(k, j)] = E[tri(k, j)];
+      if constexpr (SPL::enabled && PAT_M.nz[k][j]) { gate<AFTER>(Mr[tri(k, j)], after); H[tri(k, j)] += Mr[tri(k, j)]; }
+    } else if constexpr (PAT_H.nz[k][j]) H[tri(k, j)] = 0.0; });
+  if constexpr (k < 10) H[tri(k, k)] += act_[k] ? Dl[k] : 0.0;
+}
+template <class SPL, class LS>
+MCG_DEV void build_factor_H(const LS MS, real* L, real* dinv, const bool* act_, const real* Dl) {
+  constexpr int A = FACTOR_H_AHEAD;
+  real U[NB * (NB + 1) / 2], E[NB * (NB + 1) / 2], Mr[NB * (NB + 1) / 2];
+  static_for<A>([&](auto I) { row_H_read<SPL, NB - 1 - I>(MS, E, Mr); });
+  static_for<NB>([&](auto Kk) {
+    constexpr int k = NB - 1 - Kk;
+    if constexpr (k - A >= 0) row_H_read<SPL, k - A>(MS, E, Mr);
+    if constexpr (k == NB - 1) row_H_form<SPL, k, false>(E, Mr, U, act_, Dl, 0.0);
+    else row_H_form<SPL, k, true>(E, Mr, U, act_, Dl, dinv[k + 1]);           // behind the pivot of the row before
+    static_for<NB - 1 - k>([&](auto Rr) {
+      constexpr int r = NB - 1 - Rr;
+      if constexpr (PAT_H.nz[r][k]) {
+        const real l = L[tri(r, k)];
+        static_for<k + 1>([&](auto Jj) {
+          constexpr int j = Jj;
+          if constexpr (PAT_H.nz[r][j]) U[tri(k, j)] = fma(-l, U[tri(r, j)], U[tri(k, j)]);
+        });
+      }
+    });
+    dinv[k] = rcp_nr(U[tri(k, k)]);
+    L[tri(k, k)] = U[tri(k, k)];
+    static_for<k>([&](auto Ii) { constexpr int i = k - 1 - Ii; if constexpr (PAT_H.nz[k][i]) L[tri(k, i)] = U[tri(k, i)] * dinv[k]; });
+  });
+}
+
 // A sub-step is remote (cols) when no lane of the wave has a violated limit row on a joint other than the gear joints 6 and 8.
 // The RNE wave's side of that decision, from the q slots (the waves of a workgroup cover the same lanes and read the same q): the same
 // compares as the limit rows of robot_substep, from which the main wave decides.
@@ -1431,8 +1496,7 @@ MCG_DEV void helper_substep(ModelPtr Pm, const LS MS) {
     const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
     const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const LowScratch MW(MS);                                       // H_eq's upper rows and the columns: the lower window alone
-    build_H<SPL>(MW, L, none, zero);
-    ldl_factor<PAT_H>(L, dinv);
+    build_factor_H<SPL>(MW, L, dinv, none, zero);
     ldl_solve_unit<PAT_H, 6>(L, dinv, z6);
     ldl_solve_unit<PAT_H, 8>(L, dinv, z8);
     static_for<NB>([&](auto I) { constexpr int i = I; MW.st(LDS_Z6 + i, z6[i]); MW.st(LDS_Z8 + i, z8[i]); });
@@ -1480,11 +1544,10 @@ MCG_DEV void rne_substep(ModelPtr Pm, const LS MS) {
       const bool none[10] = {false, false, false, false, false, false, false, false, false, false};
       const real zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       const auto MW = slots();
-      build_H<SPL>(MW, L, none, zero);
+      build_factor_H<SPL>(MW, L, dinv, none, zero);                                           // build_H + ldl_factor<PAT_H>, the reads rows ahead
       static_for<NB>([&](auto I) { constexpr int i = I; x[i] = 0.0; });                       // the actuation forces: zero but for RACT_DOF
       static_for<8>([&](auto K) { constexpr int k = K; x[RACT_DOF[k]] = MW.ld(LDS_RACT + k); });
       static_for<NB>([&](auto I) { constexpr int i = I; x[i] = MW.ld(LDS_RG0 + i) + (x[i] + fs[i]); });
-      ldl_factor<PAT_H>(L, dinv);
       ldl_solve<PAT_H>(L, dinv, x);
       static_for<NB>([&](auto I) { constexpr int i = I; MW.st(LDS_RA + i, x[i]); });      // abar: the main wave finishes the gear rows
       MCG_TICK(ST_Q_COLS);
