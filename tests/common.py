@@ -5,9 +5,19 @@ import json
 import os
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(ROOT, "mycobotgym_amd", "assets")
+
+
+@pytest.fixture(scope="module")
+def torch_cuda(built):
+    """torch, on a machine with a GPU.  A GPU test file takes it with `from tests.common import torch_cuda  # noqa: F401`: pytest finds a
+    fixture imported into the module; `built` is conftest.py's."""
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
+    return torch
 
 
 def table_name(has_object=False, mesh_inertia="legacy", mocap=False):
@@ -170,13 +180,18 @@ def step_errors(envs, ora, actions):
     return e, flags_equal, o
 
 
+def sync_state(envs, s):
+    """Copy a state of the oracle (its get_state(), live or recorded; not modified) into the HIP engine."""
+    ctrl = s["ctrl"]
+    if ctrl.shape[1] < 7:           # mocap model: one actuator (the fingers) = the engine's ctrl slot 6
+        ctrl = np.concatenate([np.zeros((ctrl.shape[0], 7 - ctrl.shape[1])), ctrl], axis=1)
+    envs.set_state(qpos=s["qpos"].T.copy(), qvel=s["qvel"].T.copy(), ctrl=ctrl.T.copy(), warm=s["warm"].T.copy(),
+                   qpos_lag=s["qpos_lag"].T.copy(), goal=s["goal"].T.copy(), elapsed=s["elapsed"].copy(), episode=s["episode"].copy())
+
+
 def sync_oracle_to(envs, ora):
     """Copy the oracle's state into the HIP engine (both then continue from identical state)."""
-    s = ora.get_state()
-    if s["ctrl"].shape[1] < 7:      # mocap model: one actuator (the fingers) = the engine's ctrl slot 6
-        s["ctrl"] = np.concatenate([np.zeros((s["ctrl"].shape[0], 7 - s["ctrl"].shape[1])), s["ctrl"]], axis=1)
-    envs.set_state(qpos=s["qpos"].T.copy(), qvel=s["qvel"].T.copy(), ctrl=s["ctrl"].T.copy(), warm=s["warm"].T.copy(),
-                   qpos_lag=s["qpos_lag"].T.copy(), goal=s["goal"].T.copy(), elapsed=s["elapsed"], episode=s["episode"])
+    sync_state(envs, ora.get_state())
 
 
 def compare_step(envs, ora, actions, keys=("obs", "achieved", "desired", "reward")):

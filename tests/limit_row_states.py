@@ -12,8 +12,8 @@ The ten limit rows are dofs 0 to 9: six arm hinges (+-2.96706), the gear joints 
   above upper, dof 9 below lower (three rows); every other lane none.  Every wave takes the general iteration, with lanes of 0, 3 and 5 rows.
 
 Gear angles are uniform in [0.05, 0.3] where not stated, violation depths uniform in [1e-4, 5e-3] rad beyond the range, qvel[:, :10] uniform
-in +-2 rad/s; the ranges are the jnt_range of the controller's own model table.  The base state is the one tests/test_gpu_reach_limit_rows.py
-builds its own kinds on (its _run calls `put` for these two): reset(seed = 21), one random step, generator default_rng(5).
+in +-2 rad/s; the ranges are the jnt_range of the controller's own model table.  The base state is the one tests/reach_measures.py's limit_run
+builds tests/test_gpu_reach_limit_rows.py's kinds on (it calls `put` for these two): reset(seed = 21), one random step, generator default_rng(5).
 
 Nothing here is mutated after it is built (the arrays are read-only): the tests copy what they change."""
 from __future__ import annotations
@@ -23,11 +23,11 @@ import functools
 import numpy as np
 
 from tests.common import load_json, make_oracle, table_name
+from tests.reach_parity import N, freeze, groups
 
-N = 165
 FAMILIES = ("fingers", "many")
 CONTROLLERS = ("joint", "IK", "mocap")
-GROUPS = (slice(0, 64), slice(64, 128), slice(128, N))
+GROUPS = tuple(groups(N))
 SEED = 21
 # (dof, side) of every row by lane class; side -1: below the lower limit, +1: above the upper one
 ROWS = {
@@ -41,7 +41,7 @@ def jnt_range(controller):
 
 
 def engine_kw(controller, frame_skip=1):
-    """Keyword arguments of tests.common.make_pair / make_oracle, as tests/test_gpu_reach_limit_rows.py's _run builds its pair."""
+    """Keyword arguments of tests.common.make_pair / make_oracle, as tests/reach_measures.py's limit_run builds its pair."""
     kw = dict(controller_type=controller, reward_type="dense", seed=SEED, max_episode_steps=10 ** 9, frame_skip=frame_skip)
     if controller == "IK" and frame_skip == 1: kw["control_steps"] = 1
     return kw
@@ -77,28 +77,22 @@ def put(ora, kind, rng, jr):
     return nrows
 
 
-def _frozen(a):
-    a = np.ascontiguousarray(a)
-    a.flags.writeable = False
-    return a
-
-
 @functools.lru_cache(maxsize=None)
 def family_state(controller, kind):
-    """Family `kind` under `controller` as _run reaches it, by the oracle alone: dict(state = the oracle's state arrays [165, ...], action = the
-    float32 action _run steps it with, rows = violated rows per lane)."""
+    """Family `kind` under `controller` as limit_run reaches it, by the oracle alone: dict(state = the oracle's state arrays [165, ...], action = the
+    float32 action limit_run steps it with, rows = violated rows per lane)."""
     ora = make_oracle(N, **engine_kw(controller))
     ora.reset(seed=SEED)
     rng = np.random.default_rng(5)
     ora.step(rng.uniform(-1, 1, (N, ora.act_dim)).astype(np.float32))
     a = rng.uniform(-1, 1, (N, ora.act_dim)).astype(np.float32)
     rows = put(ora, kind, rng, jnt_range(controller))
-    return dict(state={k: _frozen(v) for k, v in ora.get_state().items()}, action=_frozen(a), rows=_frozen(rows))
+    return freeze(dict(state=ora.get_state(), action=a, rows=rows))
 
 
 def twin_state_errors(twin, state, a, ora, o_ref, prng, eps=1e-14):
     """The oracle's own sensitivity on `state` and action `a`: `twin` steps from `state` with qpos +-eps on every column; returns its largest
-    differences from oracle `ora`, which has stepped from `state` already with outputs `o_ref`, as dict(obs, q, v, w): the keys _run reports."""
+    differences from oracle `ora`, which has stepped from `state` already with outputs `o_ref`, as dict(obs, q, v, w): the keys limit_run reports."""
     s = {k: v.copy() for k, v in state.items()}
     s["qpos"] = s["qpos"] + eps * np.sign(prng.normal(size=s["qpos"].shape))
     twin.set_state(**s)

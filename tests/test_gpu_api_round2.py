@@ -18,15 +18,10 @@ import sys
 import numpy as np
 import pytest
 
+from tests.common import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 # ------------------------------------------------------------------------------------- Reach + reward_shaping (hidden cube)

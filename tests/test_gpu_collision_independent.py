@@ -4,17 +4,9 @@ import numpy as np
 import pytest
 
 from tests import indep_collision as ic
-from tests.common import load_json
+from tests.common import load_json, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch
 
 
 def _poses():

@@ -6,16 +6,9 @@ import numpy as np
 import pytest
 
 from tests import indep_collision as ic
-from tests.common import perturbed_table
+from tests.common import perturbed_table, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 def _kernel_contacts_checked(torch, tab, Q, what):

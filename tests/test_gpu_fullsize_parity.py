@@ -13,15 +13,10 @@
 import numpy as np
 import pytest
 
+from tests.common import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 N_FULL = 8192
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 def _actions(rng, n, dim, controller):

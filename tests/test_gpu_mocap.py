@@ -7,14 +7,9 @@ CPU oracle, whose weld is pinned by the reference's mocap keyframe (tests/test_o
 import numpy as np
 import pytest
 
+from tests.common import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 def _actions(rng, n, dim, quat=True):

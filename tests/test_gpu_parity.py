@@ -18,17 +18,12 @@ can therefore satisfy "1e-4 over 100 free-running steps" on this model; parity i
 import numpy as np
 import pytest
 
+from tests.common import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL_SUBSTEP = 1e-12     # measured on MI355X: obs 6e-16, qpos 6e-15 (bounds are <= 100x what is measured, per quantity)
 TOL_100_STEPS = 1e-4     # north_star tolerance
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 @pytest.mark.parametrize("controller", ["joint", "IK"])

@@ -6,14 +6,9 @@ trajectories are chaotic; reset draws bit-exact.
 import numpy as np
 import pytest
 
+from tests.common import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 @pytest.mark.parametrize("controller", ["joint", "IK"])

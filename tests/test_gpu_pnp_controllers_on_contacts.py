@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import pnp_contact_states as cs
+from tests.common import torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +26,6 @@ pytestmark = pytest.mark.gpu
 BOUNDS = {"IK": dict(obs=1e-9, qpos=1e-9, qvel=1e-6, warm=1e-6, ctrl=1e-11),
           "mocap": dict(obs=1e-10, qpos=1e-10, qvel=1e-6, warm=1e-6)}
 ROBOT = slice(0, 12)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 class _Worst:

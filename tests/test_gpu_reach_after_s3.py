@@ -32,14 +32,13 @@ import functools
 import numpy as np
 import pytest
 
+from tests import reach_parity as rp
+from tests.common import torch_cuda  # noqa: F401
+from tests.reach_parity import ARM_HI, FINGER_HI, GEAR_HI, GEAR_LO, N, SEED, SUBSTEPS
+
 pytestmark = pytest.mark.gpu
 
-N = 165
-SUBSTEPS = 20
-ARM_HI = 2.96706                                     # jnt_range[0][1] of the mycobot280 tables
-GEAR_LO, GEAR_HI, FINGER_HI = 0.0, 0.7, 0.872664     # the gear joints' range; the finger joints' is +-FINGER_HI
 MIN_PAIRS = 5
-SEED = 61
 
 CASES = ("none", "row6", "row8", "both_lower", "both_upper", "mixed", "crossing", "switch", "reset")
 RUNS = [(c, N) for c in CASES] + [("mixed", 65)]
@@ -56,60 +55,6 @@ BOUNDS = {       # obs, q, v, w: 100 x the parent build's worst error over the t
     ("reset", N): dict(obs=6.6e-14, q=5.4e-12, v=2.7e-09, w=4.4e-11),           # 6.661e-16  5.473e-14  2.738e-11  4.433e-13
     ("mixed", 65): dict(obs=8.3e-14, q=6.6e-12, v=3.3e-09, w=3.7e-11),          # 8.327e-16  6.654e-14  3.327e-11  3.714e-13
 }
-
-
-def _groups(n):
-    return [slice(g, min(g + 64, n)) for g in range(0, n, 64)]
-
-
-def _outside(rng, n, upper):
-    """Gear angles 1e-3 .. 5e-3 rad beyond the lower limit (upper[i] false) or the upper one."""
-    d = rng.uniform(1e-3, 5e-3, n)
-    return np.where(upper, GEAR_HI + d, GEAR_LO - d)
-
-
-def _inside(rng, n, upper, near=False):
-    """Gear angles inside the range, in its lower or upper part (the gear coupling pulls the two joints together): well inside, or
-    (near) 2e-3 .. 8e-3 rad from the limit."""
-    d = rng.uniform(2e-3, 8e-3, n) if near else rng.uniform(0.05, 0.3, n)
-    return np.where(upper, GEAR_HI - d, GEAR_LO + d)
-
-
-def _put(case, ora, rng, n):
-    """Write the case's state into the oracle; returns the float32 action every sub-step takes."""
-    s = ora.get_state()
-    q, qd = s["qpos"].copy(), s["qvel"].copy()
-    i = np.arange(n)
-    a = rng.uniform(-1, 1, (n, 7)).astype(np.float32)
-    up = i % 2 == 1
-    has6, has8 = np.zeros(n, bool), np.zeros(n, bool)
-    if case == "row6": has6[:] = True
-    elif case == "row8": has8[:] = True
-    elif case in ("both_lower", "both_upper"):
-        has6[:] = True; has8[:] = True; up = np.full(n, case == "both_upper")
-    elif case in ("mixed", "switch", "reset"):
-        has6 = (i % 4 == 0) | (i % 4 == 1); has8 = (i % 4 == 0) | (i % 4 == 2); up = (i // 4) % 2 == 1
-    near = case in ("row6", "row8")                  # one row in every lane: the other joint just inside, or the gear coupling lifts the row at once
-    q[:, 6] = np.where(has6, _outside(rng, n, up), _inside(rng, n, up, near))
-    q[:, 8] = np.where(has8, _outside(rng, n, up), _inside(rng, n, up, near))
-    qd[:, 6] = rng.uniform(-1.0, 1.0, n); qd[:, 8] = rng.uniform(-1.0, 1.0, n)
-    a[:, 6] = np.where(up, 1.0, -1.0)                # the gripper servo pushes towards the limit the lane's rows are on
-    if case == "crossing":
-        # lane % 4: 0 inside the lower limit moving out, 1 outside it moving in, 2 inside the upper limit moving out, 3 outside it moving in
-        c = i % 4
-        start = np.select([c == 0, c == 1, c == 2], [GEAR_LO + 2e-3, GEAR_LO - 3e-3, GEAR_HI - 2e-3], GEAR_HI + 3e-3)
-        speed = np.select([c == 0, c == 1, c == 2], [-1.0, 2.0, 1.0], -2.0)
-        for j in (6, 8):
-            q[:, j] = start + rng.uniform(-5e-4, 5e-4, n); qd[:, j] = speed * rng.uniform(0.8, 1.2, n)
-        a[:, 6] = np.where(c >= 2, 1.0, -1.0)
-    if case == "switch":
-        x = (i % 64 == 5) | (i % 64 == 30)
-        q[x, 0] = ARM_HI - 0.02; qd[x, 0] = rng.uniform(7.5, 8.5, int(x.sum())); a[x, 0] = 1.0
-    if case == "reset":
-        el = s["elapsed"].copy(); el[i % 5 == 2] = 40
-        ora.set_state(elapsed=el)
-    ora.set_state(qpos=q, qvel=qd)
-    return a
 
 
 def _gear_sets(ora, qpre, lanes):
@@ -139,23 +84,16 @@ def oracle_run(case, n):
     """The case's twenty sub-steps on the CPU oracle alone: dict(action, pre / post = the state before / after every sub-step, out = the
     step's outputs, arm / gear / other [20, groups] = some lane of the workgroup holds an arm row / a gear row / a finger row when the
     sub-step starts, sign / aset [20, n] = _gear_sets of the lanes of remote sub-steps (aset -1 elsewhere and in lanes reset by the sub-step))."""
-    from tests.common import make_oracle
-    ora = make_oracle(n, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=1,
-                      max_episode_steps=50 if case == "reset" else 10 ** 9)
-    ora.reset(seed=SEED)
     rng = np.random.default_rng([SEED, CASES.index(case), n])
-    ora.step(rng.uniform(-1, 1, (n, ora.act_dim)).astype(np.float32))      # warm start, lagged q and ctrl of a running episode
-    a = _put(case, ora, rng, n)
-    groups = _groups(n)
-    r = dict(action=a, pre=[], post=[], out=[], arm=np.zeros((SUBSTEPS, len(groups)), bool), gear=np.zeros((SUBSTEPS, len(groups)), bool),
+    ora = rp.oracle(n, 1, SEED, rp.episode_limit(case), running=rng)
+    a = rp.put_gear_case(case, ora, rng, n)
+    groups = rp.groups(n)
+    r = dict(action=a, arm=np.zeros((SUBSTEPS, len(groups)), bool), gear=np.zeros((SUBSTEPS, len(groups)), bool),
              other=np.zeros((SUBSTEPS, len(groups)), bool), sign=np.zeros((SUBSTEPS, n), np.int64), aset=-np.ones((SUBSTEPS, n), np.int64))
-    for k in range(SUBSTEPS):
-        pre = ora.get_state()
-        o = ora.step(a)
+
+    def rows_and_sets(k, pre, o):
         q = pre["qpos"]
-        arm = (np.abs(q[:, :6]) > ARM_HI).any(axis=1)
-        fing = (np.abs(q[:, [7, 9]]) > FINGER_HI).any(axis=1)
-        gear = (q[:, [6, 8]] < GEAR_LO).any(axis=1) | (q[:, [6, 8]] > GEAR_HI).any(axis=1)
+        arm, gear, fing = rp.limit_rows_of(q)
         done = o["terminated"].astype(bool) | o["truncated"].astype(bool)
         for g, sl in enumerate(groups):
             r["arm"][k, g], r["gear"][k, g], r["other"][k, g] = arm[sl].any(), gear[sl].any(), fing[sl].any()
@@ -163,17 +101,14 @@ def oracle_run(case, n):
                 lanes = [j for j in range(sl.start, sl.stop) if not done[j]]
                 sg, st = _gear_sets(ora, q, lanes)
                 r["sign"][k, lanes] = sg[lanes]; r["aset"][k, lanes] = st[lanes]
-        r["pre"].append(pre); r["out"].append(o); r["post"].append(ora.get_state())
-    for v in r.values():
-        for x in (v if isinstance(v, list) else [v]):
-            for y in (x.values() if isinstance(x, dict) else [x]): y.flags.writeable = False
-    return r
+
+    r.update(rp.record_substeps(ora, a, each=rows_and_sets))
+    return rp.freeze(r)
 
 
 def check_paths(case, n, r):
     """The sub-steps take the paths the case is about."""
-    show = lambda m: " | ".join("".join("X" if x else "." for x in m[:, g]) for g in range(m.shape[1]))
-    print(f"\n{case} ({n}): sub-steps with an arm row, per workgroup: {show(r['arm'])}\n{case} ({n}): sub-steps with a gear row, per workgroup: {show(r['gear'])}")
+    print(f"\n{case} ({n}): sub-steps with an arm row, per workgroup: {rp.show(r['arm'])}\n{case} ({n}): sub-steps with a gear row, per workgroup: {rp.show(r['gear'])}")
     assert not r["other"].any()                                                      # no finger row: the arm rows alone switch the path
     if case != "switch": assert not r["arm"].any()                                   # twenty remote sub-steps in every workgroup
     q = np.stack([s["qpos"] for s in r["pre"]])
@@ -185,7 +120,7 @@ def check_paths(case, n, r):
         assert int((row[:, :, j] & ~row[:, :, 1 - j]).sum()) >= 5 * n                # ... and in a quarter of all (lane, sub-step) pairs at least
     if case in ("both_lower", "both_upper"): assert row[0].all()
     if case in ("mixed", "switch", "reset"):
-        for g, sl in enumerate(_groups(n)):
+        for g, sl in enumerate(rp.groups(n)):
             if sl.stop - sl.start >= 4:
                 assert sorted(set((row[0, sl, 0] + 2 * row[0, sl, 1]).tolist())) == [0, 1, 2, 3], g      # all four kinds of lane in the wave
     if case == "crossing":
@@ -217,51 +152,11 @@ def coverage():
     return cnt
 
 
-def _sync(envs, s):
-    envs.set_state(qpos=s["qpos"].T.copy(), qvel=s["qvel"].T.copy(), ctrl=s["ctrl"].T.copy(), warm=s["warm"].T.copy(),
-                   qpos_lag=s["qpos_lag"].T.copy(), goal=s["goal"].T.copy(), elapsed=s["elapsed"].copy(), episode=s["episode"].copy())
-
-
 def measure(case, n):
     """Worst errors over the twenty sub-steps and the n lanes: dict(obs, q, v, w)."""
-    import torch
-    from mycobotgym_amd import MyCobotVecEnv
     r = oracle_run(case, n)
     check_paths(case, n, r)
-    envs = MyCobotVecEnv(n, device="cuda:0", has_object=False, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=1,
-                         max_episode_steps=50 if case == "reset" else 10 ** 9)
-    envs.reset(seed=SEED)
-    envs.counters(clear=True)
-    a = torch.as_tensor(r["action"].copy())
-    w = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
-    for k in range(SUBSTEPS):
-        _sync(envs, r["pre"][k])
-        obs, rew, term, trunc, info = envs.step(a)
-        o, so = r["out"][k], r["post"][k]
-        assert np.array_equal(obs["desired_goal"].cpu().numpy(), o["desired"]), (case, k)
-        assert np.array_equal(term.cpu().numpy(), o["terminated"].astype(bool)) and np.array_equal(trunc.cpu().numpy(), o["truncated"].astype(bool)), (case, k)
-        assert np.array_equal(info["is_success"].cpu().numpy(), o["is_success"].astype(bool)), (case, k)
-        e = max(float(np.abs(obs["observation"].cpu().numpy() - o["obs"]).max()), float(np.abs(obs["achieved_goal"].cpu().numpy() - o["achieved"]).max()),
-                float(np.abs(rew.cpu().numpy() - o["reward"]).max()))
-        st = envs.get_state()
-        gq, gv, gw = (st[x].cpu().numpy().T for x in ("qpos", "qvel", "warm"))
-        assert all(np.isfinite(x).all() for x in (gq, gv, gw))
-        assert np.array_equal(st["elapsed"].cpu().numpy(), so["elapsed"]) and np.array_equal(st["episode"].cpu().numpy(), so["episode"]), (case, k)
-        ew, den = np.abs(gw - so["warm"]).max(axis=1), np.abs(so["warm"]).max(axis=1)
-        ew = np.where(den > 0, ew / np.where(den > 0, den, 1.0), ew)
-        w = dict(obs=max(w["obs"], e), q=max(w["q"], float(np.abs(gq - so["qpos"]).max())), v=max(w["v"], float(np.abs(gv - so["qvel"]).max())),
-                 w=max(w["w"], float(ew.max())))
-    assert envs.counters()["bad_state_resets"] == 0
-    envs.close()
-    print(f"{case} ({n}): " + " ".join(f"{x} {v:.3e}" for x, v in w.items()))
-    return w
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
+    return rp.measure_substeps(r, lambda frame_skip: rp.engine(n, frame_skip, SEED, rp.episode_limit(case)), f"{case} ({n})")
 
 
 def test_oracle_covers_every_active_set():
@@ -273,4 +168,4 @@ def test_oracle_covers_every_active_set():
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_substeps_against_the_oracle(torch_cuda, case, n):
     w, b = measure(case, n), BOUNDS[(case, n)]
-    assert w["obs"] <= b["obs"] and w["q"] <= b["q"] and w["v"] <= b["v"] and w["w"] <= b["w"], (w, b)
+    assert rp.within(w, b), (w, b)

@@ -46,7 +46,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_gpu_reach_after_s3 import _put, _sync
+from tests import reach_parity as rp
+from tests.common import torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -91,21 +92,13 @@ def _step_from(ora, s, q, qd, a, n):
     return _warnings(ora, n) > w0, out, ora.get_state()
 
 
-def _frozen(x):
-    for y in (x.values() if isinstance(x, dict) else [x]): y.flags.writeable = False
-    return x
-
-
 @functools.lru_cache(maxsize=None)
 def oracle_run(n):
     """The run's one sub-step on the CPU oracle alone, with the special lanes and without them (`clean`):
     dict(kind, action, pre, out, post, bad, why, pre_clean, out_clean, post_clean)."""
-    from tests.common import make_oracle
-    ora = make_oracle(n, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=1, max_episode_steps=10 ** 9)
-    ora.reset(seed=SEED)
     rng = np.random.default_rng([SEED, n])
-    ora.step(rng.uniform(-1, 1, (n, ora.act_dim)).astype(np.float32))      # warm start, lagged q and ctrl of a running episode
-    a = _put("mixed", ora, rng, n)
+    ora = rp.oracle(n, 1, SEED, running=rng)
+    a = rp.put_gear_case("mixed", ora, rng, n)
     s = ora.get_state()
     kind = kinds_of(n)
     name = np.array([EDGE_KINDS[k] if k >= 0 else "" for k in kind])
@@ -151,8 +144,8 @@ def oracle_run(n):
     bad = fired | bad_q | bad_v
     why = np.array(["".join(c for c, m in (("a", fired[i]), ("v", bad_v[i] and not fired[i]), ("q", bad_q[i] and not fired[i])) if m) for i in range(n)])
     assert not fired_c.any() and not over(post_c["qpos"]).any() and not over(post_c["qvel"]).any()
-    return dict(kind=kind, name=name, action=_frozen(a), pre=_frozen(pre), out=_frozen(out), post=_frozen(post), bad=_frozen(bad), why=why,
-                fired=_frozen(fired), hinge=hinge, sign=sign, pre_clean=_frozen(pre_c), out_clean=_frozen(out_c), post_clean=_frozen(post_c))
+    return dict(kind=kind, name=name, action=rp.freeze(a), pre=rp.freeze(pre), out=rp.freeze(out), post=rp.freeze(post), bad=rp.freeze(bad), why=why,
+                fired=rp.freeze(fired), hinge=hinge, sign=sign, pre_clean=rp.freeze(pre_c), out_clean=rp.freeze(out_c), post_clean=rp.freeze(post_c))
 
 
 def check_sides(n, r):
@@ -174,12 +167,8 @@ def check_sides(n, r):
 
 
 def _engine_step(torch, n, pre, action):
-    from mycobotgym_amd import MyCobotVecEnv
-    envs = MyCobotVecEnv(n, device="cuda:0", has_object=False, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=1,
-                         max_episode_steps=10 ** 9)
-    envs.reset(seed=SEED)
-    envs.counters(clear=True)
-    _sync(envs, pre)
+    envs = rp.engine(n, 1, SEED)
+    rp.sync_state(envs, pre)
     obs, rew, term, trunc, info = envs.step(torch.as_tensor(action.copy()))
     st = envs.get_state()
     g = dict(obs=obs["observation"].cpu().numpy(), achieved=obs["achieved_goal"].cpu().numpy(), desired=obs["desired_goal"].cpu().numpy(),
@@ -235,10 +224,8 @@ BOUNDS2 = {      # the env-step of two sub-steps: 100 x the parent build's worst
 def oracle_run2(n):
     """The same start state, the `below` lanes made ordinary, taken through an env-step of TWO sub-steps (frame_skip = 2): the lanes
     that go bad do so in the first, and the second runs from the reset state: dict(action, pre, out, post, bad1, warned)."""
-    from tests.common import make_oracle
     r = oracle_run(n)
-    ora = make_oracle(n, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=2, max_episode_steps=10 ** 9)
-    ora.reset(seed=SEED)
+    ora = rp.oracle(n, 2, SEED)
     below = np.char.find(r["name"], "below") >= 0
     pre = {k: np.where(below.reshape((-1,) + (1,) * (v.ndim - 1)), r["pre_clean"][k], v) for k, v in r["pre"].items()}
     ora.set_state(**pre)
@@ -249,18 +236,14 @@ def oracle_run2(n):
     bad1 = r["bad"] & ~below
     assert np.array_equal(warned, bad1)                                   # the oracle reset those lanes, in its first or at the start of its second step
     assert (np.abs(post["qpos"]) <= 1.0).all() and (np.abs(post["qvel"]) <= LIMIT).all()      # and nothing goes bad in the second
-    return dict(action=r["action"], pre=_frozen(pre), out=_frozen(out), post=_frozen(post), bad1=_frozen(bad1), name=r["name"])
+    return dict(action=r["action"], pre=rp.freeze(pre), out=rp.freeze(out), post=rp.freeze(post), bad1=rp.freeze(bad1), name=r["name"])
 
 
 def measure2(torch, n):
     """-> (lanes that end at the reset state [n], lanes the oracle reset [n], resets counted, errors by class of lane)."""
-    from mycobotgym_amd import MyCobotVecEnv
     r = oracle_run2(n)
-    envs = MyCobotVecEnv(n, device="cuda:0", has_object=False, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=2,
-                         max_episode_steps=10 ** 9)
-    envs.reset(seed=SEED)
-    envs.counters(clear=True)
-    _sync(envs, r["pre"])
+    envs = rp.engine(n, 2, SEED)
+    rp.sync_state(envs, r["pre"])
     obs, rew, term, trunc, info = envs.step(torch.as_tensor(r["action"].copy()))
     st = envs.get_state()
     g = dict(obs=obs["observation"].cpu().numpy(), achieved=obs["achieved_goal"].cpu().numpy(), reward=rew.cpu().numpy(),
@@ -275,13 +258,6 @@ def measure2(torch, n):
     print(f"{n} two sub-steps: lanes the oracle reset {np.nonzero(r['bad1'])[0].tolist()}, lanes that END at the reset state "
           f"{np.nonzero(at_reset)[0].tolist()}, resets counted {counted}")
     return at_reset, r["bad1"], counted, err
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 @pytest.mark.parametrize("n", RUNS)

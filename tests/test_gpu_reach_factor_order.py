@@ -14,9 +14,9 @@ and then factor.  The two must give the same bits: each element takes the same f
     elimination in extended precision on these very matrices stays below 1e-13 in that measure, the scaled condition numbers are below
     1e3, so 1e-12 stands as the issue states it.
 
-(b) Sub-steps and whole env-steps against the CPU oracle, on the states of tests/test_gpu_reach_side_wave_slots.py (its oracle runs,
-    shared through its cache): no gear row; row 6 only; row 8 only; both rows at either limit; an arm limit violated from the first
-    sub-step, so that the RNE wave skips its solve and the main wave takes the unchanged route; remote -> main-wave solve -> remote;
+(b) Sub-steps and whole env-steps against the CPU oracle, on the states of tests/test_gpu_reach_side_wave_slots.py (the oracle runs of
+    tests/reach_measures.py, shared through its cache): no gear row; row 6 only; row 8 only; both rows at either limit; an arm limit
+    violated from the first sub-step, so that the RNE wave skips its solve and the main wave takes the unchanged route; remote -> main-wave solve -> remote;
     an auto-reset; at 165 environments (two full workgroups and a ragged one) and mixed lanes at 65.  Added here: three free-running
     env-steps with the auto-reset at the end of the second (`reset3`).  Bounds: 100 x the parent build's errors on the same states
     (profiles/r14/factor_order_parent.log); the figures are in the comments.
@@ -26,9 +26,10 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_gpu_reach_after_s3 import SEED, _sync
-from tests.test_gpu_reach_side_wave_slots import (N, RUNS, _engine, _errors, _within, _worst, measure_env_steps, measure_substeps,
-                                                  oracle_run)
+from tests import reach_parity as rp
+from tests.common import torch_cuda  # noqa: F401
+from tests.reach_measures import SLOT_RUNS as RUNS, measure_slot_env_steps, measure_slot_substeps, slot_engine, slot_oracle_run
+from tests.reach_parity import N, SEED
 
 NB, TRI = 12, 78
 PAR = (-1, 0, 1, 2, 3, 4, 5, 6, 5, 8, 5, 5)          # mcg_dynamics.hpp
@@ -101,8 +102,7 @@ def factor_cases():
         # H from the table's own (rounded) entries, formed as the device forms it: (H_eq + M) + D
         Hs[c] = np.tril(E) + np.tril(M); Hs[c][np.arange(10), np.arange(10)] += D * act
         Hs[c] = np.tril(Hs[c]) + np.tril(Hs[c], -1).T
-    for x in (table, Hs): x.flags.writeable = False
-    return table, Hs
+    return rp.freeze((table, Hs))
 
 
 def ldl_numpy(H, b, dtype=np.float64):
@@ -149,13 +149,6 @@ def test_numpy_factor_against_extended_precision():
     assert np.finfo(np.longdouble).eps < 1e-18                         # extended precision is what it says
     assert d.min() < 2e-7 and d.max() > 5e5
     assert (worst <= EPS / 10).all() and cond < 1e3, (worst, cond)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 def run_factor(torch, fn, table):
@@ -231,53 +224,34 @@ RESET3_BOUNDS = {N: dict(obs=4.738e-06, q=1.675e-06, v=3.159e-04, w=1.365e-04)} 
 def oracle_reset3(n):
     """Three whole env-steps from the `reset` case's state, the episodes of a fifth of the lanes one step younger: the second env-step
     truncates and auto-resets them, the third runs the fresh lanes next to running ones."""
-    from tests.common import make_oracle
-    r = oracle_run("reset", n)
+    r = slot_oracle_run("reset", n)
     late = np.arange(n) % 5 == 2
     el = r["env_pre"]["elapsed"].copy(); el[late] = 48
-    ora = make_oracle(n, frame_skip=20, controller_type="joint", reward_type="dense", seed=SEED, max_episode_steps=50)
-    ora.reset(seed=SEED)
-    ora.set_state(**dict(r["env_pre"], elapsed=el))
-    pre, out, post = ora.get_state(), [], []
-    for k in range(3):
-        out.append(ora.step(r["action"])); post.append(ora.get_state())
-    tr = [o["truncated"].astype(bool) for o in out]
+    r3 = rp.replay_env_steps(rp.oracle(n, 20, SEED, 50), dict(r["env_pre"], elapsed=el), r["action"], steps=3)
+    tr = [o["truncated"].astype(bool) for o in r3["env_out"]]
     assert not tr[0].any() and np.array_equal(tr[1], late) and not tr[2].any()
-    for x in [pre] + out + post:
-        for y in x.values(): y.flags.writeable = False
-    return dict(action=r["action"], pre=pre, out=out, post=post)
+    return dict(action=r["action"], **rp.freeze(r3))
 
 
 def measure_reset3(n):
-    import torch
-    r = oracle_reset3(n)
-    envs = _engine("reset", n, 20)
-    a = torch.as_tensor(r["action"].copy())
-    _sync(envs, r["pre"])
-    w = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
-    for k in range(3):
-        w = _worst(w, _errors(envs, *envs.step(a), r["out"][k], r["post"][k], ("reset3", k)))
-    assert envs.counters()["bad_state_resets"] == 0
-    envs.close()
-    print(f"reset3 ({n}) env-steps: " + " ".join(f"{x} {v:.3e}" for x, v in w.items()))
-    return w
+    return rp.measure_env_steps(oracle_reset3(n), lambda frame_skip: slot_engine("reset", n, frame_skip), f"reset3 ({n}) env-steps")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_substeps_against_the_oracle(torch_cuda, case, n):
-    w, b = measure_substeps(case, n), SUB_BOUNDS[(case, n)]
-    assert _within(w, b), (w, b)
+    w, b = measure_slot_substeps(case, n), SUB_BOUNDS[(case, n)]
+    assert rp.within(w, b), (w, b)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_env_steps_against_the_oracle(torch_cuda, case, n):
-    w, b = measure_env_steps(case, n), ENV_BOUNDS[(case, n)]
-    assert _within(w, b), (w, b)
+    w, b = measure_slot_env_steps(case, n), ENV_BOUNDS[(case, n)]
+    assert rp.within(w, b), (w, b)
 
 
 @pytest.mark.gpu
 def test_three_env_steps_with_an_auto_reset(torch_cuda):
     w, b = measure_reset3(N), RESET3_BOUNDS[N]
-    assert _within(w, b), (w, b)
+    assert rp.within(w, b), (w, b)

@@ -22,12 +22,11 @@ qpos / qvel / observation absolute, the warm start (= qacc) relative to the lane
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from tests import reach_parity as rp
+from tests.common import step_errors, sync_oracle_to, torch_cuda  # noqa: F401
+from tests.reach_parity import ARM_HI, N
 
-N = 165
-ARM_HI = 2.96706                                     # jnt_range[0][1] of the mycobot280 tables; the gear joints' range is [0, 0.7]
-GEAR_HI, FINGER_HI = 0.7, 0.872664
-GROUPS = [slice(0, 64), slice(64, 128), slice(128, N)]
+pytestmark = pytest.mark.gpu
 
 BOUNDS = {
     "mixed": dict(obs=5.7e-11, q=9.9e-11, v=1.3e-08, w=5.1e-10),      # 5.732e-13  9.947e-13  1.380e-10  5.174e-12
@@ -36,31 +35,9 @@ BOUNDS = {
 }
 
 
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-def _pair(seed, max_episode_steps=10 ** 9):
-    """Engine and oracle after a reset and one ordinary step: warm start, lagged q and ctrl are those of a running episode."""
-    from tests.common import make_pair, step_errors, sync_oracle_to
-    envs, ora = make_pair(N, controller_type="joint", reward_type="dense", seed=seed, max_episode_steps=max_episode_steps, frame_skip=20)
-    envs.reset(seed=seed); ora.reset(seed=seed)
-    rng = np.random.default_rng(seed)
-    sync_oracle_to(envs, ora)
-    _, flags_equal, _ = step_errors(envs, ora, rng.uniform(-1, 1, (N, envs.action_dim)).astype(np.float32))
-    assert flags_equal
-    return envs, ora, rng
-
-
 def _state_errors(envs, ora):
-    st, so = envs.get_state(), ora.get_state()
-    gq, gv, gw = (st[k].cpu().numpy().T for k in ("qpos", "qvel", "warm"))
-    assert all(np.isfinite(x).all() for x in (gq, gv, gw, so["qpos"], so["qvel"], so["warm"]))
-    w = np.abs(gw - so["warm"]).max(axis=1) / np.abs(so["warm"]).max(axis=1)
-    return float(np.abs(gq - so["qpos"]).max()), float(np.abs(gv - so["qvel"]).max()), float(w.max())
+    eq, ev, ew, _ = rp.state_errors(envs, ora, relative_warm=True)
+    return float(eq.max()), float(ev.max()), float(ew.max())
 
 
 def _mixed_gear_state(ora, rng, cross):
@@ -74,7 +51,7 @@ def _mixed_gear_state(ora, rng, cross):
     q[:, 8] = np.where((i % 4 == 0) | (i % 4 == 2), below[:, 1], inside[:, 1])
     a = rng.uniform(-1, 1, (N, 7)).astype(np.float32)
     a[:, 6] = np.where((i // 4) % 2 == 1, 1.0, -1.0)
-    a[GROUPS[1], 6] = 1.0
+    a[rp.groups(N)[1], 6] = 1.0
     if cross:
         c = (i % 64 == 5) | (i % 64 == 30)
         q[c, 0] = ARM_HI - 0.02; qd[c, 0] = rng.uniform(7.5, 8.5, int(c.sum())); a[c, 0] = 1.0
@@ -85,30 +62,24 @@ def _mixed_gear_state(ora, rng, cross):
 def _substep_paths(ora, a, seed):
     """Per sub-step and workgroup, from a twin oracle stepped with frame_skip = 1 (the joint controller writes the same ctrl in every
     env-step): does some lane hold an arm row (the main wave solves), a gear row (the columns are read)?"""
-    from tests.common import make_oracle
-    twin = make_oracle(N, controller_type="joint", reward_type="dense", seed=seed, max_episode_steps=10 ** 9, frame_skip=1)
-    twin.reset(seed=seed); twin.set_state(**ora.get_state())
+    twin = rp.oracle(N, 1, seed)
+    twin.set_state(**ora.get_state())
     arm, gear = np.zeros((20, 3), bool), np.zeros((20, 3), bool)
     for k in range(20):
-        tq = twin.get_state()["qpos"]
-        assert not (np.abs(tq[:, [7, 9]]) > FINGER_HI).any()                        # no finger row: the arm rows alone switch the path
-        out = (np.abs(tq[:, :6]) > ARM_HI).any(axis=1)
-        row = (tq[:, 6] < 0) | (tq[:, 8] < 0) | (tq[:, 6] > GEAR_HI) | (tq[:, 8] > GEAR_HI)
-        for g, sl in enumerate(GROUPS):
-            arm[k, g] = out[sl].any(); gear[k, g] = row[sl].any()
+        out, row, fing = rp.limit_rows_of(twin.get_state()["qpos"])
+        assert not fing.any()                                                       # no finger row: the arm rows alone switch the path
+        arm[k], gear[k] = rp.per_group(out, N), rp.per_group(row, N)
         twin.step(a)
     return arm, gear
 
 
 def measure_env_step(cross):
     """Worst errors of one env-step over the 165 lanes: dict(obs, q, v, w)."""
-    from tests.common import step_errors, sync_oracle_to
     seed = 51
-    envs, ora, rng = _pair(seed)
+    envs, ora, rng = rp.running_pair("joint", 20, seed)
     a = _mixed_gear_state(ora, rng, cross)
     arm, gear = _substep_paths(ora, a, seed)
-    show = lambda m: " | ".join("".join("X" if x else "." for x in m[:, g]) for g in range(3))
-    print(f"\nsub-steps with an arm row, per workgroup: {show(arm)}\nsub-steps with a gear row, per workgroup: {show(gear)}")
+    print(f"\nsub-steps with an arm row, per workgroup: {rp.show(arm)}\nsub-steps with a gear row, per workgroup: {rp.show(gear)}")
     assert gear[:, 0].all() and gear[:, 2].all()                                     # columns read in every sub-step ...
     assert gear[0, 1] and not gear[10:, 1].any()                                     # ... and in the first ones only
     for g in range(3):
@@ -131,8 +102,7 @@ def measure_env_step(cross):
 
 def measure_auto_reset():
     """Worst errors over three free-running env-steps (observation: of all three; state: after the last): dict(obs, q, v, w)."""
-    from tests.common import step_errors, sync_oracle_to
-    envs, ora, rng = _pair(53, max_episode_steps=50)
+    envs, ora, rng = rp.running_pair("joint", 20, 53, max_episode_steps=50)
     i = np.arange(N)
     late = i % 5 == 2                                                                # in all three workgroups, next to running lanes
     s = ora.get_state()
@@ -158,17 +128,16 @@ def measure_auto_reset():
     return w
 
 
-def _within(w, b):
-    assert w["obs"] <= b["obs"] and w["q"] <= b["q"] and w["v"] <= b["v"] and w["w"] <= b["w"], (w, b)
-
-
 def test_env_step_with_mixed_gear_rows(torch_cuda):
-    _within(measure_env_step(False), BOUNDS["mixed"])
+    w, b = measure_env_step(False), BOUNDS["mixed"]
+    assert rp.within(w, b), (w, b)
 
 
 def test_env_step_leaves_the_remote_path_and_returns(torch_cuda):
-    _within(measure_env_step(True), BOUNDS["cross"])
+    w, b = measure_env_step(True), BOUNDS["cross"]
+    assert rp.within(w, b), (w, b)
 
 
 def test_auto_reset_in_the_middle_of_three_env_steps(torch_cuda):
-    _within(measure_auto_reset(), BOUNDS["reset"])
+    w, b = measure_auto_reset(), BOUNDS["reset"]
+    assert rp.within(w, b), (w, b)

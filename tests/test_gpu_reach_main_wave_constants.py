@@ -34,16 +34,15 @@ import json
 import numpy as np
 import pytest
 
-from tests.test_gpu_reach_after_s3 import SUBSTEPS, _groups, _sync
-from tests.test_gpu_reach_side_wave_slots import _errors, _within, _worst
+from tests import reach_parity as rp
+from tests.common import torch_cuda  # noqa: F401
+from tests.reach_parity import GEAR_HI, GEAR_LO, N
 
 pytestmark = pytest.mark.gpu
 
-N = 165
 SEED = 67
 CASES = ("gear", "none", "arm")
 RUNS = [(c, N) for c in CASES] + [("gear", 65)]
-GEAR_LO, GEAR_HI = 0.0, 0.7
 
 # joint -> (solref, solimp = d0 dmax width midpoint power): one record per limit row, no two alike
 TABLE_ROWS = {
@@ -123,28 +122,16 @@ def _put(case, ora, rng, n):
 def oracle_run(case, n):
     """The case on the CPU oracle alone: dict(action; pre / post / out = state before / after and outputs of each of the twenty single
     sub-steps; env_pre = the state the env-step starts from; env_post / env_out = state and outputs after it)."""
-    from tests.common import make_oracle
-    kw = dict(controller_type="joint", reward_type="dense", seed=SEED, max_episode_steps=10 ** 9, table=table())
-    ora = make_oracle(n, frame_skip=1, **kw)
-    ora.reset(seed=SEED)
     rng = np.random.default_rng([SEED, 12, CASES.index(case), n])
-    ora.step(rng.uniform(-1, 1, (n, ora.act_dim)).astype(np.float32))      # warm start, lagged q and ctrl of a running episode
+    ora = rp.oracle(n, 1, SEED, table=table(), running=rng)
     a = _put(case, ora, rng, n)
-    r = dict(action=a, pre=[], post=[], out=[], env_post=[], env_out=[])
+    r = dict(action=a)
     start = ora.get_state()
-    for k in range(SUBSTEPS):
-        r["pre"].append(ora.get_state()); r["out"].append(ora.step(a)); r["post"].append(ora.get_state())
-    ora20 = make_oracle(n, frame_skip=20, **kw)
-    ora20.reset(seed=SEED)
-    ora20.set_state(**start)
-    r["env_pre"] = ora20.get_state()
-    r["env_out"].append(ora20.step(a)); r["env_post"].append(ora20.get_state())
+    r.update(rp.record_substeps(ora, a))
+    r.update(rp.replay_env_steps(rp.oracle(n, 20, SEED, table=table()), start, a))
     for s in r["post"] + r["env_post"]:
         assert all(np.isfinite(s[x]).all() and np.abs(s[x]).max() < 1e6 for x in ("qpos", "qvel", "warm")), case
-    for v in r.values():
-        for x in (v if isinstance(v, list) else [v]):
-            for y in (x.values() if isinstance(x, dict) else [x]): y.flags.writeable = False
-    return r
+    return rp.freeze(r)
 
 
 def check_paths(case, n, r):
@@ -161,7 +148,7 @@ def check_paths(case, n, r):
     else:
         for col, j in ((0, 6), (1, 8)):
             x = viol[:, col] / WIDTH[j]
-            for g in (g for g in _groups(n) if g.stop - g.start >= 24):      # 24 lanes: one period of the three patterns
+            for g in (g for g in rp.groups(n) if g.stop - g.start >= 24):      # 24 lanes: one period of the three patterns
                 for f in (0.1, 0.4, 0.8, 1.5):
                     for upper in (False, True):
                         m = np.isclose(x[g], f) & ((q0[g, j] > GEAR_HI) == upper)
@@ -170,7 +157,7 @@ def check_paths(case, n, r):
         assert sorted(set(kinds.tolist())) == [1, 2, 3]
     assert arm[0].any() == (case == "arm")
     if case == "arm":
-        for g in _groups(n): assert arm[0, g].any()
+        for g in rp.groups(n): assert arm[0, g].any()
     else:
         assert not arm.any()
     even = i % 2 == 0
@@ -182,52 +169,19 @@ def check_paths(case, n, r):
 
 
 def _engine(n, frame_skip):
-    from mycobotgym_amd import MyCobotVecEnv
-    envs = MyCobotVecEnv(n, device="cuda:0", has_object=False, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=frame_skip,
-                         max_episode_steps=10 ** 9, table=table())
-    envs.reset(seed=SEED)
-    envs.counters(clear=True)
-    return envs
+    return rp.engine(n, frame_skip, SEED, table=table())
 
 
 def measure_substeps(case, n):
     """Worst errors over the twenty single sub-steps and the n lanes."""
-    import torch
     r = oracle_run(case, n)
     check_paths(case, n, r)
-    envs = _engine(n, 1)
-    a = torch.as_tensor(r["action"].copy())
-    w = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
-    for k in range(SUBSTEPS):
-        _sync(envs, r["pre"][k])
-        w = _worst(w, _errors(envs, *envs.step(a), r["out"][k], r["post"][k], (case, k)))
-    assert envs.counters()["bad_state_resets"] == 0
-    envs.close()
-    print(f"{case} ({n}) sub-steps: " + " ".join(f"{x} {v:.3e}" for x, v in w.items()))
-    return w
+    return rp.measure_substeps(r, functools.partial(_engine, n), f"{case} ({n}) sub-steps")
 
 
 def measure_env_steps(case, n):
     """Worst errors after the whole env-step over the n lanes."""
-    import torch
-    r = oracle_run(case, n)
-    envs = _engine(n, 20)
-    a = torch.as_tensor(r["action"].copy())
-    _sync(envs, r["env_pre"])
-    w = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
-    for k, (o, so) in enumerate(zip(r["env_out"], r["env_post"])):
-        w = _worst(w, _errors(envs, *envs.step(a), o, so, (case, "env-step", k)))
-    assert envs.counters()["bad_state_resets"] == 0
-    envs.close()
-    print(f"{case} ({n}) env-steps: " + " ".join(f"{x} {v:.3e}" for x, v in w.items()))
-    return w
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
+    return rp.measure_env_steps(oracle_run(case, n), functools.partial(_engine, n), f"{case} ({n}) env-steps")
 
 
 def test_table_has_a_record_of_its_own_per_row_and_equality(built):
@@ -245,10 +199,10 @@ def test_table_has_a_record_of_its_own_per_row_and_equality(built):
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_substeps_against_the_oracle(torch_cuda, case, n):
     w, b = measure_substeps(case, n), SUB_BOUNDS[(case, n)]
-    assert _within(w, b), (w, b)
+    assert rp.within(w, b), (w, b)
 
 
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_env_steps_against_the_oracle(torch_cuda, case, n):
     w, b = measure_env_steps(case, n), ENV_BOUNDS[(case, n)]
-    assert _within(w, b), (w, b)
+    assert rp.within(w, b), (w, b)

@@ -4,13 +4,14 @@ launch_step picks them for every grid of more than one workgroup per CU -- on an
 robot_substep has arms of its own for them: the wave runs the composite pass itself, assembles H_eq after the bias, keeps the warm start and
 the first active set in registers, takes the Euler step through euler_accel, and meets no hand-over barrier.  Every other per-sub-step test
 runs at most 512 environments, hence the three-wave kernels.  Here MCG_NO_SPLIT=1 is in the environment when the engine is made (mcg_create
-reads it), and each case then runs a measurement another file owns, unchanged, at that file's bound: bounds taken from the oracle and from a
-different kernel than the one under test, so nothing here is fitted to the one-wave kernels.
+reads it), and each case then runs a measurement of tests/reach_measures.py that a three-wave file runs too, unchanged, at that file's
+bound: bounds taken from the oracle and from a different kernel than the one under test, so nothing here is fitted to the one-wave kernels.
 
-  * limit rows, one sub-step and one env-step: test_gpu_reach_limit_rows._run on its own kinds and on the families of limit_row_states.py;
-  * fast, wide states and mixed gear rows at +-10 rad/s: test_gpu_reach_four_waves.measure, test_gpu_reach_remote_solve.measure_mixed;
+  * limit rows, one sub-step and one env-step: limit_run on test_gpu_reach_limit_rows.py's kinds and on the families of limit_row_states.py;
+  * fast, wide states and mixed gear rows at +-10 rad/s: measure_fast_wide (test_gpu_reach_four_waves.py), measure_mixed
+    (test_gpu_reach_remote_solve.py);
   * direct solve -> general iteration -> direct solve inside one env-step, the warm start carried in registers: measure_switch;
-  * bad lanes (qvel = 1e12 / 9e9: values the kernels are written to handle): test_bad_lane_in_a_remote_substep itself;
+  * bad lanes (qvel = 1e12 / 9e9: values the kernels are written to handle): check_bad_lanes, test_bad_lane_in_a_remote_substep's body;
   * teacher-forced rollouts of 64 environments: joint, IK (control_steps 1 and 5, ctrl[:6] included), mocap, at the bounds of
     test_every_substep_of_a_100_step_rollout, test_ik_solves_teacher_forced and test_mocap_substeps_from_identical_state;
   * the natural route: an engine of one workgroup more than the CUs (plus a ragged one) without the variable, against an engine of 192 with
@@ -20,17 +21,14 @@ import numpy as np
 import pytest
 
 from tests import limit_row_states as ls
+from tests.common import make_oracle, make_pair, step_errors, sync_oracle_to, torch_cuda  # noqa: F401
+from tests.reach_measures import (FAST_WIDE_BOUNDS, MIXED_BOUNDS, SUBSTEP_BOUNDS, assert_substep, check_bad_lanes, limit_run, measure_fast_wide,
+                                  measure_mixed, measure_switch)
+from tests.reach_parity import within
 
 pytestmark = pytest.mark.gpu
 
 STATE_KEYS = ("qpos", "qvel", "ctrl", "warm", "qpos_lag", "goal", "elapsed", "episode")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
 
 
 @pytest.fixture
@@ -44,50 +42,42 @@ def one_wave(torch_cuda, monkeypatch):
 @pytest.mark.parametrize("controller", ls.CONTROLLERS)
 @pytest.mark.parametrize("kind", ["gear_pair", "gear6", "with_arm", "none", "fingers", "many"])
 def test_one_wave_substep_on_limit_states(one_wave, kind, controller):
-    from tests.test_gpu_reach_limit_families import assert_substep
-    from tests.test_gpu_reach_limit_rows import _run
-    assert_substep(_run(controller, kind, 1, twin=True), controller)
+    assert_substep(limit_run(controller, kind, 1, twin=True), controller)
 
 
 @pytest.mark.parametrize("kind", ["gear_pair", "with_arm", "many"])
 def test_one_wave_joint_env_step_on_limit_states(one_wave, kind):
-    from tests.test_gpu_reach_limit_rows import _run
-    assert _run("joint", kind, 20)["obs"] < 1e-8                                  # smoke()'s 20-sub-step bound
+    assert limit_run("joint", kind, 20)["obs"] < 1e-8                              # smoke()'s 20-sub-step bound
 
 
 # ----------------------------------------------------------------------------------------------------------------- fast, wide states
 @pytest.mark.parametrize("all_dofs", [False, True], ids=["arm", "all"])
 @pytest.mark.parametrize("controller", ls.CONTROLLERS)
 def test_one_wave_substep_on_fast_wide_states(one_wave, controller, all_dofs):
-    from tests.test_gpu_reach_four_waves import BOUNDS, measure
-    w, b = measure(controller, all_dofs), BOUNDS[controller, all_dofs]
-    assert w["obs"] <= b["obs"] and w["q"] <= b["q"] and w["v"] <= b["v"] and w["w"] <= b["w"], (w, b)
+    w, b = measure_fast_wide(controller, all_dofs), FAST_WIDE_BOUNDS[controller, all_dofs]
+    assert within(w, b), (w, b)
 
 
 def test_one_wave_substep_with_mixed_gear_rows(one_wave):
-    from tests.test_gpu_reach_remote_solve import MIXED_BOUNDS, measure_mixed
     w, b = measure_mixed("joint"), MIXED_BOUNDS["joint"]
-    assert w["obs"] <= b["obs"] and w["q"] <= b["q"] and w["v"] <= b["v"] and w["w"] <= b["w"], (w, b)
+    assert within(w, b), (w, b)
 
 
 @pytest.mark.parametrize("rows", ["direct", "general"])
 def test_one_wave_env_step_switches_solves_and_back(one_wave, rows):
-    from tests.test_gpu_reach_remote_solve import measure_switch
     worst, flags_equal = measure_switch(rows)
     assert flags_equal
     assert worst < 1e-8                                                           # smoke()'s 20-sub-step bound
 
 
 def test_one_wave_bad_lanes(one_wave):
-    from tests import test_gpu_reach_remote_solve as remote
-    remote.test_bad_lane_in_a_remote_substep(one_wave)                            # its states, its assertions
+    check_bad_lanes()                                                             # test_bad_lane_in_a_remote_substep's states and assertions
 
 
 # ------------------------------------------------------------------------------------------------------------ teacher-forced rollouts
 def _teacher_forced(n, steps, actions, **kw):
     """`steps` engine steps of `n` environments, the state re-synchronised to the oracle's before each, the action redrawn every 20:
     worst errors of observation, qpos, qvel, warm start and ctrl[:6] after each."""
-    from tests.common import make_pair, step_errors, sync_oracle_to
     seed = kw["seed"]
     envs, ora = make_pair(n, reward_type="dense", max_episode_steps=10 ** 9, frame_skip=1, **kw)
     envs.reset(seed=seed); ora.reset(seed=seed)
@@ -139,8 +129,6 @@ def test_large_grid_runs_the_kernel_the_switch_selects(torch_cuda, monkeypatch):
     with an oracle of 37 environments at the sub-step bounds; the oracle never sees the large engine."""
     torch = torch_cuda
     from mycobotgym_amd import MyCobotVecEnv
-    from tests.common import make_oracle
-    from tests.test_gpu_reach_limit_families import SUBSTEP_BOUNDS
     num_cu = torch.cuda.get_device_properties(0).multi_processor_count
     n_big, n_small, n_tail = 64 * (num_cu + 1) + 37, 192, 37
     kw = ls.engine_kw("joint")

@@ -17,25 +17,22 @@ from the state the first sub-step started from -- two of them in `reset`, whose 
                first env-step does, the second runs the fresh lanes next to running ones.
 
 165 environments (two full workgroups and a ragged one of 37 lanes), `mixed` once more at 65.  The states are those of
-tests/test_gpu_reach_after_s3.py (its _put), `arm` added here; each case's oracle runs once per session.
+tests/test_gpu_reach_after_s3.py (tests/reach_parity.py's put_gear_case), `arm` added on top; tests/reach_measures.py makes and measures them
+(slot_oracle_run; tests/test_gpu_reach_factor_order.py runs them too), each case's oracle once per session.
 
 Compared: observation (with achieved goal and reward), qpos, qvel absolute, the warm start (= qacc) relative to the lane's largest |qacc|
 (absolute where that is zero).  Bounds: 100 x the worst error of the build this change started from (every wave addressing its column from
 slot 0), measured on an MI355X on these very states in one run of this file's measure functions (profiles/r11/side_wave_tests_parent.log);
 the measured figures are in the comments.
 """
-import functools
-
-import numpy as np
 import pytest
 
-from tests.test_gpu_reach_after_s3 import ARM_HI, FINGER_HI, GEAR_HI, GEAR_LO, SEED, SUBSTEPS, _groups, _put, _sync
+from tests import reach_parity as rp
+from tests.common import torch_cuda  # noqa: F401
+from tests.reach_measures import SLOT_RUNS as RUNS, measure_slot_env_steps, measure_slot_substeps
+from tests.reach_parity import N
 
 pytestmark = pytest.mark.gpu
-
-N = 165
-CASES = ("none", "row6", "row8", "both_lower", "both_upper", "arm", "switch", "reset", "mixed")
-RUNS = [(c, N) for c in CASES if c != "mixed"] + [("mixed", 65)]
 
 SUB_BOUNDS = {      # single sub-steps: obs, q, v, w = 100 x the parent build's worst error (the measured figures in the comment)
     ("none", N): dict(obs=7.772e-14, q=8.162e-12, v=4.081e-09, w=4.353e-11),                # 7.772e-16  8.162e-14  4.081e-11  4.353e-13
@@ -61,165 +58,13 @@ ENV_BOUNDS = {      # whole env-steps: likewise
 }
 
 
-def _max_steps(case):
-    return 50 if case == "reset" else 10 ** 9
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_run(case, n):
-    """The case on the CPU oracle alone: dict(action; pre / post / out = state before / after and outputs of each of the twenty single
-    sub-steps; arm / gear [20, groups] = some lane of the workgroup holds an arm row / a gear row when the sub-step starts; env_pre =
-    the state the env-steps start from; env_post / env_out = state and outputs after each whole env-step)."""
-    from tests.common import make_oracle
-    kw = dict(controller_type="joint", reward_type="dense", seed=SEED, max_episode_steps=_max_steps(case))
-    ora = make_oracle(n, frame_skip=1, **kw)
-    ora.reset(seed=SEED)
-    rng = np.random.default_rng([SEED, 11, CASES.index(case), n])
-    ora.step(rng.uniform(-1, 1, (n, ora.act_dim)).astype(np.float32))      # warm start, lagged q and ctrl of a running episode
-    a = _put("mixed" if case == "arm" else case, ora, rng, n)
-    if case == "arm":
-        s = ora.get_state()
-        q, qd = s["qpos"].copy(), s["qvel"].copy()
-        x = (np.arange(n) % 64 == 5) | (np.arange(n) % 64 == 30)
-        q[x, 0] = ARM_HI + 0.03; qd[x, 0] = 0.0; a[x, 0] = 1.0
-        ora.set_state(qpos=q, qvel=qd)
-    groups = _groups(n)
-    r = dict(action=a, pre=[], post=[], out=[], env_post=[], env_out=[], arm=np.zeros((SUBSTEPS, len(groups)), bool),
-             gear=np.zeros((SUBSTEPS, len(groups)), bool))
-    start = ora.get_state()
-    for k in range(SUBSTEPS):
-        pre = ora.get_state()
-        o = ora.step(a)
-        q = pre["qpos"]
-        assert not (np.abs(q[:, [7, 9]]) > FINGER_HI).any()                # no finger row: the arm rows alone switch the path
-        arm = (np.abs(q[:, :6]) > ARM_HI).any(axis=1)
-        gear = (q[:, [6, 8]] < GEAR_LO).any(axis=1) | (q[:, [6, 8]] > GEAR_HI).any(axis=1)
-        for g, sl in enumerate(groups): r["arm"][k, g], r["gear"][k, g] = arm[sl].any(), gear[sl].any()
-        r["pre"].append(pre); r["out"].append(o); r["post"].append(ora.get_state())
-    # whole env-steps from the same state (reset: the first one ends the episode of a fifth of the lanes)
-    ora20 = make_oracle(n, frame_skip=20, **kw)
-    ora20.reset(seed=SEED)
-    if case == "reset":
-        el = start["elapsed"].copy(); el[np.arange(n) % 5 == 2] = 49
-        start = dict(start, elapsed=el)
-    ora20.set_state(**start)
-    r["env_pre"] = ora20.get_state()
-    for k in range(2 if case == "reset" else 1):
-        r["env_out"].append(ora20.step(a)); r["env_post"].append(ora20.get_state())
-    for v in r.values():
-        for x in (v if isinstance(v, list) else [v]):
-            for y in (x.values() if isinstance(x, dict) else [x]): y.flags.writeable = False
-    return r
-
-
-def check_paths(case, n, r):
-    """The sub-steps take the paths the case is about."""
-    show = lambda m: " | ".join("".join("X" if x else "." for x in m[:, g]) for g in range(m.shape[1]))
-    print(f"\n{case} ({n}): sub-steps with an arm row, per workgroup: {show(r['arm'])}\n{case} ({n}): sub-steps with a gear row, per workgroup: {show(r['gear'])}")
-    q = np.stack([s["qpos"] for s in r["pre"]])
-    row = (q[:, :, [6, 8]] < GEAR_LO) | (q[:, :, [6, 8]] > GEAR_HI)                   # [20, n, 2]
-    if case not in ("arm", "switch"): assert not r["arm"].any()                       # twenty remote sub-steps in every workgroup
-    if case == "none": assert not r["gear"].any()
-    if case in ("row6", "row8"):
-        j = 0 if case == "row6" else 1
-        assert row[0, :, j].all() and not row[0, :, 1 - j].any()
-    if case in ("both_lower", "both_upper"):
-        assert row[0].all() and ((q[0, :, [6, 8]] > GEAR_HI).all() if case == "both_upper" else (q[0, :, [6, 8]] < GEAR_LO).all())
-    if case == "arm":
-        assert r["arm"][:2].all() and r["gear"][:2].all()                             # the main wave solves, with gear rows beside the arm row
-    if case == "switch":
-        for g in range(r["arm"].shape[1]):
-            k_out = np.nonzero(r["arm"][:, g])[0]
-            assert not r["arm"][0, g] and k_out.size and k_out[0] >= 2 and k_out[-1] <= 17, (g, k_out)      # remote, main wave, remote again
-    trunc = np.stack([o["truncated"].astype(bool) for o in r["out"]])
-    if case == "reset":
-        late = np.arange(n) % 5 == 2
-        assert np.array_equal(trunc[9], late) and not trunc[:9].any() and not trunc[10:].any()      # the reset lands in the tenth sub-step
-        assert np.array_equal(r["env_out"][0]["truncated"].astype(bool), late) and not r["env_out"][1]["truncated"].any()
-    else:
-        assert not trunc.any() and not r["env_out"][0]["truncated"].any()
-
-
-def _errors(envs, obs, rew, term, trunc, info, o, so, what):
-    """Worst errors of one step's outputs and state against the oracle's (o, so): dict(obs, q, v, w); flags and counters must agree."""
-    assert np.array_equal(obs["desired_goal"].cpu().numpy(), o["desired"]), what
-    assert np.array_equal(term.cpu().numpy(), o["terminated"].astype(bool)) and np.array_equal(trunc.cpu().numpy(), o["truncated"].astype(bool)), what
-    assert np.array_equal(info["is_success"].cpu().numpy(), o["is_success"].astype(bool)), what
-    e = max(float(np.abs(obs["observation"].cpu().numpy() - o["obs"]).max()), float(np.abs(obs["achieved_goal"].cpu().numpy() - o["achieved"]).max()),
-            float(np.abs(rew.cpu().numpy() - o["reward"]).max()))
-    st = envs.get_state()
-    gq, gv, gw = (st[x].cpu().numpy().T for x in ("qpos", "qvel", "warm"))
-    assert all(np.isfinite(x).all() for x in (gq, gv, gw)), what
-    assert np.array_equal(st["elapsed"].cpu().numpy(), so["elapsed"]) and np.array_equal(st["episode"].cpu().numpy(), so["episode"]), what
-    ew, den = np.abs(gw - so["warm"]).max(axis=1), np.abs(so["warm"]).max(axis=1)
-    ew = np.where(den > 0, ew / np.where(den > 0, den, 1.0), ew)
-    return dict(obs=e, q=float(np.abs(gq - so["qpos"]).max()), v=float(np.abs(gv - so["qvel"]).max()), w=float(ew.max()))
-
-
-def _engine(case, n, frame_skip):
-    from mycobotgym_amd import MyCobotVecEnv
-    envs = MyCobotVecEnv(n, device="cuda:0", has_object=False, controller_type="joint", reward_type="dense", seed=SEED, frame_skip=frame_skip,
-                         max_episode_steps=_max_steps(case))
-    envs.reset(seed=SEED)
-    envs.counters(clear=True)
-    return envs
-
-
-def _worst(a, b):
-    return {k: max(a[k], b[k]) for k in a}
-
-
-def measure_substeps(case, n):
-    """Worst errors over the twenty single sub-steps and the n lanes."""
-    import torch
-    r = oracle_run(case, n)
-    check_paths(case, n, r)
-    envs = _engine(case, n, 1)
-    a = torch.as_tensor(r["action"].copy())
-    w = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
-    for k in range(SUBSTEPS):
-        _sync(envs, r["pre"][k])
-        w = _worst(w, _errors(envs, *envs.step(a), r["out"][k], r["post"][k], (case, k)))
-    assert envs.counters()["bad_state_resets"] == 0
-    envs.close()
-    print(f"{case} ({n}) sub-steps: " + " ".join(f"{x} {v:.3e}" for x, v in w.items()))
-    return w
-
-
-def measure_env_steps(case, n):
-    """Worst errors after each whole env-step (the engine runs on from its own state) over the n lanes."""
-    import torch
-    r = oracle_run(case, n)
-    envs = _engine(case, n, 20)
-    a = torch.as_tensor(r["action"].copy())
-    _sync(envs, r["env_pre"])
-    w = dict(obs=0.0, q=0.0, v=0.0, w=0.0)
-    for k, (o, so) in enumerate(zip(r["env_out"], r["env_post"])):
-        w = _worst(w, _errors(envs, *envs.step(a), o, so, (case, "env-step", k)))
-    assert envs.counters()["bad_state_resets"] == 0
-    envs.close()
-    print(f"{case} ({n}) env-steps: " + " ".join(f"{x} {v:.3e}" for x, v in w.items()))
-    return w
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(built):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-def _within(w, b):
-    return w["obs"] <= b["obs"] and w["q"] <= b["q"] and w["v"] <= b["v"] and w["w"] <= b["w"]
-
-
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_substeps_against_the_oracle(torch_cuda, case, n):
-    w, b = measure_substeps(case, n), SUB_BOUNDS[(case, n)]
-    assert _within(w, b), (w, b)
+    w, b = measure_slot_substeps(case, n), SUB_BOUNDS[(case, n)]
+    assert rp.within(w, b), (w, b)
 
 
 @pytest.mark.parametrize("case,n", RUNS, ids=[f"{c}-{n}" for c, n in RUNS])
 def test_env_steps_against_the_oracle(torch_cuda, case, n):
-    w, b = measure_env_steps(case, n), ENV_BOUNDS[(case, n)]
-    assert _within(w, b), (w, b)
+    w, b = measure_slot_env_steps(case, n), ENV_BOUNDS[(case, n)]
+    assert rp.within(w, b), (w, b)
